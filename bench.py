@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Throughput bench for the MI355X decode-DSP hot path (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--workload aac_synth|fir|pipeline]
+  python bench.py --gpus N --steps K --warmup W [--workload aac_synth|fir|pipeline] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what takes runs of its own: the CPU
+baselines, the f32-output synthesis reference point of the roofline and the default line's `mix` and `end_to_end`
+extras.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; a fixed, seeded sample
+of rows where the output is larger than DUMP_BYTES).
 
 One rank per GPU (torch.distributed / RCCL only for the barrier and the max-over-ranks
 of the timed region: the streams are independent, so there is no data-path collective
@@ -52,6 +57,20 @@ SEED0 = 0x12345678
 # a few hundred steps (tests/test_pipeline_gpu.py checks the same data against the oracle).  Not a performance knob:
 # nothing on the path is data-dependent.
 SPECTRUM_GAIN = 2500.0
+DUMP_BYTES = 32 << 20  # per dumped array; no workload dumps more than one, so --dump-outputs stays under 64 MB
+
+
+def sample_rows(torch, t):
+    """t's rows (first axis) as float32 on the host: all of them, or a fixed, seeded sample of them within DUMP_BYTES"""
+    k = max(1, min(t.shape[0], DUMP_BYTES // (t[0].numel() * 4)))
+    rows = np.sort(np.random.default_rng(SEED0).choice(t.shape[0], k, replace=False))
+    return t[torch.from_numpy(rows).to(t.device)].float().cpu().numpy()
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
 
 
 def lcg_tables(n=1024):
@@ -423,7 +442,9 @@ def end_to_end(args, eng, torch, dist, world, rank, device, emit=True, cpu_basel
     captured = np.frombuffer(cap_buf[:int(cap_len[0])].tobytes(), "<i2")
     out["pcm_stats"] = dict(pcm_stats_s16(lg, captured), stream=0, sample_rate=args.out_rate or src_rate, channels=out_ch,
                             access_units=units * args.steps)
-    if args.clip == E2E_CLIP and (args.out_rate or src_rate) == 16000 and out_ch == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:  # stream 0's PCM as delivered, up to its last sample
+        write_outputs(args.dump_outputs, {"stream0_pcm_s16": captured[-(DUMP_BYTES // 4):]})
+    if args.full and args.clip == E2E_CLIP and (args.out_rate or src_rate) == 16000 and out_ch == 1 and not args.no_cpu_baseline:
         want, _ = cpu_chain_decode(clip, args.steps)  # cpu_baseline leg: the checker's decode of the same stream
         cpu = pcm_stats_s16(lg, want)
         same_len = want.size == captured.size
@@ -601,10 +622,15 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--layout", default="frame", choices=["frame", "stream"],
                     help="packing of the batch: frame-major [frame][stream] (one tick of every stream after another) or stream-major")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the CPU baselines, the f32-output synthesis reference "
+                         "point of the roofline, and the pipeline line's `mix` and `end_to_end` extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, a seeded sample of rows if large)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--cpu-baseline-all-cores", action="store_true", help="(default now; kept so that older command lines still run)")
     ap.add_argument("--cpu-baseline-single-core-only", action="store_true",
-                    help="skip the one-process-per-core leg of the CPU baseline (saves ~10 s)")
+                    help="--full: skip the one-process-per-core leg of the CPU baseline (saves ~10 s)")
     ap.add_argument("--separate-s16", action="store_true",
                     help="pipeline: f32 FIR output and a separate f32 -> interleaved s16 kernel instead of the conversion in the FIR's "
                          "epilogue (same bytes out, tests/test_pipeline_gpu.py; the chain measured before the bf16 FIR, DESIGN.md 4.2)")
@@ -621,7 +647,7 @@ def main():
                          "withdrawn -- the platform computes it wrongly at this batch size, profiles/r04_lanes_corruption.md -- and "
                          "'fused' runs it through SK_AAC_TAIL_ONE_LAUNCH=1 with \"valid\": false in its line)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="pipeline: skip the two extra measurements the default line carries (the mixed-window synthesis launch and a "
+                    help="pipeline, --full: skip the two extra measurements the line carries (the mixed-window synthesis launch and a "
                          "few seconds of the whole decode through the scheduler)")
     ap.add_argument("--entropy-threads", type=int, default=0, help="end_to_end: host threads for the AAC front-end (0 = cores - 1, split over ranks)")
     ap.add_argument("--tick-wait-us", type=int, default=0, help="end_to_end: how long a non-empty batch waits for more frames (0 = library default 200)")
@@ -640,6 +666,8 @@ def main():
     ap.add_argument("--out-rate", type=int, default=16000, help="end_to_end: DecodeOptions.output_sample_rate (0 = source rate)")
     ap.add_argument("--out-channels", type=int, default=1, help="end_to_end: DecodeOptions.output_channels (0 = source)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.tail == "fused":
         os.environ["SK_AAC_TAIL_ONE_LAUNCH"] = "1"  # only read by a packed-f32 build, whose line is then marked invalid
 
@@ -661,9 +689,10 @@ def main():
 
     # child processes are started before anything here initialises the GPU
     all_cores = whole_decode = None
-    if not args.no_cpu_baseline and args.workload in CPU_BASELINES and world == 1 and not args.cpu_baseline_single_core_only:
+    baselines = args.full and not args.no_cpu_baseline
+    if baselines and args.workload in CPU_BASELINES and world == 1 and not args.cpu_baseline_single_core_only:
         all_cores = cpu_baseline_all_cores(args.workload)
-    if not args.no_cpu_baseline and args.workload in ("pipeline", "end_to_end") and world == 1 and rank == 0:
+    if baselines and args.workload in ("pipeline", "end_to_end") and world == 1 and rank == 0:
         # the whole decode on the host's cores, beside the end_to_end figure (north_star: "the reference ... CPU path timed on the
         # node's own host cores in the same run")
         whole_decode = cpu_baseline_all_cores("decode", 6.0)
@@ -789,10 +818,13 @@ def main():
                                  "audio_data_to_f32_channels: s / 32768)"}["f32" if args.separate_s16 else args.chain]
             workload = ("aac_lc decode tail: %d streams x %d frames, 48 kHz stereo: IMDCT+window+OLA -> 48k->16k MFMA FIR -> "
                         "interleaved s16 (%s), %s-major batch; %s" % (streams, frames, "separate kernel" if args.separate_s16 else "in the FIR epilogue", args.layout, chain_note))
+            outputs = lambda: {"pcm_s16_16k": sample_rows(torch, s16_out[:, :n_out])}  # [stream][16 kHz frame][ch]
         else:
             def step():
                 timed("k_aac_synth", lambda: plan.run_f32(coeffs, pcm))
             workload = "aac_lc_synth: %d streams x %d frames, 48 kHz stereo, IMDCT+window+OLA, f32 planar out, %s-major batch" % (streams, frames, args.layout)
+            by_stream = pcm.view(frames, streams, ch, 1024).transpose(0, 1) if args.layout == "frame" else pcm.view(streams, frames, ch, 1024)
+            outputs = lambda: {"pcm_f32_48k": sample_rows(torch, by_stream)}  # [stream][frame][ch][sample]
     elif args.workload == "pcm":
         # soundkit::audio_bytes / the worker's output stage as one elementwise pass: f32 -> s16 with the reference's
         # float_sample_to_i16 rounding, 512 Mi samples (2 GiB in, 1 GiB out)
@@ -806,6 +838,7 @@ def main():
         def step():
             timed("k_convert", lambda: eng.pcm_convert_dev("FLOAT_TO_I16_ROUND", x, y, n_samples))
         workload = "audio_bytes conversion FLOAT_TO_I16_ROUND: %d f32 samples -> s16" % n_samples
+        outputs = lambda: {"pcm_s16": sample_rows(torch, y.view(-1, 1 << 16))}  # [64 Ki-sample block][sample]
     elif args.workload == "resample":
         # the reference's production option (soundkit-decoder lib.rs:4740-4744): 44.1 kHz sources to 16 kHz through the
         # generic-ratio resampler (rubato SincFixedIn, Linear: two 256-tap dot products per output, k_sinc_resample)
@@ -823,6 +856,7 @@ def main():
                 eng.set_resampler_exact(True)
             timed("k_sinc_resample", lambda: eng.downsample_dev(x, frames_in, rows, frames_in, 44100, 16000, y, n_out))
         workload = "downsample_audio 44.1k->16k (generic ratio): %d streams x 2 ch x 1 s, f32" % streams
+        outputs = lambda: {"pcm_f32_16k": sample_rows(torch, y)}  # [stream * ch][sample]
     else:
         frames_in = 48000
         rows = streams * ch
@@ -836,6 +870,7 @@ def main():
         def step():
             timed("k_fir_48k_16k", lambda: eng.downsample_48k_16k_dev(x, frames_in, rows, frames_in, y, n_out))
         workload = "downsample_audio 48k->16k: %d streams x 2 ch x 1 s, f32" % streams
+        outputs = lambda: {"pcm_f32_16k": sample_rows(torch, y)}  # [stream * ch][sample]
 
     torch.cuda.synchronize()  # inputs were produced on torch's stream; the engine runs on its own
     for _ in range(args.warmup):
@@ -856,8 +891,10 @@ def main():
     torch.cuda.synchronize()
     from soundkit_amd import sharding
     elapsed = sharding.reduce_elapsed(time.perf_counter() - t0, device)  # max over ranks
+    if rank == 0 and args.dump_outputs:  # before anything below launches on the same streams' state
+        write_outputs(args.dump_outputs, outputs())
     synth_f32_ms = None
-    if rank == 0 and args.workload == "pipeline" and args.chain == "s16" and not args.separate_s16:
+    if args.full and rank == 0 and args.workload == "pipeline" and args.chain == "s16" and not args.separate_s16:
         # reference point for the roofline: the same kernel writing f32 PCM (8 KiB per channel-frame instead of 6), a few
         # launches outside the timed region (profiles/r02_pmc_aac_synth.md has both under the counters).
         scratch = torch.empty_like(coeffs)
@@ -1049,7 +1086,7 @@ def main():
         if mix_report:
             out["mix"] = mix_report
         stalled = False
-        extras = (args.workload == "pipeline" and args.chain == "s16" and not args.separate_s16 and not args.mix and world == 1
+        extras = (args.full and args.workload == "pipeline" and args.chain == "s16" and not args.separate_s16 and not args.mix and world == 1
                   and not args.no_extras and args.layout == "frame")
         if extras:
             # (a) SURVEY 8d's mixed-window batch through the same synthesis launch (planar s16 out): per ten frames one
@@ -1111,6 +1148,7 @@ def main():
             a2 = copy.copy(args)
             a2.workload, a2.front_end, a2.gpu_entropy = "end_to_end", "gpu", True
             a2.steps, a2.warmup = 180, 4   # 4096 streams x 48 units x 180 = 35.4 M access units: 3-4 s at the measured rates (10 M/s)
+            a2.dump_outputs = None
             try:
                 e2e = end_to_end(a2, eng, torch, dist, world, rank, device, emit=False)
             except EndToEndStalled:
@@ -1126,7 +1164,7 @@ def main():
                                  "note": "everything in the timed region: ADTS framing on host threads, Huffman decode / stereo tools / TNS, "
                                          "synthesis, streaming 48 -> 16 kHz resampler, mono downmix, s16 pack on the GPU, D2H, delivery; "
                                          "host-fed (the 16-core share frames and delivers), not a kernel figure"}
-        if world == 1 and not args.no_cpu_baseline and args.workload in CPU_BASELINES:
+        if world == 1 and baselines and args.workload in CPU_BASELINES:
             single = CPU_BASELINES[args.workload](6.0 if all_cores else 15.0)
             single["build"] = "-O2 -ffp-contract=off (portable oracle/libsk_oracle.so)"
             # the stated baseline is the host's cores all busy; the single-thread figure sits beside it, as does the

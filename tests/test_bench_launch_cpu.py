@@ -61,8 +61,8 @@ def test_under_an_external_launcher_it_is_one_rank():
 
 
 def test_a_stalled_extra_still_prints_the_line_and_exits_non_zero():
-    """the default line's end_to_end extra stalling must not look like rc 0 to the driver (bench.py: print_line_and_leave_if_stalled)"""
-    r = run(["--gpus", "1"], WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", SK_BENCH_DRY_STALL="1")
+    """the --full line's end_to_end extra stalling must not look like rc 0 to the driver (bench.py: print_line_and_leave_if_stalled)"""
+    r = run(["--gpus", "1", "--full"], WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", SK_BENCH_DRY_STALL="1")
     assert r.returncode == 3, (r.returncode, r.stderr)
     out = json.loads(r.stdout.strip())
     assert out["n_gpus"] == 1 and "stalled" in out["end_to_end"]["error"]
@@ -73,6 +73,29 @@ def test_refuses_a_world_that_is_not_what_was_asked_for():
     assert r.returncode != 0 and "--gpus 4 but WORLD_SIZE=2" in r.stderr and not r.stdout.strip()
     r = run(["--gpus", "1"], WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     assert r.returncode != 0 and not r.stdout.strip()
+
+
+def test_steps_below_one_are_refused():
+    r = run(["--gpus", "1", "--steps", "0"], WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr and not r.stdout.strip()
+
+
+def test_dumped_outputs_are_a_fixed_sample_within_the_size_limit(tmp_path):
+    """--dump-outputs: float32 .npy files, the same rows of the same output in every run, at most DUMP_BYTES per array"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    s16 = torch.arange(4096, dtype=torch.int16).view(-1, 1, 1).expand(4096, 5000, 2)  # every sample holds its row's index
+    a = bench.sample_rows(torch, s16)
+    assert a.dtype == np.float32 and a.shape[1:] == (5000, 2) and 1 < a.shape[0] < 4096 and a.nbytes <= bench.DUMP_BYTES
+    assert np.array_equal(a, bench.sample_rows(torch, s16))
+    rows = a[:, 0, 0]
+    assert np.all(np.diff(rows) > 0) and np.all(a == rows[:, None, None])  # whole rows, each once, in order
+    small = torch.rand(7, 100)
+    assert np.array_equal(bench.sample_rows(torch, small), small.numpy())  # a small output is dumped whole
+    bench.write_outputs(str(tmp_path / "d"), {"pcm_s16_16k": a})
+    back = np.load(str(tmp_path / "d" / "pcm_s16_16k.npy"))
+    assert back.dtype == np.float32 and np.array_equal(back, a)
 
 
 def test_native_oracle_build_gives_the_portable_results(tmp_path):
