@@ -107,6 +107,7 @@ def lib():
         L.sko_resampler_process_partial.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]
         L.sko_resampler_process_partial.restype = C.c_size_t
         L.sko_resampler_taps_phase0.argtypes = [vp, vp]
+        L.sko_resampler_sincs.argtypes = [vp, vp]
         L.sko_downsample_out_max.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32]
         L.sko_downsample_out_max.restype = C.c_size_t
         L.sko_downsample_planar.argtypes = [vp, C.c_size_t, C.c_int, C.c_uint32, C.c_uint32, vp, C.c_size_t]
@@ -337,6 +338,15 @@ def resampler_taps(ratio):
     lib().sko_resampler_taps_phase0(r, _vp(taps))
     lib().sko_resampler_free(r)
     return taps
+
+
+def resampler_sincs(ratio):
+    """rubato's whole sub-filter table for this ratio: [256 sub-phases][256 taps] f32 (row 0 = resampler_taps(ratio))"""
+    r = lib().sko_resampler_new(ratio, 1024, 1)
+    sincs = np.empty((256, 256), np.float32)
+    lib().sko_resampler_sincs(r, _vp(sincs))
+    lib().sko_resampler_free(r)
+    return sincs
 
 
 def downsample_planar(planar, in_hz, out_hz):

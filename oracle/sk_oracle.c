@@ -671,6 +671,7 @@ size_t sko_resampler_output_frames_max(const sko_resampler *r) {
 }
 
 void sko_resampler_taps_phase0(const sko_resampler *r, float *taps) { memcpy(taps, r->sincs, sizeof(float) * SINC_LEN); }
+void sko_resampler_sincs(const sko_resampler *r, float *sincs) { memcpy(sincs, r->sincs, sizeof(float) * SINC_LEN * OVERSAMPLING); }
 
 /* rubato interpolator scalar get_sinc_interpolated: 8 running sums over the 256 taps */
 static float sinc_dot(const float *wave, const float *sinc) {

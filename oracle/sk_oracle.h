@@ -167,6 +167,8 @@ size_t sko_resampler_process_partial(sko_resampler *r, const float *in, size_t i
                                      size_t n_in, float *out, size_t out_stride);
 /* the 256 taps of sub-filter 0 (what a ratio with zero fractional phase uses) */
 void sko_resampler_taps_phase0(const sko_resampler *r, float *taps256);
+/* the whole sub-filter table, [256 sub-phases][256 taps] (sincs[sub * 256 + p], the order sinc_dot reads) */
+void sko_resampler_sincs(const sko_resampler *r, float *sincs65536);
 
 /* soundkit/src/audio_pipeline.rs:438-493 downsample_audio on planar f32 input:
  * returns output frames per channel; out must hold sko_downsample_out_max(frames, in_hz, out_hz). */

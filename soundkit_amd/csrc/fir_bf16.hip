@@ -68,7 +68,8 @@ __host__ __device__ constexpr int products_of(int s, bool in16) { return in16 &&
 //     x = x1 + x2 (x1 = x toward zero in f16, x2 = x - x1: exact, |x2| < 2^-10 |x|),
 //     h * 2^16 = h1 + h2 + r (rounded to nearest: |h2| <= 2^-12 |h1|, |r| <= 2^-24 |h1|)
 // so that x1h1 + x1h2 + x2h1 leaves out only x2h2 < 2^-22 |x||h| and r -- measured against an f64 evaluation 1.0e-7 relative
-// RMS (tests/fir_split_model.py; the bf16 form with five products: 1.4e-7).  Eleven significand bits per value instead of eight: three products where bf16 needs five, and a
+// RMS (tests/fir_split_model.py; the bf16 form with five products: 1.4e-7 at full scale only -- on s16 rows it leaves out x2h3
+// with x2 the whole low byte, an absolute error floor of a few thousandths of a step, tests/test_full_device_gpu.py).  Eleven significand bits per value instead of eight: three products where bf16 needs five, and a
 // window whose largest tap is below 2^-13 of the peak needs only x1h1.  24 MFMAs per tile instead of 36.
 __device__ constexpr int kProductsF16[kWindows] = {kFirProductsF16[0], kFirProductsF16[1], kFirProductsF16[2], kFirProductsF16[3], kFirProductsF16[4],
                                                      kFirProductsF16[5], kFirProductsF16[6], kFirProductsF16[7], kFirProductsF16[8], kFirProductsF16[9]};
