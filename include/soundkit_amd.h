@@ -363,7 +363,8 @@ typedef struct sk_mp3_tables {
     uint8_t pretab[22];
     float window[512];             /* Table B.3 */
 } sk_mp3_tables;
-typedef struct sk_mp3_codebook sk_mp3_codebook; /* host-side: validated copies + prefix-decoding tables; no GPU involved */
+typedef struct sk_mp3_codebook sk_mp3_codebook; /* validated copies + prefix-decoding tables on the host; sk_mp3_set_codebook puts
+                                                 * a flattened form on an engine for the device Huffman stage */
 int sk_mp3_codebook_create(const sk_mp3_tables *, sk_mp3_codebook **out); /* SK_MP3_INVALID: a code set that is no prefix code */
 void sk_mp3_codebook_destroy(sk_mp3_codebook *);
 int sk_mp3_iso_tables(sk_mp3_tables *out);            /* the standard's tables; hlen / hcod point to static storage */
@@ -387,6 +388,46 @@ typedef struct sk_mp3_granule_data {
 int sk_mp3_decode_main_data(const sk_mp3_codebook *, const sk_mp3_frame_info *header, const sk_mp3_side_info *side, const uint8_t *main,
                             size_t main_len, sk_mp3_granule_data out[2][2]);
 
+/* ---- parts 2 + 3 on the GPU (mp3_entropy.hip) ----
+ * The code book of an engine's device Huffman stage: a flattened form of the validated tries of `cb` (NULL = the standard's
+ * tables) -- per distinct code table a first-level look-up on the next 8 bits, further levels for the longer codes (any
+ * prefix code set sk_mp3_codebook_create accepts, codes of up to 32 bits), slen, lsf_partitions and per sampling rate the
+ * region boundaries of the long / short / mixed cut.  Replaces the engine's previous one.  Until it is called the entry
+ * points below return SK_ERR_UNSUPPORTED.
+ * sk_mp3_codebook_flatten is the host half alone: the blob as 32-bit words (layout: csrc/mp3_codebook_blob.h);
+ * *words receives the size, SK_ERR_CAPACITY if it exceeds cap (out may be NULL with cap 0 to ask for the size). */
+int sk_mp3_codebook_flatten(const sk_mp3_codebook *cb, uint32_t *out, size_t cap_words, size_t *words);
+int sk_mp3_set_codebook(sk_engine *, const sk_mp3_codebook *cb);
+/* One frame for the device stage: header and side information as the host parsed them, and where its assembled main data
+ * (sk_mp3_main_data: reservoir bytes + the frame's own) lies in the call's byte buffer.  Laid out like the access units of
+ * sk_tick_run_au: byte_offset a multiple of 4, at least 8 bytes of the buffer behind every frame's data (zero by convention;
+ * the kernel never takes a bit from beyond byte_len).  byte_len at most 1 MiB; an MPEG-2 / 2.5 scalefac_compress at most 511. */
+typedef struct sk_mp3_frame_item {
+    sk_mp3_frame_info header;
+    sk_mp3_side_info side;
+    uint32_t byte_offset;
+    uint32_t byte_len;
+} sk_mp3_frame_item;
+/* The stage alone, results on the host -- the device counterpart of sk_mp3_decode_main_data, and equal to it in every
+ * field: out[frame][granule][channel], only the cells a frame has are written. */
+int sk_mp3_entropy_decode(sk_engine *, const sk_mp3_frame_item *frames, uint32_t n_frames, const uint8_t *main_bytes, size_t main_len,
+                          sk_mp3_granule_data *out /*[n_frames][2][2]*/);
+/* Huffman stage -> requantisation -> hybrid synthesis, the integers and lines staying on the device.  streams[i] is the
+ * open stream frame i belongs to (frames of one stream in order).  A frame any of whose granule-channels the Huffman stage
+ * rejects is dropped as the host path drops it: entropy_status[i] is that status (SK_MP3_*), the frame takes no room in
+ * pcm_out and its stream's overlap / polyphase state is not touched.  The other frames' samples (samples_per_channel x
+ * channels, interleaved) follow one another in pcm_out in frame order; stage_status[i] (may be NULL) is what
+ * sk_mp3_decode_granules_* would have reported for the frame's granules (the first non-zero one; such a frame keeps its room,
+ * filled as that function fills it).  *samples_written = samples in pcm_out, at most out_cap (else SK_ERR_CAPACITY, nothing
+ * synthesised).  The statuses cross back between the first kernel and the two later ones: one synchronisation more per
+ * call than sk_mp3_decode_granules_*. */
+int sk_mp3_decode_frames_f32(sk_engine *, const sk_mp3_frame_item *frames, const uint32_t *streams, uint32_t n_frames, const uint8_t *main_bytes,
+                             size_t main_len, float *pcm_out, size_t out_cap, int32_t *entropy_status, int32_t *stage_status,
+                             size_t *samples_written);
+int sk_mp3_decode_frames_s16(sk_engine *, const sk_mp3_frame_item *frames, const uint32_t *streams, uint32_t n_frames, const uint8_t *main_bytes,
+                             size_t main_len, int16_t *pcm_out, size_t out_cap, int32_t *entropy_status, int32_t *stage_status,
+                             size_t *samples_written);
+
 /* Mp3Decoder (soundkit-mp3/src/lib.rs:147-374): bytes in at any chunking, interleaved PCM out.  One call decodes every
  * complete frame its input buffer holds -- framing, reservoir, scale factors and Huffman on the host, then ONE
  * requantisation launch and ONE hybrid-synthesis launch over all their granules -- subject to the reference's output rule:
@@ -401,6 +442,14 @@ typedef struct sk_mp3_decoder sk_mp3_decoder;
 int sk_mp3_decoder_create(sk_engine *, const sk_mp3_codebook *, sk_mp3_decoder **out);
 void sk_mp3_decoder_destroy(sk_mp3_decoder *);
 int sk_mp3_decoder_reset(sk_mp3_decoder *);                                           /* lib.rs:180-185 */
+/* on != 0: scale factors and Huffman decode run on the GPU (sk_mp3_set_codebook with the decoder's code book, then one
+ * sk_mp3_decode_frames_* per call); framing, side information and the bit reservoir stay on the host.  Same samples, `written`,
+ * return codes and sk_mp3_decoder_info as with the host stage, for any input at any chunking.  Default off.
+ * The device code book is the ENGINE's (one at a time): a GPU-mode decoder installs its own before each call, which is safe for
+ * decoders of one engine that share a code book (the usual case: the standard's) or a thread; decoders with DIFFERENT code books
+ * driven from different threads need an engine each.
+ * SK_ERR_UNSUPPORTED in a build without the device stage. */
+int sk_mp3_decoder_set_gpu_entropy(sk_mp3_decoder *, int on);
 /* sample_rate / channels are 0 until the first frame was decoded (Option::None, lib.rs:167-173); buffer_len: lib.rs:176 */
 int sk_mp3_decoder_info(const sk_mp3_decoder *, uint32_t *sample_rate, uint8_t *channels, size_t *buffer_len, uint64_t *frames_decoded);
 int sk_mp3_decoder_decode_i16(sk_mp3_decoder *, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written);
@@ -636,6 +685,23 @@ typedef struct sk_tick_input {
 int sk_tick_run_mixed(sk_engine *, const sk_tick_stream *streams, uint32_t n_streams, const sk_tick_input *in, uint8_t *out_bytes,
                       size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap, uint32_t *n_outputs, size_t *out_bytes_used);
 
+/* sk_tick_run_mixed with the MP3 streams' Huffman stage on the device as well (sk_mp3_set_codebook first): instead of
+ * mp3_granules / mp3_descs / mp3_is (leave them NULL / 0) the MP3 streams' units arrive as FRAMES with their assembled main data,
+ * laid out as for sk_mp3_decode_frames_*, listed stream by stream in the order of `streams`; an MP3 stream's n_frames counts its
+ * frames here.  Same outputs as sk_tick_run_mixed gives for the same streams with the host stage.  A frame any of whose
+ * granule-channels the stage rejects is dropped as the host path drops it: no output record, its rows enter no resampler, the
+ * stream's synthesis state is as if the frame had never been queued, and the stream goes on.  The verdicts cross back before the
+ * tick is planned: one synchronisation more than sk_tick_run_mixed. */
+typedef struct sk_tick_mp3_frames {
+    const sk_mp3_frame_item *frames;
+    uint32_t n_frames;
+    const uint8_t *main_bytes;
+    size_t main_len;
+} sk_tick_mp3_frames;
+int sk_tick_run_mixed_md(sk_engine *, const sk_tick_stream *streams, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md,
+                         uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap, uint32_t *n_outputs,
+                         size_t *out_bytes_used);
+
 /* The same tick with the entropy front-end on the GPU too (SURVEY 8f ranks 1 + 4): instead of spectra, the raw access
  * units (ADTS headers stripped) of every stream.  units[k] addresses unit k in au_bytes; units are listed stream by
  * stream in the order of `streams`, byte_offset is a multiple of 4 and every unit is followed by >= 8 zero bytes.
@@ -697,7 +763,11 @@ typedef struct sk_pipeline_config {
     uint32_t gpu_entropy;                /* 1: the host threads only frame the ADTS stream; Huffman decode, stereo tools and TNS
                                           * run on the GPU too (sk_tick_run_au).  0 (default): host front-end (sk_tick_run).
                                           * 2: the host threads do the Huffman decode only and hand over i16 quantised values +
-                                          * side records; dequantisation, PNS, stereo tools and TNS run on the GPU (sk_tick_run_q) */
+                                          * side records; dequantisation, PNS, stereo tools and TNS run on the GPU (sk_tick_run_q)
+                                          * 3: 1, and the MP3 streams' entropy passes stop behind the bit reservoir: scale factors and
+                                          * Huffman decode run in the tick (sk_tick_run_mixed_md).  SK_PIPELINE_MP3_GPU_ENTROPY=1 in the
+                                          * environment makes a pipeline created with 1 behave as 3.  SK_ERR_UNSUPPORTED in a build
+                                          * without the device stage */
     uint32_t lanes;                      /* engines the streams are spread over, each with its own batches and submission
                                           * thread, so that ticks overlap on the device; lane 0 is the caller's engine, the
                                           * others are created on the same device.  0 = 2 with gpu_entropy and max_streams >= two ticks' worth of

@@ -87,6 +87,16 @@ class Mp3GranuleData(C.Structure):
                 ("intensity_scale", C.c_uint8), ("part2_bits", C.c_uint16), ("nonzero_lines", C.c_uint16), ("part3_bits", C.c_uint16), ("status", C.c_int32)]
 
 
+class Mp3FrameItem(C.Structure):
+    """sk_mp3_frame_item"""
+    _fields_ = [("header", Mp3FrameInfo), ("side", Mp3SideInfo), ("byte_offset", C.c_uint32), ("byte_len", C.c_uint32)]
+
+
+class TickMp3Frames(C.Structure):
+    """sk_tick_mp3_frames"""
+    _fields_ = [("frames", C.c_void_p), ("n_frames", C.c_uint32), ("main_bytes", C.c_void_p), ("main_len", C.c_size_t)]
+
+
 class TickStream(C.Structure):
     """sk_tick_stream"""
     _fields_ = [("stream", C.c_uint32), ("n_frames", C.c_uint32), ("out_bits", C.c_uint8), ("out_channels", C.c_uint8),
@@ -280,6 +290,12 @@ _sig = {
     "sk_mp3_decoder_decode_i16": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "sk_mp3_decoder_decode_i32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "sk_mp3_decoder_decode_f32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_mp3_codebook_flatten": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "sk_mp3_set_codebook": (_i, [_vp, _vp]),
+    "sk_mp3_entropy_decode": (_i, [_vp, _vp, _u32, _vp, _sz, _vp]),
+    "sk_mp3_decode_frames_f32": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "sk_mp3_decode_frames_s16": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "sk_mp3_decoder_set_gpu_entropy": (_i, [_vp, _i]),
     "sk_mp3_set_band_tables": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "sk_mp3_requantize": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "sk_aac_entropy_decode": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _vp, _vp]),
@@ -296,6 +312,7 @@ _sig = {
     "sk_tick_out_bound": (_sz, [_vp, _u32, C.POINTER(_u32)]),
     "sk_tick_out_bound_on": (_sz, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "sk_tick_run": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_tick_run_mixed_md": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
     "sk_tick_run_mixed": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",

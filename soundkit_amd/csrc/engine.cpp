@@ -231,6 +231,11 @@ struct sk_engine {
     uint8_t *d_mp3_rq = nullptr;
     uint16_t mp3_bands[sk::kMp3Rates][sk::kMp3BandRow] = {};  // [37] = long bands below line 36 (mixed blocks), 0xffff: none
     bool mp3_bands_set[sk::kMp3Rates] = {};
+    // mp3_entropy.hip: the flattened code book (sk_mp3_set_codebook) on the device and as uploaded; frames | items | main data in,
+    // cells | statuses out
+    uint32_t *d_mp3_cb = nullptr;
+    std::vector<uint32_t> mp3_cb_host;
+    DevBuf mp3e_in, mp3e_out;
 
     // tables
     float *d_tables = nullptr;
@@ -637,6 +642,9 @@ void sk_engine_destroy(sk_engine *e) try {
         e->tick_au.release();
         e->tick_side.release();
         e->tick_q.release();
+        e->mp3e_in.release();
+        e->mp3e_out.release();
+        if (e->d_mp3_cb) (void)hipFree(e->d_mp3_cb);
         if (e->h_arena) (void)hipHostFree(e->h_arena);
         if (e->h_status) (void)hipHostFree(e->h_status);
         if (e->h_out) (void)hipHostFree(e->h_out);
@@ -1953,8 +1961,10 @@ int ensure_mp3(sk_engine *e) {
 }
 
 // e->mu held, device selected
+// rows (device_ptrs only): where granule i's first channel sits in xr / pcm_out, in 576-line rows, when the granules are not
+// packed back to back (sk_mp3_decode_frames_*: the rows of dropped frames lie in between)
 int mp3_synthesize_locked(sk_engine *e, const sk_mp3_granule_desc *descs, const float *xr, void *pcm_out, uint32_t n, int32_t *status,
-                          bool s16, bool device_ptrs) {
+                          bool s16, bool device_ptrs, const uint32_t *rows = nullptr) {
     int rc = ensure_mp3(e);
     if (rc != SK_OK) return rc;
     if (!e->mp3_window_set) return SK_ERR_UNSUPPORTED;  // no synthesis window: sk_mp3_set_synthesis_window first
@@ -1993,7 +2003,7 @@ int mp3_synthesize_locked(sk_engine *e, const sk_mp3_granule_desc *descs, const 
         if (ok[i])
             for (uint32_t c = 0; c < d.channels; ++c) {
                 sk::SynthTask &t = tasks[e->state_task[d.stream * 2 + c]];
-                entries[t.begin + t.count++] = sk::SynthEntry{(uint32_t)(off + c), (uint32_t)d.block_type[c] | ((uint32_t)d.mixed_block_flag[c] << 2) |
+                entries[t.begin + t.count++] = sk::SynthEntry{(uint32_t)((rows ? rows[i] : off) + c), (uint32_t)d.block_type[c] | ((uint32_t)d.mixed_block_flag[c] << 2) |
                                                                                        ((uint32_t)(d.channels - 1) << 3) | (c << 4)};
             }
         off += d.channels;
@@ -2177,6 +2187,32 @@ int sk_mp3_set_band_tables(sk_engine *e, uint32_t sample_rate, const uint16_t *l
 
 namespace {
 
+// what the kernel gets of one granule, and the host's verdict on it (a rejected granule: slot 0xff, the kernel writes silence)
+int32_t mp3_requant_record(const sk_engine *e, const sk_mp3_requant_granule &g, uint32_t off, sk::Mp3RequantRecord &r) {
+    std::memset(&r, 0, sizeof r);
+    r.off = off;
+    r.channels = g.channels;
+    const int slot = mp3_rate_slot(g.sample_rate);
+    const bool joint = g.channels == 2 && (g.ms_stereo || g.intensity_stereo);
+    int32_t st = SK_OK;
+    if (slot < 0 || !e->mp3_bands_set[slot]) st = SK_MP3_UNSUPPORTED;  // no band table for this rate: sk_mp3_set_band_tables first
+    for (uint32_t c = 0; c < g.channels && st == SK_OK; ++c) {
+        const sk_mp3_requant_channel &ch = g.ch[c];
+        if (ch.block_type > 3 || ch.mixed_block_flag > 1 || ch.scalefac_scale > 1 || ch.preflag > 1 || (ch.mixed_block_flag && ch.block_type != 2))
+            st = SK_MP3_INVALID;
+        else if (ch.mixed_block_flag && e->mp3_bands[slot][37] == 0xffff) st = SK_MP3_UNSUPPORTED;
+    }
+    if (st == SK_OK && joint) {
+        // the stereo step pairs line i of one channel with line i of the other: both must be cut up the same way
+        if ((g.ch[0].block_type == 2) != (g.ch[1].block_type == 2) || g.ch[0].mixed_block_flag != g.ch[1].mixed_block_flag) st = SK_MP3_INVALID;
+    }
+    r.slot = st == SK_OK ? (uint8_t)slot : 0xff;
+    r.flags = joint ? (uint8_t)((g.ms_stereo ? 1 : 0) | (g.intensity_stereo ? 2 : 0) | (g.lsf ? 4 : 0) | ((g.intensity_stereo & 2) ? 8 : 0)) : 0;
+    r.ch[0] = g.ch[0];
+    if (g.channels == 2) r.ch[1] = g.ch[1];
+    return st;
+}
+
 // e->mu held, device selected: records + integers up, the kernel; the lines stay on the device in e->out_buf.  pcm_bytes: room
 // the caller wants in e->in_buf afterwards (the kernel is done with it by then in stream order) -- reserved HERE, before
 // anything is enqueued, because DevBuf::reserve frees what it replaces.
@@ -2187,31 +2223,9 @@ int mp3_requantize_locked(sk_engine *e, const sk_mp3_requant_granule *granules, 
     std::vector<sk::Mp3RequantRecord> records(n);
     uint64_t off = 0;
     for (uint32_t i = 0; i < n; ++i) {
-        const sk_mp3_requant_granule &g = granules[i];
-        sk::Mp3RequantRecord &r = records[i];
-        std::memset(&r, 0, sizeof r);
-        r.off = (uint32_t)off;
-        r.channels = g.channels;
-        off += g.channels;
-        const int slot = mp3_rate_slot(g.sample_rate);
-        const bool joint = g.channels == 2 && (g.ms_stereo || g.intensity_stereo);
-        int32_t st = SK_OK;
-        if (slot < 0 || !e->mp3_bands_set[slot]) st = SK_MP3_UNSUPPORTED;  // no band table for this rate: sk_mp3_set_band_tables first
-        for (uint32_t c = 0; c < g.channels && st == SK_OK; ++c) {
-            const sk_mp3_requant_channel &ch = g.ch[c];
-            if (ch.block_type > 3 || ch.mixed_block_flag > 1 || ch.scalefac_scale > 1 || ch.preflag > 1 || (ch.mixed_block_flag && ch.block_type != 2))
-                st = SK_MP3_INVALID;
-            else if (ch.mixed_block_flag && e->mp3_bands[slot][37] == 0xffff) st = SK_MP3_UNSUPPORTED;
-        }
-        if (st == SK_OK && joint) {
-            // the stereo step pairs line i of one channel with line i of the other: both must be cut up the same way
-            if ((g.ch[0].block_type == 2) != (g.ch[1].block_type == 2) || g.ch[0].mixed_block_flag != g.ch[1].mixed_block_flag) st = SK_MP3_INVALID;
-        }
+        const int32_t st = mp3_requant_record(e, granules[i], (uint32_t)off, records[i]);
+        off += granules[i].channels;
         if (status) status[i] = st;
-        r.slot = st == SK_OK ? (uint8_t)slot : 0xff;
-        r.flags = joint ? (uint8_t)((g.ms_stereo ? 1 : 0) | (g.intensity_stereo ? 2 : 0) | (g.lsf ? 4 : 0) | ((g.intensity_stereo & 2) ? 8 : 0)) : 0;
-        r.ch[0] = g.ch[0];
-        if (g.channels == 2) r.ch[1] = g.ch[1];
     }
     if (off * 576 > 0xffffffffull) return SK_ERR_INVALID_ARG;
     const size_t lines = (size_t)off * 576, rec_bytes = (size_t)n * sizeof(sk::Mp3RequantRecord);
@@ -2267,6 +2281,361 @@ int mp3_decode_granules(sk_engine *e, const sk_mp3_requant_granule *granules, co
 }
 
 }  // namespace
+
+// ---- Layer III parts 2 + 3 on the device (mp3_entropy.hip) -------------------------------------------------------------------
+
+namespace {
+
+// Lanes of a wave that carry a granule-channel: 64 >> shift.  A wave runs the union of its lanes' paths and until its slowest
+// lane is done; fewer items per wave means more waves to hide the table and bitstream latencies behind (the same trade as
+// EntropyArgs::lane_shift).  SK_MP3_ENTROPY_LANE_SHIFT=0..3 overrides the default for measurements (profiles/r05_mp3_entropy.md).
+uint32_t mp3_entropy_lane_shift() {
+    static const uint32_t shift = [] {
+        const char *s = std::getenv("SK_MP3_ENTROPY_LANE_SHIFT");
+        const int v = s ? std::atoi(s) : 0;
+        return (uint32_t)(v < 0 ? 0 : (v > 3 ? 3 : v));
+    }();
+    return shift;
+}
+
+// INVALID_ARG for a frame list the kernel must not see; *rows = 576-line rows of all frames together
+int mp3_check_frames(const sk_mp3_frame_item *frames, uint32_t n, size_t main_len, uint64_t *rows) {
+    if (main_len > 0xffffffffull - 16) return SK_ERR_INVALID_ARG;
+    uint64_t r = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_mp3_frame_item &f = frames[i];
+        if (f.side.granules < 1 || f.side.granules > 2 || f.side.channels < 1 || f.side.channels > 2) return SK_ERR_INVALID_ARG;
+        // (a 13818-3 scalefac_compress has 9 bits: beyond that the scale-factor lengths it stands for exceed a word)
+        if (f.header.version != 1)
+            for (int c = 0; c < f.side.channels; ++c)
+                if (f.side.gr[0][c].scalefac_compress > 511) return SK_ERR_INVALID_ARG;
+        if ((f.byte_offset & 3u) || f.byte_len > (1u << 20) || (uint64_t)f.byte_offset + f.byte_len + 8 > main_len) return SK_ERR_INVALID_ARG;
+        r += (uint64_t)f.side.granules * f.side.channels;
+    }
+    if (r * 576 > 0xffffffffull || (uint64_t)n * 4 > 0xffffffffull) return SK_ERR_INVALID_ARG;
+    *rows = r;
+    return SK_OK;
+}
+
+struct Mp3EntropyOut {  // where a launch left its results (e->mp3e_out)
+    sk::Mp3EntropyCell *cells = nullptr;
+    int32_t *status = nullptr;  // [n_frames * 4]
+};
+
+// e->mu held, device selected, frames checked.  Frame i's integers go to d_is + (first_row[i] + granule * channels + channel) * 576;
+// with d_records its scale factors go to record first_record[i] + granule.  Returns with the kernel queued.
+// bytes == nullptr: the main data of the engine's previous launch is still in place (same main_len), only the frame list differs.
+int mp3_entropy_launch(sk_engine *e, const sk_mp3_frame_item *frames, uint32_t n, const uint8_t *bytes, size_t main_len, int16_t *d_is,
+                       const uint32_t *first_row, sk::Mp3RequantRecord *d_records, const uint32_t *first_record, Mp3EntropyOut *out) {
+    if (!e->d_mp3_cb) return SK_ERR_UNSUPPORTED;  // no code book on this engine: sk_mp3_set_codebook first
+    std::vector<sk::Mp3EntropyItem> items;
+    items.reserve((size_t)n * 4);
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_mp3_side_info &side = frames[i].side;
+        for (uint32_t gr = 0; gr < side.granules; ++gr)
+            for (uint32_t ch = 0; ch < side.channels; ++ch)
+                items.push_back(sk::Mp3EntropyItem{i, first_row[i] + gr * side.channels + ch, d_records ? first_record[i] + gr : 0xffffffffu, (uint8_t)gr, (uint8_t)ch, {0, 0}});
+    }
+    // a wave's lanes should have about the same number of codes to read: longest granule-channels first
+    std::stable_sort(items.begin(), items.end(), [&](const sk::Mp3EntropyItem &a, const sk::Mp3EntropyItem &b) {
+        return frames[a.frame].side.gr[a.gr][a.ch].part2_3_length > frames[b.frame].side.gr[b.gr][b.ch].part2_3_length;
+    });
+    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t frames_bytes = (size_t)n * sizeof(sk_mp3_frame_item), items_bytes = items.size() * sizeof(sk::Mp3EntropyItem);
+    // main data | frames | items: the main data first, so that a second launch over fewer frames finds it where it was
+    const size_t bytes_at = 0, frames_at = up256(main_len + 16), items_at = frames_at + up256(frames_bytes);
+    const size_t cells_bytes = (size_t)n * 4 * sizeof(sk::Mp3EntropyCell), status_at = up256(cells_bytes);
+    if (!bytes && e->mp3e_in.cap < items_at + items_bytes) return SK_ERR_INTERNAL;  // (a first launch over more frames made the room)
+    SK_HIP(e->mp3e_in.reserve(items_at + items_bytes + 16), "alloc mp3 entropy input");
+    SK_HIP(e->mp3e_out.reserve(status_at + (size_t)n * 4 * sizeof(int32_t)), "alloc mp3 entropy output");
+    uint8_t *d_in = (uint8_t *)e->mp3e_in.p, *d_out = (uint8_t *)e->mp3e_out.p;
+    SK_HIP(hipMemcpyAsync(d_in + frames_at, frames, frames_bytes, hipMemcpyHostToDevice, e->stream), "H2D mp3 frames");
+    SK_HIP(hipMemcpyAsync(d_in + items_at, items.data(), items_bytes, hipMemcpyHostToDevice, e->stream), "H2D mp3 entropy items");
+    if (bytes) SK_HIP(hipMemcpyAsync(d_in + bytes_at, bytes, main_len, hipMemcpyHostToDevice, e->stream), "H2D mp3 main data");
+    SK_HIP(hipMemsetAsync(d_out, 0, status_at + (size_t)n * 4 * sizeof(int32_t), e->stream), "clear mp3 entropy cells");
+    SK_HIP(hipStreamSynchronize(e->stream), "mp3 entropy upload");  // the items go out of scope
+    sk::Mp3EntropyArgs a{};
+    a.blob = e->d_mp3_cb;
+    a.lds_words = ((const sk::Mp3CodebookHeader *)e->mp3_cb_host.data())->lds_words;
+    a.frames = (const sk_mp3_frame_item *)(d_in + frames_at);
+    a.bytes = d_in + bytes_at;
+    a.items = (const sk::Mp3EntropyItem *)(d_in + items_at);
+    a.n_items = (uint32_t)items.size();
+    a.lane_shift = mp3_entropy_lane_shift();
+    a.is = d_is;
+    a.records = d_records;
+    a.cells = (sk::Mp3EntropyCell *)d_out;
+    a.status = (int32_t *)(d_out + status_at);
+    SK_HIP(sk::launch_mp3_entropy(a, e->stream), "launch mp3 entropy");
+    out->cells = a.cells;
+    out->status = a.status;
+    return SK_OK;
+}
+
+int mp3_decode_frames(sk_engine *e, const sk_mp3_frame_item *frames, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t main_len,
+                      void *pcm_out, size_t out_cap, int32_t *entropy_status, int32_t *stage_status, size_t *written, bool s16) {
+    if (!e || !written || (n && (!frames || !streams || !bytes || !entropy_status)) || (out_cap && !pcm_out)) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    if (n == 0) return SK_OK;
+    uint64_t rows = 0;
+    int rc = mp3_check_frames(frames, n, main_len, &rows);
+    if (rc != SK_OK) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (frames[i].header.channels != frames[i].side.channels || frames[i].header.granules != frames[i].side.granules) return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e, ComputeTurn{});
+    rc = ensure_mp3(e);
+    if (rc == SK_OK) rc = ensure_mp3_requant(e);
+    if (rc != SK_OK) return rc;
+    if (!e->mp3_window_set) return SK_ERR_UNSUPPORTED;  // no synthesis window: sk_mp3_set_synthesis_window first
+    if (!e->d_mp3_cb) return SK_ERR_UNSUPPORTED;        // no code book: sk_mp3_set_codebook first
+
+    // every frame's granules as the host path would queue them -- the fields that come out of the side information; the
+    // scale factors and preflag are the kernel's to fill in
+    std::vector<sk::Mp3RequantRecord> records;
+    std::vector<sk_mp3_granule_desc> descs;
+    std::vector<int32_t> requant_status;
+    std::vector<uint32_t> first_row(n), first_record(n);
+    uint32_t row = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_mp3_frame_info &h = frames[i].header;
+        const sk_mp3_side_info &side = frames[i].side;
+        const bool joint = h.mode == 1;
+        first_row[i] = row;
+        first_record[i] = (uint32_t)records.size();
+        for (int gr = 0; gr < side.granules; ++gr) {
+            sk_mp3_requant_granule g;
+            std::memset(&g, 0, sizeof g);
+            g.sample_rate = h.sample_rate;
+            g.channels = side.channels;
+            g.ms_stereo = joint && (h.mode_ext & 2);
+            g.intensity_stereo = joint && (h.mode_ext & 1);
+            g.lsf = h.version != 1;
+            // sk_mp3_granule_data::intensity_scale of the right channel: scalefac_compress & 1 (13818-3 2.4.3.2)
+            if (g.lsf && g.intensity_stereo && side.channels == 2 && (side.gr[gr][1].scalefac_compress & 1)) g.intensity_stereo |= 2;
+            sk_mp3_granule_desc desc;
+            std::memset(&desc, 0, sizeof desc);
+            desc.stream = streams[i];
+            desc.channels = side.channels;
+            for (int ch = 0; ch < side.channels; ++ch) {
+                const sk_mp3_granule_side &s = side.gr[gr][ch];
+                sk_mp3_requant_channel &c = g.ch[ch];
+                c.global_gain = s.global_gain, c.scalefac_scale = s.scalefac_scale, c.preflag = g.lsf ? 0 : s.preflag;
+                c.block_type = s.block_type, c.mixed_block_flag = s.mixed_block_flag;
+                std::memcpy(c.subblock_gain, s.subblock_gain, 3);
+                desc.block_type[ch] = s.block_type, desc.mixed_block_flag[ch] = s.mixed_block_flag;
+            }
+            sk::Mp3RequantRecord r;
+            requant_status.push_back(mp3_requant_record(e, g, row, r));
+            records.push_back(r);
+            descs.push_back(desc);
+            row += side.channels;
+        }
+    }
+    const uint32_t n_granules = (uint32_t)records.size();
+    const size_t width = s16 ? sizeof(int16_t) : sizeof(float);
+    const size_t rec_bytes = (size_t)n_granules * sizeof(sk::Mp3RequantRecord), is_at = (rec_bytes + 255) & ~(size_t)255;
+    const size_t lines = (size_t)rows * 576;
+    // e->in_buf: records | integers, and once the requantisation has read them, the PCM (in stream order); e->out_buf: the lines
+    SK_HIP(e->in_buf.reserve(std::max(is_at + lines * sizeof(int16_t), lines * width) + 16), "alloc mp3 frames input");
+    SK_HIP(e->out_buf.reserve(lines * sizeof(float) + 16), "alloc mp3 frames lines");
+    uint8_t *d_in = (uint8_t *)e->in_buf.p;
+    SK_HIP(hipMemcpyAsync(d_in, records.data(), rec_bytes, hipMemcpyHostToDevice, e->stream), "H2D mp3 granule records");
+    Mp3EntropyOut eo;
+    rc = mp3_entropy_launch(e, frames, n, bytes, main_len, (int16_t *)(d_in + is_at), first_row.data(), (sk::Mp3RequantRecord *)d_in, first_record.data(), &eo);
+    if (rc != SK_OK) return rc;
+    std::vector<int32_t> cell_status((size_t)n * 4);
+    SK_HIP(hipMemcpyAsync(cell_status.data(), eo.status, cell_status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H mp3 entropy statuses");
+    SK_HIP(hipStreamSynchronize(e->stream), "mp3 entropy sync");  // the one synchronisation the host stage does not need
+
+    // a frame any of whose granule-channels failed is dropped: no samples, no synthesis, its stream's state untouched
+    std::vector<sk_mp3_granule_desc> kept_descs;
+    std::vector<uint32_t> kept_rows, kept_granule;
+    size_t samples = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_mp3_side_info &side = frames[i].side;
+        int32_t worst = SK_OK;
+        for (int gr = 0; gr < side.granules; ++gr)
+            for (int ch = 0; ch < side.channels; ++ch)
+                if (worst == SK_OK) worst = cell_status[(size_t)i * 4 + gr * 2 + ch];
+        entropy_status[i] = worst;
+        if (stage_status) stage_status[i] = SK_OK;
+        if (worst != SK_OK) continue;
+        for (int gr = 0; gr < side.granules; ++gr) {
+            kept_descs.push_back(descs[first_record[i] + gr]);
+            kept_rows.push_back(first_row[i] + (uint32_t)gr * side.channels);
+            kept_granule.push_back(first_record[i] + gr);
+        }
+        samples += (size_t)side.granules * side.channels * 576;
+    }
+    if (samples > out_cap) return SK_ERR_CAPACITY;
+    if (kept_descs.empty()) return SK_OK;
+
+    sk::Mp3RequantArgs a{};
+    a.records = (const sk::Mp3RequantRecord *)d_in;
+    a.is = (const int16_t *)(d_in + is_at);
+    a.xr = (float *)e->out_buf.p;
+    a.n = n_granules;
+    a.pow43 = (const float *)e->d_mp3_rq;
+    a.root4 = a.pow43 + sk::kMp3Pow43;
+    a.is_k = a.root4 + 4;
+    a.bands = (const uint16_t *)(e->d_mp3_rq + kRqBandsAt);
+    a.pretab = e->d_mp3_rq + kRqPretabAt;
+    a.line_map = (const uint32_t *)(e->d_mp3_rq + kRqMapAt);
+    SK_HIP(sk::launch_mp3_requant(a, e->stream), "launch mp3 requantisation");
+    SK_HIP(hipMemsetAsync(e->in_buf.p, 0, lines * width, e->stream), "clear mp3 output");  // granules the synthesis rejects stay silent
+    std::vector<int32_t> synth_status(kept_descs.size(), 0);
+    rc = mp3_synthesize_locked(e, kept_descs.data(), (const float *)e->out_buf.p, e->in_buf.p, (uint32_t)kept_descs.size(), synth_status.data(), s16, true,
+                               kept_rows.data());
+    if (rc != SK_OK) return rc;
+    // the surviving frames' PCM sits at their rows: runs of neighbours leave in one copy each
+    size_t out_at = 0;
+    for (uint32_t i = 0; i < n;) {
+        if (entropy_status[i] != SK_OK) {
+            ++i;
+            continue;
+        }
+        uint32_t j = i;
+        size_t run = 0;
+        while (j < n && entropy_status[j] == SK_OK) run += (size_t)frames[j].side.granules * frames[j].side.channels * 576, ++j;
+        SK_HIP(hipMemcpyAsync((uint8_t *)pcm_out + out_at * width, d_in + (size_t)first_row[i] * 576 * width, run * width, hipMemcpyDeviceToHost, e->stream), "D2H mp3 pcm");
+        out_at += run;
+        i = j;
+    }
+    SK_HIP(hipStreamSynchronize(e->stream), "mp3 frames sync");
+    if (stage_status) {
+        size_t k = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (entropy_status[i] != SK_OK) continue;
+            for (int gr = 0; gr < frames[i].side.granules; ++gr, ++k) {
+                const int32_t st = synth_status[k] != SK_OK ? synth_status[k] : requant_status[kept_granule[k]];
+                if (stage_status[i] == SK_OK) stage_status[i] = st;
+            }
+        }
+    }
+    *written = samples;
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C++" {
+namespace sk {
+
+// The engine's device code book := this blob (sk_mp3_codebook_flatten).  Nothing is uploaded when the engine holds it already,
+// so that a decoder handle or a scheduler lane may call this before every batch.
+int mp3_install_codebook(sk_engine *e, const uint32_t *words, size_t n_words) {
+    if (!e || !words || n_words < sizeof(Mp3CodebookHeader) / 4) return SK_ERR_INVALID_ARG;
+    const Mp3CodebookHeader &h = *(const Mp3CodebookHeader *)words;
+    if (h.words != n_words || h.lds_words > n_words || h.lds_words < sizeof(Mp3CodebookHeader) / 4 || (h.lds_words & 3u) ||
+        h.lds_words > sizeof(Mp3CodebookHeader) / 4 + (34u << kMp3L1Bits))
+        return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    if (e->d_mp3_cb && e->mp3_cb_host.size() == n_words && std::memcmp(e->mp3_cb_host.data(), words, n_words * sizeof(uint32_t)) == 0) return SK_OK;
+    DeviceGuard guard(e);
+    SK_HIP(hipStreamSynchronize(e->stream), "mp3 code book: wait for the kernels that read the old one");
+    uint32_t *fresh = nullptr;
+    SK_HIP(hipMalloc((void **)&fresh, n_words * sizeof(uint32_t) + 16), "alloc mp3 code book");
+    const hipError_t he = hipMemcpy(fresh, words, n_words * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+        (void)hipFree(fresh);
+        return e->hip_fail(he, "upload mp3 code book");
+    }
+    if (e->d_mp3_cb) (void)hipFree(e->d_mp3_cb);
+    e->d_mp3_cb = fresh;
+    e->mp3_cb_host.assign(words, words + n_words);
+    return SK_OK;
+}
+
+}  // namespace sk
+}  // extern "C++"
+
+extern "C" {
+
+int sk_mp3_set_codebook(sk_engine *e, const sk_mp3_codebook *cb) try {
+    sk::abi_enter();
+    if (!e) return SK_ERR_INVALID_ARG;
+    sk_mp3_codebook *own = nullptr;
+    if (!cb) {
+        const int rc = sk_mp3_codebook_create_iso(&own);
+        if (rc != SK_OK) return rc;
+        cb = own;
+    }
+    struct Guard {
+        sk_mp3_codebook *p;
+        ~Guard() { sk_mp3_codebook_destroy(p); }
+    } guard{own};
+    size_t words = 0;
+    int rc = sk_mp3_codebook_flatten(cb, nullptr, 0, &words);
+    if (rc != SK_OK && rc != SK_ERR_CAPACITY) return rc;
+    std::vector<uint32_t> blob(words);
+    rc = sk_mp3_codebook_flatten(cb, blob.data(), blob.size(), &words);
+    if (rc != SK_OK) return rc;
+    return sk::mp3_install_codebook(e, blob.data(), blob.size());
+} catch (...) {
+    return sk::abi_caught("sk_mp3_set_codebook");
+}
+
+int sk_mp3_entropy_decode(sk_engine *e, const sk_mp3_frame_item *frames, uint32_t n, const uint8_t *bytes, size_t main_len, sk_mp3_granule_data *out) try {
+    sk::abi_enter();
+    if (!e || (n && (!frames || !bytes || !out))) return SK_ERR_INVALID_ARG;
+    if (n == 0) return SK_OK;
+    uint64_t rows = 0;
+    int rc = mp3_check_frames(frames, n, main_len, &rows);
+    if (rc != SK_OK) return rc;
+    std::vector<uint32_t> first_row(n);
+    uint32_t row = 0;
+    for (uint32_t i = 0; i < n; ++i) first_row[i] = row, row += (uint32_t)frames[i].side.granules * frames[i].side.channels;
+    std::vector<int16_t> is((size_t)rows * 576);
+    std::vector<sk::Mp3EntropyCell> cells((size_t)n * 4);
+    {
+        std::lock_guard<std::mutex> lock(e->mu);
+        DeviceGuard guard(e, ComputeTurn{});
+        SK_HIP(e->in_buf.reserve(is.size() * sizeof(int16_t) + 16), "alloc mp3 entropy integers");
+        Mp3EntropyOut eo;
+        rc = mp3_entropy_launch(e, frames, n, bytes, main_len, (int16_t *)e->in_buf.p, first_row.data(), nullptr, nullptr, &eo);
+        if (rc != SK_OK) return rc;
+        SK_HIP(hipMemcpyAsync(is.data(), e->in_buf.p, is.size() * sizeof(int16_t), hipMemcpyDeviceToHost, e->stream), "D2H mp3 integers");
+        SK_HIP(hipMemcpyAsync(cells.data(), eo.cells, cells.size() * sizeof(sk::Mp3EntropyCell), hipMemcpyDeviceToHost, e->stream), "D2H mp3 entropy cells");
+        SK_HIP(hipStreamSynchronize(e->stream), "mp3 entropy sync");
+    }
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_mp3_side_info &side = frames[i].side;
+        for (uint32_t gr = 0; gr < side.granules; ++gr)
+            for (uint32_t ch = 0; ch < side.channels; ++ch) {
+                const sk::Mp3EntropyCell &c = cells[(size_t)i * 4 + gr * 2 + ch];
+                sk_mp3_granule_data &g = out[(size_t)i * 4 + gr * 2 + ch];
+                std::memset(&g, 0, sizeof g);
+                std::memcpy(g.is, is.data() + ((size_t)first_row[i] + gr * side.channels + ch) * 576, sizeof g.is);
+                std::memcpy(g.scalefac_l, c.scalefac_l, sizeof g.scalefac_l);
+                std::memcpy(g.scalefac_s, c.scalefac_s, sizeof g.scalefac_s);
+                g.preflag = c.preflag, g.intensity_scale = c.intensity_scale;
+                g.part2_bits = c.part2_bits, g.nonzero_lines = c.nonzero_lines, g.part3_bits = c.part3_bits;
+                g.status = c.status;
+            }
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp3_entropy_decode");
+}
+
+int sk_mp3_decode_frames_f32(sk_engine *e, const sk_mp3_frame_item *frames, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t main_len,
+                             float *pcm_out, size_t out_cap, int32_t *entropy_status, int32_t *stage_status, size_t *written) try {
+    sk::abi_enter();
+    return mp3_decode_frames(e, frames, streams, n, bytes, main_len, pcm_out, out_cap, entropy_status, stage_status, written, false);
+} catch (...) {
+    return sk::abi_caught("sk_mp3_decode_frames_f32");
+}
+
+int sk_mp3_decode_frames_s16(sk_engine *e, const sk_mp3_frame_item *frames, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t main_len,
+                             int16_t *pcm_out, size_t out_cap, int32_t *entropy_status, int32_t *stage_status, size_t *written) try {
+    sk::abi_enter();
+    return mp3_decode_frames(e, frames, streams, n, bytes, main_len, pcm_out, out_cap, entropy_status, stage_status, written, true);
+} catch (...) {
+    return sk::abi_caught("sk_mp3_decode_frames_s16");
+}
+
+}  // extern "C"
 
 int sk_mp3_requantize(sk_engine *e, const sk_mp3_requant_granule *granules, const int16_t *is, float *xr, uint32_t n, int32_t *status) try {
     sk::abi_enter();
@@ -2794,11 +3163,19 @@ struct TickCall {           // one sk_tick_stream
     uint32_t ulen = 1024;   // PCM frames per unit: 1024 (AAC access unit) or 576 (MP3 granule); a unit's channel rows are 1024 floats apart
 };
 
+struct TickMp3Frames {  // sk_tick_run_mixed_md: the granules' integers and scale factors are still Huffman codes -- the frames that
+                        // survived the first pass (tick_impl_md), whose main data is on the device already (e->mp3e_in)
+    const sk_mp3_frame_item *frames = nullptr;
+    uint32_t n = 0;
+    size_t main_len = 0;
+    const uint32_t *first_row = nullptr, *first_record = nullptr;  // per frame: its first 576-line row / granule among the tick's
+};
 struct TickMp3 {  // the MP3 part of sk_tick_input
     const sk_mp3_requant_granule *granules = nullptr;
     const sk_mp3_granule_desc *descs = nullptr;
     const int16_t *is = nullptr;
     uint32_t n = 0;
+    const TickMp3Frames *md = nullptr;  // instead of `is` (and of the granules' scale factors and preflag)
 };
 
 }  // namespace
@@ -3030,9 +3407,16 @@ int tick_mp3_queue(sk_engine *e, const TickMp3 &mp3, float *pcm_rows, AuxArena &
     const size_t lines = (size_t)off * 576;
     SK_HIP(e->tick_mp3_in.reserve(lines * sizeof(int16_t) + 16), "alloc tick mp3 quantised lines");
     SK_HIP(e->tick_mp3_xr.reserve(lines * sizeof(float) + 16), "alloc tick mp3 lines");
-    SK_HIP(hipMemcpyAsync(e->tick_mp3_in.p, mp3.is, lines * sizeof(int16_t), hipMemcpyHostToDevice, e->stream), "H2D tick mp3 quantised lines");
     sk::Mp3RequantArgs q{};
     SK_HIP(aux.put(records, e->stream, &q.records), "upload tick mp3 granule records");
+    if (mp3.md) {  // the Huffman stage writes the integers where the host's would have been copied to, and the scale factors into the records
+        Mp3EntropyOut eo;
+        rc = mp3_entropy_launch(e, mp3.md->frames, mp3.md->n, nullptr, mp3.md->main_len, (int16_t *)e->tick_mp3_in.p, mp3.md->first_row,
+                                const_cast<sk::Mp3RequantRecord *>(q.records), mp3.md->first_record, &eo);
+        if (rc != SK_OK) return rc;
+    } else {
+        SK_HIP(hipMemcpyAsync(e->tick_mp3_in.p, mp3.is, lines * sizeof(int16_t), hipMemcpyHostToDevice, e->stream), "H2D tick mp3 quantised lines");
+    }
     q.is = (const int16_t *)e->tick_mp3_in.p;
     q.xr = (float *)e->tick_mp3_xr.p;
     q.n = n;
@@ -3072,7 +3456,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
     if (!au_mode && !q_mode && n_frames && (!descs || !coeffs)) return SK_ERR_INVALID_ARG;
     if (q_mode && n_frames && (!descs || !q_quant)) return SK_ERR_INVALID_ARG;
     if (au_mode && n_frames && !au_bytes) return SK_ERR_INVALID_ARG;
-    if (mp3.n && (!mp3.granules || !mp3.descs || !mp3.is)) return SK_ERR_INVALID_ARG;
+    if (mp3.n && (!mp3.granules || !mp3.descs || (!mp3.is && !mp3.md))) return SK_ERR_INVALID_ARG;
     *n_outs = 0;
     if (out_bytes) *out_bytes = 0;
     if (n_streams == 0) return n_frames == 0 && mp3.n == 0 ? SK_OK : SK_ERR_INVALID_ARG;
@@ -3608,12 +3992,26 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
 // The tick proper (tick_body) under the engine's lock, with the host-side state it advances -- the streaming resamplers'
 // fill, chunk count and time index -- put back when it fails part-way: a failed launch leaves the batch's streams to be
 // ended by the caller, and the engine's bookkeeping must not have run ahead of what the device did.
+int tick_impl_locked(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_aac_frame_desc *descs, const float *coeffs,
+                     const sk_au_item *units, const uint8_t *au_bytes, size_t au_len, uint32_t n_frames, uint8_t *out, size_t out_cap,
+                     sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes, const EntropyProbe *probe,
+                     const uint8_t *q_sides, const int16_t *q_quant, const TickMp3 &mp3);
+
 int tick_impl(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_aac_frame_desc *descs, const float *coeffs,
               const sk_au_item *units, const uint8_t *au_bytes, size_t au_len, uint32_t n_frames, uint8_t *out, size_t out_cap,
               sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes, const EntropyProbe *probe = nullptr,
               const uint8_t *q_sides = nullptr, const int16_t *q_quant = nullptr, const TickMp3 &mp3 = TickMp3{}) {
     if (!e) return SK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(e->mu);
+    return tick_impl_locked(e, ts, n_streams, descs, coeffs, units, au_bytes, au_len, n_frames, out, out_cap, outs, outs_cap, n_outs, out_bytes, probe,
+                            q_sides, q_quant, mp3);
+}
+
+// e->mu held
+int tick_impl_locked(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_aac_frame_desc *descs, const float *coeffs,
+                     const sk_au_item *units, const uint8_t *au_bytes, size_t au_len, uint32_t n_frames, uint8_t *out, size_t out_cap,
+                     sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes, const EntropyProbe *probe,
+                     const uint8_t *q_sides, const int16_t *q_quant, const TickMp3 &mp3) {
     TickWhere where(e);
     struct Saved {
         uint32_t id, fill;
@@ -3641,6 +4039,108 @@ int tick_impl(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
         if (rc != SK_ERR_TIMEOUT) (void)hipStreamSynchronize(e->stream);
     }
     return rc;
+}
+
+
+// sk_tick_run_mixed_md: the MP3 streams' units arrive as frames with main data (ts[i].n_frames = frames of stream i).  A first
+// pass of k_mp3_entropy gives every frame's verdict (one synchronisation: a dropped frame changes its stream's unit count, which the
+// tick's plan is made from); the frames that decode become the tick's granules, and the tick runs the stage a second time over them,
+// straight into its integer rows and granule records (0.35 ms per 131 072 granule-channels each time, the main data uploaded once).
+int tick_impl_md(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md, uint8_t *out,
+                 size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) {
+    if (!e || !in || !md || !n_outs || (n_streams && !ts) || (md->n_frames && (!md->frames || !md->main_bytes))) return SK_ERR_INVALID_ARG;
+    if (in->n_mp3_granules || in->mp3_granules || in->mp3_is) return SK_ERR_INVALID_ARG;  // the MP3 units in ONE form
+    const uint32_t n = md->n_frames;
+    uint64_t rows_all = 0, listed = 0;
+    int rc = mp3_check_frames(md->frames, n, md->main_len, &rows_all);
+    if (rc != SK_OK) return rc;
+    for (uint32_t i = 0; i < n_streams; ++i)
+        if (ts[i].codec == SK_TICK_MP3) listed += ts[i].n_frames;
+    if (listed != n) return SK_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n; ++i)
+        if (md->frames[i].header.channels != md->frames[i].side.channels || md->frames[i].header.granules != md->frames[i].side.granules) return SK_ERR_INVALID_ARG;
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    std::lock_guard<std::mutex> lock(e->mu);
+    const std::chrono::steady_clock::time_point t_locked = std::chrono::steady_clock::now();
+    std::chrono::steady_clock::time_point t_queued = t_locked;
+    std::vector<int32_t> cell_status((size_t)n * 4);
+    if (n) {
+        DeviceGuard guard(e);
+        std::vector<uint32_t> first_row(n);
+        uint32_t row = 0;
+        for (uint32_t i = 0; i < n; ++i) first_row[i] = row, row += (uint32_t)md->frames[i].side.granules * md->frames[i].side.channels;
+        SK_HIP(e->tick_mp3_in.reserve((size_t)rows_all * 576 * sizeof(int16_t) + 16), "alloc tick mp3 quantised lines");
+        Mp3EntropyOut eo;
+        rc = mp3_entropy_launch(e, md->frames, n, md->main_bytes, md->main_len, (int16_t *)e->tick_mp3_in.p, first_row.data(), nullptr, nullptr, &eo);
+        if (rc != SK_OK) return rc;
+        t_queued = std::chrono::steady_clock::now();
+        SK_HIP(hipMemcpyAsync(cell_status.data(), eo.status, cell_status.size() * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H tick mp3 entropy statuses");
+        SK_HIP(hipStreamSynchronize(e->stream), "tick mp3 entropy sync");
+    }
+    const std::chrono::steady_clock::time_point t_verdicts = std::chrono::steady_clock::now();
+    // the frames that decode, as the granules sk_tick_run_mixed takes (what comes from the side information; the stage fills in the rest)
+    std::vector<sk_tick_stream> kept_ts(ts, ts + n_streams);
+    std::vector<sk_mp3_frame_item> kept;
+    std::vector<uint32_t> first_row, first_record;
+    std::vector<sk_mp3_requant_granule> granules;
+    std::vector<sk_mp3_granule_desc> descs;
+    uint32_t at = 0, row = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        if (ts[i].codec != SK_TICK_MP3) continue;
+        uint32_t units = 0;
+        for (uint32_t k = 0; k < ts[i].n_frames; ++k, ++at) {
+            const sk_mp3_frame_item &f = md->frames[at];
+            bool ok = true;
+            for (int gr = 0; gr < f.side.granules; ++gr)
+                for (int ch = 0; ch < f.side.channels; ++ch) ok = ok && cell_status[(size_t)at * 4 + gr * 2 + ch] == SK_OK;
+            if (!ok) continue;  // dropped as the host path drops it: no unit, no output record, the stream goes on
+            kept.push_back(f);
+            first_row.push_back(row);
+            first_record.push_back((uint32_t)granules.size());
+            const bool joint = f.header.mode == 1;
+            for (int gr = 0; gr < f.side.granules; ++gr) {
+                sk_mp3_requant_granule g;
+                std::memset(&g, 0, sizeof g);
+                g.sample_rate = f.header.sample_rate;
+                g.channels = f.side.channels;
+                g.ms_stereo = joint && (f.header.mode_ext & 2);
+                g.intensity_stereo = joint && (f.header.mode_ext & 1);
+                g.lsf = f.header.version != 1;
+                if (g.lsf && g.intensity_stereo && f.side.channels == 2 && (f.side.gr[gr][1].scalefac_compress & 1)) g.intensity_stereo |= 2;
+                sk_mp3_granule_desc d;
+                std::memset(&d, 0, sizeof d);
+                d.stream = ts[i].stream;
+                d.channels = f.side.channels;
+                for (int ch = 0; ch < f.side.channels; ++ch) {
+                    const sk_mp3_granule_side &gs = f.side.gr[gr][ch];
+                    sk_mp3_requant_channel &c = g.ch[ch];
+                    c.global_gain = gs.global_gain, c.scalefac_scale = gs.scalefac_scale, c.preflag = g.lsf ? 0 : gs.preflag;
+                    c.block_type = gs.block_type, c.mixed_block_flag = gs.mixed_block_flag;
+                    std::memcpy(c.subblock_gain, gs.subblock_gain, 3);
+                    d.block_type[ch] = gs.block_type, d.mixed_block_flag[ch] = gs.mixed_block_flag;
+                }
+                granules.push_back(g);
+                descs.push_back(d);
+                row += f.side.channels;
+                units += 1;
+            }
+        }
+        kept_ts[i].n_frames = units;
+    }
+    static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
+    if (trace) {
+        auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+        std::fprintf(stderr, "sk_tick: mp3 huffman stage in the tick: %u frames, %u dropped | lock %.2f  upload+queue %.2f  verdicts %.2f  granules %.2f ms\n", n,
+                     n - (uint32_t)kept.size(), ms(t_begin, t_locked), ms(t_locked, t_queued), ms(t_queued, t_verdicts), ms(t_verdicts, std::chrono::steady_clock::now()));
+    }
+    TickMp3Frames frames_form;
+    frames_form.frames = kept.data(), frames_form.n = (uint32_t)kept.size(), frames_form.main_len = md->main_len;
+    frames_form.first_row = first_row.data(), frames_form.first_record = first_record.data();
+    TickMp3 mp3;
+    mp3.granules = granules.data(), mp3.descs = descs.data(), mp3.n = (uint32_t)granules.size();
+    mp3.md = &frames_form;
+    return tick_impl_locked(e, kept_ts.data(), n_streams, in->descs, in->coeffs, in->units, in->au_bytes, in->au_bytes_len, in->n_aac_units, out, out_cap, outs,
+                            outs_cap, n_outs, out_bytes, nullptr, (const uint8_t *)in->q_sides, in->q_quant, mp3);
 }
 
 }  // namespace
@@ -3683,6 +4183,18 @@ int sk_tick_run_mixed(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams
                      n_outs, out_bytes, nullptr, (const uint8_t *)in->q_sides, in->q_quant, mp3);
 } catch (...) {
     return sk::abi_caught("sk_tick_run_mixed");
+}
+
+int sk_tick_run_mixed_md(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md, uint8_t *out,
+                         size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) try {
+    sk::abi_enter();
+    if (!in) return SK_ERR_INVALID_ARG;
+    const int forms = (in->coeffs ? 1 : 0) + (in->units ? 1 : 0) + (in->q_sides ? 1 : 0);
+    if (forms > 1 || (in->n_aac_units && forms == 0)) return SK_ERR_INVALID_ARG;  // the AAC units in ONE form
+    if (in->q_sides && in->n_aac_units && (!in->q_quant || !in->descs)) return SK_ERR_INVALID_ARG;
+    return tick_impl_md(e, ts, n_streams, in, md, out, out_cap, outs, outs_cap, n_outs, out_bytes);
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_mixed_md");
 }
 
 int sk_aac_entropy_decode(sk_engine *e, const uint32_t *streams, const uint32_t *units_per_stream, uint32_t n_streams,

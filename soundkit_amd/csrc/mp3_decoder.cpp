@@ -6,30 +6,30 @@
 // code tables, the two count1 tables, the scale-factor length and partition tables, Table B.8 -- is NOT in this file: it
 // arrives through sk_mp3_tables in the standard's own presentation (a length and a bit pattern per code) and is turned into
 // binary decoding tries here.  Host code throughout; the arithmetic behind it (requantisation, stereo, reorder, hybrid
-// synthesis) runs on the GPU, one launch each per decode call (mp3_requant.hip, mp3_hybrid.hip).
+// synthesis) runs on the GPU, one launch each per decode call (mp3_requant.hip, mp3_hybrid.hip).  The same stage exists on the
+// device (mp3_entropy.hip, with this file's functions as its specification): sk_mp3_codebook_flatten below makes its code book,
+// and a decoder switched to it (sk_mp3_decoder_set_gpu_entropy) decodes through mp3_decoder_gpu.cpp.
 #include "../../include/soundkit_amd.h"
 #include "sk_abi.h"
 #include "mp3_iso_tables.h"
+#include "mp3_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
 #include <vector>
 
-struct sk_mp3_codebook {
-    struct Trie {
-        std::vector<int32_t> next;  // [node][bit]: > 0 child node, <= 0: -(symbol) - 1 ... 0 = empty
-        uint8_t xlen = 0, linbits = 0;
-        // the next kLutBits bits of the stream -> (length << 16 | symbol + 1) of the code they start with, 0 if that code is longer
-        // (or the bits are no code): one look-up for the short codes, which are the frequent ones; the trie walk for the rest
-        std::vector<uint32_t> lut;
-    };
-    static constexpr int kLutBits = 10;
-    Trie big[32], count1[2];
-    sk_mp3_tables t;  // hlen / hcod pointers inside are not kept (copied into the tries)
-};
+namespace sk_mp3_internal {
+GpuHooks &gpu_hooks() {
+    static GpuHooks hooks;
+    return hooks;
+}
+}  // namespace sk_mp3_internal
 
 namespace {
+
+using namespace sk_mp3_internal;
 
 constexpr int32_t kEmpty = 0;
 inline int32_t leaf(int symbol) { return -symbol - 1; }
@@ -299,6 +299,104 @@ int huffman(const sk_mp3_codebook &cb, const sk_mp3_frame_info &h, const sk_mp3_
     return SK_OK;
 }
 
+// ---- the code book for the device stage (mp3_codebook_blob.h) -------------------------------------------------------------
+
+int trie_height(const sk_mp3_codebook::Trie &t, int32_t node) {  // longest path below `node`, in bits (<= 32: trie_add)
+    int h = 0;
+    for (int bit = 0; bit < 2; ++bit) {
+        const int32_t slot = t.next[(size_t)node * 2 + bit];
+        h = std::max(h, slot > 0 ? 1 + trie_height(t, slot) : (slot < 0 ? 1 : 0));
+    }
+    return h;
+}
+
+// the table of `width` bits that decodes from `node` on, at blob[at .. at + 2^width); deeper tables are appended to the blob
+void flatten_table(const sk_mp3_codebook::Trie &t, int xlen, int32_t node, int width, size_t at, std::vector<uint32_t> &blob) {
+    for (uint32_t v = 0; v < (1u << width); ++v) {
+        int32_t at_node = node;
+        uint32_t entry = 0;
+        for (int depth = 1; depth <= width; ++depth) {
+            const int32_t slot = t.next[(size_t)at_node * 2 + ((v >> (width - depth)) & 1u)];
+            if (slot == kEmpty) break;
+            if (slot < 0) {
+                const int symbol = -slot - 1;
+                const uint32_t xy = xlen ? (uint32_t)(symbol / xlen) << 4 | (uint32_t)(symbol % xlen) : (uint32_t)symbol;
+                entry = 0x8000u | (uint32_t)depth << 16 | xy;
+                break;
+            }
+            at_node = slot;
+            if (depth == width) {
+                // the codes that go on behind these `width` bits: a table of their own, as wide as the longest of them (8 bits at most)
+                const int below = std::min<int>(trie_height(t, at_node), (int)sk::kMp3L1Bits);
+                const size_t sub = blob.size();
+                blob.resize(sub + ((size_t)1 << below), 0u);
+                flatten_table(t, xlen, at_node, below, sub, blob);
+                entry = 0x80000000u | (uint32_t)below << 26 | (uint32_t)sub;
+            }
+        }
+        blob[at + v] = entry;
+    }
+}
+
+void flatten(const sk_mp3_codebook &cb, std::vector<uint32_t> &blob) {
+    constexpr size_t kHeaderWords = sizeof(sk::Mp3CodebookHeader) / 4, kL1 = (size_t)1 << sk::kMp3L1Bits;
+    sk::Mp3CodebookHeader h;
+    std::memset(&h, 0, sizeof h);
+    // first-level tables, one per distinct code set
+    const sk_mp3_codebook::Trie *tries[34];
+    int xlens[34];
+    for (int i = 0; i < 32; ++i) tries[i] = &cb.big[i], xlens[i] = cb.big[i].xlen;
+    for (int k = 0; k < 2; ++k) tries[32 + k] = &cb.count1[k], xlens[32 + k] = 0;
+    size_t first[34], n_first = 0;
+    for (int i = 0; i < 34; ++i) {
+        first[i] = 0;
+        if (tries[i]->next.empty()) continue;
+        int same = -1;
+        for (int j = 0; j < i && same < 0; ++j)
+            if (!tries[j]->next.empty() && tries[j]->next == tries[i]->next && xlens[j] == xlens[i]) same = j;
+        first[i] = same >= 0 ? first[same] : kHeaderWords + kL1 * n_first++;
+    }
+    h.lds_words = (uint32_t)(kHeaderWords + kL1 * n_first);
+    blob.assign(h.lds_words, 0u);
+    for (int i = 0; i < 34; ++i) {
+        if (tries[i]->next.empty()) continue;
+        bool done = false;
+        for (int j = 0; j < i; ++j) done = done || (first[j] == first[i] && !tries[j]->next.empty());
+        if (!done) flatten_table(*tries[i], xlens[i], 0, (int)sk::kMp3L1Bits, first[i], blob);
+    }
+    for (int i = 0; i < 32; ++i)
+        if (cb.big[i].xlen) h.big[i] = (uint32_t)cb.big[i].xlen | (uint32_t)cb.big[i].linbits << 8 | (uint32_t)first[i] << 16;
+    for (int k = 0; k < 2; ++k) h.count1[k] = (uint32_t)first[32 + k];
+    std::memcpy(h.slen, cb.t.slen, sizeof h.slen);
+    std::memcpy(h.lsf_partitions, cb.t.lsf_partitions, sizeof h.lsf_partitions);
+    for (int row = 0; row < 9; ++row) {
+        h.rates_present[row] = cb.t.rates_present[row] ? 1 : 0;
+        if (!cb.t.rates_present[row]) continue;
+        const uint16_t *lo = cb.t.long_offsets[row], *so = cb.t.short_offsets[row];
+        for (int cut = 0; cut < 3; ++cut) {  // the band widths of huffman(), summed up once
+            int widths[64], n_widths = 0;
+            if (cut == 0) {
+                for (int band = 0; band < 22; ++band) widths[n_widths++] = lo[band + 1] - lo[band];
+            } else {
+                int first_short = 0;
+                if (cut == 2) {
+                    for (int band = 0; band < 22 && lo[band + 1] <= 36; ++band) widths[n_widths++] = lo[band + 1] - lo[band];
+                    while (first_short < 13 && 3 * so[first_short] < 36) ++first_short;
+                }
+                for (int band = first_short; band < 13; ++band)
+                    for (int w = 0; w < 3; ++w) widths[n_widths++] = so[band + 1] - so[band];
+            }
+            int at = 0;
+            for (int count = 0; count < (int)sk::kMp3RegionCounts; ++count) {
+                h.region[row][cut][count] = (uint16_t)(at > 576 ? 576 : at);
+                if (count < n_widths) at += widths[count];
+            }
+        }
+    }
+    h.words = (uint32_t)blob.size();
+    std::memcpy(blob.data(), &h, sizeof h);
+}
+
 }  // namespace
 
 extern "C" {
@@ -390,6 +488,20 @@ int sk_mp3_codebook_create_iso(sk_mp3_codebook **out) try {
     return sk::abi_caught("sk_mp3_codebook_create_iso");
 }
 
+// The device form of a code book (mp3_codebook_blob.h).  Pure host code.
+int sk_mp3_codebook_flatten(const sk_mp3_codebook *cb, uint32_t *out, size_t cap_words, size_t *words) try {
+    sk::abi_enter();
+    if (!cb || !words || (cap_words && !out)) return SK_ERR_INVALID_ARG;
+    std::vector<uint32_t> blob;
+    flatten(*cb, blob);
+    *words = blob.size();
+    if (blob.size() > cap_words) return SK_ERR_CAPACITY;
+    std::memcpy(out, blob.data(), blob.size() * sizeof(uint32_t));
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp3_codebook_flatten");
+}
+
 int sk_mp3_decode_main_data(const sk_mp3_codebook *cb, const sk_mp3_frame_info *h, const sk_mp3_side_info *side, const uint8_t *main, size_t main_len,
                             sk_mp3_granule_data out[2][2]) try {
     sk::abi_enter();
@@ -428,52 +540,11 @@ int sk_mp3_decode_main_data(const sk_mp3_codebook *cb, const sk_mp3_frame_info *
 
 // ---- the decoder handle ---------------------------------------------------------------------------------------------------
 
-struct sk_mp3_decoder {
-    sk_engine *engine = nullptr;
-    const sk_mp3_codebook *cb = nullptr;
-    sk_mp3_codebook *own_cb = nullptr;  // the standard's tables, when the caller passed none
-    std::vector<uint8_t> buffer, reservoir;
-    uint32_t sample_rate = 0;  // of the first frame (Option::get_or_insert, lib.rs:203-204)
-    uint8_t channels = 0;
-    uint64_t frames = 0;
-    uint32_t free_format_bytes = 0;  // a free-format stream's frame length once measured (sk_mp3_scan_free)
-    bool stream_open = false;
-    uint32_t stream = 0;
-    uint8_t stream_channels = 0;
-    // scratch of one call
-    std::vector<sk_mp3_frame_info> found;
-    std::vector<sk_mp3_requant_granule> granules;
-    std::vector<sk_mp3_granule_desc> descs;
-    std::vector<int16_t> is;
-    std::vector<float> pcm;
-    std::vector<int32_t> status;
-    std::vector<uint8_t> staged_reservoir, main;
-    struct Queued {
-        uint32_t first_granule, granules;
-        size_t first_sample, samples;
-    };
-    std::vector<Queued> queued;
-};
-
 namespace {
-
-constexpr size_t kMaxBuffered = 4u * 1024 * 1024;  // MAX_MP3_STREAM_BUFFER_BYTES, lib.rs:155
-constexpr size_t kReservoirKept = 2048;            // main_data_begin reaches back 511 bytes at most
-
-// soundkit-mp3/src/lib.rs:387-396
-int32_t mp3_f32_to_i32(float sample) {
-    const float scaled = std::round(sample * 2147483648.0f);  // i32::MAX as f32
-    if (scaled > 2147483648.0f) return INT32_MAX;
-    if (scaled < -2147483648.0f) return INT32_MIN;
-    if (scaled != scaled) return 0;
-    if (scaled >= 2147483648.0f) return INT32_MAX;  // Rust's saturating `as`
-    return (int32_t)scaled;
-}
-
-enum class Out { I16, I32, F32 };
 
 int decode(sk_mp3_decoder *d, const uint8_t *input, size_t len, void *out, size_t out_cap, size_t *written, Out kind) {
     if (!d || !written || (len && !input) || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    if (d->gpu_entropy) return gpu_hooks().decode(d, input, len, out, out_cap, written, kind);  // mp3_decoder_gpu.cpp
     *written = 0;
     if (d->buffer.size() + len > kMaxBuffered) return SK_PIPE_CHUNK_TOO_LARGE;
     d->buffer.insert(d->buffer.end(), input, input + len);
@@ -680,6 +751,26 @@ int sk_mp3_decoder_reset(sk_mp3_decoder *d) try {
     return SK_OK;
 } catch (...) {
     return sk::abi_caught("sk_mp3_decoder_reset");
+}
+
+int sk_mp3_decoder_set_gpu_entropy(sk_mp3_decoder *d, int on) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (on) {
+        const GpuHooks &hooks = gpu_hooks();
+        if (!hooks.install_codebook || !hooks.decode) return SK_ERR_UNSUPPORTED;  // built without the device stage
+        size_t words = 0;
+        int rc = sk_mp3_codebook_flatten(d->cb, nullptr, 0, &words);
+        if (rc != SK_OK && rc != SK_ERR_CAPACITY) return rc;
+        d->gpu_blob.resize(words);
+        rc = sk_mp3_codebook_flatten(d->cb, d->gpu_blob.data(), words, &words);
+        if (rc == SK_OK) rc = hooks.install_codebook(d->engine, d->gpu_blob.data(), words);
+        if (rc != SK_OK) return rc;
+    }
+    d->gpu_entropy = on != 0;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp3_decoder_set_gpu_entropy");
 }
 
 int sk_mp3_decoder_info(const sk_mp3_decoder *d, uint32_t *sample_rate, uint8_t *channels, size_t *buffer_len, uint64_t *frames) try {

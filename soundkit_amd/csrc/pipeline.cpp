@@ -16,6 +16,7 @@
 // delivered, so its frames reach the engine in order and its outputs never overtake each other.
 #include "../../include/soundkit_amd.h"
 #include "sk_abi.h"
+#include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage
 
 #include <hip/hip_runtime.h>
 
@@ -104,6 +105,11 @@ struct Batch {
     std::vector<sk_mp3_granule_desc> mp3_desc;
     int16_t *mp3_is = nullptr;  // pinned: [granule][channel][576], 2 x 576 per granule reserved
     size_t n_mp3 = 0, mp3_rows = 0;
+    // the same streams with the Huffman stage on the device (sk_lane::mp3_gpu): frames whose main data lies in au_bytes, and how
+    // many of them each entry of ts brought (ts itself keeps counting granules: the budget and the output bound are in granules)
+    std::vector<sk_mp3_frame_item> mp3_frames;
+    std::vector<uint32_t> mp3_frames_of;
+    size_t n_mp3_frames = 0;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -121,6 +127,8 @@ struct Batch {
         au_used = 0;
         n_mp3 = 0;
         mp3_rows = 0;
+        n_mp3_frames = 0;
+        mp3_frames_of.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -175,6 +183,10 @@ struct sk_lane {
     std::mutex mp3_mu;
     sk_mp3_codebook *mp3_cb = nullptr;
     std::atomic<bool> mp3_ready{false};
+    // gpu_entropy = 3: the MP3 streams' passes stop behind the bit reservoir; scale factors and Huffman codes are the tick's
+    // (sk_tick_run_mixed_md, reached through pipeline_gpu_hooks()).  cfg.gpu_entropy holds 1 then: the AAC streams' mode.
+    bool mp3_gpu = false;
+    std::vector<uint32_t> mp3_blob;  // mp3_cb flattened for the device (sk_mp3_codebook_flatten)
 
     std::vector<std::thread> workers;
     std::thread submitter;
@@ -250,6 +262,9 @@ struct Parsed {  // what one worker pass produced for one stream
     std::vector<sk_mp3_requant_granule> mp3_gr;
     std::vector<sk_mp3_granule_desc> mp3_desc;
     std::vector<int16_t> mp3_is;
+    // ... or, with the Huffman stage on the device, its frames (byte_offset into mp3_bytes; n_au_bytes = mp3_bytes.size())
+    std::vector<sk_mp3_frame_item> mp3_frames;
+    std::vector<uint8_t> mp3_bytes;
 };
 
 // 1 = a chunk was appended to s.pending, 0 = nothing queued right now, -1 = the end-of-stream marker was taken (s.saw_eof set)
@@ -281,6 +296,14 @@ int pull_input(PStream &s) {
 // The tables an MP3 stream needs: the code book for the host's Huffman stage, band tables and synthesis window on the engine;
 // the batches get their granule arrays.  Once per lane, at the first MP3 stream.
 int ensure_mp3(sk_lane *p);
+}  // namespace
+namespace sk_mp3_internal {
+PipelineGpuHooks &pipeline_gpu_hooks() {
+    static PipelineGpuHooks hooks;
+    return hooks;
+}
+}  // namespace sk_mp3_internal
+namespace {
 
 // What the stream's first bytes are (detect_audio at lib.rs:3042 looks at magic numbers; on this path two formats exist):
 // an ID3v2 tag or an MPEG audio sync with a layer field -> MP3; an ADTS sync (layer bits 00) -> AAC.  0 = not enough bytes yet.
@@ -353,7 +376,11 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
             main.resize(s.mp3_reservoir.size() + h.frame_bytes);
             if (ok) ok = sk_mp3_main_data(frame, h.frame_bytes, &h, &side, s.mp3_reservoir.data(), s.mp3_reservoir.size(), main.data(), main.size(), &main_len) == SK_OK;
             sk_mp3_granule_data data[2][2];
-            if (ok) ok = sk_mp3_decode_main_data(p->mp3_cb, &h, &side, main.data(), main_len, data) == SK_OK;
+            if (ok && !p->mp3_gpu) ok = sk_mp3_decode_main_data(p->mp3_cb, &h, &side, main.data(), main_len, data) == SK_OK;
+            if (ok && p->mp3_gpu && r.n_frames > 0 && r.mp3_bytes.size() + main_len + 12 > p->au_pass_budget) {  // what one batch can take
+                r.budget_stop = true;
+                break;
+            }
             const bool joint = h.mode == 1;
             if (ok) {
                 if (s.engine_stream == kNoStream) {  // the first frame that decodes fixes rate and channels (lib.rs:203-204)
@@ -377,7 +404,20 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     fail(SK_MP3_UNSUPPORTED, "Decoding failed: MP3 sample rate or channel count changed mid-stream");
                     break;
                 }
-                for (int gr = 0; gr < h.granules; ++gr) {
+                if (p->mp3_gpu) {  // the pass ends behind the reservoir: the frame and its main data go to the tick as they are
+                    sk_mp3_frame_item item;
+                    std::memset(&item, 0, sizeof item);
+                    item.header = h;
+                    item.side = side;
+                    item.byte_offset = (uint32_t)r.mp3_bytes.size();
+                    item.byte_len = (uint32_t)main_len;
+                    r.mp3_bytes.insert(r.mp3_bytes.end(), main.data(), main.data() + main_len);
+                    r.mp3_bytes.resize((r.mp3_bytes.size() + 8 + 3) & ~(size_t)3, 0);  // 4-byte aligned, >= 8 zero bytes behind it
+                    r.mp3_frames.push_back(item);
+                    r.n_frames += h.granules;
+                    r.n_au_bytes = r.mp3_bytes.size();
+                }
+                for (int gr = 0; gr < h.granules && !p->mp3_gpu; ++gr) {
                     sk_mp3_requant_granule g;
                     std::memset(&g, 0, sizeof g);
                     g.sample_rate = h.sample_rate;
@@ -550,13 +590,27 @@ int ensure_mp3(sk_lane *p) {
         rc = sk_mp3_codebook_create(&t, &p->mp3_cb);
         if (rc != SK_OK) return rc;
     }
+    if (p->mp3_gpu && p->mp3_blob.empty()) {
+        size_t words = 0;
+        rc = sk_mp3_codebook_flatten(p->mp3_cb, nullptr, 0, &words);
+        if (rc != SK_OK && rc != SK_ERR_CAPACITY) return rc;
+        std::vector<uint32_t> blob(words);
+        rc = sk_mp3_codebook_flatten(p->mp3_cb, blob.data(), blob.size(), &words);
+        if (rc == SK_OK) rc = sk_mp3_internal::pipeline_gpu_hooks().install_codebook(p->engine, blob.data(), blob.size());
+        if (rc != SK_OK) return rc;
+        p->mp3_blob.swap(blob);
+    }
     {
         // the batches' granule arrays: workers copy into disjoint ranges without the lock, so they are sized once, here, while
         // no MP3 claim can exist yet (an MP3 pass reaches the batches only behind this function)
         std::lock_guard<std::mutex> bl(p->batch_mu);
         for (Batch &b : p->batches) {
-            if (b.mp3_is) continue;
+            if (b.mp3_is || !b.mp3_frames.empty()) continue;
             const size_t cap = p->cfg.max_frames_per_tick;
+            if (p->mp3_gpu) {  // frames instead of granules and integers (a frame has at least one granule)
+                b.mp3_frames.resize(cap);
+                continue;
+            }
             if (hipHostMalloc((void **)&b.mp3_is, cap * 2 * 576 * sizeof(int16_t) + 64, hipHostMallocPortable) != hipSuccess) {
                 b.mp3_is = nullptr;
                 return SK_ERR_OOM;
@@ -649,7 +703,7 @@ void worker_body(sk_lane *p) {
         }
         // claim room in the batch being filled
         Batch *b;
-        size_t desc_at, float_at, au_at, mp3_at = 0, mp3_row_at = 0;
+        size_t desc_at, float_at, au_at, mp3_at = 0, mp3_row_at = 0, mp3_frame_at = 0;
         {
             std::unique_lock<std::mutex> lk(p->batch_mu);
             p->workers_waiting_room.fetch_add(1);
@@ -667,9 +721,12 @@ void worker_body(sk_lane *p) {
             au_at = b->au_used;
             mp3_at = b->n_mp3;
             mp3_row_at = b->mp3_rows;
+            mp3_frame_at = b->n_mp3_frames;
+            b->mp3_frames_of.push_back((uint32_t)r.mp3_frames.size());
             if (r.mp3) {
                 b->n_mp3 += r.n_frames;
                 b->mp3_rows += r.mp3_is.size() / 576;
+                b->n_mp3_frames += r.mp3_frames.size();
             } else {
                 b->n_descs += r.n_frames;
             }
@@ -699,7 +756,13 @@ void worker_body(sk_lane *p) {
             b->entries.push_back(std::move(be));
             b->writers += 1;
         }
-        if (r.n_frames && r.mp3) {
+        if (r.n_frames && r.mp3 && p->mp3_gpu) {
+            std::memcpy(b->au_bytes + au_at, r.mp3_bytes.data(), r.n_au_bytes);
+            for (size_t k = 0; k < r.mp3_frames.size(); ++k) {
+                b->mp3_frames[mp3_frame_at + k] = r.mp3_frames[k];
+                b->mp3_frames[mp3_frame_at + k].byte_offset += (uint32_t)au_at;
+            }
+        } else if (r.n_frames && r.mp3) {
             std::memcpy(b->mp3_gr.data() + mp3_at, r.mp3_gr.data(), r.n_frames * sizeof(sk_mp3_requant_granule));
             std::memcpy(b->mp3_desc.data() + mp3_at, r.mp3_desc.data(), r.n_frames * sizeof(sk_mp3_granule_desc));
             std::memcpy(b->mp3_is + mp3_row_at * 576, r.mp3_is.data(), r.mp3_is.size() * sizeof(int16_t));
@@ -732,7 +795,7 @@ void push_error(PStream &s, int32_t status, const std::string &msg) {
 }
 
 void submit_body(sk_lane *p) {
-    std::vector<sk_tick_stream> ts;
+    std::vector<sk_tick_stream> ts, ts_md;
     for (;;) {
         Batch *b;
         int index;
@@ -801,7 +864,22 @@ void submit_body(sk_lane *p) {
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
             if (b->recs.size() < max_out) b->recs.resize(max_out);
-            if (b->rc == SK_OK && b->n_mp3) {  // streams of both codecs in this tick: the AAC units in the lane's form, the MP3 granules beside them
+            if (b->rc == SK_OK && b->n_mp3 && p->mp3_gpu) {  // the same with the MP3 streams' Huffman stage in the tick as well
+                const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+                sk_tick_input in{};
+                in.n_aac_units = n_frames;
+                if (n_frames) in.units = b->units.data();
+                in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
+                ts_md = ts;  // an MP3 stream's units are frames there
+                for (size_t row = 0; row < ts_md.size(); ++row)
+                    if (ts_md[row].codec == SK_TICK_MP3) ts_md[row].n_frames = b->mp3_frames_of[b->row_of[row]];
+                sk_tick_mp3_frames md{b->mp3_frames.data(), (uint32_t)b->n_mp3_frames, b->au_bytes, b->au_used + 8};
+                // (the lane's first engine is the caller's: something else may have put its own code book there since)
+                b->rc = hooks.install_codebook(p->engine, p->mp3_blob.data(), p->mp3_blob.size());
+                if (b->rc == SK_OK)
+                    b->rc = hooks.tick_md(p->engine, ts_md.data(), (uint32_t)ts_md.size(), &in, &md, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out,
+                                          &b->n_out, &used);
+            } else if (b->rc == SK_OK && b->n_mp3) {  // streams of both codecs in this tick: the AAC units in the lane's form, the MP3 granules beside them
                 sk_tick_input in{};
                 in.n_aac_units = n_frames;
                 if (p->cfg.gpu_entropy == 2) in.descs = b->descs.data(), in.q_sides = b->au_bytes, in.q_quant = reinterpret_cast<const int16_t *>(b->coeffs);
@@ -1100,7 +1178,7 @@ PStream *stream_of(sk_lane *p, uint32_t handle) {
 
 namespace {
 
-int lane_create(sk_engine *e, const sk_pipeline_config *cfg, OutQueue *oq, uint32_t lane_index, uint32_t n_lanes, sk_lane **out) {
+int lane_create(sk_engine *e, const sk_pipeline_config *cfg, bool mp3_gpu, OutQueue *oq, uint32_t lane_index, uint32_t n_lanes, sk_lane **out) {
     if (!e || !out) return SK_ERR_INVALID_ARG;
     *out = nullptr;
     sk_lane *p = new (std::nothrow) sk_lane();
@@ -1110,6 +1188,7 @@ int lane_create(sk_engine *e, const sk_pipeline_config *cfg, OutQueue *oq, uint3
     p->lane_index = lane_index;
     p->n_lanes = n_lanes;
     if (cfg) p->cfg = *cfg;
+    p->mp3_gpu = mp3_gpu;
     if (!p->cfg.entropy_threads) {
         const unsigned cpus = usable_cpus();  // leave room for the submission + delivery threads and the callers' own
         p->cfg.entropy_threads = cpus > 5 ? std::min(cpus - 5, 64u) : 1;
@@ -1478,6 +1557,18 @@ int sk_pipeline_create(sk_engine *e, const sk_pipeline_config *cfg, sk_pipeline 
     *out = nullptr;
     sk_pipeline_config c{};
     if (cfg) c = *cfg;
+    // gpu_entropy = 3 is 1 for the AAC streams, plus the MP3 streams' Huffman stage in the tick; SK_PIPELINE_MP3_GPU_ENTROPY=1 makes a
+    // pipeline created with 1 one of those (read once)
+    static const bool mp3_gpu_env = [] {
+        const char *v = std::getenv("SK_PIPELINE_MP3_GPU_ENTROPY");
+        return v && v[0] == '1';
+    }();
+    const bool mp3_gpu = c.gpu_entropy == 3 || (c.gpu_entropy == 1 && mp3_gpu_env);
+    if (mp3_gpu) {
+        const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+        if (!hooks.tick_md || !hooks.install_codebook) return SK_ERR_UNSUPPORTED;  // built without the device stage
+        c.gpu_entropy = 1;
+    }
     // A stream hands a tick at most `max_stream_frames_per_tick` units and is not scheduled again until that tick has been delivered, so
     // with N streams a tick carries well under N times that: the quota decides how full the ticks are, and a tick costs ~2 ms of waits
     // and launches whatever its size.  With the GPU front-end (where the host threads only frame) the default is 32 units -- two
@@ -1515,7 +1606,7 @@ int sk_pipeline_create(sk_engine *e, const sk_pipeline_config *cfg, sk_pipeline 
         }
         sk_lane *lane = nullptr;
         p->oqs.emplace_back(new OutQueue());
-        rc = lane_create(le, &lane_cfg, p->oqs.back().get(), i, n_lanes, &lane);
+        rc = lane_create(le, &lane_cfg, mp3_gpu, p->oqs.back().get(), i, n_lanes, &lane);
         if (rc == SK_OK) p->lanes.push_back(lane);
     }
     if (rc != SK_OK) {

@@ -1,0 +1,16 @@
+// pipeline_mp3_gpu.cpp -- what lets the batch scheduler run its MP3 streams' Huffman stage in the tick (sk_pipeline_config::gpu_entropy
+// = 3): the two engine entry points pipeline.cpp must not name itself (mp3_internal.h says why), put into its table when the
+// library is loaded.  Everything else of the mode is in pipeline.cpp (parse_some_mp3 stops behind the reservoir and stages frames +
+// main data; the submission thread calls tick_md).
+#include "mp3_internal.h"
+
+namespace {
+
+const bool g_hooked = [] {
+    sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+    hooks.install_codebook = sk::mp3_install_codebook;
+    hooks.tick_md = sk_tick_run_mixed_md;
+    return true;
+}();
+
+}  // namespace

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/soundkit_amd.h"  // sk_mp3_requant_channel
+#include "mp3_codebook_blob.h"
 
 namespace sk {
 
@@ -341,6 +342,38 @@ struct Mp3RequantArgs {
     const uint32_t *line_map;  // [kMp3Rates][long | short | mixed][576]: dest | band << 10 | (window + 1) << 15 of every bitstream-order line
 };
 hipError_t launch_mp3_requant(const Mp3RequantArgs &a, hipStream_t s);
+
+// mp3_entropy.hip -- parts 2 and 3 of the Layer III main data (scale factors, big-values pairs, count1 quadruples), one
+// granule-channel per lane.  The code book: mp3_codebook_blob.h.
+static_assert(kMp3BlobRates == kMp3Rates, "one region table per band-table slot");
+struct Mp3EntropyItem {  // one granule-channel
+    uint32_t frame;      // index into frames
+    uint32_t row;        // its 576 integers go to is + row * 576
+    uint32_t record;     // Mp3RequantRecord that takes its scale factors and preflag, or 0xffffffff (then the cell takes them)
+    uint8_t gr, ch, reserved[2];
+};
+struct Mp3EntropyCell {  // sk_mp3_granule_data without the integers; cell = frame * 4 + granule * 2 + channel
+    uint8_t scalefac_l[22];
+    uint8_t scalefac_s[13][3];
+    uint8_t preflag, intensity_scale, reserved;
+    uint16_t part2_bits, nonzero_lines, part3_bits, reserved2;
+    int32_t status;
+};
+static_assert(sizeof(Mp3EntropyCell) == 76, "packed by hand");
+struct Mp3EntropyArgs {
+    const uint32_t *blob;         // the code book (global memory: the tables of the longer codes are read from here)
+    uint32_t lds_words;
+    const sk_mp3_frame_item *frames;
+    const uint8_t *bytes;         // every frame's main data at frames[i].byte_offset (a multiple of 4), >= 8 bytes of room behind each
+    const Mp3EntropyItem *items;  // sorted by part2_3_length, so that a wave's lanes have about the same number of codes to read
+    uint32_t n_items;
+    uint32_t lane_shift;          // the first 64 >> lane_shift lanes of a wave carry an item each (0..3)
+    int16_t *is;                  // rows of 576
+    Mp3RequantRecord *records;    // or null
+    Mp3EntropyCell *cells;        // zeroed by the caller
+    int32_t *status;              // [cell]: the cells' status fields again, packed (what the fused paths copy back)
+};
+hipError_t launch_mp3_entropy(const Mp3EntropyArgs &a, hipStream_t s);
 
 // aac_entropy.hip -- the AAC-LC front-end on the device, one stream per lane
 }  // namespace sk

@@ -1,5 +1,6 @@
 """Host-side mirror of soundkit-mp3's decoder (soundkit-mp3/src/lib.rs:147-374): frame sync, header, side information,
-the bit reservoir, scale factors and the Huffman stage on the host (csrc/mp3_bitstream.cpp, csrc/mp3_decoder.cpp);
+the bit reservoir, scale factors and the Huffman stage on the host (csrc/mp3_bitstream.cpp, csrc/mp3_decoder.cpp) -- or the last
+two on the GPU (csrc/mp3_entropy.hip: set_codebook / entropy_decode / decode_frames, Mp3Decoder(gpu_entropy=True));
 requantisation, joint stereo and the short-block reorder (csrc/mp3_requant.hip) and the hybrid synthesis filterbank
 (csrc/mp3_hybrid.hip) on the GPU; the reference's `f32_to_i16` tail.  The standard's data tables (ISO/IEC 11172-3 B.3 /
 B.6 / B.7 / B.8, 13818-3 2.4.3.2) are csrc/mp3_iso_tables.h; `Mp3Decoder()` uses them unless given another Codebook."""
@@ -7,7 +8,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (Mp3FrameInfo, Mp3GranuleData, Mp3GranuleDesc, Mp3RequantGranule, Mp3SideInfo, SoundkitError, check, lib)
+from ._lib import (Mp3FrameInfo, Mp3FrameItem, Mp3GranuleData, Mp3GranuleDesc, Mp3RequantGranule, Mp3SideInfo, SoundkitError, check,
+                   lib)
 from .engine import _ptr, default_engine
 
 
@@ -180,6 +182,64 @@ def decode_main_data(codebook, info, side, main):
     return rc, out
 
 
+# ---- parts 2 + 3 on the GPU (csrc/mp3_entropy.hip) -----------------------------------------------------------------------------
+
+def codebook_flatten(codebook):
+    """sk_mp3_codebook_flatten: the device form of a code book as uint32 words (layout: csrc/mp3_codebook_blob.h)"""
+    n = C.c_size_t(0)
+    rc = lib.sk_mp3_codebook_flatten(codebook._h, None, 0, C.byref(n))
+    if rc not in (0, -7):  # SK_ERR_CAPACITY: the size was asked for
+        check(rc, "sk_mp3_codebook_flatten")
+    out = np.zeros(n.value, np.uint32)
+    check(lib.sk_mp3_codebook_flatten(codebook._h, _ptr(out), out.size, C.byref(n)), "sk_mp3_codebook_flatten")
+    return out
+
+
+def set_codebook(codebook=None, engine=None):
+    """the code book of the engine's device Huffman stage; None: the standard's tables"""
+    engine = engine or default_engine()
+    check(lib.sk_mp3_set_codebook(engine._h, codebook._h if codebook is not None else None), "sk_mp3_set_codebook", engine._h)
+
+
+def pack_frames(frames):
+    """frames: iterable of (Mp3FrameInfo, Mp3SideInfo, main data bytes) -> (Mp3FrameItem array, n, uint8 buffer) laid out as
+    sk_mp3_entropy_decode / sk_mp3_decode_frames_* take them (offsets multiples of 4, 8 zero bytes behind each)"""
+    frames = list(frames)
+    items = (Mp3FrameItem * max(len(frames), 1))()
+    at, chunks = 0, []
+    for i, (info, side, main) in enumerate(frames):
+        main = bytes(main)
+        C.memmove(C.byref(items[i].header), C.byref(info), C.sizeof(Mp3FrameInfo))
+        C.memmove(C.byref(items[i].side), C.byref(side), C.sizeof(Mp3SideInfo))
+        items[i].byte_offset, items[i].byte_len = at, len(main)
+        room = (len(main) + 8 + 3) & ~3
+        chunks.append(main + bytes(room - len(main)))
+        at += room
+    buf = np.frombuffer(b"".join(chunks) or bytes(8), np.uint8)
+    return items, len(frames), buf
+
+
+def entropy_decode(items, n, buf, engine=None, out=None):
+    """sk_mp3_entropy_decode -> (status, Mp3GranuleData[n][2][2]); only the cells a frame has are written"""
+    engine = engine or default_engine()
+    if out is None:
+        out = (((Mp3GranuleData * 2) * 2) * max(n, 1))()
+    return lib.sk_mp3_entropy_decode(engine._h, items, n, _ptr(buf), buf.size, out), out
+
+
+def decode_frames(items, streams, n, buf, engine=None, s16=False, out_cap=None):
+    """sk_mp3_decode_frames_* -> (status, pcm[:written], entropy_status[n], stage_status[n])"""
+    engine = engine or default_engine()
+    streams = np.ascontiguousarray(streams, np.uint32)
+    cap = n * MAX_SAMPLES_PER_FRAME if out_cap is None else out_cap
+    pcm = np.zeros(max(cap, 1), np.int16 if s16 else np.float32)
+    es, ss = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    written = C.c_size_t(0)
+    fn = lib.sk_mp3_decode_frames_s16 if s16 else lib.sk_mp3_decode_frames_f32
+    rc = fn(engine._h, items, _ptr(streams), n, _ptr(buf), buf.size, _ptr(pcm), cap, _ptr(es), _ptr(ss), C.byref(written))
+    return rc, pcm[:written.value], es[:n], ss[:n]
+
+
 MAX_SAMPLES_PER_FRAME = 2304
 
 
@@ -187,12 +247,18 @@ class Mp3Decoder:
     """soundkit-mp3's Mp3Decoder (soundkit-mp3/src/lib.rs:147-374): new / sample_rate / channels / buffer_len / reset /
     decode_i16 / decode_i32 / decode_f32, bytes in at any chunking, interleaved samples out; errors raise SoundkitError"""
 
-    def __init__(self, codebook=None, engine=None):
+    def __init__(self, codebook=None, engine=None, gpu_entropy=False):
+        """gpu_entropy: scale factors and Huffman decode on the GPU as well (sk_mp3_decoder_set_gpu_entropy); same results"""
         self._engine = engine or default_engine()
         self._codebook = codebook  # None: Mp3Decoder::new() -- the standard's tables
         self._h = C.c_void_p()
         check(lib.sk_mp3_decoder_create(self._engine._h, codebook._h if codebook is not None else None, C.byref(self._h)),
               "sk_mp3_decoder_create", self._engine._h)
+        if gpu_entropy:
+            self.set_gpu_entropy(True)
+
+    def set_gpu_entropy(self, on):
+        check(lib.sk_mp3_decoder_set_gpu_entropy(self._h, 1 if on else 0), "sk_mp3_decoder_set_gpu_entropy", self._engine._h)
 
     def close(self):
         if self._h:

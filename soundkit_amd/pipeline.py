@@ -34,6 +34,8 @@ class BatchScheduler:
     """One per GPU.  Keyword arguments are the fields of sk_pipeline_config (0 / missing = default)."""
 
     def __init__(self, engine=None, **config):
+        """config: the fields of sk_pipeline_config.  gpu_entropy: 0 host front-end, 1 AAC front-end on the GPU, 2 host Huffman decode +
+        device rest, 3 = 1 with the MP3 streams' scale factors and Huffman decode in the tick as well"""
         self.engine = engine or default_engine()
         cfg = PipelineConfig()
         for k, v in config.items():
