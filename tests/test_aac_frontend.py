@@ -291,8 +291,8 @@ def snr_against_source(decoded_left, source_left):
 
 
 def source_wav():
-    from test_pcm_gpu import read_wav
-    _, pcm = read_wav(os.path.join(GOLD, "wav_stereo_A_Tusk.wav"))
+    from twin_fit import read_wav
+    _, pcm, _ = read_wav(os.path.join(GOLD, "wav_stereo_A_Tusk.wav"))
     return np.frombuffer(pcm, "<i2").reshape(-1, 2).T.astype(np.float32) / 32768.0
 
 

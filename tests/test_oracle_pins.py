@@ -7,6 +7,9 @@ import os
 import numpy as np
 import pytest
 
+import f64_ref as R
+import twin_fit as T
+
 
 def test_imdct_zero_input(oracle):  # dsp.rs:616-624
     out = oracle.imdct_direct_f32(np.zeros(8, np.float32))
@@ -240,17 +243,10 @@ def test_config1_wav_stereo_plumbing_on_the_cpu_path(oracle):
     s16le_to_i16 -> deinterleave_vecs_i16 -> vec_i16_to_f32 -> vec_f32_to_i16 -> interleave_vecs_i16 as restated by
     the oracle, checked against the definitions (audio_bytes.rs:231, :264, :250; audio_pipeline.rs:17-38).  The GPU
     suite runs the same chain through the product (tests/test_pcm_gpu.py::test_config1_wav_stereo_plumbing)."""
-    import struct
-    data = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wav_stereo_A_Tusk.wav"), "rb").read()
-    assert len(data) == 189518 and data[:4] == b"RIFF" and data[8:12] == b"WAVE"
-    pos, fmt, pcm = 12, None, None
-    while pos + 8 <= len(data):  # walk the chunks as WavStreamProcessor::add does (wav.rs:95-262): no 44-byte assumption
-        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
-        if cid == b"fmt ":
-            fmt = struct.unpack("<HHIIHH", data[pos + 8:pos + 24])
-        elif cid == b"data":
-            pcm = data[pos + 8:pos + 8 + size]
-        pos += 8 + size + (size & 1)
+    path = T.golden("wav_stereo_A_Tusk.wav")
+    assert os.path.getsize(path) == 189518
+    fmt, pcm, ext = T.read_wav(path)  # the chunk walk of WavStreamProcessor::add (wav.rs:95-262): no 44-byte assumption
+    assert ext is None
     assert fmt == (1, 2, 16000, 64000, 4, 16) and len(pcm) == 189440
     src = np.frombuffer(pcm, "<i2")
     i16 = oracle.pcm_convert("S16LE_TO_I16", pcm)
@@ -267,3 +263,178 @@ def test_config1_wav_stereo_plumbing_on_the_cpu_path(oracle):
     assert np.abs(back.astype(np.int32) - want.astype(np.int32)).max() <= 1
     inter = np.asarray(oracle.interleave_i16(back)).view("<i2")  # interleave_vecs_i16 returns little-endian bytes
     assert inter.shape == (2 * 47360,) and np.array_equal(inter[0::2], back[0]) and np.array_equal(inter[1::2], back[1])
+
+
+# ---- the reference's twin recordings (tests/twin_fit.py, tests/golden/README.md) ---------------------------------------------
+# The resampler part of the oracle is a restatement of rubato that everything else in this suite takes its taps,
+# alignment and gain from.  These pins hold it against recordings the reference keeps of one clip at 48, 16 and 8 kHz: gain,
+# delay and pass-band.  Tap identity stays unpinned (another good low-pass at the same cut and delay scores the same).
+
+def _clip_f32(rate):
+    return (T.twin_s16(rate).astype(np.float32) / np.float32(32768.0))[None]
+
+
+@pytest.mark.parametrize("in_hz,out_hz", T.PAIRS)
+def test_twin_downsample_planar(oracle, in_hz, out_hz):
+    """downsample_audio (audio_pipeline.rs:438-493) of the higher-rate file meets the lower-rate file: every band's SNR, the
+    gain and the delay (floors and measured figures: twin_fit.TWIN_PINS); so does the worker's full step, the same output
+    through float_sample_to_i16 (soundkit-decoder lib.rs:1815-1827), at the floors of its own"""
+    y = oracle.downsample_planar(_clip_f32(in_hz), in_hz, out_hz)[0]
+    assert y.size == {(48000, 16000): 47316, (48000, 8000): 23658, (16000, 8000): 23615}[(in_hz, out_hz)]
+    T.assert_twin(y, in_hz, out_hz, "f32", "oracle one-shot")
+    q = oracle.pcm_convert("FLOAT_TO_I16_ROUND", y)
+    assert np.array_equal(q, R.float_sample_to_i16(y))
+    T.assert_twin(q.astype(np.float64) / 32768.0, in_hz, out_hz, "s16", "oracle one-shot, rounded")
+
+
+def _chunk_sizes(chunking, total):
+    if chunking == "ones":  # the first 2 000 samples one at a time, then larger chunks
+        return [1] * 2000 + [4096] * ((total - 2000 + 4095) // 4096)
+    size = total if chunking == "whole" else int(chunking)
+    return [size] * ((total + size - 1) // size)
+
+
+@pytest.mark.parametrize("chunking", ["ones", "417", "4800", "whole"])
+@pytest.mark.parametrize("in_hz,out_hz", T.PAIRS)
+def test_twin_streaming_resampler(oracle, in_hz, out_hz, chunking):
+    """StreamingResampler (soundkit-decoder lib.rs:1917-2060) fed the higher-rate file in chunks and flushed: the same pins,
+    and the samples do not depend on the chunking (they are the one-shot call's, which pads and trims the same way)"""
+    x = _clip_f32(in_hz)
+    s = oracle.StreamingResampler(in_hz, out_hz, 1)
+    parts, pos = [], 0
+    for size in _chunk_sizes(chunking, x.shape[1]):
+        parts.append(s.process(x[:, pos:pos + size]))
+        pos += size
+    assert pos >= x.shape[1]
+    parts.append(s.flush())
+    y = np.concatenate(parts, 1)[0]
+    T.assert_twin(y, in_hz, out_hz, "f32", "oracle streaming %s" % chunking)
+    assert np.array_equal(y, oracle.downsample_planar(x, in_hz, out_hz)[0])
+
+
+def _cut_taps(cut, like):
+    """phase 0 of a Blackman-Harris^2 windowed sinc cut at `cut` of the output Nyquist, laid out and normalised as the
+    oracle's 48 -> 16 kHz taps are (tap p sits at 256 p + 255 of the 65 536-point prototype, centre 32 768), in f64"""
+    pos = 256.0 * np.arange(256) + 255.0
+    a = 2.0 * np.pi * pos / 65536.0
+    win = (0.35875 - 0.48829 * np.cos(a) + 0.14128 * np.cos(2 * a) - 0.01168 * np.cos(3 * a)) ** 2
+    taps = win * np.sinc((pos - 32768.0) * (cut / 3.0) / 256.0)
+    return taps * (like.sum() / taps.sum())
+
+
+def _bf16_truncate(taps):
+    return (np.asarray(taps, np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+
+
+def test_twin_fit_negative_controls(oracle):
+    """What the pins tell apart, at 48 -> 16 kHz with the float64 FIR of tests/f64_ref.py: the unaltered filter passes, and each
+    altered one fails the same assertion for its own reason (the quantity named in the message)."""
+    x = _clip_f32(48000)
+    taps = oracle.resampler_taps(16000 / 48000).astype(np.float64)
+    n_out = 47316
+
+    def run(label, **kw):
+        return T.twin_findings(R.fir_48k_16k(x, n_out, **kw)[0], 48000, 16000)[0], label
+
+    assert run("unaltered") == ([], "unaltered")
+    T.assert_twin(R.fir_48k_16k(x, n_out)[0], 48000, 16000, "f32", "f64 FIR, the oracle's taps")
+    # the 0.95 cut restated here is the oracle's filter to f32 rounding: the 0.80 control below differs in the cut alone
+    assert np.abs(_cut_taps(0.95, taps) - taps).max() < 1e-6
+    assert run("0.95 restated", taps=_cut_taps(0.95, taps)) == ([], "0.95 restated")
+
+    zeroed = taps.copy()
+    zeroed[100] = 0.0
+    controls = [
+        ("cut at 0.80 of Nyquist", dict(taps=_cut_taps(0.80, taps)), "snr<7000"),
+        ("tap 100 zeroed", dict(taps=zeroed), "gain"),
+        ("taps x 1.001", dict(taps=taps * 1.001), "gain"),
+        ("alignment 3m - 126", dict(delay=R.FIR_DELAY + 1), "delay"),
+        ("taps truncated to bf16", dict(taps=_bf16_truncate(taps)), "gain"),
+    ]
+    for label, kw, reason in controls:
+        y = R.fir_48k_16k(x, n_out, **kw)[0]
+        with pytest.raises(AssertionError, match=reason):
+            T.assert_twin(y, 48000, 16000, "f32", label)
+        tripped = T.twin_findings(y, 48000, 16000)[0]
+        assert reason in tripped, (label, tripped)
+        if label in ("taps x 1.001", "alignment 3m - 126"):  # SNR alone misses these two: the same filter otherwise
+            assert tripped == [reason], (label, tripped)
+    assert "snr<3000" in T.twin_findings(R.fir_48k_16k(x, n_out, taps=zeroed)[0], 48000, 16000)[0]
+
+
+def test_twin_wav_headers():
+    """the 24-bit and float32 WAVs are WAVE_FORMAT_EXTENSIBLE; the walk is WavStreamProcessor::add's (soundkit/src/wav.rs:95-262)"""
+    for name, size, bits, align, code, data_len in (("wav_24_A_Tusk.wav", 142182, 24, 3, 1, 142080),
+                                                    ("wav_32f_A_Tusk.wav", 189554, 32, 4, 3, 189440)):
+        assert os.path.getsize(T.golden(name)) == size
+        fmt, pcm, ext = T.read_wav(T.golden(name))
+        assert fmt == (0xFFFE, 1, 16000, 16000 * align, align, bits), name
+        assert ext == {"fmt_size": 40, "valid_bits": bits, "channel_mask": 4, "sub_format": code}, name
+        assert len(pcm) == data_len == 47360 * align
+
+
+def _s24_values(raw):
+    b = np.asarray(raw, np.uint8).reshape(-1, 3).astype(np.int32)
+    v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+    return np.where(v >= 1 << 23, v - (1 << 24), v).astype(np.int32)
+
+
+def test_twin_files_are_one_clip():
+    """file to file, no code of ours between: the s32 file is the s16 file << 16, the 24-bit WAV is the s32 file >> 8, the float
+    WAV is the s16 file / 32768; the 48 and 8 kHz files are exactly 3 x and 1/2 the length"""
+    tw = T.pcm_twins()
+    s16, s32, f32 = tw["s16"].view("<i2"), tw["s32"].view("<i4"), tw["f32"].view("<f4")
+    assert s16.size == s32.size == f32.size == 47360 and tw["s24"].size == 3 * 47360
+    assert T.twin_s16(48000).size == 142080 and T.twin_s16(8000).size == 23680
+    assert np.array_equal(s32 >> 16, s16) and not np.any(s32 & 0xFFFF)
+    assert np.array_equal(s32 >> 8, _s24_values(tw["s24"]))
+    assert np.array_equal(f32.astype(np.float64) * 32768.0, s16.astype(np.float64))
+
+
+def test_twin_pcm_relations_exact(oracle):
+    """every conversion between the clip's four sample formats lands on the twin file bit for bit, whole file
+    (audio_bytes.rs:3-373, audio_pipeline.rs:17-98, soundkit-decoder lib.rs:1815-1827, :3458, :3563-3660)"""
+    tw = T.pcm_twins()
+    s16, s32, f32 = tw["s16"].view("<i2"), tw["s32"].view("<i4"), tw["f32"].view("<f4")
+    same = np.array_equal
+    assert same(oracle.pcm_convert("S32LE_TO_I16", tw["s32"]), s16)
+    assert same(oracle.exact_signed_pcm_to_i16(oracle.FMT_S32LE, tw["s32"]), tw["s16"])
+    assert same(oracle.pcm_convert("S24LE_TO_I16", tw["s24"]), s16)
+    assert same(oracle.exact_signed_pcm_to_i16(oracle.FMT_S24LE, tw["s24"]), tw["s16"])
+    assert same(oracle.pcm_convert("I16LE_TO_F32", tw["s16"]).view(np.uint32), f32.view(np.uint32))
+    assert same(oracle.pcm_convert("VEC_I16_TO_F32", s16).view(np.uint32), f32.view(np.uint32))
+    assert same(oracle.pcm_convert("S32LE_TO_F32", tw["s32"]).view(np.uint32), f32.view(np.uint32))
+    assert same(oracle.decoder_bytes_to_f32_planar(oracle.FMT_S32LE, tw["s32"], 1)[0].view(np.uint32), f32.view(np.uint32))
+    assert same(oracle.core_bytes_to_f32_planar(oracle.FMT_S32LE, tw["s32"], 1)[0].view(np.uint32), f32.view(np.uint32))
+    assert same(oracle.pcm_convert("FLOAT_TO_I16_ROUND", f32), s16)
+    assert same(oracle.f32_planar_to_bytes(oracle.FMT_S16LE, f32[None]), tw["s16"])
+    assert same(oracle.planar_f32_to_s16_interleaved(f32[None]), s16)
+    assert same(oracle.pcm_convert("S24LE_TO_I32", tw["s24"]), s32 >> 8)
+
+
+def _check_scaled_by_32767(got, s16):
+    """F32LE_TO_I16 / VEC_F32_TO_I16 scale by 32767 and truncate (audio_bytes.rs:167-175): on x = s / 32768 they cannot give s
+    back, but never exceed it in magnitude and miss it by one step at most"""
+    got, s = got.astype(np.int32), s16.astype(np.int32)
+    assert np.all(np.abs(got) <= np.abs(s)) and np.abs(got - s).max() <= 1
+    assert np.array_equal(got, np.trunc(s.astype(np.float64) / 32768.0 * 32767.0).astype(np.int32))  # exact in f64, and f32 agrees
+
+
+def test_twin_pcm_relations_that_are_not_identities(oracle):
+    tw = T.pcm_twins()
+    s16, s32, f32 = tw["s16"].view("<i2"), tw["s32"].view("<i4"), tw["f32"].view("<f4")
+    _check_scaled_by_32767(oracle.pcm_convert("F32LE_TO_I16", tw["f32"]), s16)
+    _check_scaled_by_32767(oracle.pcm_convert("VEC_F32_TO_I16", f32), s16)
+    # S32LE_TO_S24 keeps the low 24 bits (audio_bytes.rs:101-110), which is not the 24-bit file's sample
+    assert np.array_equal(oracle.pcm_convert("S32LE_TO_S24", tw["s32"]), s32 & 0x00FFFFFF)
+
+
+def test_twin_big_endian_ops_equal_their_little_endian_forms(oracle):
+    tw = T.pcm_twins()
+    for be, le, key, width in (("S32BE_TO_I16", "S32LE_TO_I16", "s32", 4), ("S24BE_TO_I16", "S24LE_TO_I16", "s24", 3),
+                               ("S32BE_TO_F32", "S32LE_TO_F32", "s32", 4), ("S32BE_TO_S24", "S32LE_TO_S24", "s32", 4),
+                               ("S16BE_TO_I16", "S16LE_TO_I16", "s16", 2), ("F32BE_TO_I16", "F32LE_TO_I16", "f32", 4)):
+        got = oracle.pcm_convert(be, T.swap_bytes(tw[key], width))
+        want = oracle.pcm_convert(le, tw[key])
+        assert got.dtype == want.dtype and np.array_equal(got.view(np.uint8), want.view(np.uint8)), be
+    assert np.array_equal(oracle.pcm_convert("S16BE_TO_I16", T.swap_bytes(tw["s16"], 2)), tw["s16"].view("<i2"))

@@ -1,12 +1,11 @@
 """HIP sample-width / interleave kernels vs the oracle: bit-exact (integer, byte and exact-f32 work)."""
-import struct
-
 import numpy as np
 import pytest
 
 import soundkit_amd
 from soundkit_amd import audio_bytes, audio_pipeline, decoder
 from soundkit_amd.audio_types import AudioData, EncodingFlag, Endianness
+from twin_fit import read_wav
 
 pytestmark = pytest.mark.gpu
 
@@ -153,26 +152,10 @@ def test_downmix_and_exact(engine, oracle):
         assert np.array_equal(engine.exact_to_i16(fmt, raw), oracle.exact_signed_pcm_to_i16(fmt, raw))
 
 
-def read_wav(path):
-    """Walk the RIFF chunks as WavStreamProcessor::add does (soundkit/src/wav.rs:95-262)."""
-    data = open(path, "rb").read()
-    assert data[:4] == b"RIFF" and data[8:12] == b"WAVE"
-    pos, fmt, pcm = 12, None, None
-    while pos + 8 <= len(data):
-        cid, size = data[pos:pos + 4], struct.unpack("<I", data[pos + 4:pos + 8])[0]
-        body = data[pos + 8:pos + 8 + size]
-        if cid == b"fmt ":
-            fmt = struct.unpack("<HHIIHH", body[:16])
-        elif cid == b"data":
-            pcm = body
-        pos += 8 + size + (size & 1)
-    return fmt, pcm
-
-
 def test_config1_wav_stereo_plumbing(engine, oracle):
     """BASELINE configs[0]: s16le <-> f32 + deinterleave on testdata/wav_stereo (fixture copy)."""
     import os
-    fmt, pcm = read_wav(os.path.join(os.path.dirname(__file__), "golden", "wav_stereo_A_Tusk.wav"))
+    fmt, pcm, _ = read_wav(os.path.join(os.path.dirname(__file__), "golden", "wav_stereo_A_Tusk.wav"))
     tag, ch, rate, _, align, bits = fmt
     assert (tag, ch, rate, align, bits) == (1, 2, 16000, 4, 16) and len(pcm) == 189440
     i16 = audio_bytes.s16le_to_i16(pcm)
