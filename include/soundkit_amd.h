@@ -646,8 +646,9 @@ typedef struct sk_tick_output {
     uint32_t bytes;        /* frames * channels * bits / 8 */
     int32_t status;        /* 0, or the sk_frame_status of an access unit the engine rejected: the stream ends there */
     uint8_t channels, bits;
-    uint16_t reserved;
+    uint16_t reserved;     /* flags: SK_TICK_OUT_FLOAT (bit 0): the samples are 32-bit floats, not signed integers (only sk_tick_run_pcm sets it) */
 } sk_tick_output;
+#define SK_TICK_OUT_FLOAT 1u
 
 /* upper bounds for the two output arrays of a tick: from the table alone (a resampling stream is taken for the largest ratio there
  * is, 8 -> 48 kHz: 48 KB per chunk and output channel at 32 bits), or -- _on -- from what the engine knows of the streams (their
@@ -701,6 +702,46 @@ typedef struct sk_tick_mp3_frames {
 int sk_tick_run_mixed_md(sk_engine *, const sk_tick_stream *streams, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md,
                          uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap, uint32_t *n_outputs,
                          size_t *out_bytes_used);
+
+/* ---- the tick of the WAV / raw PCM streams -------------------------------------------------------------------------- */
+/* What the reference's worker does to the AudioData a WavStreamProcessor / RawPcmStreamProcessor hands it -- apply_output_options,
+ * soundkit-decoder lib.rs:3324-3456 -- for every unit (= one piece of one `add`) of every listed stream, in one launch sequence:
+ *   24- / 32-bit signed -> 16 bit, same rate and channels: exact_signed_pcm_to_i16 (lib.rs:3458-3489), one output per unit;
+ *   any other change without a rate change: audio_data_to_f32_channels (non-finite -> 0) -> mono downmix when out_channels <
+ *     channels -> f32_channels_to_bytes, one output per unit, in registers (k_pcm_direct);
+ *   a rate change: bytes -> planar f32 straight into the stream's resampler rows (k_pcm_ingest) -> the resampler rounds the other
+ *     ticks use -> downmix -> bytes, one output per completed 4096-frame chunk, plus the flushed and trimmed tail with `flush`.
+ * Outputs are signed little-endian, except that 32-bit output of a float source stays float (lib.rs:3377-3382: SK_TICK_OUT_FLOAT in
+ * the record's `reserved`).  A stream with nothing to change (the fast path, lib.rs:3339-3345) needs no device and is refused here
+ * (SK_ERR_INVALID_ARG): its pieces are delivered as they are.
+ * Limits: 1 or 2 channels (SK_ERR_UNSUPPORTED for more: the resampler state has two rows per stream, and the only downmix is to
+ * mono), 16- / 24- / 32-bit samples (the eight SK_FMT_* formats), a unit of at most 2 GiB - 1, at most 2^31 - 1 frames per stream
+ * and tick.  units: stream by stream in the order of `streams`; byte_offset is a multiple of 16 (the caller packs the pieces that
+ * way: a lane then reads 16 samples with 16-byte loads), byte_len a whole number of frames, > 0.  A resampling stream names the
+ * engine stream that holds its resampler (sk_stream_open with the source's rate and channels, sk_resampler_open); `stream` is
+ * ignored otherwise.  Blocks until out_bytes holds the results.  On failure the resamplers' bookkeeping is as before the call. */
+typedef struct sk_pcm_tick_stream {
+    uint32_t stream;      /* engine stream (resample = 1 only) */
+    uint32_t n_units;     /* units of this stream in the tick (may be 0 with flush) */
+    uint8_t format;       /* SK_FMT_* of the source */
+    uint8_t channels;     /* of the source: 1 or 2 */
+    uint8_t out_bits;     /* DecodeOptions::output_bits_per_sample resolved: 16 / 24 / 32 */
+    uint8_t out_channels; /* DecodeOptions::output_channels resolved (source channels when None) */
+    uint8_t resample;     /* 1: route through the stream's resampler */
+    uint8_t flush;        /* 1: end of stream: flush the resampler after these units (resample = 1 only) */
+    uint8_t reserved[2];
+} sk_pcm_tick_stream;
+typedef struct sk_pcm_unit {
+    uint64_t byte_offset; /* into `bytes`, a multiple of 16 */
+    uint32_t byte_len;
+    uint32_t reserved;
+} sk_pcm_unit;
+/* upper bounds for the two output arrays of such a tick (0 for a table sk_tick_run_pcm would refuse) */
+size_t sk_tick_pcm_out_bound_on(sk_engine *, const sk_pcm_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                uint32_t *max_outputs);
+int sk_tick_run_pcm(sk_engine *, const sk_pcm_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                    const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                    uint32_t *n_outputs, size_t *out_bytes_used);
 
 /* The same tick with the entropy front-end on the GPU too (SURVEY 8f ranks 1 + 4): instead of spectra, the raw access
  * units (ADTS headers stripped) of every stream.  units[k] addresses unit k in au_bytes; units are listed stream by
@@ -791,8 +832,10 @@ typedef struct sk_audio_info { /* AudioData (soundkit/src/audio_types.rs:9-61) m
     int32_t status;          /* error only: the sk_status / sk_aac_status behind DecodeError::DecodingFailed */
     uint8_t bits_per_sample, channel_count;
     uint8_t is_error;        /* 1: the data is the error's message and the stream has ended */
-    uint8_t reserved;
+    uint8_t reserved;        /* flags: SK_AUDIO_FLOAT (EncodingFlag::PCMFloat), SK_AUDIO_BIG_ENDIAN (Endianness::BigEndian); 0 = signed little-endian */
 } sk_audio_info;
+#define SK_AUDIO_FLOAT 1u
+#define SK_AUDIO_BIG_ENDIAN 2u
 
 typedef struct sk_pipeline_stats {
     uint64_t ticks, frames, outputs, errors;
@@ -814,6 +857,16 @@ int sk_pipeline_create(sk_engine *, const sk_pipeline_config *cfg /* NULL = defa
 void sk_pipeline_destroy(sk_pipeline *);
 /* DecodePipeline::spawn_with_options for an ADTS AAC-LC stream (lib.rs:2590-2700, 2750-2786) */
 int sk_pipeline_spawn(sk_pipeline *, const sk_decode_options *opt /* NULL = defaults */, uint32_t *handle);
+/* DecodePipeline::spawn_raw_pcm_with_options (lib.rs:2469-2486): a stream of headerless PCM in the given format.  It has its
+ * decoder from the start and does not detect.  SK_ERR_INVALID_ARG: the validate() of RawPcmFormat (raw_pcm.rs:117-125: rate and channels
+ * > 0) or a format outside SK_FMT_*. */
+typedef struct sk_raw_pcm_format {
+    uint32_t sample_rate;
+    uint8_t channels;
+    uint8_t format;   /* SK_FMT_*: linear16 = SK_FMT_S16LE, l16 = SK_FMT_S16BE, linear32 = SK_FMT_F32LE (raw_pcm.rs:62-87) */
+    uint16_t reserved;
+} sk_raw_pcm_format;
+int sk_pipeline_spawn_raw_pcm(sk_pipeline *, const sk_raw_pcm_format *format, const sk_decode_options *opt /* NULL = defaults */, uint32_t *handle);
 int sk_pipeline_send(sk_pipeline *, uint32_t handle, const uint8_t *data, size_t len);   /* lib.rs:2795-2835 */
 int sk_pipeline_finish(sk_pipeline *, uint32_t handle);                                   /* lib.rs:2838-2840 */
 /* 1 = one output copied to data / info; 0 = nothing ready; SK_PIPE_CLOSED = ended and drained; SK_ERR_CAPACITY =
@@ -831,6 +884,28 @@ int sk_pipeline_get_stats(sk_pipeline *, sk_pipeline_stats *out);
 /* Where every thread of the scheduler stands, the batches, the stream table in counts and the engine's stage, as text
  * (what SK_PIPELINE_WATCHDOG=<seconds> prints when ticks stop).  Takes no lock it could block on.  Returns the length. */
 size_t sk_pipeline_debug_dump(sk_pipeline *, char *buf, size_t cap);
+
+/* ---- WAV and raw PCM stream processors (host only) --------------------------------------------------------------- */
+/* WavStreamProcessor::add (soundkit/src/wav.rs:95-324) and RawPcmStreamProcessor::add / flush (soundkit/src/raw_pcm.rs:150-190), the
+ * front of the scheduler's WAV / raw PCM streams, by themselves.  One `add` takes a chunk of the stream (at most 4 MiB) and gives back
+ * at most one piece: the whole PCM frames available now -- *piece_len bytes (0: nothing yet) that start *piece_offset bytes into the
+ * stream (counted over everything ever added), and, when `piece` is not NULL, a pointer to them that is valid until the next call on
+ * the same object.  SK_PCM_ERR_STREAM: the stream is rejected; *_last_error has the reference's text. */
+enum sk_pcm_stream_status { SK_PCM_ERR_STREAM = -401 };
+typedef struct sk_wav_reader sk_wav_reader;
+int sk_wav_reader_create(sk_wav_reader **out);
+void sk_wav_reader_destroy(sk_wav_reader *);
+int sk_wav_reader_add(sk_wav_reader *, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece);
+/* what the fmt chunk said (zeros before it has been seen); is_float: format tag 3 (for WAVE_FORMAT_EXTENSIBLE: of the sub-format);
+ * total_frames: of the data chunk as declared, 0 while unknown (wav.rs:86-93) */
+int sk_wav_reader_info(const sk_wav_reader *, uint32_t *sample_rate, uint32_t *channels, uint32_t *bits, int *is_float, uint64_t *total_frames);
+const char *sk_wav_reader_last_error(const sk_wav_reader *);
+typedef struct sk_raw_pcm_framer sk_raw_pcm_framer;
+int sk_raw_pcm_framer_create(uint32_t bytes_per_frame, sk_raw_pcm_framer **out);
+void sk_raw_pcm_framer_destroy(sk_raw_pcm_framer *);
+int sk_raw_pcm_framer_add(sk_raw_pcm_framer *, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece);
+int sk_raw_pcm_framer_flush(sk_raw_pcm_framer *); /* end of stream: SK_PCM_ERR_STREAM when a partial frame is left */
+const char *sk_raw_pcm_framer_last_error(const sk_raw_pcm_framer *);
 
 #ifdef __cplusplus
 }

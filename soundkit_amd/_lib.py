@@ -19,6 +19,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -104: "UnsupportedSamplingFrequencyIndex", -105: "UnsupportedChannelConfig", -106: "UnsupportedFeature",
              -107: "InvalidConfig", -108: "InvalidBitstream",
              -301: "Mp3NeedMore", -302: "Mp3NoSync", -303: "Mp3Unsupported", -304: "Mp3Invalid",
+             -401: "PcmStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -114,6 +115,22 @@ class TickOutput(C.Structure):
     """sk_tick_output"""
     _fields_ = [("stream_index", C.c_uint32), ("frames", C.c_uint32), ("byte_offset", C.c_uint64), ("bytes", C.c_uint32),
                 ("status", C.c_int32), ("channels", C.c_uint8), ("bits", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class PcmTickStream(C.Structure):
+    """sk_pcm_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("format", C.c_uint8), ("channels", C.c_uint8), ("out_bits", C.c_uint8),
+                ("out_channels", C.c_uint8), ("resample", C.c_uint8), ("flush", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class PcmUnit(C.Structure):
+    """sk_pcm_unit"""
+    _fields_ = [("byte_offset", C.c_uint64), ("byte_len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RawPcmFormatC(C.Structure):
+    """sk_raw_pcm_format"""
+    _fields_ = [("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("format", C.c_uint8), ("reserved", C.c_uint16)]
 
 
 class PipelineConfig(C.Structure):
@@ -314,6 +331,19 @@ _sig = {
     "sk_tick_run": (_i, [_vp, _vp, _u32, _vp, _vp, _u32, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
     "sk_tick_run_mixed_md": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
     "sk_tick_run_mixed": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_tick_pcm_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_pcm": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_pipeline_spawn_raw_pcm": (_i, [_vp, _vp, _vp, C.POINTER(_u32)]),
+    "sk_wav_reader_create": (_i, [C.POINTER(_vp)]),
+    "sk_wav_reader_destroy": (None, [_vp]),
+    "sk_wav_reader_add": (_i, [_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(_sz), C.POINTER(_vp)]),
+    "sk_wav_reader_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_i), C.POINTER(C.c_uint64)]),
+    "sk_wav_reader_last_error": (C.c_char_p, [_vp]),
+    "sk_raw_pcm_framer_create": (_i, [_u32, C.POINTER(_vp)]),
+    "sk_raw_pcm_framer_destroy": (None, [_vp]),
+    "sk_raw_pcm_framer_add": (_i, [_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(_sz), C.POINTER(_vp)]),
+    "sk_raw_pcm_framer_flush": (_i, [_vp]),
+    "sk_raw_pcm_framer_last_error": (C.c_char_p, [_vp]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <atomic>
 #include <thread>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <new>
@@ -251,6 +252,7 @@ struct sk_engine {
     bool sinc_exact = false;  // sk_engine_set_resampler_exact: the scalar form that keeps rubato's order of operations
     // sk_tick_run: synthesis output, resampler output, packed bytes, small-array arena (+ pinned host mirror)
     DevBuf tick_pcm, tick_res, tick_out, tick_arena, tick_au, tick_side, tick_q, tick_mp3_in, tick_mp3_xr;
+    DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
     void *d_ec_blob = nullptr;
@@ -562,6 +564,7 @@ const char *sk_strerror(int status) try {
     case SK_MP3_NO_SYNC: return "not an MPEG audio frame header";
     case SK_MP3_UNSUPPORTED: return "unsupported MPEG audio layer or feature";
     case SK_MP3_INVALID: return "invalid MP3 side information";
+    case SK_PCM_ERR_STREAM: return "WAV / raw PCM stream rejected";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -642,6 +645,7 @@ void sk_engine_destroy(sk_engine *e) try {
         e->tick_au.release();
         e->tick_side.release();
         e->tick_q.release();
+        e->tick_pcm_in.release();
         e->mp3e_in.release();
         e->mp3e_out.release();
         if (e->d_mp3_cb) (void)hipFree(e->d_mp3_cb);
@@ -3445,6 +3449,119 @@ int tick_mp3_queue(sk_engine *e, const TickMp3 &mp3, float *pcm_rows, AuxArena &
 }
 
 
+// Queues the copy of a tick's packed output to the caller's buffer.  Into pinned memory the copy is queued like a kernel and the
+// bounded wait that follows is the tick's only wait.  A caller's pageable buffer would make hipMemcpyAsync itself wait for everything
+// queued so far, unbounded: such a buffer (the scheduler's are pinned; a test's numpy array is not) gets the bytes through the
+// engine's pinned bounce buffer: *bounce is then where they arrive, to be copied to `out` after the wait.
+int tick_queue_d2h(sk_engine *e, uint8_t *out, const uint8_t *d_out, size_t bytes, uint8_t **bounce) {
+    *bounce = nullptr;
+    hipPointerAttribute_t pa{};
+    const bool pinned = hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost;
+    if (!pinned) (void)hipGetLastError();
+    if (!pinned) {
+        if (e->h_out_cap < bytes) {
+            if (e->h_out) (void)hipHostFree(e->h_out);
+            e->h_out = nullptr;
+            e->h_out_cap = 0;
+            SK_HIP(hipHostMalloc((void **)&e->h_out, bytes + bytes / 4 + 4096, hipHostMallocDefault), "alloc pinned output bounce");
+            e->h_out_cap = bytes + bytes / 4 + 4096;
+        }
+        *bounce = e->h_out;
+    }
+    SK_HIP(hipMemcpyAsync(*bounce ? *bounce : out, d_out, bytes, hipMemcpyDeviceToHost, e->stream), "D2H tick output");
+    return SK_OK;
+}
+
+// The resampler rounds of a tick, shared by tick_body (decoded units: row copies) and tick_pcm_body (PCM units: k_pcm_ingest).  A row
+// holds kRsMaxFill samples behind its history, so a stream's input of a tick goes down in rounds: queue what fits, one launch for all
+// streams, rs_process_ready, again.  Then the flush of the streams that end (StreamingResampler::flush, lib.rs:2017-2058).
+struct RsRounds {
+    std::function<uint32_t(size_t ci)> total_in;  // input frames call ci's stream brings in this tick
+    // queue the frames [calls[ci].consumed, + take) of call ci for rows that hold `fill` frames; returns how many it queued
+    // (1 ... take: a source may prefer to cut elsewhere)
+    std::function<uint32_t(size_t ci, uint32_t take, uint32_t fill)> append;
+    std::function<int()> launch;  // upload and launch what append has queued since the last launch (SK_OK when nothing was)
+    std::function<bool(size_t ci)> flush;  // the stream of call ci ends with this tick
+    std::function<std::vector<std::pair<uint32_t, uint32_t>> &(size_t ci)> chunks;  // where call ci's AudioData boundaries go
+    std::function<void(int)> sub;  // section timer (SK_TICK_TRACE)
+};
+
+int rs_run_rounds(sk_engine *e, std::vector<RsCall> &calls, float *d_res, size_t res_stride, uint32_t res_cap, AuxArena &aux, const RsRounds &h) {
+    std::vector<size_t> ready;
+    std::vector<uint32_t> before;
+    int rc = SK_OK;
+    for (;;) {
+        ready.clear();
+        bool queued = false;
+        for (size_t ci = 0; ci < calls.size(); ++ci) {
+            RsCall &c = calls[ci];
+            StreamInfo &s = e->streams[c.id];
+            const uint32_t take = std::min(h.total_in(ci) - c.consumed, kRsMaxFill - s.rs_fill);  // a tick's units of a stream: one round
+            if (take) {
+                const uint32_t got = h.append(ci, take, s.rs_fill);
+                if (got == 0 || got > take) return SK_ERR_INTERNAL;
+                s.rs_fill += got;
+                c.consumed += got;
+                queued = true;
+            }
+            if (s.rs_fill >= kRsChunk) ready.push_back(ci);
+        }
+        h.sub(0);
+        if (!queued && ready.empty()) break;
+        rc = h.launch();
+        if (rc != SK_OK) return rc;
+        h.sub(1);
+        if (!ready.empty()) {
+            rc = rs_process_ready(e, calls, ready, d_res, res_stride, res_cap, aux);
+            if (rc != SK_OK) return rc;
+            h.sub(2);
+            for (size_t ci : ready) {  // one AudioData per chunk (lib.rs:1979-2003), empty ones are not sent
+                RsCall &c = calls[ci];
+                for (const auto &o : c.outs)
+                    if (o.second) h.chunks(ci).emplace_back(o.first, o.second);
+                c.outs.clear();
+            }
+        }
+    }
+    // end of stream: StreamingResampler::flush (lib.rs:2017-2058); a stream that failed is not flushed
+    std::vector<sk::RowCopy> pads;
+    ready.clear();
+    for (size_t ci = 0; ci < calls.size(); ++ci) {
+        if (!h.flush(ci)) continue;
+        RsCall &c = calls[ci];
+        StreamInfo &s = e->streams[c.id];
+        const uint32_t remaining = s.rs_fill, padded = kRsChunk - remaining;
+        c.trim = 0;
+        if (remaining > 0 && padded > 0)
+            c.trim = (uint32_t)std::llround(((double)padded * (double)s.rs_out_hz) / (double)s.rs_in_hz);
+        for (uint32_t ch = 0; ch < c.channels && padded; ++ch)
+            for (uint32_t o = 0; o < padded; o += 8192)
+                pads.push_back(sk::RowCopy{0, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + remaining + o,
+                                           std::min<uint32_t>(8192, padded - o), 0});
+        s.rs_fill = kRsChunk;
+        ready.push_back(ci);
+    }
+    if (!ready.empty()) {
+        if (!pads.empty()) {
+            const sk::RowCopy *d_pads = nullptr;
+            SK_HIP(aux.put(pads, e->stream, &d_pads), "upload tick pad jobs");
+            for (size_t j0 = 0; j0 < pads.size(); j0 += 65535)
+                SK_HIP(sk::launch_row_copies(e->d_zeros, e->d_rs, d_pads + j0,
+                                             (uint32_t)std::min<size_t>(65535, pads.size() - j0), e->stream), "tick pad chunk");
+        }
+        before.clear();
+        for (size_t ci : ready) before.push_back(calls[ci].produced);
+        rc = rs_process_ready(e, calls, ready, d_res, res_stride, res_cap, aux);
+        if (rc != SK_OK) return rc;
+        for (size_t k = 0; k < ready.size(); ++k) {
+            const RsCall &c = calls[ready[k]];
+            const uint32_t got = c.produced - before[k];
+            if (got > c.trim) h.chunks(ready[k]).emplace_back(before[k], got - c.trim);
+        }
+    }
+    return SK_OK;
+}
+
 int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_aac_frame_desc *descs, const float *coeffs,
               const sk_au_item *units, const uint8_t *au_bytes, size_t au_len, uint32_t n_frames, uint8_t *out, size_t out_cap,
               sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes, const EntropyProbe *probe,
@@ -3778,113 +3895,65 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
         SK_HIP(e->tick_res.reserve(res_rows * res_stride * 4 + 16), "alloc tick resampler output");
         d_res = (float *)e->tick_res.p;
         std::vector<sk::RowCopy> jobs;
-        std::vector<size_t> ready;
-        std::vector<uint32_t> before;
         sub(3);
-        for (;;) {
-            jobs.clear();
-            ready.clear();
-            for (size_t ci = 0; ci < calls.size(); ++ci) {
-                RsCall &c = calls[ci];
-                const TickCall &t = tc[call_stream[ci]];
-                StreamInfo &s = e->streams[c.id];
-                const uint32_t total_in = t.good * t.ulen;
-                uint32_t take = std::min(total_in - c.consumed, kRsMaxFill - s.rs_fill);  // a tick's units of a stream: one round
-                // Pieces never straddle a unit of the packed synthesis output.  Whole units whose rows lie a constant distance apart
-                // (the usual case: a stream's units of a tick) go down as ONE job per channel.
-                size_t run_at = 0;        // index in `jobs` of the open run's first channel, valid while run_pieces > 0
-                uint32_t run_pieces = 0;
-                uint64_t run_row = 0, run_stride = 0;
-                while (take) {
-                    const uint32_t frame = c.consumed / t.ulen, within = c.consumed % t.ulen;
-                    const uint32_t n = std::min(take, t.ulen - within);
-                    const uint64_t row = unit_row(call_stream[ci], frame);
-                    const bool whole = within == 0 && n == t.ulen;
-                    bool joined = false;
-                    if (whole && run_pieces) {
-                        const uint64_t stride = row - run_row;  // (of a row above the run's last one; anything else starts a new run)
-                        if (row > run_row && (run_pieces == 1 || stride == run_stride) && stride * 1024 <= 0xffffffffull) {
-                            for (uint32_t ch = 0; ch < c.channels; ++ch) {
-                                jobs[run_at + ch].pieces += 1;
-                                jobs[run_at + ch].src_stride = (uint32_t)(stride * 1024);
-                            }
-                            run_stride = stride, run_row = row, run_pieces += 1;
-                            joined = true;
+        RsRounds rounds;
+        rounds.total_in = [&](size_t ci) { return tc[call_stream[ci]].good * tc[call_stream[ci]].ulen; };
+        rounds.append = [&](size_t ci, uint32_t take, uint32_t fill) {
+            const RsCall &c = calls[ci];
+            const TickCall &t = tc[call_stream[ci]];
+            uint32_t consumed = c.consumed;
+            const uint32_t taken = take;
+            // Pieces never straddle a unit of the packed synthesis output.  Whole units whose rows lie a constant distance apart
+            // (the usual case: a stream's units of a tick) go down as ONE job per channel.
+            size_t run_at = 0;        // index in `jobs` of the open run's first channel, valid while run_pieces > 0
+            uint32_t run_pieces = 0;
+            uint64_t run_row = 0, run_stride = 0;
+            while (take) {
+                const uint32_t frame = consumed / t.ulen, within = consumed % t.ulen;
+                const uint32_t n = std::min(take, t.ulen - within);
+                const uint64_t row = unit_row(call_stream[ci], frame);
+                const bool whole = within == 0 && n == t.ulen;
+                bool joined = false;
+                if (whole && run_pieces) {
+                    const uint64_t stride = row - run_row;  // (of a row above the run's last one; anything else starts a new run)
+                    if (row > run_row && (run_pieces == 1 || stride == run_stride) && stride * 1024 <= 0xffffffffull) {
+                        for (uint32_t ch = 0; ch < c.channels; ++ch) {
+                            jobs[run_at + ch].pieces += 1;
+                            jobs[run_at + ch].src_stride = (uint32_t)(stride * 1024);
                         }
+                        run_stride = stride, run_row = row, run_pieces += 1;
+                        joined = true;
                     }
-                    if (!joined) {
-                        run_at = jobs.size();
-                        for (uint32_t ch = 0; ch < c.channels; ++ch)  // MP3 rows hold q / 32768 already: a plain copy
-                            jobs.push_back(sk::RowCopy{(row + ch) * 1024 + within, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + s.rs_fill, n,
-                                                       t.mp3 ? 0u : 1u});
-                        run_pieces = whole ? 1 : 0;
-                        run_row = row;
-                    }
-                    s.rs_fill += n;
-                    c.consumed += n;
-                    take -= n;
                 }
-                if (s.rs_fill >= kRsChunk) ready.push_back(ci);
-            }
-            sub(0);
-            if (jobs.empty() && ready.empty()) break;
-            if (!jobs.empty()) {
-                const sk::RowCopy *d_jobs = nullptr;
-                SK_HIP(aux.put(jobs, e->stream, &d_jobs), "upload tick append jobs");
-                for (size_t j0 = 0; j0 < jobs.size(); j0 += 65535)
-                    SK_HIP(sk::launch_row_copies(d_pcm, e->d_rs, d_jobs + j0, (uint32_t)std::min<size_t>(65535, jobs.size() - j0),
-                                                 e->stream), "tick append chunk");
-            }
-            sub(1);
-            if (!ready.empty()) {
-                rc = rs_process_ready(e, calls, ready, d_res, res_stride, res_cap, aux);
-                if (rc != SK_OK) return rc;
-                sub(2);
-                for (size_t ci : ready) {  // one AudioData per chunk (lib.rs:1979-2003), empty ones are not sent
-                    RsCall &c = calls[ci];
-                    for (const auto &o : c.outs)
-                        if (o.second) tc[call_stream[ci]].chunks.emplace_back(o.first, o.second);
-                    c.outs.clear();
+                if (!joined) {
+                    run_at = jobs.size();
+                    for (uint32_t ch = 0; ch < c.channels; ++ch)  // MP3 rows hold q / 32768 already: a plain copy
+                        jobs.push_back(sk::RowCopy{(row + ch) * 1024 + within, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + fill, n,
+                                                   t.mp3 ? 0u : 1u});
+                    run_pieces = whole ? 1 : 0;
+                    run_row = row;
                 }
+                fill += n;
+                consumed += n;
+                take -= n;
             }
-        }
-        // end of stream: StreamingResampler::flush (lib.rs:2017-2058); a stream that failed is not flushed
-        std::vector<sk::RowCopy> pads;
-        ready.clear();
-        for (size_t ci = 0; ci < calls.size(); ++ci) {
-            const uint32_t i = call_stream[ci];
-            if (!ts[i].flush || tc[i].good != ts[i].n_frames) continue;
-            RsCall &c = calls[ci];
-            StreamInfo &s = e->streams[c.id];
-            const uint32_t remaining = s.rs_fill, padded = kRsChunk - remaining;
-            c.trim = 0;
-            if (remaining > 0 && padded > 0)
-                c.trim = (uint32_t)std::llround(((double)padded * (double)s.rs_out_hz) / (double)s.rs_in_hz);
-            for (uint32_t ch = 0; ch < c.channels && padded; ++ch)
-                for (uint32_t o = 0; o < padded; o += 8192)
-                    pads.push_back(sk::RowCopy{0, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + remaining + o,
-                                               std::min<uint32_t>(8192, padded - o), 0});
-            s.rs_fill = kRsChunk;
-            ready.push_back(ci);
-        }
-        if (!ready.empty()) {
-            if (!pads.empty()) {
-                const sk::RowCopy *d_pads = nullptr;
-                SK_HIP(aux.put(pads, e->stream, &d_pads), "upload tick pad jobs");
-                for (size_t j0 = 0; j0 < pads.size(); j0 += 65535)
-                    SK_HIP(sk::launch_row_copies(e->d_zeros, e->d_rs, d_pads + j0,
-                                                 (uint32_t)std::min<size_t>(65535, pads.size() - j0), e->stream), "tick pad chunk");
-            }
-            before.clear();
-            for (size_t ci : ready) before.push_back(calls[ci].produced);
-            rc = rs_process_ready(e, calls, ready, d_res, res_stride, res_cap, aux);
-            if (rc != SK_OK) return rc;
-            for (size_t k = 0; k < ready.size(); ++k) {
-                const RsCall &c = calls[ready[k]];
-                const uint32_t got = c.produced - before[k];
-                if (got > c.trim) tc[call_stream[ready[k]]].chunks.emplace_back(before[k], got - c.trim);
-            }
-        }
+            return taken;
+        };
+        rounds.launch = [&]() -> int {
+            if (jobs.empty()) return SK_OK;
+            const sk::RowCopy *d_jobs = nullptr;
+            SK_HIP(aux.put(jobs, e->stream, &d_jobs), "upload tick append jobs");
+            for (size_t j0 = 0; j0 < jobs.size(); j0 += 65535)
+                SK_HIP(sk::launch_row_copies(d_pcm, e->d_rs, d_jobs + j0, (uint32_t)std::min<size_t>(65535, jobs.size() - j0),
+                                             e->stream), "tick append chunk");
+            jobs.clear();
+            return SK_OK;
+        };
+        rounds.flush = [&](size_t ci) { return ts[call_stream[ci]].flush && tc[call_stream[ci]].good == ts[call_stream[ci]].n_frames; };
+        rounds.chunks = [&](size_t ci) -> std::vector<std::pair<uint32_t, uint32_t>> & { return tc[call_stream[ci]].chunks; };
+        rounds.sub = sub;
+        rc = rs_run_rounds(e, calls, d_res, res_stride, res_cap, aux, rounds);
+        if (rc != SK_OK) return rc;
     }
 
     sub(3);
@@ -3958,23 +4027,8 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
         const sk::PackJob *d_packs = nullptr;
         SK_HIP(aux.put(packs, e->stream, &d_packs), "upload pack jobs");
         SK_HIP(sk::launch_pack_jobs(d_packs, (uint32_t)packs.size(), max_pack_frames, e->stream), "launch pack");
-        // Into pinned memory the copy is queued like a kernel and the bounded wait below is the tick's only wait.  A caller's
-        // pageable buffer would make hipMemcpyAsync itself wait for everything queued so far, unbounded: such a buffer (the
-        // scheduler's are pinned; a test's numpy array is not) gets the bytes through the engine's pinned bounce buffer.
-        hipPointerAttribute_t pa{};
-        const bool pinned = hipPointerGetAttributes(&pa, out) == hipSuccess && pa.type == hipMemoryTypeHost;
-        if (!pinned) (void)hipGetLastError();
-        if (!pinned) {
-            if (e->h_out_cap < cursor) {
-                if (e->h_out) (void)hipHostFree(e->h_out);
-                e->h_out = nullptr;
-                e->h_out_cap = 0;
-                SK_HIP(hipHostMalloc((void **)&e->h_out, cursor + cursor / 4 + 4096, hipHostMallocDefault), "alloc pinned output bounce");
-                e->h_out_cap = cursor + cursor / 4 + 4096;
-            }
-            bounce = e->h_out;
-        }
-        SK_HIP(hipMemcpyAsync(bounce ? bounce : out, d_out, cursor, hipMemcpyDeviceToHost, e->stream), "D2H tick output");
+        rc = tick_queue_d2h(e, out, d_out, cursor, &bounce);
+        if (rc != SK_OK) return rc;
     }
     lap(3);
     rc = wait_stream(e, "tick: waiting for the device at the end of the tick");
@@ -3988,6 +4042,29 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
     if (out_bytes) *out_bytes = cursor;
     return SK_OK;
 }
+
+// The host-side state a tick advances -- the streaming resamplers' fill, chunk count and time index -- as it stood before the tick
+struct RsSaved {
+    struct Saved {
+        uint32_t id, fill;
+        uint64_t chunks;
+        double last;
+    };
+    std::vector<Saved> saved;
+    void add(const sk_engine *e, uint32_t id) {
+        if (!stream_ok(e, id) || !e->streams[id].rs_open) return;
+        const StreamInfo &s = e->streams[id];
+        saved.push_back(Saved{id, s.rs_fill, s.rs_chunks, s.rs_last_index});
+    }
+    void restore(sk_engine *e) const {
+        for (const Saved &v : saved) {
+            StreamInfo &s = e->streams[v.id];
+            s.rs_fill = v.fill;
+            s.rs_chunks = v.chunks;
+            s.rs_last_index = v.last;
+        }
+    }
+};
 
 // The tick proper (tick_body) under the engine's lock, with the host-side state it advances -- the streaming resamplers'
 // fill, chunk count and time index -- put back when it fails part-way: a failed launch leaves the batch's streams to be
@@ -4013,26 +4090,13 @@ int tick_impl_locked(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams,
                      sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes, const EntropyProbe *probe,
                      const uint8_t *q_sides, const int16_t *q_quant, const TickMp3 &mp3) {
     TickWhere where(e);
-    struct Saved {
-        uint32_t id, fill;
-        uint64_t chunks;
-        double last;
-    };
-    std::vector<Saved> saved;
+    RsSaved saved;
     for (uint32_t i = 0; ts && i < n_streams; ++i)
-        if (ts[i].resample && stream_ok(e, ts[i].stream) && e->streams[ts[i].stream].rs_open) {
-            const StreamInfo &s = e->streams[ts[i].stream];
-            saved.push_back(Saved{ts[i].stream, s.rs_fill, s.rs_chunks, s.rs_last_index});
-        }
+        if (ts[i].resample) saved.add(e, ts[i].stream);
     const int rc = tick_body(e, ts, n_streams, descs, coeffs, units, au_bytes, au_len, n_frames, out, out_cap, outs, outs_cap, n_outs,
                              out_bytes, probe, q_sides, q_quant, mp3);
     if (rc != SK_OK) {
-        for (const Saved &v : saved) {
-            StreamInfo &s = e->streams[v.id];
-            s.rs_fill = v.fill;
-            s.rs_chunks = v.chunks;
-            s.rs_last_index = v.last;
-        }
+        saved.restore(e);
         if (n_outs) *n_outs = 0;
         if (out_bytes) *out_bytes = 0;
         // whatever was queued before the failure must be off the stream before the caller reuses its buffers
@@ -4041,6 +4105,309 @@ int tick_impl_locked(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams,
     return rc;
 }
 
+
+// ---- sk_tick_run_pcm: the tick of the WAV / raw PCM streams ------------------------------------------------------------------
+
+struct PcmCall {  // one sk_pcm_tick_stream
+    uint32_t first = 0;        // index of its first unit
+    uint32_t frame_bytes = 0;  // of the source
+    uint32_t total_frames = 0;
+    uint32_t ch_out = 0;
+    uint8_t fmt_out = 0;       // SK_FMT_S16LE / S24LE / S32LE / F32LE
+    bool exact = false, float_out = false;
+    int rs_call = -1;
+    uint32_t unit = 0, within = 0;  // where the resampler rounds stand: unit (relative to first) and frame inside it
+    std::vector<std::pair<uint32_t, uint32_t>> chunks;  // (column, frames) of each resampled AudioData
+};
+
+bool pcm_fmt_is_float(int fmt) { return fmt == SK_FMT_F32LE || fmt == SK_FMT_F32BE; }
+uint32_t pcm_fmt_bits(int fmt) { return fmt <= SK_FMT_S16BE ? 16 : (fmt <= SK_FMT_S24BE ? 24 : 32); }
+
+// Checks the table and fills in what follows from it.  SK_OK, or the status sk_tick_run_pcm returns.
+int pcm_tick_plan(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, size_t bytes_len,
+                  std::vector<PcmCall> &pc) {
+    pc.assign(n_streams, PcmCall{});
+    std::vector<uint8_t> seen(e->streams.size(), 0);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_pcm_tick_stream &t = ts[i];
+        PcmCall &c = pc[i];
+        if (t.format > SK_FMT_F32BE) return SK_ERR_INVALID_ARG;
+        if (t.channels == 0 || t.out_channels == 0) return SK_ERR_INVALID_ARG;
+        if (t.channels > SK_MAX_CHANNELS) return SK_ERR_UNSUPPORTED;
+        if (t.out_bits != 16 && t.out_bits != 24 && t.out_bits != 32) return SK_ERR_INVALID_ARG;
+        const uint32_t bits = pcm_fmt_bits(t.format);
+        // the fast path (lib.rs:3339-3345) needs no device: such a stream's pieces are delivered as they are, by the caller
+        if (!t.resample && t.out_bits == bits && t.out_channels == t.channels) return SK_ERR_INVALID_ARG;
+        if (t.resample) {
+            if (!stream_ok(e, t.stream) || !e->streams[t.stream].rs_open || e->streams[t.stream].channels != t.channels) return SK_ERR_BAD_STREAM;
+            if (seen[t.stream]++) return SK_ERR_INVALID_ARG;  // a stream appears once per tick
+        } else if (t.flush) {
+            return SK_ERR_INVALID_ARG;
+        }
+        c.first = (uint32_t)at;
+        c.frame_bytes = bits / 8 * t.channels;
+        c.ch_out = t.out_channels < t.channels ? t.out_channels : t.channels;
+        c.float_out = t.out_bits == 32 && pcm_fmt_is_float(t.format);  // lib.rs:3377-3382
+        c.fmt_out = (uint8_t)(c.float_out ? SK_FMT_F32LE : (t.out_bits == 16 ? SK_FMT_S16LE : (t.out_bits == 24 ? SK_FMT_S24LE : SK_FMT_S32LE)));
+        c.exact = !t.resample && t.out_channels == t.channels && t.out_bits == 16 && !pcm_fmt_is_float(t.format) && bits > 16;  // lib.rs:3349-3356
+        if (at + t.n_units > n_units) return SK_ERR_INVALID_ARG;
+        uint64_t frames = 0;
+        for (uint32_t u = 0; u < t.n_units; ++u) {
+            const sk_pcm_unit &un = units[at + u];
+            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len > 0x7fffffffu || un.byte_len % c.frame_bytes) return SK_ERR_INVALID_ARG;
+            if (un.byte_offset > bytes_len || un.byte_len > bytes_len - un.byte_offset) return SK_ERR_INVALID_ARG;
+            frames += un.byte_len / c.frame_bytes;
+        }
+        if (frames > 0x7fffffffull) return SK_ERR_INVALID_ARG;
+        c.total_frames = (uint32_t)frames;
+        at += t.n_units;
+    }
+    return at == n_units ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// frames one 4096-frame chunk of this stream's resampler can produce (+ slack)
+uint64_t pcm_chunk_out_frames(const StreamInfo &s) {
+    return (uint64_t)std::ceil((double)kRsChunk * (double)s.rs_out_hz / (double)s.rs_in_hz) + 2;
+}
+
+size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                          uint32_t *max_outputs) {
+    std::vector<PcmCall> pc;
+    if (max_outputs) *max_outputs = 0;
+    if (pcm_tick_plan(e, ts, n_streams, units, n_units, (size_t)-1, pc) != SK_OK) return 0;
+    size_t bytes = 0;
+    uint64_t outs = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const uint64_t frame_out = (uint64_t)ts[i].out_bits / 8 * pc[i].ch_out;
+        if (ts[i].resample) {
+            const StreamInfo &s = e->streams[ts[i].stream];
+            const uint64_t chunks = ((uint64_t)s.rs_fill + pc[i].total_frames) / kRsChunk + 1;  // + the flush
+            bytes += chunks * (pcm_chunk_out_frames(s) * frame_out + 16) + 16;
+            outs += chunks;
+        } else {
+            bytes += (uint64_t)pc[i].total_frames * frame_out + (uint64_t)ts[i].n_units * 16 + 16;
+            outs += ts[i].n_units;
+        }
+    }
+    if (max_outputs) *max_outputs = (uint32_t)std::min<uint64_t>(outs + 1, 0xffffffffu);
+    return bytes;
+}
+
+int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                  size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) {
+    if (!e || !n_outs || (n_streams && !ts) || (n_units && (!units || !bytes))) return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    if (n_streams == 0) return n_units == 0 ? SK_OK : SK_ERR_INVALID_ARG;
+    DeviceGuard guard(e);
+    std::vector<PcmCall> pc;
+    int rc = pcm_tick_plan(e, ts, n_streams, units, n_units, bytes_len, pc);
+    if (rc != SK_OK) return rc;
+
+    // from here to the tick's last wait the device belongs to this engine (see g_device_turn)
+    std::unique_lock<std::mutex> turn;
+    if (g_engines_on_device[e->device & 15].load() > kTurnFrom) turn = std::unique_lock<std::mutex>(g_device_turn[e->device & 15]);
+
+    // ---- the resampling streams' calls and what they can produce ----
+    std::vector<RsCall> calls;
+    std::vector<uint32_t> call_stream;  // RsCall -> index into ts
+    size_t res_rows = 0;
+    uint32_t res_cap = 0;
+    uint64_t chunk_bound = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        if (!ts[i].resample) continue;
+        const StreamInfo &s = e->streams[ts[i].stream];
+        RsCall c;
+        c.id = ts[i].stream;
+        c.channels = ts[i].channels;
+        c.row0 = res_rows;
+        res_rows += c.channels;
+        pc[i].rs_call = (int)calls.size();
+        calls.push_back(c);
+        call_stream.push_back(i);
+        const uint64_t max_chunks = ((uint64_t)s.rs_fill + pc[i].total_frames) / kRsChunk + 1;
+        if (max_chunks * pcm_chunk_out_frames(s) > 0x7fffffffull) return SK_ERR_INVALID_ARG;
+        res_cap = std::max<uint32_t>(res_cap, (uint32_t)(max_chunks * pcm_chunk_out_frames(s)));
+        chunk_bound += max_chunks;
+    }
+    const size_t res_stride = ((size_t)res_cap + 3) & ~(size_t)3;
+    if (res_rows * res_stride > 0xffffffffull) return SK_ERR_INVALID_ARG;
+
+    const size_t arena_bytes = ((size_t)4 << 20) + (size_t)n_units * 256 + (size_t)n_streams * 1024 + (size_t)chunk_bound * 512;
+    SK_HIP(e->tick_pcm_in.reserve(bytes_len + 64), "alloc tick pcm input");
+    SK_HIP(e->tick_arena.reserve(arena_bytes), "alloc tick arena");
+    if (e->h_arena_cap < e->tick_arena.cap) {
+        if (e->h_arena) (void)hipHostFree(e->h_arena);
+        e->h_arena = nullptr;
+        e->h_arena_cap = 0;
+        SK_HIP(hipHostMalloc((void **)&e->h_arena, e->tick_arena.cap, hipHostMallocDefault), "alloc pinned arena");
+        e->h_arena_cap = e->tick_arena.cap;
+    }
+    AuxArena aux{(uint8_t *)e->tick_arena.p, e->tick_arena.cap, 0, e->h_arena};
+    const uint8_t *d_in = (const uint8_t *)e->tick_pcm_in.p;
+    e->where.store("tick (pcm): upload, ingest, resampler rounds");
+    if (bytes_len) SK_HIP(hipMemcpyAsync(e->tick_pcm_in.p, bytes, bytes_len, hipMemcpyHostToDevice, e->stream), "H2D tick pcm bytes");
+
+    // ---- streaming resamplers: k_pcm_ingest in the place of the row copies ----
+    float *d_res = nullptr;
+    if (!calls.empty()) {
+        SK_HIP(e->tick_res.reserve(res_rows * res_stride * 4 + 16), "alloc tick resampler output");
+        d_res = (float *)e->tick_res.p;
+        std::vector<sk::PcmIngestJob> jobs;
+        uint32_t max_samples = 0;
+        RsRounds rounds;
+        rounds.total_in = [&](size_t ci) { return pc[call_stream[ci]].total_frames; };
+        rounds.append = [&](size_t ci, uint32_t take, uint32_t fill) {
+            const uint32_t i = call_stream[ci];
+            PcmCall &c = pc[i];
+            uint32_t taken = 0;
+            while (take) {
+                const sk_pcm_unit &un = units[c.first + c.unit];
+                const uint32_t left = un.byte_len / c.frame_bytes - c.within;
+                uint32_t n = std::min(take, left);
+                // a unit that does not fit is cut where its next piece starts 16-byte aligned again (c.within stays a multiple of kPcmCutFrames)
+                if (n < left) n &= ~(sk::kPcmCutFrames - 1);
+                if (n == 0) break;
+                sk::PcmIngestJob j{};
+                j.src = d_in + un.byte_offset + (size_t)c.within * c.frame_bytes;
+                j.dst0 = e->d_rs + ((uint64_t)calls[ci].id * 2) * kRsRow + kRsBase + kRsHist + fill;
+                j.dst1 = j.dst0 + kRsRow;
+                j.frames = n;
+                j.fmt = ts[i].format;
+                j.ch = ts[i].channels;
+                jobs.push_back(j);
+                max_samples = std::max(max_samples, n * ts[i].channels);
+                fill += n, taken += n, take -= n;
+                c.within += n;
+                if (n != left) break;  // the rest of this unit goes down in the next round
+                c.unit += 1, c.within = 0;
+            }
+            return taken;
+        };
+        rounds.launch = [&]() -> int {
+            if (jobs.empty()) return SK_OK;
+            const sk::PcmIngestJob *d_jobs = nullptr;
+            SK_HIP(aux.put(jobs, e->stream, &d_jobs), "upload tick pcm ingest jobs");
+            SK_HIP(sk::launch_pcm_ingest(d_jobs, (uint32_t)jobs.size(), max_samples, e->stream), "tick pcm ingest");
+            jobs.clear();
+            max_samples = 0;
+            return SK_OK;
+        };
+        rounds.flush = [&](size_t ci) { return ts[call_stream[ci]].flush != 0; };
+        rounds.chunks = [&](size_t ci) -> std::vector<std::pair<uint32_t, uint32_t>> & { return pc[call_stream[ci]].chunks; };
+        rounds.sub = [](int) {};
+        rc = rs_run_rounds(e, calls, d_res, res_stride, res_cap, aux, rounds);
+        if (rc != SK_OK) return rc;
+    }
+
+    // ---- output records, and the jobs that fill them ----
+    e->where.store("tick (pcm): direct conversion, pack");
+    std::vector<sk::PcmDirectJob> directs;
+    std::vector<sk::PackJob> packs;
+    uint32_t n_rec = 0, max_pack_frames = 0, max_direct_samples = 0;
+    size_t cursor = 0;
+    uint8_t *d_out = nullptr;
+    auto emit = [&](uint32_t stream_index, uint32_t frames, const PcmCall &c, uint32_t bits) -> sk_tick_output * {
+        if (n_rec >= outs_cap) return nullptr;
+        sk_tick_output &o = outs[n_rec++];
+        o.stream_index = stream_index;
+        o.frames = frames;
+        o.channels = (uint8_t)c.ch_out;
+        o.bits = (uint8_t)bits;
+        o.reserved = c.float_out ? SK_TICK_OUT_FLOAT : 0;
+        o.status = 0;
+        o.bytes = frames * c.ch_out * (bits / 8);
+        o.byte_offset = cursor;
+        cursor += ((size_t)o.bytes + 15) & ~(size_t)15;
+        return &o;
+    };
+    // first pass sizes the output, second creates the jobs (the device buffer may move when it grows)
+    for (int pass = 0; pass < 2; ++pass) {
+        n_rec = 0;
+        cursor = 0;
+        for (uint32_t i = 0; i < n_streams; ++i) {
+            const sk_pcm_tick_stream &t = ts[i];
+            const PcmCall &c = pc[i];
+            if (!t.resample) {
+                for (uint32_t u = 0; u < t.n_units; ++u) {
+                    const sk_pcm_unit &un = units[c.first + u];
+                    const uint32_t frames = un.byte_len / c.frame_bytes;
+                    sk_tick_output *o = emit(i, frames, c, t.out_bits);
+                    if (!o) return SK_ERR_INVALID_ARG;
+                    if (pass) {
+                        sk::PcmDirectJob j{};
+                        j.src = d_in + un.byte_offset;
+                        j.dst = d_out + o->byte_offset;
+                        j.frames = frames;
+                        j.fmt_in = t.format, j.fmt_out = c.fmt_out, j.ch_in = t.channels, j.ch_out = (uint8_t)c.ch_out;
+                        j.exact = c.exact ? 1 : 0;
+                        directs.push_back(j);
+                        max_direct_samples = std::max(max_direct_samples, frames * t.channels);
+                    }
+                }
+            } else {
+                const RsCall &rs = calls[(size_t)c.rs_call];
+                for (const auto &chunk : c.chunks) {
+                    sk_tick_output *o = emit(i, chunk.second, c, t.out_bits);
+                    if (!o) return SK_ERR_INVALID_ARG;
+                    if (pass) {
+                        const float *src = d_res + rs.row0 * res_stride + chunk.first;
+                        packs.push_back(sk::PackJob{src, src + res_stride, d_out + o->byte_offset, chunk.second, t.channels, (uint8_t)c.ch_out, t.out_bits,
+                                                    (uint8_t)(c.float_out ? sk::kPackPlainF32 : sk::kPackPlain)});
+                        max_pack_frames = std::max(max_pack_frames, chunk.second);
+                    }
+                }
+            }
+        }
+        if (pass == 0) {
+            if (cursor > out_cap || (cursor && !out)) return SK_ERR_INVALID_ARG;
+            SK_HIP(e->tick_out.reserve(cursor + 16), "alloc tick output");
+            d_out = (uint8_t *)e->tick_out.p;
+        }
+    }
+    if (!directs.empty()) {
+        const sk::PcmDirectJob *d_jobs = nullptr;
+        SK_HIP(aux.put(directs, e->stream, &d_jobs), "upload tick pcm direct jobs");
+        SK_HIP(sk::launch_pcm_direct(d_jobs, (uint32_t)directs.size(), max_direct_samples, e->stream), "tick pcm direct");
+    }
+    if (!packs.empty()) {
+        const sk::PackJob *d_packs = nullptr;
+        SK_HIP(aux.put(packs, e->stream, &d_packs), "upload pack jobs");
+        SK_HIP(sk::launch_pack_jobs(d_packs, (uint32_t)packs.size(), max_pack_frames, e->stream), "launch pack");
+    }
+    uint8_t *bounce = nullptr;
+    if (cursor) {
+        rc = tick_queue_d2h(e, out, d_out, cursor, &bounce);
+        if (rc != SK_OK) return rc;
+    }
+    rc = wait_stream(e, "tick (pcm): waiting for the device at the end of the tick");
+    if (rc != SK_OK) return rc;
+    if (bounce) std::memcpy(out, bounce, cursor);
+    *n_outs = n_rec;
+    if (out_bytes) *out_bytes = cursor;
+    return SK_OK;
+}
+
+// tick_pcm_body under the engine's lock; the resamplers' host bookkeeping is put back when it fails, as tick_impl_locked does
+int tick_pcm_impl(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                  size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) {
+    if (!e) return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    TickWhere where(e);
+    RsSaved saved;
+    for (uint32_t i = 0; ts && i < n_streams; ++i)
+        if (ts[i].resample) saved.add(e, ts[i].stream);
+    const int rc = tick_pcm_body(e, ts, n_streams, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes);
+    if (rc != SK_OK) {
+        saved.restore(e);
+        if (n_outs) *n_outs = 0;
+        if (out_bytes) *out_bytes = 0;
+        // whatever was queued before the failure must be off the stream before the caller reuses its buffers
+        if (rc != SK_ERR_TIMEOUT) (void)hipStreamSynchronize(e->stream);
+    }
+    return rc;
+}
 
 // sk_tick_run_mixed_md: the MP3 streams' units arrive as frames with main data (ts[i].n_frames = frames of stream i).  A first
 // pass of k_mp3_entropy gives every frame's verdict (one synchronisation: a dropped frame changes its stream's unit count, which the
@@ -4195,6 +4562,26 @@ int sk_tick_run_mixed_md(sk_engine *e, const sk_tick_stream *ts, uint32_t n_stre
     return tick_impl_md(e, ts, n_streams, in, md, out, out_cap, outs, outs_cap, n_outs, out_bytes);
 } catch (...) {
     return sk::abi_caught("sk_tick_run_mixed_md");
+}
+
+size_t sk_tick_pcm_out_bound_on(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!ts && n_streams) || (!units && n_units)) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, ts, n_streams, units, n_units, max_outputs);
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_pcm_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_pcm(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                    size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) try {
+    sk::abi_enter();
+    return tick_pcm_impl(e, ts, n_streams, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes);
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_pcm");
 }
 
 int sk_aac_entropy_decode(sk_engine *e, const uint32_t *streams, const uint32_t *units_per_stream, uint32_t n_streams,

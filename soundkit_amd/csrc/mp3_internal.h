@@ -98,6 +98,10 @@ struct PipelineGpuHooks {
     int (*install_codebook)(sk_engine *, const uint32_t *words, size_t n_words) = nullptr;
     int (*tick_md)(sk_engine *, const sk_tick_stream *, uint32_t, const sk_tick_input *, const sk_tick_mp3_frames *, uint8_t *, size_t, sk_tick_output *,
                    uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_mixed_md
+    // the WAV / raw PCM streams' tick; with these absent a PCM stream that needs a conversion ends with SK_ERR_UNSUPPORTED
+    int (*tick_pcm)(sk_engine *, const sk_pcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
+                    sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_pcm
+    size_t (*tick_pcm_out_bound)(sk_engine *, const sk_pcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
 };
 PipelineGpuHooks &pipeline_gpu_hooks();  // pipeline.cpp
 }  // namespace sk_mp3_internal

@@ -7,6 +7,7 @@
 // aligned access the element size allows (8/12/16 B loads, 8/16 B stores), integer results
 // are bit-exact, and float->int follows Rust's `as` casts (truncate, saturate, NaN -> 0).
 #include "sk_device.h"
+#include "pcm_sample.h"  // the per-sample arithmetic, shared with pcm_tick.hip
 
 #include "../../include/soundkit_amd.h"
 
@@ -14,32 +15,7 @@ namespace sk {
 
 namespace {
 
-// ---- Rust cast semantics ---------------------------------------------------------------
-__device__ __forceinline__ int f32_as_i32(float x) {
-    if (x != x) return 0;
-    if (x <= -2147483648.0f) return INT32_MIN;
-    if (x >= 2147483648.0f) return INT32_MAX;
-    return (int)x;
-}
-__device__ __forceinline__ int f32_as_i16(float x) {
-    if (x != x) return 0;
-    if (x <= -32768.0f) return -32768;
-    if (x >= 32767.0f) return 32767;
-    return (int)x;
-}
-__device__ __forceinline__ float clamp1(float x) {  // f32::clamp(-1, 1): NaN stays NaN
-    if (x < -1.0f) x = -1.0f;
-    if (x > 1.0f) x = 1.0f;
-    return x;
-}
-__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xff) << 8) | ((v >> 8) & 0xff); }
-__device__ __forceinline__ int sext24(uint32_t v) { return (int)(((v & 0xffffffu) ^ 0x800000u) - 0x800000u); }
-__device__ __forceinline__ int sext16(uint32_t v) { return (int)(short)(unsigned short)v; }
-__device__ __forceinline__ uint32_t be24(uint32_t v) { return ((v & 0xff) << 16) | (v & 0xff00) | ((v >> 16) & 0xff); }
 
-// soundkit-decoder lib.rs:1815-1827; the f64-free exact form of sk_device.h (exhaustively equal, tools/check_f32_rounding.c)
-__device__ __forceinline__ int float_sample_to_i16(float s) { return dev_float_sample_to_i16_f32(s); }
 __device__ __forceinline__ int mp3_f32_to_i16(float s) {  // soundkit-mp3 lib.rs:376-385
     const float scaled = roundf(s * 32767.0f);
     if (scaled > 32767.0f) return 32767;
@@ -51,13 +27,6 @@ __device__ __forceinline__ int mp3_f32_to_i32(float s) {  // soundkit-mp3 lib.rs
     if (scaled > 2147483648.0f) return INT32_MAX;
     if (scaled < -2147483648.0f) return INT32_MIN;
     return f32_as_i32(scaled);
-}
-__device__ __forceinline__ int f32_to_i32_pcm(float x) {  // audio_bytes.rs:194-199 (both scales are 2^31 in f32)
-    return f32_as_i32(clamp1(x) * 2147483648.0f);
-}
-__device__ __forceinline__ int f32_to_s24_pcm(float x) {  // audio_bytes.rs:210-216
-    const float c = clamp1(x);
-    return c >= 0.0f ? f32_as_i32(c * 8388607.0f) : f32_as_i32(c * 8388608.0f);
 }
 
 // raw = the input element's bytes, little-endian packed in the low bits; returns output bits
@@ -112,23 +81,6 @@ __device__ __forceinline__ uint32_t extract(const uint32_t (&w)[IB], int s) {
     return (uint32_t)(pair >> sh) & 0xffffff;
 }
 
-// Scalar element access.  2- and 4-byte elements are naturally aligned (API contract), so they move
-// as one typed access; only 3-byte samples go byte by byte.  (Splitting a sign-extended value into
-// byte stores is also what hipcc 7.2 folds into a zero-extending v_perm_b32 -- avoid that shape.)
-__device__ __forceinline__ uint32_t load_raw_scalar(const uint8_t *p, int ib) {
-    if (ib == 4) return *reinterpret_cast<const uint32_t *>(p);
-    if (ib == 2) return *reinterpret_cast<const uint16_t *>(p);
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-}
-__device__ __forceinline__ void store_raw_scalar(uint8_t *p, uint32_t v, int ob) {
-    if (ob == 4) {
-        *reinterpret_cast<uint32_t *>(p) = v;
-    } else if (ob == 2) {
-        *reinterpret_cast<uint16_t *>(p) = (uint16_t)v;
-    } else {
-        p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16);
-    }
-}
 
 // grid-stride over groups of 4 samples; VEC = both buffers 16-byte aligned
 template <int OP, bool VEC>
@@ -222,21 +174,6 @@ __global__ __launch_bounds__(256) void k_deinterleave_s24(const uint8_t *in, int
     }
 }
 
-__device__ __forceinline__ float sample_to_f32(int variant, int fmt, uint32_t raw) {
-    float s;
-    switch (fmt) {
-    case SK_FMT_F32LE: s = __uint_as_float(raw); break;
-    case SK_FMT_F32BE: s = __uint_as_float(bswap32(raw)); break;
-    case SK_FMT_S16LE: s = (float)sext16(raw) / 32768.0f; break;
-    case SK_FMT_S16BE: s = (float)sext16(bswap16(raw)) / 32768.0f; break;
-    case SK_FMT_S24LE: s = (float)sext24(raw) / (variant == 0 ? 8388608.0f : 2147483648.0f); break;
-    case SK_FMT_S24BE: s = (float)sext24(be24(raw)) / 8388608.0f; break;
-    case SK_FMT_S32LE: s = (float)(int)raw / 2147483648.0f; break;
-    default: s = (float)(int)bswap32(raw) / 2147483648.0f; break;
-    }
-    if (variant == 0 && !isfinite(s)) s = 0.0f;  // soundkit-decoder lib.rs:3614
-    return s;
-}
 
 __global__ __launch_bounds__(256) void k_bytes_to_f32_planar(int variant, int fmt, int bps, const uint8_t *in,
                                                              size_t frames, uint32_t ch, float *planar) {
@@ -276,17 +213,6 @@ __global__ __launch_bounds__(256) void k_s16le_stereo_to_f32_planar(const uint8_
     }
 }
 
-__device__ __forceinline__ uint32_t f32_to_sample(int fmt, float x) {
-    switch (fmt) {
-    case SK_FMT_F32LE: return __float_as_uint(x);
-    case SK_FMT_S16LE: return (uint32_t)float_sample_to_i16(x) & 0xffff;
-    case SK_FMT_S24LE: {  // soundkit-decoder lib.rs:3649-3661
-        const float c = clamp1(x);
-        return (uint32_t)(c >= 0.0f ? f32_as_i32(c * 8388607.0f) : f32_as_i32(c * 8388608.0f)) & 0xffffff;
-    }
-    default: return (uint32_t)f32_to_i32_pcm(x);  // S32LE, lib.rs:3664-3677
-    }
-}
 
 __global__ __launch_bounds__(256) void k_f32_planar_to_bytes(int fmt, int bps, const float *planar, size_t frames,
                                                              uint32_t ch, uint8_t *out) {
@@ -383,13 +309,8 @@ __global__ __launch_bounds__(256) void k_downmix_mono(const float *planar, size_
 __global__ __launch_bounds__(256) void k_exact_to_i16(int fmt, const uint8_t *in, size_t samples, uint8_t *out) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < samples; i += stride) {
-        int s;
-        switch (fmt) {
-        case SK_FMT_S24LE: s = sext24(load_raw_scalar(in + i * 3, 3)) >> 8; break;
-        case SK_FMT_S24BE: s = sext24(be24(load_raw_scalar(in + i * 3, 3))) >> 8; break;
-        case SK_FMT_S32LE: s = (int)reinterpret_cast<const uint32_t *>(in)[i] >> 16; break;
-        default: s = (int)bswap32(reinterpret_cast<const uint32_t *>(in)[i]) >> 16; break;
-        }
+        const uint32_t raw = (fmt == SK_FMT_S24LE || fmt == SK_FMT_S24BE) ? load_raw_scalar(in + i * 3, 3) : reinterpret_cast<const uint32_t *>(in)[i];
+        const uint32_t s = exact_sample_to_i16(fmt, raw);
         reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)s;
     }
 }
@@ -409,7 +330,7 @@ __global__ __launch_bounds__(256) void k_pack_jobs(const PackJob *jobs, uint32_t
     const uint32_t f0 = blockIdx.x * 1024;
     if (f0 >= job.frames) return;
     const uint32_t f1 = min(f0 + 1024u, job.frames);
-    const int fmt = job.bits == 16 ? SK_FMT_S16LE : (job.bits == 24 ? SK_FMT_S24LE : SK_FMT_S32LE);
+    const int fmt = job.mode == kPackPlainF32 ? SK_FMT_F32LE : (job.bits == 16 ? SK_FMT_S16LE : (job.bits == 24 ? SK_FMT_S24LE : SK_FMT_S32LE));
     const uint32_t bps = job.bits / 8;
     for (uint32_t f = f0 + threadIdx.x; f < f1; f += 256) {
         float x[2];

@@ -16,7 +16,8 @@
 // delivered, so its frames reach the engine in order and its outputs never overtake each other.
 #include "../../include/soundkit_amd.h"
 #include "sk_abi.h"
-#include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage
+#include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
+#include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
 #include <hip/hip_runtime.h>
 
@@ -47,6 +48,7 @@ struct Output {
     int32_t status = 0;
     uint32_t rate = 0, frames = 0;
     uint8_t bits = 0, channels = 0;
+    uint8_t flags = 0;          // SK_AUDIO_FLOAT | SK_AUDIO_BIG_ENDIAN (sk_audio_info::reserved)
     std::vector<uint8_t> data;  // PCM bytes, or the error text
 };
 
@@ -74,8 +76,22 @@ struct PStream {
     uint8_t codec = 0;
     std::vector<uint8_t> mp3_reservoir;  // main data of the frames seen so far (main_data_begin reaches back into it)
     uint32_t mp3_free_format = 0;        // a free-format stream's frame length once measured (sk_mp3_scan_free)
+    // WAV / raw PCM streams (FormatDecoder::Wav / RawPcm, lib.rs:2292-2297): the stream processor, and what its first piece decided
+    std::unique_ptr<sk_pcm::WavStream> wav;
+    std::unique_ptr<sk_pcm::RawPcmStream> raw;
+    sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
+    bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
+    uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
+    uint8_t pcm_fmt = 0, pcm_flags = 0;  // SK_FMT_* of the source (kPcmTick) / SK_AUDIO_* of its pieces
+    uint8_t pcm_bits = 0;
+    uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2;
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2;
+// The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
+// 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
+constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
+constexpr size_t kMinDetectionBytes = 8192, kMaxDetectionBytes = 65536;  // MIN_ / MAX_DETECTION_BYTES, lib.rs:75-76
 
 struct BatchEntry {  // bookkeeping beside one sk_tick_stream
     uint32_t handle = 0;
@@ -87,6 +103,10 @@ struct BatchEntry {  // bookkeeping beside one sk_tick_stream
     // (stereo tools, TNS, the unit's tail) can be given the reference's message by parsing them again on the host
     std::vector<uint8_t> raw;
     std::vector<uint32_t> raw_len;
+    // a WAV / raw PCM stream's pass: it has no row in the AAC / MP3 tick; `pre` are the pieces of a fast-path stream (lib.rs:3339-3345),
+    // delivered as they are, in front of whatever the PCM tick gives the entry (nothing, for such a stream)
+    bool pcm = false, pcm_row = false;  // pcm_row: it has a row in the batch's PCM tick
+    std::vector<Output> pre;
 };
 
 struct Batch {
@@ -110,6 +130,13 @@ struct Batch {
     std::vector<sk_mp3_frame_item> mp3_frames;
     std::vector<uint32_t> mp3_frames_of;
     size_t n_mp3_frames = 0;
+    // WAV / raw PCM streams' units (sk_tick_run_pcm through pipeline_gpu_hooks()): pieces in pcm_bytes (pinned, ensure_pcm), one table
+    // row per stream with units or a flush, pcm_entry[row] = its entry
+    uint8_t *pcm_bytes = nullptr;
+    size_t pcm_cap = 0, pcm_used = 0;
+    std::vector<sk_pcm_tick_stream> pcm_ts;
+    std::vector<sk_pcm_unit> pcm_units;
+    std::vector<uint32_t> pcm_entry;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -129,6 +156,10 @@ struct Batch {
         mp3_rows = 0;
         n_mp3_frames = 0;
         mp3_frames_of.clear();
+        pcm_used = 0;
+        pcm_ts.clear();
+        pcm_units.clear();
+        pcm_entry.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -187,6 +218,9 @@ struct sk_lane {
     // (sk_tick_run_mixed_md, reached through pipeline_gpu_hooks()).  cfg.gpu_entropy holds 1 then: the AAC streams' mode.
     bool mp3_gpu = false;
     std::vector<uint32_t> mp3_blob;  // mp3_cb flattened for the device (sk_mp3_codebook_flatten)
+    // WAV / raw PCM: the batches' pinned byte buffers, made when the first stream that needs the PCM tick shows up
+    std::mutex pcm_mu;
+    std::atomic<bool> pcm_ready{false};
 
     std::vector<std::thread> workers;
     std::thread submitter;
@@ -242,6 +276,8 @@ void release_device_side(sk_lane *p, PStream &s) {
         s.pending_pos = 0;
         s.mp3_reservoir.clear();
         s.mp3_reservoir.shrink_to_fit();
+        s.wav.reset();
+        s.raw.reset();
     }
     if (engine_stream != kNoStream) (void)sk_stream_close(p->engine, engine_stream);  // also drops its resampler
     if (fe) sk_aac_decoder_destroy(fe);
@@ -265,6 +301,12 @@ struct Parsed {  // what one worker pass produced for one stream
     // ... or, with the Huffman stage on the device, its frames (byte_offset into mp3_bytes; n_au_bytes = mp3_bytes.size())
     std::vector<sk_mp3_frame_item> mp3_frames;
     std::vector<uint8_t> mp3_bytes;
+    // a WAV / raw PCM stream's pass (n_frames stays 0): pieces for the PCM tick, each at a 16-byte aligned offset of pcm_bytes, or --
+    // fast path -- finished outputs; `more`: the pass stopped at a limit with input left
+    bool pcm = false, more = false;
+    std::vector<uint8_t> pcm_bytes;
+    std::vector<sk_pcm_unit> pcm_units;
+    std::vector<Output> pre;
 };
 
 // 1 = a chunk was appended to s.pending, 0 = nothing queued right now, -1 = the end-of-stream marker was taken (s.saw_eof set)
@@ -308,6 +350,13 @@ namespace {
 // What the stream's first bytes are (detect_audio at lib.rs:3042 looks at magic numbers; on this path two formats exist):
 // an ID3v2 tag or an MPEG audio sync with a layer field -> MP3; an ADTS sync (layer bits 00) -> AAC.  0 = not enough bytes yet.
 uint8_t sniff_codec(const uint8_t *d, size_t n) {
+    // RIFF....WAVE / RF64....WAVE -> WAV (AudioType::Wav, lib.rs:3090-3093); fewer than 12 bytes that may still become that: wait
+    if (n >= 4 && (std::memcmp(d, "RIFF", 4) == 0 || std::memcmp(d, "RF64", 4) == 0)) {
+        if (n < 12) return 0;
+        if (std::memcmp(d + 8, "WAVE", 4) == 0) return kCodecWav;
+    } else if (n > 0 && n < 4 && (std::memcmp(d, "RIFF", n) == 0 || std::memcmp(d, "RF64", n) == 0)) {
+        return 0;
+    }
     if (n >= 3 && d[0] == 'I' && d[1] == 'D' && d[2] == '3') return kCodecMp3;
     for (size_t i = 0; i + 1 < n; ++i)
         if (d[i] == 0xff && (d[i + 1] & 0xe0) == 0xe0) return ((d[i + 1] >> 1) & 3) == 0 ? kCodecAac : kCodecMp3;
@@ -459,9 +508,173 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
     }
 }
 
+
+// The batches' pinned buffers for PCM pieces.  Once per lane, at the first stream that needs the PCM tick.
+int ensure_pcm(sk_lane *p) {
+    if (p->pcm_ready.load(std::memory_order_acquire)) return SK_OK;
+    std::lock_guard<std::mutex> lk(p->pcm_mu);
+    if (p->pcm_ready.load(std::memory_order_relaxed)) return SK_OK;
+    std::lock_guard<std::mutex> bl(p->batch_mu);  // no claim can name these buffers yet: a PCM pass stages units only behind this function
+    for (Batch &b : p->batches) {
+        if (b.pcm_bytes) continue;
+        if (hipHostMalloc((void **)&b.pcm_bytes, kPcmTickBytes + 64, hipHostMallocPortable) != hipSuccess) {
+            b.pcm_bytes = nullptr;
+            return SK_ERR_OOM;
+        }
+        b.pcm_cap = kPcmTickBytes;
+    }
+    p->pcm_ready.store(true, std::memory_order_release);
+    return SK_OK;
+}
+
+// The first piece of a WAV / raw PCM stream fixes what apply_output_options (lib.rs:3324-3456) does with all of them: nothing
+// (the fast path), or a conversion -- the PCM tick's, which needs the stream's format among SK_FMT_*, one or two channels and,
+// for a rate change, an engine stream with a resampler.  false: the stream has failed (r says how).
+bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
+    auto fail = [&](int32_t st, const std::string &msg) {
+        r.failed = true;
+        r.fail_status = st;
+        r.fail_msg = msg;
+        return false;
+    };
+    uint32_t rate, channels, bits;
+    bool is_float, big_endian = false;
+    if (s.wav) {
+        rate = s.wav->sample_rate(), channels = s.wav->channels(), bits = s.wav->bits(), is_float = s.wav->is_float();
+    } else {
+        const int f = s.raw_format.format;
+        rate = s.raw_format.sample_rate, channels = s.raw_format.channels;
+        bits = f <= SK_FMT_S16BE ? 16 : (f <= SK_FMT_S24BE ? 24 : 32);
+        is_float = f >= SK_FMT_F32LE;
+        big_endian = (f & 1) != 0;
+    }
+    if (channels > 255 || bits > 255) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: WAV channel count or sample width above 255");
+    s.rate = rate;
+    s.channels = (uint8_t)channels;
+    s.pcm_bits = (uint8_t)bits;
+    s.pcm_flags = (uint8_t)((is_float ? SK_AUDIO_FLOAT : 0) | (big_endian ? SK_AUDIO_BIG_ENDIAN : 0));
+    const uint32_t target_rate = s.opt.output_sample_rate ? s.opt.output_sample_rate : rate;
+    const uint32_t target_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : bits;
+    const uint32_t target_channels = s.opt.output_channels ? s.opt.output_channels : channels;
+    if (target_rate == rate && target_bits == bits && target_channels == channels) {
+        s.pcm_route = kPcmFast;
+        return true;
+    }
+    // audio_data_to_f32_channels (lib.rs:3563-3617) and exact_signed_pcm_to_i16 take 16 / 24 / 32-bit samples
+    if (is_float && bits != 32) return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: floating-point PCM must contain 32-bit samples");
+    if (bits != 16 && bits != 24 && bits != 32)
+        return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
+    if (channels > SK_MAX_CHANNELS)
+        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
+    const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
+    s.pcm_fmt = (uint8_t)((bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : (is_float ? SK_FMT_F32LE : SK_FMT_S32LE))) + (big_endian ? 1 : 0));
+    int rc = ensure_pcm(p);
+    if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+    s.resample = target_rate != rate;
+    if (s.resample) {
+        rc = sk_stream_open(p->engine, rate, s.channels, &s.engine_stream);
+        if (rc != SK_OK) return fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
+        rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
+        if (rc != SK_OK) return fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
+    }
+    s.pcm_route = kPcmTick;
+    return true;
+}
+
+// A WAV / raw PCM stream's pass.  Unit boundaries are the reference worker's: one `process` per received chunk, each giving at most one
+// piece (lib.rs:3006-3029); a WAV stream's first `process` is the detection buffer -- chunks gathered until kMinDetectionBytes are there
+// or the stream ends, at most kMaxDetectionBytes of them -- and the rest of the chunk that completed it a second one (lib.rs:2926-3003).
+// `room` bounds the outputs of the pass (one per piece, or one per completed 4096-frame chunk through the resampler); a piece is
+// never split, so the last one may overshoot.
+void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    auto fail = [&](int32_t st, const std::string &msg) {
+        r.failed = true;
+        r.fail_status = st;
+        r.fail_msg = msg;
+    };
+    uint32_t outputs = 0;
+    auto process = [&](const uint8_t *data, size_t len) -> bool {
+        sk_pcm::Piece piece;
+        std::string err;
+        const bool ok = s.wav ? s.wav->add(data, len, piece, err) : s.raw->add(data, len, piece, err);
+        if (!ok) {
+            fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
+            return false;
+        }
+        if (piece.len == 0) return true;
+        if (!s.pcm_route && !pcm_open(p, s, r)) return false;
+        const uint32_t frame_bytes = (uint32_t)s.pcm_bits / 8 * s.channels;
+        const uint32_t frames = (uint32_t)(piece.len / frame_bytes);
+        if (s.pcm_route == kPcmFast) {
+            Output o;
+            o.rate = s.rate, o.frames = frames, o.bits = s.pcm_bits, o.channels = s.channels, o.flags = s.pcm_flags;
+            o.data.assign(piece.data, piece.data + piece.len);
+            r.pre.push_back(std::move(o));
+            outputs += 1;
+            return true;
+        }
+        const size_t at = (r.pcm_bytes.size() + 15) & ~(size_t)15;
+        r.pcm_bytes.resize(at);
+        r.pcm_bytes.insert(r.pcm_bytes.end(), piece.data, piece.data + piece.len);
+        r.pcm_units.push_back(sk_pcm_unit{at, (uint32_t)piece.len, 0});
+        if (s.resample) {
+            outputs += (s.pcm_fill + frames) / 4096;
+            s.pcm_fill = (s.pcm_fill + frames) % 4096;
+        } else {
+            outputs += 1;
+        }
+        return true;
+    };
+    if (s.codec == kCodecWav && !s.pcm_detected) {
+        while (s.pending.size() - s.pending_pos < kMinDetectionBytes && !s.saw_eof)
+            if (pull_input(s) == 0) return;  // needs more input
+        s.wav.reset(new sk_pcm::WavStream());
+        s.pcm_detected = true;
+        const uint8_t *d = s.pending.data() + s.pending_pos;
+        const size_t n = s.pending.size() - s.pending_pos, first = std::min(n, kMaxDetectionBytes);
+        bool ok = process(d, first);
+        if (ok && n > first) ok = process(d + first, n - first);
+        s.pending.clear();
+        s.pending.shrink_to_fit();
+        s.pending_pos = 0;
+        if (!ok) return;
+    }
+    while (!r.failed) {
+        if (s.saw_eof) {  // flush_decoder (lib.rs:3139-3169): the framer's partial frame is an error, the resampler is flushed by the tick
+            std::string err;
+            if (s.raw && !s.raw->flush(err)) fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
+            else r.eof = true;
+            break;
+        }
+        std::vector<uint8_t> chunk;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            if (s.in.empty()) break;
+            // the pass's limits: the output queue's room, the units of one stream in a tick, the bytes one tick takes
+            const size_t next = s.in.front().size();
+            if (next && (outputs >= room || r.pcm_units.size() + r.pre.size() >= p->cfg.max_stream_frames_per_tick ||
+                         (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes))) {
+                r.more = true;
+                break;
+            }
+            chunk = std::move(s.in.front());
+            s.in.pop_front();
+        }
+        if (chunk.empty()) {
+            s.saw_eof = true;
+            continue;
+        }
+        s.queued_bytes.fetch_sub(chunk.size());
+        if (!process(chunk.data(), chunk.size())) break;
+    }
+    r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
+}
+
 // Pulls ADTS frames out of the stream's byte queue and runs the front-end on them, at most `limit` frames.
 void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_frame_desc *descs, std::vector<uint8_t> &au_stage,
-                sk_au_item *au_items, Parsed &r) {
+                sk_au_item *au_items, uint32_t room, Parsed &r) {
     const bool gpu_entropy = p->cfg.gpu_entropy == 1;
     const bool quant = p->cfg.gpu_entropy == 2;  // host Huffman decode, the rest of the front-end on the device (sk_tick_run_q)
     auto fail = [&](int32_t st, const std::string &msg) {
@@ -480,6 +693,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
     }
     if (s.codec == kCodecMp3) {
         parse_some_mp3(p, s, limit, r);
+        return;
+    }
+    if (s.codec == kCodecWav || s.codec == kCodecRawPcm) {
+        parse_some_pcm(p, s, room, r);
         return;
     }
     while (r.n_frames < limit && !r.failed) {
@@ -667,7 +884,7 @@ void worker_body(sk_lane *p) {
         const uint32_t limit = std::min(per_stream, s.resample ? (room > per_stream / 4 ? per_stream : 4 * room) : room);
         try {
             thread_debug_point(0);
-            parse_some(p, s, limit, coeffs.data(), descs.data(), au_stage, au_items.data(), r);
+            parse_some(p, s, limit, coeffs.data(), descs.data(), au_stage, au_items.data(), room, r);
         } catch (...) {
             // whatever was thrown while this stream's input was parsed is this stream's error and nobody else's
             // (soundkit-decoder/src/lib.rs:3131-3134); the frames of this pass are dropped with it
@@ -681,11 +898,11 @@ void worker_body(sk_lane *p) {
         }
         {
             std::lock_guard<std::mutex> lk(s.mu);  // read by mark_schedulable and the state dump
-            s.more = (r.n_frames == limit || r.budget_stop) && !r.eof && !r.failed;
+            s.more = (r.pcm ? r.more : (r.n_frames == limit || r.budget_stop)) && !r.eof && !r.failed;
         }
         p->parse_ns.fetch_add(ns_since(t0));
         p->workers_parsing.fetch_sub(1);
-        if (r.n_frames == 0 && !r.eof && !r.failed) {  // nothing complete yet
+        if (r.n_frames == 0 && r.pcm_units.empty() && r.pre.empty() && !r.eof && !r.failed) {  // nothing complete yet
             bool dropped;
             {
                 std::lock_guard<std::mutex> lk(s.mu);
@@ -703,7 +920,7 @@ void worker_body(sk_lane *p) {
         }
         // claim room in the batch being filled
         Batch *b;
-        size_t desc_at, float_at, au_at, mp3_at = 0, mp3_row_at = 0, mp3_frame_at = 0;
+        size_t desc_at, float_at, au_at, mp3_at = 0, mp3_row_at = 0, mp3_frame_at = 0, pcm_at = 0;
         {
             std::unique_lock<std::mutex> lk(p->batch_mu);
             p->workers_waiting_room.fetch_add(1);
@@ -711,7 +928,8 @@ void worker_body(sk_lane *p) {
                 const Batch &f = p->batches[p->filling];
                 return p->stop || (f.n_descs + f.n_mp3 + r.n_frames <= p->cfg.max_frames_per_tick &&
                                    (gpu_entropy ? f.au_used + r.n_au_bytes <= f.au_cap : f.n_floats + r.n_floats <= f.coeff_cap) &&
-                                   (!quant || f.au_used + r.n_au_bytes <= f.au_cap));
+                                   (!quant || f.au_used + r.n_au_bytes <= f.au_cap) &&
+                                   (r.pcm_units.empty() || f.pcm_used + r.pcm_bytes.size() <= f.pcm_cap));
             });
             p->workers_waiting_room.fetch_sub(1);
             if (p->stop) return;
@@ -748,6 +966,32 @@ void worker_body(sk_lane *p) {
             be.fail_msg = std::move(r.fail_msg);
             be.raw = std::move(r.raw);
             be.raw_len = std::move(r.raw_len);
+            if (r.pcm) {  // no row in the AAC / MP3 tick; a row of the PCM tick when it brings units or ends a resampler
+                be.pcm = true;
+                be.pre = std::move(r.pre);
+                t.n_frames = 0;
+                t.flush = 0;
+                if (s.pcm_route == kPcmTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
+                    pcm_at = b->pcm_used;
+                    b->pcm_used += r.pcm_bytes.size();
+                    sk_pcm_tick_stream pt{};
+                    pt.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
+                    pt.n_units = (uint32_t)r.pcm_units.size();
+                    pt.format = s.pcm_fmt;
+                    pt.channels = s.channels;
+                    pt.out_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits;
+                    pt.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
+                    pt.resample = s.resample ? 1 : 0;
+                    pt.flush = (r.eof && s.resample) ? 1 : 0;
+                    b->pcm_ts.push_back(pt);
+                    be.pcm_row = true;
+                    b->pcm_entry.push_back((uint32_t)b->entries.size());
+                    for (sk_pcm_unit u : r.pcm_units) {
+                        u.byte_offset += pcm_at;
+                        b->pcm_units.push_back(u);
+                    }
+                }
+            }
             if (s.engine_stream == kNoStream) {  // ended before a single header was seen: nothing for the device
                 t.n_frames = 0;
                 t.flush = 0;
@@ -756,7 +1000,9 @@ void worker_body(sk_lane *p) {
             b->entries.push_back(std::move(be));
             b->writers += 1;
         }
-        if (r.n_frames && r.mp3 && p->mp3_gpu) {
+        if (r.pcm) {
+            if (!r.pcm_units.empty()) std::memcpy(b->pcm_bytes + pcm_at, r.pcm_bytes.data(), r.pcm_bytes.size());
+        } else if (r.n_frames && r.mp3 && p->mp3_gpu) {
             std::memcpy(b->au_bytes + au_at, r.mp3_bytes.data(), r.n_au_bytes);
             for (size_t k = 0; k < r.mp3_frames.size(); ++k) {
                 b->mp3_frames[mp3_frame_at + k] = r.mp3_frames[k];
@@ -834,17 +1080,21 @@ void submit_body(sk_lane *p) {
         b->entry_row.assign(n_streams, kNoStream);
         for (uint32_t i = 0; i < n_streams; ++i) {
             PStream &s = *p->streams[b->entries[i].handle];
-            if (s.engine_stream == kNoStream) continue;
+            if (s.engine_stream == kNoStream || b->entries[i].pcm) continue;
             ts.push_back(b->ts[i]);
             b->entry_row[i] = (uint32_t)b->row_of.size();
             b->row_of.push_back(i);
         }
-        uint32_t max_out = 0;
+        uint32_t max_out = 0, pcm_max_out = 0;
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
-        if (!ts.empty()) {
-            const size_t bound = sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out);
+        const sk_mp3_internal::PipelineGpuHooks &pcm_hooks = sk_mp3_internal::pipeline_gpu_hooks();
+        if (!ts.empty() || !b->pcm_ts.empty()) {
+            size_t bound = ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out);
+            if (!b->pcm_ts.empty())  // the PCM tick's outputs follow the other tick's in the same buffer
+                bound += 16 + pcm_hooks.tick_pcm_out_bound(p->engine, b->pcm_ts.data(), (uint32_t)b->pcm_ts.size(), b->pcm_units.data(),
+                                                           (uint32_t)b->pcm_units.size(), &pcm_max_out);
             if (bound > b->out_pinned_cap) {
                 // Pinned memory is slow to get (10 ms per 64 MB on an idle device, many times that beside a running lane): the
                 // bound is the engine's own (the streams' real ratios and widths, not the 8 -> 48 kHz stereo 32-bit case), with room
@@ -863,7 +1113,9 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            if (b->recs.size() < max_out) b->recs.resize(max_out);
+            if (b->recs.size() < (size_t)max_out + pcm_max_out) b->recs.resize((size_t)max_out + pcm_max_out);
+        }
+        if (!ts.empty()) {
             if (b->rc == SK_OK && b->n_mp3 && p->mp3_gpu) {  // the same with the MP3 streams' Huffman stage in the tick as well
                 const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
                 sk_tick_input in{};
@@ -901,10 +1153,30 @@ void submit_body(sk_lane *p) {
                 b->rc = sk_tick_run(p->engine, ts.data(), (uint32_t)ts.size(), b->descs.data(), b->coeffs, n_frames, b->out_pinned,
                                     b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
         }
+        if (b->rc == SK_OK && !b->pcm_ts.empty()) {  // the PCM streams' tick of this round, behind the other one
+            const uint32_t first_row = (uint32_t)b->row_of.size();
+            const size_t base = (used + 15) & ~(size_t)15;
+            uint32_t n_pcm_out = 0;
+            size_t pcm_used = 0;
+            b->rc = pcm_hooks.tick_pcm(p->engine, b->pcm_ts.data(), (uint32_t)b->pcm_ts.size(), b->pcm_units.data(), (uint32_t)b->pcm_units.size(),
+                                       b->pcm_bytes, b->pcm_used, b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, pcm_max_out,
+                                       &n_pcm_out, &pcm_used);
+            if (b->rc == SK_OK) {
+                for (uint32_t k = 0; k < n_pcm_out; ++k) {
+                    b->recs[b->n_out + k].stream_index += first_row;
+                    b->recs[b->n_out + k].byte_offset += base;
+                }
+                b->n_out += n_pcm_out;
+                for (uint32_t row = 0; row < b->pcm_entry.size(); ++row) {
+                    b->entry_row[b->pcm_entry[row]] = first_row + row;
+                    b->row_of.push_back(b->pcm_entry[row]);
+                }
+            }
+        }
         p->submit_where = 4;
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
-        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3);
+        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->pcm_units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -999,6 +1271,12 @@ void deliver_body(sk_lane *p) {
                                                           // arrives later finds the stream idle and frees the slot itself
             {
                 std::lock_guard<std::mutex> lk(s.mu);
+                for (Output &o : be.pre) {  // a fast-path PCM stream's pieces, as they are
+                    if (s.cancelled || s.finished) break;
+                    s.out.push_back(std::move(o));
+                    p->n_outputs.fetch_add(1);
+                }
+                be.pre.clear();
                 for (uint32_t k = row == kNoStream ? 0 : b->rec_begin[row]; row != kNoStream && rc == SK_OK && k < b->rec_begin[row + 1]; ++k) {
                     const sk_tick_output &r = b->recs[k];
                     if (s.cancelled || s.finished) continue;
@@ -1013,11 +1291,12 @@ void deliver_body(sk_lane *p) {
                     o.frames = r.frames;
                     o.bits = r.bits;
                     o.channels = r.channels;
+                    o.flags = (r.reserved & SK_TICK_OUT_FLOAT) ? SK_AUDIO_FLOAT : 0;
                     o.data.assign(b->out_pinned + r.byte_offset, b->out_pinned + r.byte_offset + r.bytes);
                     s.out.push_back(std::move(o));
                     p->n_outputs.fetch_add(1);
                 }
-                if (rc != SK_OK && !s.finished) {
+                if (rc != SK_OK && !s.finished && !(be.pcm && !be.pcm_row)) {
                     push_error(s, rc, std::string("Decoding failed: engine tick: ") + sk_strerror(rc));
                     s.finished = true;
                     p->n_errors.fetch_add(1);
@@ -1379,13 +1658,16 @@ void lane_destroy(sk_lane *p) {
         if (b.au_bytes) (void)hipHostFree(b.au_bytes);
         if (b.out_pinned) (void)hipHostFree(b.out_pinned);
         if (b.mp3_is) (void)hipHostFree(b.mp3_is);
+        if (b.pcm_bytes) (void)hipHostFree(b.pcm_bytes);
     }
     if (p->mp3_cb) sk_mp3_codebook_destroy(p->mp3_cb);
     delete p;
 }
 
-int lane_spawn(sk_lane *p, const sk_decode_options *opt, uint32_t *handle) {
+int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle) {
     if (!p || !handle) return SK_ERR_INVALID_ARG;
+    // RawPcmFormat::validate (raw_pcm.rs:117-125), and the sample formats there are
+    if (raw && (raw->sample_rate == 0 || raw->channels == 0 || raw->format > SK_FMT_F32BE)) return SK_ERR_INVALID_ARG;
     if (const int dead = p->fatal.load()) return dead;
     sk_decode_options o{};
     if (opt) o = *opt;
@@ -1418,6 +1700,18 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, uint32_t *handle) {
     s.codec = 0;
     s.mp3_reservoir.clear();
     s.mp3_free_format = 0;
+    s.wav.reset();
+    s.raw.reset();
+    s.raw_format = sk_raw_pcm_format{};
+    s.pcm_detected = false;
+    s.pcm_route = 0, s.pcm_fmt = 0, s.pcm_flags = 0, s.pcm_bits = 0;
+    s.pcm_fill = 0;
+    if (raw) {  // spawn_raw_pcm_with_options (lib.rs:2475-2486): the stream has its decoder from the start and does not detect
+        s.codec = kCodecRawPcm;
+        s.raw_format = *raw;
+        const size_t width = raw->format <= SK_FMT_S16BE ? 2 : (raw->format <= SK_FMT_S24BE ? 3 : 4);
+        s.raw.reset(new sk_pcm::RawPcmStream(width * raw->channels));
+    }
     *handle = h;
     return SK_OK;
 }
@@ -1448,7 +1742,7 @@ int take_output(sk_lane *p, PStream &s, uint32_t handle, uint8_t *data, size_t c
     info->bits_per_sample = o.bits;
     info->channel_count = o.channels;
     info->is_error = o.is_error ? 1 : 0;
-    info->reserved = 0;
+    info->reserved = o.flags;
     info->status = o.status;
     if (o.data.size() > cap) return SK_ERR_CAPACITY;
     if (!o.data.empty()) std::memcpy(data, o.data.data(), o.data.size());
@@ -1529,6 +1823,16 @@ int lane_get_stats(sk_lane *p, sk_pipeline_stats *out) {
 
 }  // namespace
 
+struct sk_wav_reader {
+    sk_pcm::WavStream stream;
+    std::string error;
+};
+struct sk_raw_pcm_framer {
+    explicit sk_raw_pcm_framer(uint32_t bytes_per_frame) : stream(bytes_per_frame) {}
+    sk_pcm::RawPcmStream stream;
+    std::string error;
+};
+
 // ---- the pipeline: lanes behind one handle space ---------------------------------------------------------------
 struct sk_pipeline {
     std::vector<sk_lane *> lanes;
@@ -1546,6 +1850,24 @@ inline sk_lane *lane_of(sk_pipeline *p, uint32_t handle, uint32_t *inner) {
     const uint32_t n = (uint32_t)p->lanes.size();
     *inner = handle / n;
     return p->lanes[handle % n];
+}
+
+int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle) {
+    if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)p->lanes.size();
+    const uint32_t first = p->next_lane.fetch_add(1) % n;
+    int rc = SK_ERR_CAPACITY;
+    for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
+        const uint32_t li = (first + k) % n;
+        uint32_t inner = 0;
+        rc = lane_spawn(p->lanes[li], opt, raw, &inner);
+        if (rc == SK_OK) {
+            *handle = inner * n + li;
+            return SK_OK;
+        }
+        if (rc != SK_ERR_CAPACITY) return rc;
+    }
+    return rc;
 }
 }  // namespace
 
@@ -1643,23 +1965,17 @@ void sk_pipeline_destroy(sk_pipeline *p) try {
 
 int sk_pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, uint32_t *handle) try {
     sk::abi_enter();
-    if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
-    const uint32_t n = (uint32_t)p->lanes.size();
-    const uint32_t first = p->next_lane.fetch_add(1) % n;
-    int rc = SK_ERR_CAPACITY;
-    for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
-        const uint32_t li = (first + k) % n;
-        uint32_t inner = 0;
-        rc = lane_spawn(p->lanes[li], opt, &inner);
-        if (rc == SK_OK) {
-            *handle = inner * n + li;
-            return SK_OK;
-        }
-        if (rc != SK_ERR_CAPACITY) return rc;
-    }
-    return rc;
+    return pipeline_spawn(p, opt, nullptr, handle);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn");
+}
+
+int sk_pipeline_spawn_raw_pcm(sk_pipeline *p, const sk_raw_pcm_format *format, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    if (!format) return SK_ERR_INVALID_ARG;
+    return pipeline_spawn(p, opt, format, handle);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_raw_pcm");
 }
 
 int sk_pipeline_send(sk_pipeline *p, uint32_t handle, const uint8_t *data, size_t len) try {
@@ -1793,6 +2109,105 @@ int sk_pipeline_get_stats(sk_pipeline *p, sk_pipeline_stats *out) try {
     return SK_OK;
 } catch (...) {
     return sk::abi_caught("sk_pipeline_get_stats");
+}
+
+// ---- the two stream processors by themselves (pcm_stream.h), for callers and tests without a GPU ----
+
+int sk_wav_reader_create(sk_wav_reader **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_wav_reader();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_wav_reader_create");
+}
+
+void sk_wav_reader_destroy(sk_wav_reader *r) try {
+    sk::abi_enter();
+    delete r;
+} catch (...) {
+    (void)sk::abi_caught("sk_wav_reader_destroy");
+}
+
+int sk_wav_reader_add(sk_wav_reader *r, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece) try {
+    sk::abi_enter();
+    if (!r || (len && !bytes) || !piece_offset || !piece_len) return SK_ERR_INVALID_ARG;
+    sk_pcm::Piece got;
+    *piece_offset = 0, *piece_len = 0;
+    if (piece) *piece = nullptr;
+    if (!r->stream.add(bytes, len, got, r->error)) return SK_PCM_ERR_STREAM;
+    *piece_offset = got.stream_offset, *piece_len = got.len;
+    if (piece) *piece = got.data;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_wav_reader_add");
+}
+
+int sk_wav_reader_info(const sk_wav_reader *r, uint32_t *sample_rate, uint32_t *channels, uint32_t *bits, int *is_float, uint64_t *total_frames) try {
+    sk::abi_enter();
+    if (!r) return SK_ERR_INVALID_ARG;
+    if (sample_rate) *sample_rate = r->stream.sample_rate();
+    if (channels) *channels = r->stream.channels();
+    if (bits) *bits = r->stream.bits();
+    if (is_float) *is_float = r->stream.is_float() ? 1 : 0;
+    if (total_frames) *total_frames = r->stream.total_frames();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_wav_reader_info");
+}
+
+const char *sk_wav_reader_last_error(const sk_wav_reader *r) try {
+    sk::abi_enter();
+    return r ? r->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_wav_reader_last_error");
+    return "";
+}
+
+int sk_raw_pcm_framer_create(uint32_t bytes_per_frame, sk_raw_pcm_framer **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_raw_pcm_framer(bytes_per_frame);
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_raw_pcm_framer_create");
+}
+
+void sk_raw_pcm_framer_destroy(sk_raw_pcm_framer *f) try {
+    sk::abi_enter();
+    delete f;
+} catch (...) {
+    (void)sk::abi_caught("sk_raw_pcm_framer_destroy");
+}
+
+int sk_raw_pcm_framer_add(sk_raw_pcm_framer *f, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece) try {
+    sk::abi_enter();
+    if (!f || (len && !bytes) || !piece_offset || !piece_len) return SK_ERR_INVALID_ARG;
+    sk_pcm::Piece got;
+    *piece_offset = 0, *piece_len = 0;
+    if (piece) *piece = nullptr;
+    if (!f->stream.add(bytes, len, got, f->error)) return SK_PCM_ERR_STREAM;
+    *piece_offset = got.stream_offset, *piece_len = got.len;
+    if (piece) *piece = got.data;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_raw_pcm_framer_add");
+}
+
+int sk_raw_pcm_framer_flush(sk_raw_pcm_framer *f) try {
+    sk::abi_enter();
+    if (!f) return SK_ERR_INVALID_ARG;
+    return f->stream.flush(f->error) ? SK_OK : SK_PCM_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_raw_pcm_framer_flush");
+}
+
+const char *sk_raw_pcm_framer_last_error(const sk_raw_pcm_framer *f) try {
+    sk::abi_enter();
+    return f ? f->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_raw_pcm_framer_last_error");
+    return "";
 }
 
 int sk_debug_throw_in_thread(int n, int where) {

@@ -10,6 +10,8 @@ const bool g_hooked = [] {
     sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     hooks.install_codebook = sk::mp3_install_codebook;
     hooks.tick_md = sk_tick_run_mixed_md;
+    hooks.tick_pcm = sk_tick_run_pcm;  // the WAV / raw PCM streams' tick comes the same way
+    hooks.tick_pcm_out_bound = sk_tick_pcm_out_bound_on;
     return true;
 }();
 

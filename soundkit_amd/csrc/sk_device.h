@@ -428,6 +428,7 @@ enum PackMode : uint8_t {
     kPackViaS16 = 1,  // src is synthesis output: q = float_sample_to_i16(x); the f32 is q / 32768
     kPackDirect = 2,  // fast path (lib.rs:3339-3345): the bytes are q itself, s16le
     kPackFromQ = 3,   // src is q / 32768 already (MP3 rows of a tick): the fast path's bytes are (int)(x * 32768), exact
+    kPackPlainF32 = 4,  // kPackPlain with float output (bits = 32): a float source asked for 32 bits stays float (lib.rs:3377-3382)
 };
 struct PackJob {
     const float *src0, *src1;  // channel rows (src1 unused when ch_in == 1)
@@ -436,5 +437,29 @@ struct PackJob {
     uint8_t ch_in, ch_out, bits, mode;  // ch_out < ch_in: downmix to mono (lib.rs:3492-3561); bits 16 / 24 / 32
 };
 hipError_t launch_pack_jobs(const PackJob *jobs, uint32_t n_jobs, uint32_t max_frames, hipStream_t s);
+
+// pcm_tick.hip -- the PCM streams' tick (sk_tick_run_pcm): one launch per kind for all units of all streams
+constexpr uint32_t kPcmSliceSamples = 4096;  // samples (frames x channels) one workgroup converts: 256 lanes x 16 samples
+constexpr uint32_t kPcmCutFrames = 16;       // a unit is cut for the resampler rounds at multiples of this: 16 frames of any width are whole 16-byte groups
+// bytes -> bytes without a rate change: exact_signed_pcm_to_i16, or to f32 -> mono downmix -> f32_channels_to_bytes in registers
+struct PcmDirectJob {
+    const uint8_t *src;  // 16-byte aligned, interleaved samples of format fmt_in
+    uint8_t *dst;        // 16-byte aligned
+    uint32_t frames;
+    uint8_t fmt_in;      // SK_FMT_*
+    uint8_t fmt_out;     // SK_FMT_S16LE / S24LE / S32LE / F32LE
+    uint8_t ch_in, ch_out;  // 1 or 2; ch_out < ch_in: downmix to mono
+    uint32_t exact;      // 1: exact_signed_pcm_to_i16 (fmt_in signed 24 / 32 bit, fmt_out S16LE, ch_out == ch_in)
+    uint32_t pad;
+};
+hipError_t launch_pcm_direct(const PcmDirectJob *jobs, uint32_t n_jobs, uint32_t max_samples /* frames x channels of the largest job */, hipStream_t s);
+// bytes -> planar f32 (audio_data_to_f32_channels) straight into the stream's resampler staging rows
+struct PcmIngestJob {
+    const uint8_t *src;  // 16-byte aligned
+    float *dst0, *dst1;  // where the piece starts in the channel rows (any 4-byte alignment); dst1 unused when ch == 1
+    uint32_t frames;
+    uint8_t fmt, ch, pad[2];
+};
+hipError_t launch_pcm_ingest(const PcmIngestJob *jobs, uint32_t n_jobs, uint32_t max_samples, hipStream_t s);
 
 }  // namespace sk

@@ -449,6 +449,38 @@ class Engine:
         return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes())
                 for r in recs[:n_out.value]]
 
+    def tick_run_pcm(self, streams, units):
+        """One tick of WAV / raw PCM streams (sk_tick_run_pcm).  streams: list of dicts {format (FMT_*), channels, out_bits,
+        out_channels, n_units, and for a rate change: stream, resample, flush}; units: the pieces (bytes) of all streams, stream by
+        stream in the order of `streams`.  Each is packed at a 16-byte aligned offset of one buffer, as the scheduler does it.
+        -> list of (stream_index, status, frames, channels, bits, bytes, is_float)."""
+        import ctypes as C
+        from ._lib import PcmTickStream, PcmUnit, TickOutput
+        ts = (PcmTickStream * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            ts[i].format, ts[i].channels = int(s["format"]), int(s["channels"])
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+        n = len(units)
+        table = (PcmUnit * max(n, 1))()
+        total = 0
+        for k, u in enumerate(units):
+            table[k].byte_offset, table[k].byte_len = total, len(u)
+            total += (len(u) + 15) & ~15
+        blob = np.zeros(max(total, 16), np.uint8)
+        for k, u in enumerate(units):
+            blob[table[k].byte_offset:table[k].byte_offset + len(u)] = np.frombuffer(bytes(u), np.uint8)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_pcm_out_bound_on(self._h, ts, len(streams), table, n, C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_pcm(self._h, ts, len(streams), table, n, _ptr(blob), total, _ptr(out), out.size, recs, max_out.value,
+                                  C.byref(n_out), C.byref(used)), "sk_tick_run_pcm", self._h)
+        return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                for r in recs[:n_out.value]]
+
     def tick_run_au(self, streams, access_units):
         """sk_tick_run_au: as tick_run, but the entropy front-end runs on the GPU.  access_units: the raw access
         units (bytes) of all streams, stream by stream in the order of `streams`."""

@@ -3,16 +3,20 @@ top of the batch scheduler (csrc/pipeline.cpp): `DecodePipeline.spawn_with_optio
 `send / finish / try_recv / recv / cancel / queued_input_bytes`, but instead of one worker thread per stream every
 handle feeds one shared scheduler per GPU (entropy decode on host threads, everything after it batched on the GPU).
 
-Input: ADTS AAC-LC.  The reference's other formats stay with their CPU decoders (out of scope)."""
+Input: ADTS AAC-LC and MPEG Layer III (the stream's first bytes choose), WAV / RF64 (`RIFF....WAVE`: the walker of
+soundkit/src/wav.rs, then the reference's output stage -- sample width, mono downmix, rate -- in one batched GPU tick for all such
+streams; a stream with nothing to change is passed through as it is, any width and channel count), and headerless PCM through
+`spawn_raw_pcm[_with_options](RawPcmFormat)`.  AudioData from WAV / raw PCM streams carries the real `audio_format` and `endianness`.
+The reference's other formats stay with their CPU decoders (out of scope)."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
-from ._lib import AudioInfo, DecodeOptionsC, PipelineConfig, PipelineStats, SoundkitError, check, lib
+from ._lib import AudioInfo, DecodeOptionsC, PipelineConfig, PipelineStats, RawPcmFormatC, SoundkitError, check, lib
 from .audio_types import AudioData, EncodingFlag, Endianness
-from .engine import default_engine
+from .engine import FMT_F32LE, FMT_S16BE, FMT_S16LE, default_engine
 
 SK_PIPE_INPUT_FULL, SK_PIPE_CLOSED, SK_PIPE_CHUNK_TOO_LARGE, SK_ERR_CAPACITY = -201, -202, -203, -7
 
@@ -22,6 +26,31 @@ class DecodeOptions:  # lib.rs:147-151
     output_bits_per_sample: Optional[int] = None
     output_sample_rate: Optional[int] = None
     output_channels: Optional[int] = None
+
+
+@dataclass
+class RawPcmFormat:  # soundkit/src/raw_pcm.rs:39-126; `format` is one of engine.FMT_*
+    sample_rate: int
+    channels: int
+    format: int = FMT_S16LE
+
+    def __post_init__(self):  # validate, raw_pcm.rs:117-125
+        if self.sample_rate == 0:
+            raise ValueError("Raw PCM sample rate must be > 0")
+        if self.channels == 0:
+            raise ValueError("Raw PCM channel count must be > 0")
+
+    @classmethod
+    def linear16(cls, sample_rate, channels):  # signed 16-bit little-endian, raw_pcm.rs:62-69
+        return cls(sample_rate, channels, FMT_S16LE)
+
+    @classmethod
+    def l16(cls, sample_rate, channels):  # RFC 3551 L16: signed 16-bit big-endian, raw_pcm.rs:71-78
+        return cls(sample_rate, channels, FMT_S16BE)
+
+    @classmethod
+    def linear32(cls, sample_rate, channels):  # 32-bit float little-endian, raw_pcm.rs:80-87
+        return cls(sample_rate, channels, FMT_F32LE)
 
 
 class DecodeError(Exception):  # lib.rs:108-141
@@ -64,6 +93,17 @@ class BatchScheduler:
         rc = lib.sk_pipeline_spawn(self._h, C.byref(o), C.byref(handle))
         if rc != 0:
             raise SoundkitError(rc, "sk_pipeline_spawn")
+        return DecodePipelineHandle(self, handle.value)
+
+    def spawn_raw_pcm(self, format, options=None):
+        """DecodePipeline::spawn_raw_pcm_with_options (lib.rs:2475-2486): a stream of headerless PCM"""
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        f = RawPcmFormatC(format.sample_rate, format.channels, format.format, 0)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_raw_pcm(self._h, C.byref(f), C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_raw_pcm")
         return DecodePipelineHandle(self, handle.value)
 
     def wait_outputs(self, timeout_ms=100, cap=256):
@@ -128,7 +168,9 @@ class DecodePipelineHandle:
         payload = self._buf[:i.bytes].tobytes()
         if i.is_error:
             return DecodeError("DecodingFailed", payload.decode("utf-8", "replace"), i.status)
-        return AudioData(i.bits_per_sample, i.channel_count, i.sampling_rate, payload, EncodingFlag.PCMSigned, Endianness.LittleEndian)
+        return AudioData(i.bits_per_sample, i.channel_count, i.sampling_rate, payload,
+                         EncodingFlag.PCMFloat if i.reserved & 1 else EncodingFlag.PCMSigned,
+                         Endianness.BigEndian if i.reserved & 2 else Endianness.LittleEndian)
 
     def try_recv(self):
         """None when nothing is ready (or the stream has ended and is drained); else AudioData or a DecodeError value."""
@@ -177,7 +219,7 @@ def default_scheduler():
 
 
 class DecodePipeline:
-    """lib.rs:2590-2786, for ADTS AAC-LC"""
+    """lib.rs:2590-2786"""
 
     @staticmethod
     def spawn():
@@ -186,3 +228,11 @@ class DecodePipeline:
     @staticmethod
     def spawn_with_options(options):
         return default_scheduler().spawn(options)
+
+    @staticmethod
+    def spawn_raw_pcm(format):
+        return default_scheduler().spawn_raw_pcm(format, DecodeOptions())
+
+    @staticmethod
+    def spawn_raw_pcm_with_options(format, options):
+        return default_scheduler().spawn_raw_pcm(format, options)
