@@ -591,6 +591,28 @@ int sk_downsample_48k_16k_frames_s16_to_f32_dev(sk_engine *, const int16_t *d_pc
                                                 uint32_t channels, uint32_t n_streams, uint32_t frames_per_stream,
                                                 float *d_out, size_t out_stride, uint32_t *out_frames);
 
+/* The same resample step at ANY pair of the reference's COMMON_SAMPLE_RATES the matrix-core resampler takes (44.1 kHz sources
+ * above all): one-shot downsample_audio over the frames_per_stream * 1024 samples of every stream -- the chunk is the whole input,
+ * the index walk starts at -128, *out_frames = sk_downsample_out_frames(frames_per_stream * 1024, in_hz, out_hz), no resampler
+ * state is kept.  Input exactly as sk_downsample_48k_16k_frames_s16_to_s16_dev reads it: sample n of (stream s, channel c), value
+ * s16 / 32768, at d_pcm16[s * stream_stride + (n / 1024) * frame_stride + c * 1024 + n % 1024]; strides in samples, multiples of 4;
+ * d_pcm16 8-byte aligned; channels 1 or 2.  The samples enter the matrix cores as two f16 planes, the effective filter of every
+ * output (the blend of its two sub-filters) times 2^16 as two f16 planes, three products per window: <= 1e-6 relative RMS against
+ * an f64 evaluation like the f32 route (sk_downsample_f32_dev), but not its bits.
+ *   _to_s16: d_out[s][m][c] interleaved s16 = float_sample_to_i16 of the filter's f32 result, out_stride frames per stream, 8-byte
+ *            aligned; frames at and beyond *out_frames are not written.
+ *   _to_f32: row s * channels + c of d_out, out_stride floats per row.
+ * 48000 -> 16000 is sk_downsample_48k_16k_frames_s16_to_{s16,f32}_dev.  Returns SK_ERR_UNSUPPORTED -- and writes nothing -- for
+ * rates outside the common set, for a step in_hz / out_hz the matrix-core form does not take (beyond about 6.9: 88.2 and 96 kHz
+ * to 8 kHz among the common rates; widen to f32 rows and call sk_downsample_f32_dev), and while sk_engine_set_resampler_exact is
+ * on: this entry has no scalar form and never changes arithmetic silently.  n_streams == 0 or no output frames: SK_OK. */
+int sk_downsample_frames_s16_to_s16_dev(sk_engine *, const int16_t *d_pcm16, size_t stream_stride, size_t frame_stride,
+                                        uint32_t channels, uint32_t n_streams, uint32_t frames_per_stream, uint32_t in_hz,
+                                        uint32_t out_hz, int16_t *d_out, size_t out_stride, uint32_t *out_frames);
+int sk_downsample_frames_s16_to_f32_dev(sk_engine *, const int16_t *d_pcm16, size_t stream_stride, size_t frame_stride,
+                                        uint32_t channels, uint32_t n_streams, uint32_t frames_per_stream, uint32_t in_hz,
+                                        uint32_t out_hz, float *d_out, size_t out_stride, uint32_t *out_frames);
+
 /* In a library built with packed-f32 instructions (sk_kernels_use_packed_f32() == 1) this entry point is WITHDRAWN: it returns
  * SK_ERR_UNSUPPORTED for every plan -- use the two calls -- unless SK_AAC_TAIL_ONE_LAUNCH=1 is in the environment, which is for
  * reproducing the defect only: a kernel whose waves run the synthesis with packed-f32 instructions while others of them run

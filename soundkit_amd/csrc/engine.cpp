@@ -1886,6 +1886,95 @@ int sk_downsample_f32_dev(sk_engine *e, const float *d_in, size_t in_stride, uin
     return sk::abi_caught("sk_downsample_f32_dev");
 }
 
+// The one-shot resampler of the device-resident decode tail at any ratio of the common rates the matrix-core form takes: planar
+// s16 frames in (sk_aac_plan_run_s16_planar_dev's layout), interleaved s16 or f32 rows out.  48 -> 16 kHz is the fixed filter's own
+// pair of entry points.  No scalar form behind it: exact mode and the steep ratios are refused, never computed another way.
+static int sinc_from_s16(sk_engine *e, const int16_t *d_pcm16, size_t stream_stride, size_t frame_stride, uint32_t channels,
+                         uint32_t n_streams, uint32_t frames_per_stream, uint32_t in_hz, uint32_t out_hz, int16_t *d_out16,
+                         float *d_out32, size_t out_stride, uint32_t *out_frames) {
+    if (!e || channels < 1 || channels > SK_MAX_CHANNELS) return SK_ERR_INVALID_ARG;
+    if (!common_rate(in_hz) || !common_rate(out_hz)) return SK_ERR_UNSUPPORTED;
+    if (in_hz == 48000 && out_hz == 16000)
+        return fir_from_s16(e, d_pcm16, stream_stride, frame_stride, channels, n_streams, frames_per_stream, d_out16, d_out32, out_stride,
+                            out_frames);
+    const uint64_t samples = (uint64_t)frames_per_stream * SK_AAC_FRAME_LEN;
+    if (samples > 0x7ffff000ull) return SK_ERR_INVALID_ARG;  // 32-bit sample indices inside the kernels
+    const double ratio = (double)out_hz / (double)in_hz, step = 1.0 / ratio;
+    IndexSet set;
+    make_index_set(ratio, -128.0, (uint32_t)samples, set);
+    const uint32_t n_out = set.count;
+    if (out_frames) *out_frames = n_out;
+    if (e->sinc_exact) return SK_ERR_UNSUPPORTED;
+    if (n_streams == 0 || n_out == 0) return SK_OK;
+    const size_t want = sk::sinc_mfma_scratch_bytes(1, n_out, step);
+    if (!want) return SK_ERR_UNSUPPORTED;  // a step the matrix-core form does not take (decided by the ratio alone)
+    if ((uint64_t)n_streams * channels > 0xffffffffull) return SK_ERR_INVALID_ARG;
+    if (!d_pcm16 || (!d_out16 && !d_out32) || out_stride < n_out || frame_stride < (size_t)channels * SK_AAC_FRAME_LEN ||
+        stream_stride % 4 || frame_stride % 4 || ((uintptr_t)d_pcm16 & 7) || (d_out16 && ((uintptr_t)d_out16 & 7)) ||
+        (d_out32 && ((uintptr_t)d_out32 & 3)))
+        return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e, ComputeTurn{});
+    int table = -1;
+    int rc = ratio_table_for(e, in_hz, out_hz, &table);
+    if (rc != SK_OK) return rc;
+    const size_t starts_bytes = (set.starts.size() * sizeof(double) + 255) & ~(size_t)255;
+    SK_HIP(e->aux2_buf.reserve(starts_bytes + 4096), "alloc index scratch");
+    SK_HIP(hipMemcpyAsync(e->aux2_buf.p, set.starts.data(), set.starts.size() * sizeof(double), hipMemcpyHostToDevice, e->stream),
+           "upload time indices");
+    SK_HIP(hipMemcpyAsync((uint8_t *)e->aux2_buf.p + starts_bytes, &set.count, sizeof(uint32_t), hipMemcpyHostToDevice, e->stream),
+           "upload output count");
+    // a failed allocation is an error, never another arithmetic (see sk_downsample_f32_dev)
+    SK_HIP(e->sinc_scratch.reserve(want), "alloc resampler tap fragments");
+    sk::SincS16Args a{};
+    a.stream_stride = stream_stride;
+    a.frame_stride = frame_stride;
+    a.channels = channels;
+    a.in_frames = (uint32_t)samples;
+    a.out_stride = out_stride;
+    a.sincs = e->ratio_tables[(size_t)table].d_sincs;
+    a.set_starts = (const double *)e->aux2_buf.p;
+    a.set_count = (const uint32_t *)((const uint8_t *)e->aux2_buf.p + starts_bytes);
+    a.starts_stride = (uint32_t)set.starts.size();
+    a.step = 1.0 / e->ratio_tables[(size_t)table].ratio;
+    a.out_count = n_out;
+    a.scratch = e->sinc_scratch.p, a.scratch_bytes = e->sinc_scratch.cap;
+    // rows beyond the grid limit of sk_downsample_f32_dev's launches go in parts (an even number of rows each: whole streams)
+    const uint64_t rows = (uint64_t)n_streams * channels;
+    const uint64_t rows_per_launch = 65535ull * sk::sinc_rows_per_block();
+    for (uint64_t r0 = 0; r0 < rows; r0 += rows_per_launch) {
+        sk::SincS16Args part = a;
+        part.rows = (uint32_t)std::min<uint64_t>(rows_per_launch, rows - r0);
+        const size_t stream0 = (size_t)(r0 / channels);
+        part.in16 = d_pcm16 + stream0 * stream_stride;
+        if (d_out16) part.out16 = d_out16 + stream0 * out_stride * channels;
+        else part.out32 = d_out32 + (size_t)r0 * out_stride;
+        SK_HIP(sk::launch_sinc_rows_s16(part, e->stream), "launch sinc resample (s16 frame rows)");
+    }
+    SK_HIP(hipStreamSynchronize(e->stream), "resample sync");  // the index set lives in host memory until the copy is done
+    return SK_OK;
+}
+
+int sk_downsample_frames_s16_to_s16_dev(sk_engine *e, const int16_t *d_pcm16, size_t stream_stride, size_t frame_stride, uint32_t channels,
+                                        uint32_t n_streams, uint32_t frames_per_stream, uint32_t in_hz, uint32_t out_hz, int16_t *d_out,
+                                        size_t out_stride, uint32_t *out_frames) try {
+    sk::abi_enter();
+    return sinc_from_s16(e, d_pcm16, stream_stride, frame_stride, channels, n_streams, frames_per_stream, in_hz, out_hz, d_out, nullptr,
+                         out_stride, out_frames);
+} catch (...) {
+    return sk::abi_caught("sk_downsample_frames_s16_to_s16_dev");
+}
+
+int sk_downsample_frames_s16_to_f32_dev(sk_engine *e, const int16_t *d_pcm16, size_t stream_stride, size_t frame_stride, uint32_t channels,
+                                        uint32_t n_streams, uint32_t frames_per_stream, uint32_t in_hz, uint32_t out_hz, float *d_out,
+                                        size_t out_stride, uint32_t *out_frames) try {
+    sk::abi_enter();
+    return sinc_from_s16(e, d_pcm16, stream_stride, frame_stride, channels, n_streams, frames_per_stream, in_hz, out_hz, nullptr, d_out,
+                         out_stride, out_frames);
+} catch (...) {
+    return sk::abi_caught("sk_downsample_frames_s16_to_f32_dev");
+}
+
 int sk_downsample_f32(sk_engine *e, const float *in, uint32_t rows, uint32_t frames, uint32_t in_hz, uint32_t out_hz,
                       float *out, uint32_t out_cap, uint32_t *out_frames) try {
     sk::abi_enter();

@@ -324,6 +324,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_sinc_resample(SincArgs a, uint3
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMfmaRows = SK_MFMA_ROWS;           // rows per workgroup: row groups of 16
 constexpr int kMfmaTiles = SK_MFMA_TILES;         // tiles (of 16 outputs) per workgroup at most: one per wave
@@ -354,7 +355,11 @@ __device__ __forceinline__ void split3(float x0, float x1, uint32_t &p1, uint32_
     p3 = __builtin_amdgcn_perm(__float_as_uint(s1), __float_as_uint(s0), 0x07060302u);
 }
 
-// grid (tiles, sets), one wave: the A fragments [window][plane][lane] of tile t of index set `set`, and its TileMeta
+// grid (tiles, sets), one wave: the A fragments [window][plane][lane] of tile t of index set `set`, and its TileMeta.
+// F16 (for k_sinc_mfma_s16): the same effective filter g times 2^16 as two f16 planes instead of three bf16 planes -- the first g
+// rounded to nearest, the second the f16 of what is left (|h2| <= 2^-11 |h1|; what both leave out is below 2^-22 |g|).  The largest
+// tap of any table is the cut-off frequency (0.95 at most), so g * 2^16 stays under the largest f16 (65504).
+template <bool F16>
 __global__ __launch_bounds__(64) void k_sinc_taps(SincArgs a, uint32_t n_tiles, uint32_t tile_first, uint32_t max_windows, u32x4 *frags, TileMeta *meta) {
     const int lane = threadIdx.x, i = lane & 15, q = lane >> 4;
     const uint32_t t = tile_first + blockIdx.x, set = blockIdx.y;  // t: tile of the row; storage is per pass (n_tiles of them)
@@ -377,7 +382,8 @@ __global__ __launch_bounds__(64) void k_sinc_taps(SincArgs a, uint32_t n_tiles, 
     const bool valid = (uint32_t)i <= last;
     const float *s0 = a.sincs + (size_t)at.sub0 * 256, *s1 = a.sincs + (size_t)((at.sub0 + 1) & 255) * 256;
     const int delta = index0 - base;
-    u32x4 *out = frags + ((size_t)set * n_tiles + blockIdx.x) * max_windows * 3 * 64 + lane;
+    constexpr int kPlanes = F16 ? 2 : 3;
+    u32x4 *out = frags + ((size_t)set * n_tiles + blockIdx.x) * max_windows * kPlanes * 64 + lane;
     for (int s = 0; s < windows; ++s) {
         float g[8];
 #pragma unroll
@@ -390,12 +396,20 @@ __global__ __launch_bounds__(64) void k_sinc_taps(SincArgs a, uint32_t n_tiles, 
         u32x4 pl[3];
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
-            uint32_t p1, p2, p3;
-            split3(g[2 * h], g[2 * h + 1], p1, p2, p3);
-            pl[0][h] = p1, pl[1][h] = p2, pl[2][h] = p3;
+            if constexpr (F16) {
+                typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+                const float g0 = g[2 * h] * 65536.0f, g1 = g[2 * h + 1] * 65536.0f;  // exact
+                const f16x2 h1 = {(_Float16)g0, (_Float16)g1};                      // to nearest
+                const f16x2 h2 = {(_Float16)(g0 - (float)h1.x), (_Float16)(g1 - (float)h1.y)};  // the differences are exact
+                pl[0][h] = __builtin_bit_cast(uint32_t, h1), pl[1][h] = __builtin_bit_cast(uint32_t, h2);
+            } else {
+                uint32_t p1, p2, p3;
+                split3(g[2 * h], g[2 * h + 1], p1, p2, p3);
+                pl[0][h] = p1, pl[1][h] = p2, pl[2][h] = p3;
+            }
         }
 #pragma unroll
-        for (int k = 0; k < 3; ++k) out[(size_t)(s * 3 + k) * 64] = pl[k];
+        for (int k = 0; k < kPlanes; ++k) out[(size_t)(s * kPlanes + k) * 64] = pl[k];
     }
 }
 
@@ -616,6 +630,211 @@ __global__ __launch_bounds__(kMfmaTiles * 64, SK_MFMA_BLOCKS) void k_sinc_mfma(S
     }
 }
 
+// ---- the matrix-core form on s16 frame rows ----------------------------------------------------------------------------------------
+// The decode tail's samples are 16-bit integers (the synthesis kernel's planar s16, frame-packed: SincS16Args), and an s16 value is
+// exactly two f16 values (dev_split_pair16_f16, as the 48 -> 16 kHz filter takes them).  With the filter as two f16 planes of
+// g * 2^16 (k_sinc_taps<true>) a window is the three products  x1h1, x1h2, x2h1  instead of six: what is left out is x2h2, below
+// 2^-21 |x||g|, and the taps' own remainder below 2^-22 |g| (1e-7 relative RMS against f64 in the numpy model, 4e-7 measured
+// with the accumulation: DESIGN.md 4.4).  The accumulator carries 2^15 * 2^16; the factor goes into the epilogue.
+// Against k_sinc_mfma: samples arrive as 16-byte groups of eight (a group never straddles a 1024-sample frame: bases are multiples
+// of eight), are split once with three and a half vector instructions per sample and fill two planes (100 KB) with 16-byte LDS
+// writes; one index set per call, so a workgroup loads its tap fragments once; the two row groups of a window alternate on the
+// matrix pipe; the s16 form interleaves rows 2k / 2k + 1 in registers (the neighbouring lane holds the other channel).
+constexpr int kS16Groups = kMfmaSpan / 8;  // 16-byte groups staged per row
+
+// OUT: 0 = f32 rows, 1 = s16 mono, 2 = s16 stereo interleaved
+template <int OUT>
+__global__ __launch_bounds__(kMfmaTiles * 64, 1) void k_sinc_mfma_s16(SincS16Args a, uint32_t n_tiles, uint32_t tile_first, uint32_t max_windows,
+                                                                     uint32_t tiles_per_block, uint32_t row_blocks_per_group, int out_vec,
+                                                                     const u32x4 *frags, const TileMeta *meta) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char planes[];  // [2][kMfmaRows][kMfmaPitch]
+    const int lane = threadIdx.x & 63, j = lane & 15, q = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t n_row_blocks = (a.rows + kMfmaRows - 1) / kMfmaRows;
+    const uint32_t rb_begin = blockIdx.x * row_blocks_per_group;
+    const uint32_t rb_end = min(n_row_blocks, rb_begin + row_blocks_per_group);
+    const uint32_t l0 = blockIdx.y * tiles_per_block;  // first tile of the workgroup within this pass (storage index)
+    const uint32_t t0 = tile_first + l0;               // ... and within the row
+    const uint32_t t = t0 + (uint32_t)wave;
+    const uint32_t count = a.out_count;
+    if (16u * t0 >= count) return;  // (block-uniform; the host's grid has no such workgroup)
+    const TileMeta *tm = meta + l0;
+    const uint32_t nt = min(min(tiles_per_block, n_tiles - l0), (count - 16u * t0 + 15u) / 16u);
+    const int base_first = tm[0].base;
+    int span = 0;
+    for (uint32_t k = 0; k < nt; ++k) span = max(span, tm[k].base + 32 * tm[k].windows - base_first);
+    if (span > kMfmaSpan || tm[0].windows == 0) return;  // (the host sized the launch for this step: not reached)
+
+    // the wave's tap fragments: up to 12 windows x 2 planes in registers for the whole run of row blocks
+    const bool has_tile = (uint32_t)wave < nt;
+    const int off = has_tile ? __builtin_amdgcn_readfirstlane(tm[has_tile ? wave : 0].base - base_first) : 0;  // a multiple of 8
+    const int windows = has_tile ? __builtin_amdgcn_readfirstlane(tm[has_tile ? wave : 0].windows) : 0;
+    u32x4 h[kMaxWindows][2];
+    {
+        const u32x4 *fa = frags + ((size_t)l0 + (uint32_t)wave) * max_windows * 2 * 64 + lane;
+#pragma unroll
+        for (int s = 0; s < kMaxWindows; ++s)
+            if (s < windows) {
+#pragma unroll
+                for (int k = 0; k < 2; ++k)  // issued HERE by hand, as in k_sinc_mfma
+                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(h[s][k]) : "v"(fa + (size_t)(s * 2 + k) * 64) : "memory");
+            }
+    }
+    bool taps_pending = true;
+
+    // a row block's samples: 32 rows x span from base_first, eight samples (16 bytes) per lane and load; a wave takes four rows,
+    // 88 groups each.  The address is computed per group: the span crosses one or two frame boundaries, whose stride is the caller's.
+    constexpr int kStageR = kMfmaRows / kMfmaTiles, kStageC = (kS16Groups + 63) / 64;
+    const uint32_t sh = a.channels - 1;  // channels 1 -> 0, 2 -> 1
+    u32x4 pre[kStageR][kStageC];
+    auto fetch = [&](uint32_t rb) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kStageR; ++k) {
+            const uint32_t row = rb * kMfmaRows + (uint32_t)(wave + kMfmaTiles * k);
+            const bool live = row < a.rows;
+            const int16_t *src = a.in16 + (size_t)((live ? row : 0) >> sh) * a.stream_stride + (size_t)(((live ? row : 0) & sh) << 10);
+#pragma unroll
+            for (int cc = 0; cc < kStageC; ++cc) {
+                const int g = lane + 64 * cc;
+                const long n = (long)base_first + 8 * g;  // a multiple of 8; the rows hold whole frames: a group is inside or outside
+                pre[k][cc] = (u32x4){0u, 0u, 0u, 0u};
+                if (live && 8 * g < span && n >= 0 && n < (long)a.in_frames) {
+                    const int16_t *at = src + (size_t)(n >> 10) * a.frame_stride + (size_t)(n & 1023);
+                    __builtin_memcpy(&pre[k][cc], __builtin_assume_aligned(at, 8), 16);  // (strides are multiples of four samples)
+                }
+            }
+        }
+    };
+    auto refill = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < kStageR; ++k) {
+            unsigned char *dst = planes + (wave + kMfmaTiles * k) * kMfmaPitch;
+#pragma unroll
+            for (int cc = 0; cc < kStageC; ++cc) {
+                const int g = lane + 64 * cc;
+                if (8 * 64 * cc >= span) continue;  // wave-uniform
+                if (g >= kS16Groups) continue;      // the row's pitch ends here
+                u32x4 p1, p2;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) {
+                    uint32_t u1, u2;
+                    dev_split_pair16_f16(pre[k][cc][d], u1, u2);
+                    p1[d] = u1, p2[d] = u2;
+                }
+                *reinterpret_cast<u32x4 *>(dst + 16 * g) = p1;
+                *reinterpret_cast<u32x4 *>(dst + kMfmaPlane + 16 * g) = p2;
+            }
+        }
+    };
+
+    fetch(rb_begin);
+    refill();
+    __syncthreads();
+    for (uint32_t rb = rb_begin; rb < rb_end; ++rb) {
+        const bool more = rb + 1 < rb_end;
+        if (more) fetch(rb + 1);  // in flight during the matrix instructions below
+        if (has_tile) {
+            if (taps_pending) {  // wave-uniform.  Vector memory returns in order: this also waits for the loads just issued, once per workgroup
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                taps_pending = false;
+            }
+            // the registers pass through this statement so that nothing that reads them is scheduled in front of the wait
+#pragma unroll
+            for (int s = 0; s < kMaxWindows; ++s) asm volatile("" : "+v"(h[s][0]), "+v"(h[s][1]));
+            constexpr int kGroups = kMfmaRows / 16;
+            static_assert(kGroups == 2, "the two row groups of a window alternate on the matrix pipe");
+            f32x4 acc[kGroups];
+#pragma unroll
+            for (int rg = 0; rg < kGroups; ++rg) acc[rg] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            struct BSet {
+                u32x4 x[2];
+            };
+            auto read_b = [&](int s, int rg) __attribute__((always_inline)) {
+                BSet b;
+                const unsigned char *bp = planes + (rg * 16 + j) * kMfmaPitch + 2 * (off + 32 * s + 8 * q);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) b.x[k] = *reinterpret_cast<const u32x4 *>(bp + k * kMfmaPlane);
+                return b;
+            };
+            // window s + 1 is on its way from LDS while the matrix instructions work on window s (past the last window the read
+            // repeats it: no branch, never beyond the tile's span); x1h1 | x1h2, x2h1, never two on one accumulator back to back
+            BSet b0 = read_b(0, 0), b1 = read_b(0, 1);
+#pragma unroll
+            for (int s = 0; s < kMaxWindows; ++s) {
+                if (s >= windows) continue;  // (wave-uniform; no break: the loop must unroll for h[s] to stay in registers)
+                const int sn = s + 1 < windows ? s + 1 : s;
+                const BSet n0 = read_b(sn, 0), n1 = read_b(sn, 1);
+                acc[0] = dev_mfma_f16(h[s][0], b0.x[0], acc[0]);
+                acc[1] = dev_mfma_f16(h[s][0], b1.x[0], acc[1]);
+                acc[0] = dev_mfma_f16(h[s][1], b0.x[0], acc[0]);
+                acc[1] = dev_mfma_f16(h[s][1], b1.x[0], acc[1]);
+                acc[0] = dev_mfma_f16(h[s][0], b0.x[1], acc[0]);
+                acc[1] = dev_mfma_f16(h[s][0], b1.x[1], acc[1]);
+                b0 = n0, b1 = n1;
+            }
+            // D[i][j]: lane (j, q) holds outputs i = 4 q .. 4 q + 3 of row j of each row group; the factor 2^-31 (s16 samples as
+            // integers, taps times 2^16) is a power of two: exact in the f32 form, inside the conversion's constants in the s16 form
+            const uint32_t mo = 16u * t + 4u * (uint32_t)q;
+            const bool whole = mo + 4u <= count;
+#pragma unroll
+            for (int rg = 0; rg < kGroups; ++rg) {
+                const uint32_t row = rb * kMfmaRows + (uint32_t)(rg * 16 + j);
+                const bool there = row < a.rows;
+                if constexpr (OUT == 0) {
+                    const f32x4 v = acc[rg] * (1.0f / 2147483648.0f);
+                    float *dst = a.out32 + (size_t)(there ? row : 0) * a.out_stride + mo;
+                    if (!there) continue;
+                    if (out_vec && whole) {
+                        *reinterpret_cast<f32x4 *>(dst) = v;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (mo + (uint32_t)r < count) dst[r] = v[r];
+                    }
+                } else {
+                    const uint32_t mine01 = dev_pack2_s16_scaled<31>(acc[rg][0], acc[rg][1]);
+                    const uint32_t mine23 = dev_pack2_s16_scaled<31>(acc[rg][2], acc[rg][3]);
+                    if constexpr (OUT == 2) {
+                        // the neighbouring row's lane (lane ^ 1) holds the other channel: two packed dwords cross by DPP quad_perm [1,0,3,2]
+                        const uint32_t other01 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine01, 0xB1, 0xF, 0xF, true);
+                        const uint32_t other23 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine23, 0xB1, 0xF, 0xF, true);
+                        u32x4 w;  // frame mo + r: L in the low half, R in the high half
+                        w[0] = (mine01 & 0xffffu) | (other01 << 16);
+                        w[1] = (mine01 >> 16) | (other01 & 0xffff0000u);
+                        w[2] = (mine23 & 0xffffu) | (other23 << 16);
+                        w[3] = (mine23 >> 16) | (other23 & 0xffff0000u);
+                        if ((j & 1) || !there) continue;  // (the rows of a stereo call come in pairs)
+                        uint32_t *dst = reinterpret_cast<uint32_t *>(a.out16) + (size_t)(row >> 1) * a.out_stride + mo;
+                        if (out_vec && whole) {
+                            *reinterpret_cast<u32x4 *>(dst) = w;
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (mo + (uint32_t)r < count) dst[r] = w[r];
+                        }
+                    } else {
+                        if (!there) continue;
+                        int16_t *dst = a.out16 + (size_t)row * a.out_stride + mo;
+                        if (out_vec == 2 && whole) {
+                            *reinterpret_cast<u32x2 *>(dst) = (u32x2){mine01, mine23};
+                        } else if (out_vec && whole) {  // rows at 4-byte boundaries only
+                            reinterpret_cast<uint32_t *>(dst)[0] = mine01;
+                            reinterpret_cast<uint32_t *>(dst)[1] = mine23;
+                        } else {  // the row's last tile, or a caller whose rows start at odd samples
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                if (mo + (uint32_t)r < count) dst[r] = (int16_t)((r < 2 ? mine01 : mine23) >> (16 * (r & 1)));
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();  // the planes have been read
+        if (more) refill();
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(256) void k_row_copies(const float *src_base, float *dst_base, const RowCopy *jobs,
                                                     uint32_t n_jobs) {
     const uint32_t j = blockIdx.y;
@@ -682,7 +901,7 @@ static hipError_t launch_sinc_mfma(const SincArgs &a, hipStream_t s) {
     if (attr != hipSuccess) return attr;
     for (uint32_t tile_first = 0; tile_first < all_tiles; tile_first += pass_tiles) {
         const uint32_t tiles = std::min(pass_tiles, all_tiles - tile_first);
-        hipLaunchKernelGGL(k_sinc_taps, dim3(tiles, a.n_sets), dim3(64), 0, s, a, pass_tiles, tile_first, windows, frags, meta);
+        hipLaunchKernelGGL(k_sinc_taps<false>, dim3(tiles, a.n_sets), dim3(64), 0, s, a, pass_tiles, tile_first, windows, frags, meta);
         // runs of row blocks per workgroup: long enough to amortise the fragments and the pipeline's fill, short enough for >= 4
         // workgroups per CU in the launch
         const uint32_t tile_chunks = (tiles + tpb - 1) / tpb;
@@ -690,6 +909,59 @@ static hipError_t launch_sinc_mfma(const SincArgs &a, hipStream_t s) {
         while (run > 1 && (uint64_t)((row_blocks + run - 1) / run) * tile_chunks < 1024) run >>= 1;
         hipLaunchKernelGGL(k_sinc_mfma, dim3((row_blocks + run - 1) / run, tile_chunks), dim3(kMfmaTiles * 64), lds_bytes, s, a, pass_tiles, tile_first, windows,
                            tpb, run, frags, meta);
+    }
+    return hipGetLastError();
+}
+
+// k_sinc_taps<true> + k_sinc_mfma_s16 in the passes of launch_sinc_mfma; the caller's scratch is sized by sinc_mfma_scratch_bytes(1, ..)
+// (three planes' worth: the two of this form fit)
+hipError_t launch_sinc_rows_s16(const SincS16Args &a, hipStream_t s) {
+    if (a.rows == 0 || a.out_count == 0) return hipSuccess;
+    if (!sinc_mfma_takes(a.step) || !a.in16 || (!a.out16 == !a.out32) || a.channels < 1 || a.channels > 2 || a.rows % a.channels ||
+        a.in_frames % 1024 || a.in_frames > 0x7ffff000u || a.stream_stride % 4 || a.frame_stride % 4 || ((uintptr_t)a.in16 & 7))
+        return hipErrorInvalidValue;
+    if (!a.scratch || sinc_mfma_scratch_bytes(1, a.out_count, a.step) > a.scratch_bytes) return hipErrorInvalidValue;
+    const uint32_t windows = sinc_mfma_windows(a.step), all_tiles = (a.out_count + 15) / 16, tpb = sinc_mfma_tiles_per_block(a.step);
+    const uint32_t pass_tiles = sinc_mfma_pass_tiles(1, a.out_count, a.step);
+    const size_t frag_bytes = (size_t)pass_tiles * windows * 2 * 1024;
+    u32x4 *frags = reinterpret_cast<u32x4 *>(a.scratch);
+    TileMeta *meta = reinterpret_cast<TileMeta *>(reinterpret_cast<unsigned char *>(a.scratch) + ((frag_bytes + 255) & ~(size_t)255));
+    SincArgs ta{};  // what k_sinc_taps reads
+    ta.sincs = a.sincs;
+    ta.set_starts = a.set_starts;
+    ta.set_count = a.set_count;
+    ta.starts_stride = a.starts_stride;
+    ta.step = a.step;
+    const uint32_t row_blocks = (a.rows + kMfmaRows - 1) / kMfmaRows;
+    constexpr size_t lds_bytes = 2 * (size_t)kMfmaPlane;
+    // widest store the caller's rows allow: 16 bytes per lane (8 for mono s16), else 4 (mono s16 rows at even samples), else by element
+    int out_vec;
+    if (a.out32) out_vec = (((uintptr_t)a.out32 & 15) == 0 && a.out_stride % 4 == 0) ? 1 : 0;
+    else if (a.channels == 2) out_vec = (((uintptr_t)a.out16 & 15) == 0 && a.out_stride % 4 == 0) ? 1 : 0;
+    else out_vec = (((uintptr_t)a.out16 & 7) == 0 && a.out_stride % 4 == 0) ? 2 : ((((uintptr_t)a.out16 & 3) == 0 && a.out_stride % 2 == 0) ? 1 : 0);
+    if (a.out16 && a.channels == 2 && ((uintptr_t)a.out16 & 3)) return hipErrorInvalidValue;
+    static const hipError_t attr = [] {
+        hipError_t e = hipSuccess;
+        for (const void *f : {reinterpret_cast<const void *>(&k_sinc_mfma_s16<0>), reinterpret_cast<const void *>(&k_sinc_mfma_s16<1>),
+                              reinterpret_cast<const void *>(&k_sinc_mfma_s16<2>)}) {
+            const hipError_t r = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (r != hipSuccess) e = r;
+        }
+        return e;
+    }();
+    if (attr != hipSuccess) return attr;
+    for (uint32_t tile_first = 0; tile_first < all_tiles; tile_first += pass_tiles) {
+        const uint32_t tiles = std::min(pass_tiles, all_tiles - tile_first);
+        hipLaunchKernelGGL(k_sinc_taps<true>, dim3(tiles, 1), dim3(64), 0, s, ta, pass_tiles, tile_first, windows, frags, meta);
+        // runs of row blocks per workgroup, as launch_sinc_mfma
+        const uint32_t tile_chunks = (tiles + tpb - 1) / tpb;
+        uint32_t run = 8;
+        while (run > 1 && (uint64_t)((row_blocks + run - 1) / run) * tile_chunks < 1024) run >>= 1;
+        const dim3 grid((row_blocks + run - 1) / run, tile_chunks), block(kMfmaTiles * 64);
+        if (a.out32) hipLaunchKernelGGL(k_sinc_mfma_s16<0>, grid, block, lds_bytes, s, a, pass_tiles, tile_first, windows, tpb, run, out_vec, frags, meta);
+        else if (a.channels == 2)
+            hipLaunchKernelGGL(k_sinc_mfma_s16<2>, grid, block, lds_bytes, s, a, pass_tiles, tile_first, windows, tpb, run, out_vec, frags, meta);
+        else hipLaunchKernelGGL(k_sinc_mfma_s16<1>, grid, block, lds_bytes, s, a, pass_tiles, tile_first, windows, tpb, run, out_vec, frags, meta);
     }
     return hipGetLastError();
 }

@@ -286,6 +286,29 @@ hipError_t launch_sinc_resample(const SincArgs &a, hipStream_t s);
 uint32_t sinc_rows_per_block();
 size_t sinc_mfma_scratch_bytes(uint32_t n_sets, uint32_t out_count, double step);  // 0: this shape stays on the scalar form
 
+// The matrix-core form on s16 frame rows (resample.hip, k_sinc_taps<true> + k_sinc_mfma_s16): the one-shot resampler of the
+// device-resident decode tail at any ratio the matrix form takes.  One index set (the walk from -128 over in_frames samples).
+struct SincS16Args {
+    const int16_t *in16;      // 8-byte aligned; sample n of row r (stream r / channels, channel r % channels), value s / 32768, at
+                              //   in16 + (r / channels) * stream_stride + (r % channels) * 1024 + (n / 1024) * frame_stride + n % 1024
+    size_t stream_stride, frame_stride;  // in samples, multiples of 4
+    uint32_t channels;        // 1 or 2
+    uint32_t rows;            // streams * channels
+    uint32_t in_frames;       // samples per row: whole frames of 1024; n < 0 and n >= in_frames read as 0
+    int16_t *out16;           // [stream][out_stride frames][channels]: float_sample_to_i16 of the f32 result, interleaved -- or
+    float *out32;             // [rows][out_stride]; one of the two
+    size_t out_stride;
+    const float *sincs;       // [256][256] sub-filter table of this ratio
+    const double *set_starts; // index of every 32nd output, as SincArgs
+    const uint32_t *set_count;  // device copy of out_count
+    uint32_t starts_stride;
+    double step;
+    uint32_t out_count;
+    void *scratch;            // sinc_mfma_scratch_bytes(1, out_count, step) bytes; 0 bytes: a ratio this form does not take
+    size_t scratch_bytes;
+};
+hipError_t launch_sinc_rows_s16(const SincS16Args &a, hipStream_t s);
+
 // batched row copies (streaming resampler bookkeeping): job j copies count floats
 struct RowCopy {
     uint64_t src_off, dst_off;  // element offsets from the two bases

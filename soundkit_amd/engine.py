@@ -357,6 +357,25 @@ class Engine:
               "sk_downsample_48k_16k_frames_s16_to_f32_dev", self._h)
         return got.value
 
+    def downsample_frames_s16_to_s16_dev(self, d_pcm16, stream_stride, frame_stride, channels, n_streams, frames_per_stream,
+                                         in_hz, out_hz, d_out, out_stride):
+        """the same resample step at any pair of the common rates the matrix-core resampler takes (one-shot, planar s16 frames in):
+        d_out [n_streams][out_stride][channels] int16; returns downsample_out_frames(frames_per_stream * 1024, in_hz, out_hz)"""
+        got = C.c_uint32()
+        check(lib.sk_downsample_frames_s16_to_s16_dev(self._h, _ptr(d_pcm16), stream_stride, frame_stride, channels, n_streams,
+                                                      frames_per_stream, in_hz, out_hz, _ptr(d_out), out_stride, C.byref(got)),
+              "sk_downsample_frames_s16_to_s16_dev", self._h)
+        return got.value
+
+    def downsample_frames_s16_to_f32_dev(self, d_pcm16, stream_stride, frame_stride, channels, n_streams, frames_per_stream,
+                                         in_hz, out_hz, d_out, out_stride):
+        """the filter output before the 16-bit stage: d_out [n_streams * channels][out_stride] float32"""
+        got = C.c_uint32()
+        check(lib.sk_downsample_frames_s16_to_f32_dev(self._h, _ptr(d_pcm16), stream_stride, frame_stride, channels, n_streams,
+                                                      frames_per_stream, in_hz, out_hz, _ptr(d_out), out_stride, C.byref(got)),
+              "sk_downsample_frames_s16_to_f32_dev", self._h)
+        return got.value
+
     def downsample_48k_16k_frames_dev(self, d_pcm, stream_stride, frame_stride, channels, n_streams, frames_per_stream,
                                       d_out, out_stride):
         got = C.c_uint32()
