@@ -47,6 +47,7 @@ extern "C" {
 
 #define SK_AAC_FRAME_LEN 1024u /* dsp.rs:9 LONG_SPECTRUM_LEN */
 #define SK_MAX_CHANNELS 2u     /* AAC-LC SCE / CPE only: decoder.rs:116-133 */
+#define SK_MAX_PCM_CHANNELS 8u /* WAV / raw PCM sources on an engine with sk_engine_enable_wide_pcm; the reference sets no limit */
 
 typedef enum sk_status {
     SK_OK = 0,
@@ -91,6 +92,16 @@ int sk_engine_create(int device, uint32_t max_streams, sk_engine **out);
 void sk_engine_destroy(sk_engine *);
 int sk_engine_device(const sk_engine *);
 uint32_t sk_engine_max_streams(const sk_engine *);
+/* Reserves max_wide_streams (<= max_streams) slots for PCM streams of 3 ... SK_MAX_PCM_CHANNELS channels (5.1 / 7.1 WAV, headerless
+ * multichannel PCM).  Opt-in because a wide stream's resampler rows cost 8 x 96 KiB of device memory, so the caller sizes the pool;
+ * an engine that never calls this behaves exactly as before.  Once per engine and before its first sk_resampler_open (which
+ * allocates the rows): SK_ERR_INVALID_ARG afterwards, or when max_wide_streams is 0 or > max_streams.  With the pool, sk_stream_open takes
+ * 3 ... 8 channels (one slot each, SK_ERR_CAPACITY when none is free; sk_stream_close returns it) and sk_tick_run_pcm takes such
+ * sources.  A wide stream serves sk_resampler_open / _close / _process_f32 / _flush_f32, sk_stream_reset and sk_tick_run_pcm only:
+ * every synthesis / AAC / MP3 entry point refuses it as it refuses a wrong channel count.  No reference counterpart (the
+ * reference's worker allocates per stream). */
+int sk_engine_enable_wide_pcm(sk_engine *, uint32_t max_wide_streams);
+uint32_t sk_engine_wide_pcm_streams(const sk_engine *); /* the reserved count, 0 if not enabled */
 void *sk_engine_hip_stream(sk_engine *); /* hipStream_t */
 int sk_engine_synchronize(sk_engine *);
 const char *sk_engine_last_hip_error(const sk_engine *);
@@ -534,6 +545,13 @@ int sk_pcm_f32_planar_to_bytes_batch_dev(sk_engine *, int fmt, const float *d_pl
 /* downmix_channels target 1 (soundkit-decoder lib.rs:3500-3509) */
 int sk_pcm_downmix_mono(sk_engine *, const float *planar, size_t frames, uint32_t ch, float *mono);
 int sk_pcm_downmix_mono_dev(sk_engine *, const float *d_planar, size_t frames, uint32_t ch, float *d_mono);
+/* All of downmix_channels (soundkit-decoder lib.rs:3492-3561) for ch <= SK_MAX_PCM_CHANNELS, f32, the reference's operations in its
+ * order: target 1 = the mean above; target 2 from more than two channels = L + 0.707 C + 0.707 Ls, R + 0.707 C + 0.707 Rs by channel
+ * index (0 1 2 4 5; channels 3, 6, 7 unused), then both divided by m = max(|L|, |R|) over the whole input when m > 1 (a NaN never
+ * raises m, an infinity does: inf * 0 = NaN as in the reference) -- two launches, the first reduces m on the device; any other
+ * target = the first min(target, ch) channels (no upmix).  out is [min(target, ch)][frames]; frames <= 2^31 - 1; target >= 1. */
+int sk_pcm_downmix(sk_engine *, const float *planar, size_t frames, uint32_t ch, uint32_t target, float *out);
+int sk_pcm_downmix_dev(sk_engine *, const float *d_planar, size_t frames, uint32_t ch, uint32_t target, float *d_out);
 /* exact_signed_pcm_to_i16 (soundkit-decoder lib.rs:3458-3489); fmt in {S24LE,S24BE,S32LE,S32BE} */
 int sk_pcm_exact_to_i16(sk_engine *, int fmt, const uint8_t *in, size_t samples, uint8_t *out_s16le);
 int sk_pcm_exact_to_i16_dev(sk_engine *, int fmt, const uint8_t *d_in, size_t samples, uint8_t *d_out_s16le);
@@ -729,16 +747,22 @@ int sk_tick_run_mixed_md(sk_engine *, const sk_tick_stream *streams, uint32_t n_
 /* What the reference's worker does to the AudioData a WavStreamProcessor / RawPcmStreamProcessor hands it -- apply_output_options,
  * soundkit-decoder lib.rs:3324-3456 -- for every unit (= one piece of one `add`) of every listed stream, in one launch sequence:
  *   24- / 32-bit signed -> 16 bit, same rate and channels: exact_signed_pcm_to_i16 (lib.rs:3458-3489), one output per unit;
- *   any other change without a rate change: audio_data_to_f32_channels (non-finite -> 0) -> mono downmix when out_channels <
- *     channels -> f32_channels_to_bytes, one output per unit, in registers (k_pcm_direct);
- *   a rate change: bytes -> planar f32 straight into the stream's resampler rows (k_pcm_ingest) -> the resampler rounds the other
- *     ticks use -> downmix -> bytes, one output per completed 4096-frame chunk, plus the flushed and trimmed tail with `flush`.
+ *   any other change without a rate change: audio_data_to_f32_channels (non-finite -> 0) -> downmix_channels when out_channels <
+ *     channels -> f32_channels_to_bytes, one output per unit (k_pcm_direct in registers; a source of more than two channels that is
+ *     downmixed: k_pcm_wide through LDS);
+ *   a rate change: bytes -> planar f32 straight into the stream's resampler rows (k_pcm_ingest / k_pcm_wide_ingest) -> the resampler
+ *     rounds the other ticks use -> downmix -> bytes, one output per completed 4096-frame chunk, plus the flushed and trimmed tail with
+ *     `flush`.  All rows of a wide source go through the resampler, those a downmix ignores included.
+ * downmix_channels (lib.rs:3492-3561) is complete: the mean for one output channel; for two from more than two the surround
+ * matrix of sk_pcm_downmix with its normalisation taken over each AudioData (one unit, or one resampled chunk); otherwise the first
+ * out_channels channels.  out_channels >= channels keeps them all: there is no upmix.
  * Outputs are signed little-endian, except that 32-bit output of a float source stays float (lib.rs:3377-3382: SK_TICK_OUT_FLOAT in
  * the record's `reserved`).  A stream with nothing to change (the fast path, lib.rs:3339-3345) needs no device and is refused here
  * (SK_ERR_INVALID_ARG): its pieces are delivered as they are.
- * Limits: 1 or 2 channels (SK_ERR_UNSUPPORTED for more: the resampler state has two rows per stream, and the only downmix is to
- * mono), 16- / 24- / 32-bit samples (the eight SK_FMT_* formats), a unit of at most 2 GiB - 1, at most 2^31 - 1 frames per stream
- * and tick.  units: stream by stream in the order of `streams`; byte_offset is a multiple of 16 (the caller packs the pieces that
+ * Limits: 1 or 2 channels, or up to SK_MAX_PCM_CHANNELS on an engine with sk_engine_enable_wide_pcm (SK_ERR_UNSUPPORTED for more, or
+ * without the pool: a wide stream's resampler state is eight rows per stream, which the caller reserves), 16- / 24- / 32-bit samples
+ * (the eight SK_FMT_* formats), a unit of at most 2 GiB - 1, at most 2^31 - 1 frames per stream and tick.
+ * units: stream by stream in the order of `streams`; byte_offset is a multiple of 16 (the caller packs the pieces that
  * way: a lane then reads 16 samples with 16-byte loads), byte_len a whole number of frames, > 0.  A resampling stream names the
  * engine stream that holds its resampler (sk_stream_open with the source's rate and channels, sk_resampler_open); `stream` is
  * ignored otherwise.  Blocks until out_bytes holds the results.  On failure the resamplers' bookkeeping is as before the call. */
@@ -746,7 +770,7 @@ typedef struct sk_pcm_tick_stream {
     uint32_t stream;      /* engine stream (resample = 1 only) */
     uint32_t n_units;     /* units of this stream in the tick (may be 0 with flush) */
     uint8_t format;       /* SK_FMT_* of the source */
-    uint8_t channels;     /* of the source: 1 or 2 */
+    uint8_t channels;     /* of the source: 1 or 2; up to SK_MAX_PCM_CHANNELS with sk_engine_enable_wide_pcm */
     uint8_t out_bits;     /* DecodeOptions::output_bits_per_sample resolved: 16 / 24 / 32 */
     uint8_t out_channels; /* DecodeOptions::output_channels resolved (source channels when None) */
     uint8_t resample;     /* 1: route through the stream's resampler */

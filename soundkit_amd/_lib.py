@@ -251,6 +251,10 @@ _sig = {
     "sk_pcm_f32_planar_to_bytes_dev": (_i, [_vp, _i, _vp, _sz, _u32, _vp]),
     "sk_pcm_downmix_mono": (_i, [_vp, _vp, _sz, _u32, _vp]),
     "sk_pcm_downmix_mono_dev": (_i, [_vp, _vp, _sz, _u32, _vp]),
+    "sk_pcm_downmix": (_i, [_vp, _vp, _sz, _u32, _u32, _vp]),
+    "sk_pcm_downmix_dev": (_i, [_vp, _vp, _sz, _u32, _u32, _vp]),
+    "sk_engine_enable_wide_pcm": (_i, [_vp, _u32]),
+    "sk_engine_wide_pcm_streams": (_u32, [_vp]),
     "sk_pcm_exact_to_i16": (_i, [_vp, _i, _vp, _sz, _vp]),
     "sk_pcm_exact_to_i16_dev": (_i, [_vp, _i, _vp, _sz, _vp]),
     "sk_downsample_48k_16k_out_frames": (_u32, [_u32]),

@@ -76,6 +76,7 @@ struct StreamInfo {
     bool open = false;
     uint32_t sample_rate = 0;
     uint8_t channels = 0;
+    int wide_slot = -1;  // streams of 3 ... 8 channels (sk_engine_enable_wide_pcm): which eight-row slot of the resampler rows is theirs
     // streaming resampler (soundkit-decoder lib.rs:1917-2060)
     bool rs_open = false;
     uint32_t rs_in_hz = 0, rs_out_hz = 0;
@@ -224,7 +225,12 @@ struct sk_engine {
 
     float *d_delay = nullptr;
     uint8_t *d_prev_shape = nullptr;
-    float *d_rs = nullptr;  // [max_streams * 2][kRsRow] (kRsBlocks blocks of 4096), allocated on first sk_resampler_open
+    float *d_rs = nullptr;  // [max_streams * 2 + max_wide * 8][kRsRow] (kRsBlocks blocks of 4096), allocated on first sk_resampler_open
+    // sk_engine_enable_wide_pcm: slots for streams of 3 ... 8 channels; slot w owns rows max_streams * 2 + w * 8 ... + 7 of d_rs
+    uint32_t max_wide = 0;
+    bool wide_enabled = false;
+    std::vector<uint32_t> free_wide;
+    uint32_t *d_wide_peak = nullptr;  // sk_pcm_downmix_dev: the one-call path's peak word
     // MP3 hybrid synthesis (mp3_hybrid.hip): tables and per-(stream, channel) state, allocated on first use
     float *d_mp3_tables = nullptr, *d_mp3_state = nullptr;
     bool mp3_window_set = false;
@@ -299,6 +305,12 @@ struct sk_aac_plan {
     uint32_t uniform_channels = 0;  // channels of every stream in the plan when they all agree (else 0)
 };
 
+// First resampler row of an open stream in d_rs.  Narrow streams keep two rows each by id; a wide stream's eight lie behind them.
+inline uint64_t rs_row0(const sk_engine *e, uint32_t id) {
+    const int w = e->streams[id].wide_slot;
+    return w < 0 ? (uint64_t)id * 2 : (uint64_t)e->max_streams * 2 + (uint64_t)w * 8;
+}
+
 #define SK_HIP(expr, what)                               \
     do {                                                  \
         hipError_t _e = (expr);                           \
@@ -353,9 +365,9 @@ struct DeviceGuard {
 
 void flush_stream_resets(sk_engine *e) {
     hipError_t he = hipSuccess;
-    if (!e->pending_rs_reset.empty() && e->d_rs) {  // the resampler rows of the streams opened since the last call: one launch
+    if (!e->pending_rs_reset.empty() && e->d_rs) {  // the resampler rows of the streams opened since the last call, as spans of two rows: one launch
         const uint32_t n = (uint32_t)e->pending_rs_reset.size();
-        if (!e->d_rs_reset_ids) he = hipMalloc((void **)&e->d_rs_reset_ids, (size_t)e->max_streams * sizeof(uint32_t));
+        if (!e->d_rs_reset_ids) he = hipMalloc((void **)&e->d_rs_reset_ids, ((size_t)e->max_streams + 4) * sizeof(uint32_t));
         if (he == hipSuccess) he = hipMemcpyAsync(e->d_rs_reset_ids, e->pending_rs_reset.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream);
         if (he == hipSuccess) he = sk::launch_zero_spans(e->d_rs, e->d_rs_reset_ids, n, 2 * kRsRow, e->stream);
         if (he != hipSuccess) (void)e->hip_fail(he, "reset resampler rows");
@@ -628,7 +640,7 @@ void sk_engine_destroy(sk_engine *e) try {
         if (e->d_reset_ids) (void)hipFree(e->d_reset_ids);
         if (e->d_rs_reset_ids) (void)hipFree(e->d_rs_reset_ids);
         e->sinc_scratch.release();
-        for (void *p : {(void *)e->d_mp3_rq, (void *)e->d_mp3_tables, (void *)e->d_mp3_state, (void *)e->d_pns, e->d_ec_blob, (void *)e->d_delay, (void *)e->d_prev_shape, (void *)e->d_rs, (void *)e->d_tables,
+        for (void *p : {(void *)e->d_mp3_rq, (void *)e->d_mp3_tables, (void *)e->d_mp3_state, (void *)e->d_pns, e->d_ec_blob, (void *)e->d_delay, (void *)e->d_prev_shape, (void *)e->d_rs, (void *)e->d_wide_peak, (void *)e->d_tables,
                         (void *)e->d_pow43, (void *)e->d_sftab, (void *)e->d_taps, (void *)e->d_afrag16, (void *)e->d_afrag_f16,
                         (void *)e->d_zeros})
             if (p) (void)hipFree(p);
@@ -665,6 +677,29 @@ int sk_engine_device(const sk_engine *e) try {
 } catch (...) {
     return sk::abi_caught("sk_engine_device");
 }
+int sk_engine_enable_wide_pcm(sk_engine *e, uint32_t max_wide_streams) try {
+    sk::abi_enter();
+    if (!e) return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    // once, and before the resampler rows exist: their allocation (the first sk_resampler_open) is sized by this
+    if (e->wide_enabled || e->d_rs || max_wide_streams == 0 || max_wide_streams > e->max_streams) return SK_ERR_INVALID_ARG;
+    e->free_wide.reserve(max_wide_streams);
+    for (uint32_t i = max_wide_streams; i-- > 0;) e->free_wide.push_back(i);
+    e->max_wide = max_wide_streams;
+    e->wide_enabled = true;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_engine_enable_wide_pcm");
+}
+
+uint32_t sk_engine_wide_pcm_streams(const sk_engine *e) try {
+    sk::abi_enter();
+    return e ? e->max_wide : 0;
+} catch (...) {
+    (void)sk::abi_caught("sk_engine_wide_pcm_streams");
+    return 0;
+}
+
 uint32_t sk_engine_max_streams(const sk_engine *e) try {
     sk::abi_enter();
     return e ? e->max_streams : 0;
@@ -743,6 +778,13 @@ int sk_engine_synchronize(sk_engine *e) try {
 
 // ---- streams --------------------------------------------------------------------------------
 
+// queues the clearing of a stream's resampler rows (flush_stream_resets): spans of two rows, one for a narrow stream, four for a wide one
+static void queue_rs_reset(sk_engine *e, uint32_t id) {
+    const uint32_t span0 = (uint32_t)(rs_row0(e, id) / 2), n = e->streams[id].wide_slot < 0 ? 1 : 4;
+    for (uint32_t k = 0; k < n; ++k) e->pending_rs_reset.push_back(span0 + k);
+    if (e->pending_rs_reset.size() >= e->max_streams) flush_stream_resets(e);
+}
+
 static int reset_stream_state(sk_engine *e, uint32_t id) {
     // overlap delay, previous window shape and PNS generator (spectral.rs:2459): queued, cleared by one launch for all the
     // streams opened in a row (flush_stream_resets, in front of the next call that touches the device)
@@ -753,9 +795,11 @@ static int reset_stream_state(sk_engine *e, uint32_t id) {
 
 int sk_stream_open(sk_engine *e, uint32_t sample_rate, uint8_t channels, uint32_t *stream_out) try {
     sk::abi_enter();
-    if (!e || !stream_out || channels < 1 || channels > SK_MAX_CHANNELS || sample_rate == 0) return SK_ERR_INVALID_ARG;
+    if (!e || !stream_out || channels < 1 || channels > SK_MAX_PCM_CHANNELS || sample_rate == 0) return SK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(e->mu);
-    if (e->free_ids.empty()) return SK_ERR_CAPACITY;
+    const bool wide = channels > SK_MAX_CHANNELS;  // PCM only, and only on an engine that reserved slots for them
+    if (wide && !e->wide_enabled) return SK_ERR_INVALID_ARG;
+    if (e->free_ids.empty() || (wide && e->free_wide.empty())) return SK_ERR_CAPACITY;
     const uint32_t id = e->free_ids.back();
     int rc = reset_stream_state(e, id);
     if (rc != SK_OK) return rc;
@@ -765,6 +809,7 @@ int sk_stream_open(sk_engine *e, uint32_t sample_rate, uint8_t channels, uint32_
     s.open = true;
     s.sample_rate = sample_rate;
     s.channels = channels;
+    if (wide) s.wide_slot = (int)e->free_wide.back(), e->free_wide.pop_back();
     *stream_out = id;
     return SK_OK;
 } catch (...) {
@@ -776,6 +821,7 @@ int sk_stream_close(sk_engine *e, uint32_t id) try {
     if (!e) return SK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(e->mu);
     if (!stream_ok(e, id)) return SK_ERR_BAD_STREAM;
+    if (e->streams[id].wide_slot >= 0) e->free_wide.push_back((uint32_t)e->streams[id].wide_slot);
     e->streams[id] = StreamInfo();
     e->free_ids.push_back(id);
     return SK_OK;
@@ -793,7 +839,7 @@ int sk_stream_reset(sk_engine *e, uint32_t id) try {
     s.rs_fill = 0;
     s.rs_chunks = 0;
     s.rs_last_index = -128.0;
-    if (s.rs_open && e->d_rs) e->pending_rs_reset.push_back(id);  // cleared with the next call's first launch (flush_stream_resets)
+    if (s.rs_open && e->d_rs) queue_rs_reset(e, id);  // cleared with the next call's first launch (flush_stream_resets)
     return reset_stream_state(e, id);
 } catch (...) {
     return sk::abi_caught("sk_stream_reset");
@@ -804,6 +850,7 @@ int sk_stream_get_state(sk_engine *e, uint32_t id, float *delay_out, uint8_t *pr
     if (!e || !delay_out || !prev_shape_out) return SK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(e->mu);
     if (!stream_ok(e, id)) return SK_ERR_BAD_STREAM;
+    if (e->streams[id].channels > SK_MAX_CHANNELS) return SK_ERR_INVALID_ARG;  // a wide PCM stream has no synthesis state
     DeviceGuard guard(e);
     const uint32_t ch = e->streams[id].channels;
     SK_HIP(hipMemcpyAsync(delay_out, e->d_delay + (size_t)id * 2048, ch * 1024 * sizeof(float), hipMemcpyDeviceToHost,
@@ -821,6 +868,7 @@ int sk_stream_set_state(sk_engine *e, uint32_t id, const float *delay, const uin
     if (!e || !delay || !prev_shape) return SK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(e->mu);
     if (!stream_ok(e, id)) return SK_ERR_BAD_STREAM;
+    if (e->streams[id].channels > SK_MAX_CHANNELS) return SK_ERR_INVALID_ARG;  // a wide PCM stream has no synthesis state
     const uint32_t ch = e->streams[id].channels;
     for (uint32_t c = 0; c < ch; ++c)
         if (prev_shape[c] > 1) return SK_ERR_INVALID_ARG;
@@ -897,7 +945,7 @@ int build_plan_host(sk_engine *e, const sk_aac_frame_desc *descs, uint32_t n, in
         const sk_aac_frame_desc &d = descs[i];
         int32_t st = SK_FRAME_OK;
         if (!stream_ok(e, d.stream)) st = SK_FRAME_BAD_STREAM;
-        else if (d.channels != e->streams[d.stream].channels) st = SK_FRAME_BAD_CHANNELS;
+        else if (d.channels != e->streams[d.stream].channels || d.channels > SK_MAX_CHANNELS) st = SK_FRAME_BAD_CHANNELS;
         else {
             for (uint32_t c = 0; c < d.channels; ++c)
                 if (d.window_sequence[c] > 3 || d.window_shape[c] > 1) st = SK_FRAME_BAD_WINDOW;
@@ -1501,6 +1549,51 @@ int sk_pcm_downmix_mono(sk_engine *e, const float *planar, size_t frames, uint32
     });
 } catch (...) {
     return sk::abi_caught("sk_pcm_downmix_mono");
+}
+// downmix_channels (lib.rs:3492-3561) as one job of the wide kernels: planar rows in, min(target, ch) planar rows out.  e->mu held.
+static int downmix_locked(sk_engine *e, const float *d_planar, size_t frames, uint32_t ch, uint32_t target, float *d_out) {
+    sk::WideJob j{};
+    j.src = d_planar, j.dst = d_out, j.src_stride = frames, j.dst_stride = frames, j.frames = (uint32_t)frames;
+    j.fmt_in = j.fmt_out = sk::kWidePlanar;
+    j.ch_in = (uint8_t)ch, j.ch_out = (uint8_t)std::min(target, ch);
+    j.peak = sk::kWideNoPeak;
+    if (j.ch_out == 2 && ch > 2) {  // the stereo branch: its peak word, cleared in stream order in front of the two launches
+        if (!e->d_wide_peak) SK_HIP(hipMalloc((void **)&e->d_wide_peak, 256), "alloc downmix peak");
+        SK_HIP(hipMemsetAsync(e->d_wide_peak, 0, sizeof(uint32_t), e->stream), "clear downmix peak");
+        j.peak = 0;
+    }
+    SK_HIP(sk::launch_pcm_wide_one(j, e->d_wide_peak, e->stream), "launch downmix");
+    return SK_OK;
+}
+static bool downmix_args_ok(size_t frames, uint32_t ch, uint32_t target) {
+    return ch >= 1 && ch <= SK_MAX_PCM_CHANNELS && target >= 1 && frames <= 0x7fffffffu;
+}
+int sk_pcm_downmix_dev(sk_engine *e, const float *d_planar, size_t frames, uint32_t ch, uint32_t target, float *d_out) try {
+    sk::abi_enter();
+    if (!e || !downmix_args_ok(frames, ch, target) || (frames && (!d_planar || !d_out))) return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    return downmix_locked(e, d_planar, frames, ch, target, d_out);
+} catch (...) {
+    return sk::abi_caught("sk_pcm_downmix_dev");
+}
+int sk_pcm_downmix(sk_engine *e, const float *planar, size_t frames, uint32_t ch, uint32_t target, float *out) try {
+    sk::abi_enter();
+    if (!e || !downmix_args_ok(frames, ch, target) || (frames && (!planar || !out))) return SK_ERR_INVALID_ARG;
+    if (frames == 0) return SK_OK;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    const size_t in_bytes = frames * ch * 4, out_bytes = frames * std::min(target, ch) * 4;
+    SK_HIP(e->in_buf.reserve(in_bytes), "alloc staging");
+    SK_HIP(e->out_buf.reserve(out_bytes), "alloc staging");
+    SK_HIP(hipMemcpyAsync(e->in_buf.p, planar, in_bytes, hipMemcpyHostToDevice, e->stream), "H2D downmix");
+    const int rc = downmix_locked(e, (const float *)e->in_buf.p, frames, ch, target, (float *)e->out_buf.p);
+    if (rc != SK_OK) return rc;
+    SK_HIP(hipMemcpyAsync(out, e->out_buf.p, out_bytes, hipMemcpyDeviceToHost, e->stream), "D2H downmix");
+    SK_HIP(hipStreamSynchronize(e->stream), "downmix sync");
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_pcm_downmix");
 }
 static bool exact_fmt_ok(int fmt) { return fmt >= SK_FMT_S24LE && fmt <= SK_FMT_S32BE; }
 int sk_pcm_exact_to_i16_dev(sk_engine *e, int fmt, const uint8_t *d_in, size_t samples, uint8_t *d_out) try {
@@ -2774,7 +2867,7 @@ int sk_resampler_open(sk_engine *e, uint32_t id, uint32_t in_hz, uint32_t out_hz
     // (like their synthesis state) are cleared by ONE launch in front of the next call that touches the device
     DeviceGuard guard(e->device);
     if (!e->d_rs) {
-        const size_t bytes = (size_t)e->max_streams * 2 * kRsRow * sizeof(float);
+        const size_t bytes = ((size_t)e->max_streams * 2 + (size_t)e->max_wide * 8) * kRsRow * sizeof(float);
         SK_HIP(hipMalloc((void **)&e->d_rs, bytes), "alloc resampler history");
         SK_HIP(hipMemsetAsync(e->d_rs, 0, bytes, e->stream), "clear resampler history");
     }
@@ -2789,8 +2882,7 @@ int sk_resampler_open(sk_engine *e, uint32_t id, uint32_t in_hz, uint32_t out_hz
     s.rs_fill = 0;
     s.rs_chunks = 0;
     s.rs_last_index = -128.0;
-    e->pending_rs_reset.push_back(id);
-    if (e->pending_rs_reset.size() >= e->max_streams) flush_stream_resets(e);
+    queue_rs_reset(e, id);
     return SK_OK;
 } catch (...) {
     return sk::abi_caught("sk_resampler_open");
@@ -2838,6 +2930,15 @@ struct AuxArena {
         used += bytes;
         if (v.empty()) return hipSuccess;
         return hipMemcpyAsync((void *)*out, src, v.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    }
+    // the same for an array the kernels write to as well
+    template <typename T>
+    hipError_t put_rw(const std::vector<T> &v, hipStream_t st, T **out) {
+        const T *p = nullptr;
+        const size_t at = used;
+        const hipError_t he = put(v, st, &p);
+        *out = he == hipSuccess ? reinterpret_cast<T *>(base + at) : nullptr;
+        return he;
     }
 };
 
@@ -2952,7 +3053,7 @@ int rs_process_ready(sk_engine *e, std::vector<RsCall> &calls, const std::vector
             for (uint32_t ch = 0; ch < c.channels; ++ch) {
                 const uint64_t off = (uint64_t)(c.row0 + ch) * out_stride + it.col;
                 if (off > 0xffffffffull) return SK_ERR_INVALID_ARG;
-                row_map.push_back((c.id * 2 + ch) * kRsBlocks + it.k);  // the chunk as a virtual row of one block's pitch
+                row_map.push_back((uint32_t)(rs_row0(e, c.id) + ch) * kRsBlocks + it.k);  // the chunk as a virtual row of one block's pitch
                 out_off.push_back((uint32_t)off);
                 row_set.push_back(it.set_index);
             }
@@ -3077,7 +3178,7 @@ int rs_process_ready(sk_engine *e, std::vector<RsCall> &calls, const std::vector
         if (!n_chunks) continue;
         const uint32_t rest = s.rs_fill - n_chunks * kRsChunk, len = kRsHist + rest, gap = n_chunks * kRsChunk;
         for (uint32_t ch = 0; ch < c.channels; ++ch) {
-            const uint64_t row = ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase;
+            const uint64_t row = (rs_row0(e, c.id) + ch) * kRsRow + kRsBase;
             slides.push_back(sk::RowCopy{row + gap, row, std::min(len, gap), 0});
             if (len > gap) tails.push_back(sk::RowCopy{row + 2ull * gap, row + gap, len - gap, 0});
         }
@@ -3147,7 +3248,7 @@ int sk_resampler_process_f32(sk_engine *e, const uint32_t *streams, uint32_t n_s
             if (take) {
                 for (uint32_t ch = 0; ch < c.channels; ++ch)
                     jobs.push_back(sk::RowCopy{(uint64_t)(c.row0 + ch) * frames + c.consumed,
-                                               ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + s.rs_fill, take, 0});
+                                               (rs_row0(e, c.id) + ch) * kRsRow + kRsBase + kRsHist + s.rs_fill, take, 0});
                 s.rs_fill += take;
                 c.consumed += take;
             }
@@ -3207,7 +3308,7 @@ int sk_resampler_flush_f32(sk_engine *e, const uint32_t *streams, uint32_t n_str
             c.trim = (uint32_t)std::llround(((double)padded * (double)s.rs_out_hz) / (double)s.rs_in_hz);
         for (uint32_t ch = 0; ch < c.channels && padded; ++ch)
             for (uint32_t o = 0; o < padded; o += 8192)
-                pads.push_back(sk::RowCopy{0, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + remaining + o,
+                pads.push_back(sk::RowCopy{0, (rs_row0(e, c.id) + ch) * kRsRow + kRsBase + kRsHist + remaining + o,
                                            std::min<uint32_t>(8192, padded - o), 0});
         s.rs_fill = kRsChunk;
         ready.push_back(ci);
@@ -3625,7 +3726,7 @@ int rs_run_rounds(sk_engine *e, std::vector<RsCall> &calls, float *d_res, size_t
             c.trim = (uint32_t)std::llround(((double)padded * (double)s.rs_out_hz) / (double)s.rs_in_hz);
         for (uint32_t ch = 0; ch < c.channels && padded; ++ch)
             for (uint32_t o = 0; o < padded; o += 8192)
-                pads.push_back(sk::RowCopy{0, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + remaining + o,
+                pads.push_back(sk::RowCopy{0, (rs_row0(e, c.id) + ch) * kRsRow + kRsBase + kRsHist + remaining + o,
                                            std::min<uint32_t>(8192, padded - o), 0});
         s.rs_fill = kRsChunk;
         ready.push_back(ci);
@@ -3676,6 +3777,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
         uint32_t k = 0;
         for (uint32_t i = 0; i < n_streams; ++i) {
             if (!stream_ok(e, ts[i].stream)) return SK_ERR_BAD_STREAM;
+            if (e->streams[ts[i].stream].channels > SK_MAX_CHANNELS) return SK_ERR_INVALID_ARG;  // a wide PCM stream decodes nothing
             if (ts[i].codec == SK_TICK_MP3) continue;
             for (uint32_t f = 0; f < ts[i].n_frames; ++f, ++k) {
                 au_descs[k] = sk_aac_frame_desc{};
@@ -3714,6 +3816,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
         for (uint32_t i = 0; i < n_streams; ++i) {
             const sk_tick_stream &t = ts[i];
             if (!stream_ok(e, t.stream)) return SK_ERR_BAD_STREAM;
+            if (e->streams[t.stream].channels > SK_MAX_CHANNELS) return SK_ERR_INVALID_ARG;  // a wide PCM stream decodes nothing
             if (seen[t.stream]++) return SK_ERR_INVALID_ARG;  // a stream appears once per tick
             if (t.out_bits != 16 && t.out_bits != 24 && t.out_bits != 32) return SK_ERR_INVALID_ARG;
             if (t.out_channels == 0) return SK_ERR_INVALID_ARG;
@@ -4017,7 +4120,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
                 if (!joined) {
                     run_at = jobs.size();
                     for (uint32_t ch = 0; ch < c.channels; ++ch)  // MP3 rows hold q / 32768 already: a plain copy
-                        jobs.push_back(sk::RowCopy{(row + ch) * 1024 + within, ((uint64_t)c.id * 2 + ch) * kRsRow + kRsBase + kRsHist + fill, n,
+                        jobs.push_back(sk::RowCopy{(row + ch) * 1024 + within, (rs_row0(e, c.id) + ch) * kRsRow + kRsBase + kRsHist + fill, n,
                                                    t.mp3 ? 0u : 1u});
                     run_pieces = whole ? 1 : 0;
                     run_row = row;
@@ -4223,7 +4326,8 @@ int pcm_tick_plan(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_s
         PcmCall &c = pc[i];
         if (t.format > SK_FMT_F32BE) return SK_ERR_INVALID_ARG;
         if (t.channels == 0 || t.out_channels == 0) return SK_ERR_INVALID_ARG;
-        if (t.channels > SK_MAX_CHANNELS) return SK_ERR_UNSUPPORTED;
+        // 3 ... 8 channels: only an engine that reserved the slots for them (sk_engine_enable_wide_pcm) takes them
+        if (t.channels > SK_MAX_CHANNELS && (t.channels > SK_MAX_PCM_CHANNELS || !e->wide_enabled)) return SK_ERR_UNSUPPORTED;
         if (t.out_bits != 16 && t.out_bits != 24 && t.out_bits != 32) return SK_ERR_INVALID_ARG;
         const uint32_t bits = pcm_fmt_bits(t.format);
         // the fast path (lib.rs:3339-3345) needs no device: such a stream's pieces are delivered as they are, by the caller
@@ -4344,7 +4448,8 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
         SK_HIP(e->tick_res.reserve(res_rows * res_stride * 4 + 16), "alloc tick resampler output");
         d_res = (float *)e->tick_res.p;
         std::vector<sk::PcmIngestJob> jobs;
-        uint32_t max_samples = 0;
+        std::vector<sk::PcmWideIngestJob> wide_jobs;  // sources of more than two channels
+        uint32_t max_samples = 0, max_wide_frames = 0;
         RsRounds rounds;
         rounds.total_in = [&](size_t ci) { return pc[call_stream[ci]].total_frames; };
         rounds.append = [&](size_t ci, uint32_t take, uint32_t fill) {
@@ -4358,15 +4463,24 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
                 // a unit that does not fit is cut where its next piece starts 16-byte aligned again (c.within stays a multiple of kPcmCutFrames)
                 if (n < left) n &= ~(sk::kPcmCutFrames - 1);
                 if (n == 0) break;
-                sk::PcmIngestJob j{};
-                j.src = d_in + un.byte_offset + (size_t)c.within * c.frame_bytes;
-                j.dst0 = e->d_rs + ((uint64_t)calls[ci].id * 2) * kRsRow + kRsBase + kRsHist + fill;
-                j.dst1 = j.dst0 + kRsRow;
-                j.frames = n;
-                j.fmt = ts[i].format;
-                j.ch = ts[i].channels;
-                jobs.push_back(j);
-                max_samples = std::max(max_samples, n * ts[i].channels);
+                const uint8_t *src = d_in + un.byte_offset + (size_t)c.within * c.frame_bytes;
+                float *row = e->d_rs + rs_row0(e, calls[ci].id) * kRsRow + kRsBase + kRsHist + fill;
+                if (ts[i].channels > SK_MAX_CHANNELS) {
+                    sk::PcmWideIngestJob j{};
+                    j.src = src, j.dst = row, j.row_stride = kRsRow, j.frames = n, j.fmt = ts[i].format, j.ch = ts[i].channels;
+                    wide_jobs.push_back(j);
+                    max_wide_frames = std::max(max_wide_frames, n);
+                } else {
+                    sk::PcmIngestJob j{};
+                    j.src = src;
+                    j.dst0 = row;
+                    j.dst1 = j.dst0 + kRsRow;
+                    j.frames = n;
+                    j.fmt = ts[i].format;
+                    j.ch = ts[i].channels;
+                    jobs.push_back(j);
+                    max_samples = std::max(max_samples, n * ts[i].channels);
+                }
                 fill += n, taken += n, take -= n;
                 c.within += n;
                 if (n != left) break;  // the rest of this unit goes down in the next round
@@ -4375,12 +4489,20 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
             return taken;
         };
         rounds.launch = [&]() -> int {
-            if (jobs.empty()) return SK_OK;
-            const sk::PcmIngestJob *d_jobs = nullptr;
-            SK_HIP(aux.put(jobs, e->stream, &d_jobs), "upload tick pcm ingest jobs");
-            SK_HIP(sk::launch_pcm_ingest(d_jobs, (uint32_t)jobs.size(), max_samples, e->stream), "tick pcm ingest");
-            jobs.clear();
-            max_samples = 0;
+            if (!jobs.empty()) {
+                const sk::PcmIngestJob *d_jobs = nullptr;
+                SK_HIP(aux.put(jobs, e->stream, &d_jobs), "upload tick pcm ingest jobs");
+                SK_HIP(sk::launch_pcm_ingest(d_jobs, (uint32_t)jobs.size(), max_samples, e->stream), "tick pcm ingest");
+                jobs.clear();
+                max_samples = 0;
+            }
+            if (!wide_jobs.empty()) {
+                const sk::PcmWideIngestJob *d_jobs = nullptr;
+                SK_HIP(aux.put(wide_jobs, e->stream, &d_jobs), "upload tick pcm wide ingest jobs");
+                SK_HIP(sk::launch_pcm_wide_ingest(d_jobs, (uint32_t)wide_jobs.size(), max_wide_frames, e->stream), "tick pcm wide ingest");
+                wide_jobs.clear();
+                max_wide_frames = 0;
+            }
             return SK_OK;
         };
         rounds.flush = [&](size_t ci) { return ts[call_stream[ci]].flush != 0; };
@@ -4394,6 +4516,10 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
     e->where.store("tick (pcm): direct conversion, pack");
     std::vector<sk::PcmDirectJob> directs;
     std::vector<sk::PackJob> packs;
+    // sources of more than two channels: every downmix without a rate change, and every pack behind the resampler rounds.  A job whose
+    // output is the stereo branch's owns a word of `peaks`, zeroed with the upload, for the first of its two launches.
+    std::vector<sk::WideJob> wides[2];  // [0] planar rows in (the pack), [1] interleaved bytes in (the direct conversion)
+    uint32_t n_peaks = 0, n_wide_peaks[2] = {0, 0}, max_wide_frames[2] = {0, 0};
     uint32_t n_rec = 0, max_pack_frames = 0, max_direct_samples = 0;
     size_t cursor = 0;
     uint8_t *d_out = nullptr;
@@ -4415,16 +4541,31 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
     for (int pass = 0; pass < 2; ++pass) {
         n_rec = 0;
         cursor = 0;
+        n_peaks = 0;
+        n_wide_peaks[0] = n_wide_peaks[1] = 0;
         for (uint32_t i = 0; i < n_streams; ++i) {
             const sk_pcm_tick_stream &t = ts[i];
             const PcmCall &c = pc[i];
+            const bool wide = t.channels > SK_MAX_CHANNELS;
+            auto wide_job = [&](const void *src, uint64_t src_stride, uint8_t fmt_in, sk_tick_output *o, uint32_t frames) {
+                sk::WideJob j{};
+                j.src = src, j.src_stride = src_stride, j.dst = d_out + o->byte_offset, j.frames = frames;
+                j.fmt_in = fmt_in, j.fmt_out = c.fmt_out, j.ch_in = t.channels, j.ch_out = (uint8_t)c.ch_out;
+                const int kind = fmt_in != sk::kWidePlanar;
+                j.peak = sk::kWideNoPeak;
+                if (c.ch_out == 2) j.peak = n_peaks++, n_wide_peaks[kind] += 1;
+                wides[kind].push_back(j);
+                max_wide_frames[kind] = std::max(max_wide_frames[kind], frames);
+            };
             if (!t.resample) {
                 for (uint32_t u = 0; u < t.n_units; ++u) {
                     const sk_pcm_unit &un = units[c.first + u];
                     const uint32_t frames = un.byte_len / c.frame_bytes;
                     sk_tick_output *o = emit(i, frames, c, t.out_bits);
                     if (!o) return SK_ERR_INVALID_ARG;
-                    if (pass) {
+                    if (pass && wide && c.ch_out < t.channels) {
+                        wide_job(d_in + un.byte_offset, 0, t.format, o, frames);
+                    } else if (pass) {
                         sk::PcmDirectJob j{};
                         j.src = d_in + un.byte_offset;
                         j.dst = d_out + o->byte_offset;
@@ -4440,7 +4581,9 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
                 for (const auto &chunk : c.chunks) {
                     sk_tick_output *o = emit(i, chunk.second, c, t.out_bits);
                     if (!o) return SK_ERR_INVALID_ARG;
-                    if (pass) {
+                    if (pass && wide) {
+                        wide_job(d_res + rs.row0 * res_stride + chunk.first, res_stride, sk::kWidePlanar, o, chunk.second);
+                    } else if (pass) {
                         const float *src = d_res + rs.row0 * res_stride + chunk.first;
                         packs.push_back(sk::PackJob{src, src + res_stride, d_out + o->byte_offset, chunk.second, t.channels, (uint8_t)c.ch_out, t.out_bits,
                                                     (uint8_t)(c.float_out ? sk::kPackPlainF32 : sk::kPackPlain)});
@@ -4464,6 +4607,18 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
         const sk::PackJob *d_packs = nullptr;
         SK_HIP(aux.put(packs, e->stream, &d_packs), "upload pack jobs");
         SK_HIP(sk::launch_pack_jobs(d_packs, (uint32_t)packs.size(), max_pack_frames, e->stream), "launch pack");
+    }
+    if (!wides[0].empty() || !wides[1].empty()) {
+        uint32_t *d_peaks = nullptr;
+        const std::vector<uint32_t> zeros(n_peaks, 0);
+        SK_HIP(aux.put_rw(zeros, e->stream, &d_peaks), "upload tick pcm wide peaks");
+        for (int kind = 0; kind < 2; ++kind) {
+            if (wides[kind].empty()) continue;
+            const sk::WideJob *d_wides = nullptr;
+            SK_HIP(aux.put(wides[kind], e->stream, &d_wides), "upload tick pcm wide jobs");
+            SK_HIP(sk::launch_pcm_wide(d_wides, (uint32_t)wides[kind].size(), n_wide_peaks[kind], max_wide_frames[kind], kind == 1, d_peaks, e->stream),
+                   "tick pcm wide");
+        }
     }
     uint8_t *bounce = nullptr;
     if (cursor) {

@@ -102,6 +102,9 @@ struct PipelineGpuHooks {
     int (*tick_pcm)(sk_engine *, const sk_pcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
                     sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_pcm
     size_t (*tick_pcm_out_bound)(sk_engine *, const sk_pcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
+    // the engine's pool of wide PCM streams (3 ... 8 channels); with these absent such a stream is refused as before
+    uint32_t (*wide_pcm_streams)(const sk_engine *) = nullptr;  // sk_engine_wide_pcm_streams
+    int (*enable_wide_pcm)(sk_engine *, uint32_t) = nullptr;    // sk_engine_enable_wide_pcm
 };
 PipelineGpuHooks &pipeline_gpu_hooks();  // pipeline.cpp
 }  // namespace sk_mp3_internal

@@ -12,46 +12,11 @@
 // aligned offset, so a lane fetches its 16 samples with 2 / 3 / 4 16-byte loads (s16 / s24 / s32 and f32; big-endian forms are
 // the same loads plus a byte swap); only a unit's last, incomplete group of 16 goes sample by sample.  The sample arithmetic is
 // pcm_sample.h's, shared with pcm.hip.
-#include "pcm_sample.h"
+#include "pcm_group.h"
 
 namespace sk {
 
 namespace {
-
-// 16 samples of IB bytes each = IB 16-byte loads; raw[s] = the sample's bytes, little-endian packed in the low bits
-template <int IB>
-__device__ __forceinline__ void load_group(const uint8_t *src, uint32_t (&raw)[16]) {
-    uint32_t w[4 * IB];
-    const uint4 *p = reinterpret_cast<const uint4 *>(src);
-#pragma unroll
-    for (int k = 0; k < IB; ++k) {
-        const uint4 v = p[k];
-        w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w;
-    }
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-        if (IB == 4) {
-            raw[s] = w[s];
-        } else if (IB == 2) {
-            raw[s] = (w[s >> 1] >> (16 * (s & 1))) & 0xffff;
-        } else {  // bytes 3s .. 3s + 2 of 48
-            const int bit = 24 * s, d = bit >> 5, sh = bit & 31;
-            const uint64_t pair = (uint64_t)w[d] | ((uint64_t)(d + 1 < 4 * IB ? w[d + 1] : 0u) << 32);
-            raw[s] = (uint32_t)(pair >> sh) & 0xffffff;
-        }
-    }
-}
-
-template <int IB>
-__device__ __forceinline__ void load_group_fmt(const uint8_t *src, size_t first_sample, uint32_t (&raw)[16]) {
-    load_group<IB>(src + first_sample * IB, raw);
-}
-
-__device__ __forceinline__ void load_group_any(int ib, const uint8_t *src, size_t first_sample, uint32_t (&raw)[16]) {
-    if (ib == 2) load_group_fmt<2>(src, first_sample, raw);
-    else if (ib == 3) load_group_fmt<3>(src, first_sample, raw);
-    else load_group_fmt<4>(src, first_sample, raw);
-}
 
 // N samples (16, or 8 after a downmix) of OB bytes each, masked to their width, as N * OB / 8 8-byte stores (dst is 8-byte aligned:
 // a job's output starts 16-byte aligned and a group is 16 ... 64 bytes)
@@ -84,8 +49,6 @@ __device__ __forceinline__ void store_group_any(int ob, uint8_t *dst, const uint
     else if (ob == 3) store_group<3, N>(dst, v);
     else store_group<4, N>(dst, v);
 }
-
-__device__ __forceinline__ int fmt_bytes(int fmt) { return fmt <= SK_FMT_S16BE ? 2 : (fmt <= SK_FMT_S24BE ? 3 : 4); }
 
 // one workgroup = kPcmSliceSamples samples of one job, a lane = 16 of them; the lane's 16 ... 64 bytes of output leave as 8-byte
 // stores (lane-strided: the measured weak spot of this kernel)
@@ -133,9 +96,6 @@ __global__ __launch_bounds__(256) void k_pcm_direct(const PcmDirectJob *jobs, ui
         }
     }
 }
-
-// LDS index of sample i of the slice: one pad float per 32, so that the lanes' 16-sample runs do not all start in one bank
-__device__ __forceinline__ uint32_t tile_at(uint32_t i) { return i + (i >> 5); }
 
 // one workgroup = kPcmSliceSamples samples of one job: converted 16 per lane into LDS, then written to the channel rows with
 // consecutive lanes on consecutive frames (coalesced dwords: a row starts at the stream's fill, so nothing wider is available)

@@ -528,7 +528,8 @@ int ensure_pcm(sk_lane *p) {
 }
 
 // The first piece of a WAV / raw PCM stream fixes what apply_output_options (lib.rs:3324-3456) does with all of them: nothing
-// (the fast path), or a conversion -- the PCM tick's, which needs the stream's format among SK_FMT_*, one or two channels and,
+// (the fast path), or a conversion -- the PCM tick's, which needs the stream's format among SK_FMT_*, one or two channels (up to
+// eight on an engine with the pool of wide streams) and,
 // for a rate change, an engine stream with a resampler.  false: the stream has failed (r says how).
 bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     auto fail = [&](int32_t st, const std::string &msg) {
@@ -564,9 +565,10 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     if (is_float && bits != 32) return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: floating-point PCM must contain 32-bit samples");
     if (bits != 16 && bits != 24 && bits != 32)
         return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
-    if (channels > SK_MAX_CHANNELS)
-        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
+    // 3 ... 8 channels: the tick takes them on an engine whose pool of wide streams was reserved (sk_engine_enable_wide_pcm)
     const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+    if (channels > SK_MAX_CHANNELS && (channels > SK_MAX_PCM_CHANNELS || !hooks.wide_pcm_streams || hooks.wide_pcm_streams(p->engine) == 0))
+        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
     if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
     s.pcm_fmt = (uint8_t)((bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : (is_float ? SK_FMT_F32LE : SK_FMT_S32LE))) + (big_endian ? 1 : 0));
     int rc = ensure_pcm(p);
@@ -1925,6 +1927,12 @@ int sk_pipeline_create(sk_engine *e, const sk_pipeline_config *cfg, sk_pipeline 
             rc = sk_engine_create(sk_engine_device(e), std::max(lane_cfg.max_streams, 16u), &le);
             if (rc != SK_OK) break;
             p->owned_engines.push_back(le);
+            // the lanes' own engines inherit the caller's pool of wide PCM streams
+            const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+            if (const uint32_t wide = hooks.wide_pcm_streams && hooks.enable_wide_pcm ? hooks.wide_pcm_streams(e) : 0) {
+                rc = hooks.enable_wide_pcm(le, std::min(wide, sk_engine_max_streams(le)));
+                if (rc != SK_OK) break;
+            }
         }
         sk_lane *lane = nullptr;
         p->oqs.emplace_back(new OutQueue());

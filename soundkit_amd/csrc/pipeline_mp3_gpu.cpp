@@ -12,6 +12,8 @@ const bool g_hooked = [] {
     hooks.tick_md = sk_tick_run_mixed_md;
     hooks.tick_pcm = sk_tick_run_pcm;  // the WAV / raw PCM streams' tick comes the same way
     hooks.tick_pcm_out_bound = sk_tick_pcm_out_bound_on;
+    hooks.wide_pcm_streams = sk_engine_wide_pcm_streams;
+    hooks.enable_wide_pcm = sk_engine_enable_wide_pcm;
     return true;
 }();
 

@@ -485,4 +485,41 @@ struct PcmIngestJob {
 };
 hipError_t launch_pcm_ingest(const PcmIngestJob *jobs, uint32_t n_jobs, uint32_t max_samples, hipStream_t s);
 
+// pcm_wide.hip -- sources of 3 ... 8 channels (SK_MAX_PCM_CHANNELS): all of downmix_channels (lib.rs:3492-3561) between a source
+// of interleaved bytes or planar f32 rows and an output of interleaved bytes or planar f32 rows.  A job is cut into slices of
+// kWideSliceFrames whole frames, one workgroup each: for every channel count and sample width a slice's input is whole 16-byte
+// groups and its output starts 16-byte aligned.
+constexpr uint32_t kWideSliceFrames = 512;
+constexpr uint8_t kWidePlanar = 0xff;  // WideJob::fmt_in / fmt_out: planar f32 rows instead of interleaved bytes
+constexpr uint32_t kWideNoPeak = 0xffffffffu;
+struct WideJob {
+    const void *src;      // interleaved samples of fmt_in, 16-byte aligned; or channel row 0 (planar)
+    void *dst;            // interleaved samples of fmt_out, 16-byte aligned; or output row 0 (planar)
+    uint64_t src_stride;  // planar source: floats from one channel row to the next
+    uint64_t dst_stride;  // planar destination: floats from one row to the next
+    uint32_t frames;
+    uint32_t peak;        // the word of the peak array that holds max(|L|, |R|) over this job's AudioData (jobs that cut one
+                          // AudioData share it), kWideNoPeak unless ch_out == 2 < ch_in
+    uint8_t fmt_in;       // SK_FMT_* or kWidePlanar
+    uint8_t fmt_out;      // SK_FMT_S16LE / S24LE / S32LE / F32LE or kWidePlanar
+    uint8_t ch_in, ch_out;  // ch_in <= 8, ch_out <= ch_in
+    uint32_t pad;
+};
+// the two launches of the surround branch: first every job's peak into peaks[] (zeroed by the caller, stream-ordered), then the
+// conversion, which scales by 1 / peak where it exceeds 1.  n_peak_jobs == 0 (no job with a peak word) skips the first.  All jobs
+// of a call have the same kind of source: bytes_in = interleaved bytes, else planar rows (that launch reserves no input tile in LDS).
+hipError_t launch_pcm_wide(const WideJob *jobs, uint32_t n_jobs, uint32_t n_peak_jobs, uint32_t max_frames, bool bytes_in, uint32_t *peaks,
+                           hipStream_t s);
+// one job over planar rows passed by value (sk_pcm_downmix_dev): nothing to upload
+hipError_t launch_pcm_wide_one(const WideJob &job, uint32_t *peaks, hipStream_t s);
+// k_pcm_ingest for any channel count: the piece's rows start at dst (row 0, at the stream's fill) and lie row_stride floats apart
+struct PcmWideIngestJob {
+    const uint8_t *src;  // 16-byte aligned
+    float *dst;
+    uint64_t row_stride;
+    uint32_t frames;
+    uint8_t fmt, ch, pad[2];
+};
+hipError_t launch_pcm_wide_ingest(const PcmWideIngestJob *jobs, uint32_t n_jobs, uint32_t max_frames, hipStream_t s);
+
 }  // namespace sk

@@ -1,8 +1,11 @@
 """Mirror of the conversion/resample end of soundkit-decoder's worker (soundkit-decoder/src/lib.rs).
 
 float_sample_to_i16 :1815, StreamingResampler :1917-2060, exact_signed_pcm_to_i16 :3458,
-downmix_channels :3492 (mono), audio_data_to_f32_channels :3563, f32_channels_to_bytes :3619,
-and the parts of apply_output_options :3324 that route between them.
+downmix_channels :3492-3561 (all three branches, up to 8 channels), audio_data_to_f32_channels :3563,
+f32_channels_to_bytes :3619, and the parts of apply_output_options :3324 that route between them.
+
+Sources of 3 ... 8 channels convert and downmix on any engine; resampling them needs an engine whose pool of wide
+streams was reserved (Engine.enable_wide_pcm): pass it as `engine`.
 """
 import numpy as np
 
@@ -56,14 +59,15 @@ def f32_channels_to_bytes(channels, bits_per_sample, output_format):
     return default_engine().f32_planar_to_bytes(fmt, channels)
 
 
-def downmix_channels(channels, target_channels):
+def downmix_channels(channels, target_channels, engine=None):
     channels = np.ascontiguousarray(channels, np.float32)
     if channels.size == 0 or target_channels == 0:
         return np.zeros((0, 0), np.float32)
-    if target_channels == 1:
-        return default_engine().downmix_mono(channels)[None, :]
-    if target_channels == 2 and channels.shape[0] > 2:
-        raise SoundkitError(-6, "surround downmix")  # lib.rs:3512-3556: out of the hot-path scope
+    eng = engine or default_engine()
+    if target_channels == 1:  # lib.rs:3500-3508, any channel count
+        return eng.downmix_mono(channels)[None, :]
+    if target_channels == 2 and channels.shape[0] > 2:  # lib.rs:3512-3556
+        return eng.downmix(channels, 2)
     return channels[:target_channels].copy()
 
 
@@ -122,8 +126,9 @@ class StreamingResampler:
 
 
 def apply_output_options(audio, output_bits_per_sample=None, output_sample_rate=None, output_channels=None,
-                         resampler=None):
-    """lib.rs:3324-3456.  Returns (list of AudioData, resampler)."""
+                         resampler=None, engine=None):
+    """lib.rs:3324-3456.  Returns (list of AudioData, resampler).  `engine`: where a new resampler opens its stream (a source
+    of more than two channels needs one with Engine.enable_wide_pcm)."""
     rate = output_sample_rate or audio.sampling_rate
     bits = output_bits_per_sample or audio.bits_per_sample
     chans = output_channels or audio.channel_count
@@ -138,7 +143,7 @@ def apply_output_options(audio, output_bits_per_sample=None, output_sample_rate=
     channels = audio_data_to_f32_channels(audio)
     if rate != audio.sampling_rate:
         if resampler is None:
-            resampler = StreamingResampler(audio.sampling_rate, rate, channels.shape[0])
+            resampler = StreamingResampler(audio.sampling_rate, rate, channels.shape[0], engine)
         elif (resampler.input_sample_rate, resampler.channels, resampler.output_sample_rate) != (
                 audio.sampling_rate, channels.shape[0], rate):
             raise ValueError("Resampler configuration changed mid-stream")

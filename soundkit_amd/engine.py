@@ -153,6 +153,14 @@ class Engine:
         check(lib.sk_engine_synchronize(self._h), "sk_engine_synchronize", self._h)
 
     # ---- streams ----------------------------------------------------------------------
+    def enable_wide_pcm(self, max_wide_streams):
+        """Reserve slots for PCM streams of 3 ... 8 channels (sk_engine_enable_wide_pcm): once, before the first resampler_open."""
+        check(lib.sk_engine_enable_wide_pcm(self._h, int(max_wide_streams)), "sk_engine_enable_wide_pcm", self._h)
+
+    @property
+    def wide_pcm_streams(self):
+        return int(lib.sk_engine_wide_pcm_streams(self._h))
+
     def open_stream(self, sample_rate=48000, channels=2):
         sid = C.c_uint32()
         check(lib.sk_stream_open(self._h, sample_rate, channels, C.byref(sid)), "sk_stream_open", self._h)
@@ -273,6 +281,14 @@ class Engine:
         ch, frames = planar.shape
         out = np.zeros(frames, np.float32)
         check(lib.sk_pcm_downmix_mono(self._h, _ptr(planar), frames, ch, _ptr(out)), "sk_pcm_downmix_mono", self._h)
+        return out
+
+    def downmix(self, planar, target):
+        """downmix_channels (soundkit-decoder lib.rs:3492-3561): [ch][frames] f32, ch <= 8 -> [min(target, ch)][frames]."""
+        planar = np.ascontiguousarray(planar, np.float32)
+        ch, frames = planar.shape
+        out = np.zeros((min(int(target), ch), frames), np.float32)
+        check(lib.sk_pcm_downmix(self._h, _ptr(planar), frames, ch, int(target), _ptr(out)), "sk_pcm_downmix", self._h)
         return out
 
     def exact_to_i16(self, fmt, data):
