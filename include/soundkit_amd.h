@@ -281,7 +281,8 @@ int sk_mp3_hybrid_synthesize_f32_dev(sk_engine *, const sk_mp3_granule_desc *des
 enum sk_mp3_status {
     SK_MP3_NEED_MORE = -301,   /* not enough bytes for the header / side information / frame / reservoir */
     SK_MP3_NO_SYNC = -302,     /* not a frame header */
-    SK_MP3_UNSUPPORTED = -303, /* Layer I / II; a free-format header whose frame length is not known (sk_mp3_scan_free measures it) */
+    SK_MP3_UNSUPPORTED = -303, /* sk_mp3_*: a Layer I / II header (sk_mpa_* read those); a free-format header whose frame length is not
+                                  known (sk_mp3_scan_free measures it; Layer I / II free format is not built) */
     SK_MP3_INVALID = -304      /* a field combination the syntax forbids */
 };
 typedef struct sk_mp3_frame_info { /* nanomp3::FrameInfo (lib.rs:188-215 reads sample_rate, channels, bitrate) + framing */
@@ -445,7 +446,10 @@ int sk_mp3_decode_frames_s16(sk_engine *, const sk_mp3_frame_item *frames, const
  * it stops once fewer than SK_MP3_MAX_SAMPLES_PER_FRAME samples of room are left (lib.rs:300-302) and fails with
  * SK_ERR_CAPACITY if a frame does not fit (lib.rs:237-243).  Input beyond 4 MiB buffered: SK_PIPE_CHUNK_TOO_LARGE
  * (lib.rs:155, 219-227).  A frame whose main data reaches further back than the reservoir holds (a stream joined in the
- * middle) is consumed without output, as are frames the later stages reject. */
+ * middle) is consumed without output, as are frames the later stages reject.
+ * A stream whose first confirmed frame (two consistent headers one frame length apart) is Layer I or II is decoded as that layer
+ * with no switch (sk_mpa_scan, sk_mpa_parse_frame, one sk_mpa_decode_frames_* per call): 384 or 1152 samples per channel and frame,
+ * the same output rules; headers of another layer are no frames of it.  Streams that start as Layer III take the path above. */
 #define SK_MP3_MAX_SAMPLES_PER_FRAME 2304u
 typedef struct sk_mp3_decoder sk_mp3_decoder;
 /* Mp3Decoder::new, lib.rs:157.  codebook NULL = the standard's tables (what nanomp3 has built in); the decoder installs the
@@ -466,6 +470,67 @@ int sk_mp3_decoder_info(const sk_mp3_decoder *, uint32_t *sample_rate, uint8_t *
 int sk_mp3_decoder_decode_i16(sk_mp3_decoder *, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written);
 int sk_mp3_decoder_decode_i32(sk_mp3_decoder *, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written);
 int sk_mp3_decoder_decode_f32(sk_mp3_decoder *, const uint8_t *input, size_t len, float *out, size_t out_cap, size_t *written);
+
+/* ---- MPEG Layer I and II (ISO/IEC 11172-3 2.4.1.5-6, 13818-3 2.4.1) ------------------------------------------------------------
+ * The other two layers nanomp3 decodes behind Mp3Decoder (soundkit-mp3/src/lib.rs:284).  No Huffman stage, no reservoir, no IMDCT:
+ * a short serial front (allocation, scale-factor selection, scale factors) that the host reads, after which every sample code of the
+ * frame stands at a computable bit position -- the kernel (csrc/mp12_synth.hip) fetches the codes from the frame's bytes as they
+ * were uploaded, requantises them and runs the same 32-band polyphase synthesis, on the same per-stream FIFO, as Layer III.
+ * The sk_mp3_* entry points above keep their Layer III-only answers; these know all three layers.
+ * Not built (SK_MP3_UNSUPPORTED / no frame): free-format Layer I / II, MPEG-2.5 with Layer I / II (not defined by the standards),
+ * CRC verification (the word is stepped over), the multichannel extension of 13818-3. */
+typedef struct sk_mpa_frame_info {
+    uint32_t offset;             /* sk_mpa_scan: position of the frame in the scanned buffer */
+    uint32_t frame_bytes;        /* header to the next header */
+    uint32_t sample_rate;
+    uint16_t bitrate_kbps, samples_per_channel; /* 384 (Layer I), 1152 (Layer II), 1152 / 576 (Layer III) */
+    uint8_t version;             /* 1, 2 or 25 (= MPEG-2.5, Layer III only) */
+    uint8_t layer;               /* 1, 2 or 3 */
+    uint8_t channels, mode, mode_ext, has_crc, padding, reserved;
+} sk_mpa_frame_info;
+/* SK_MP3_UNSUPPORTED: a free-format header of any layer (no length in it), MPEG-2.5 with Layer I / II */
+int sk_mpa_parse_header(const uint8_t *data, size_t len, sk_mpa_frame_info *out);
+/* Frames of ONE layer out of a byte stream, with sk_mp3_scan's rules (an ID3v2 tag in front is stepped over, garbage skipped, a
+ * header counts only if a header of the same version, layer and sampling rate follows it one frame length on, or the data ends
+ * there).  *layer in: 1 ... 3 = the stream's layer, headers of another are no frames; 0 = not known yet: the stream's layer is that of
+ * its first CONFIRMED frame (the following header must be in the buffer: until it is, nothing is consumed from the candidate on),
+ * and *layer receives it.  *consumed = bytes up to the first incomplete frame. */
+int sk_mpa_scan(const uint8_t *data, size_t len, uint32_t *layer, sk_mpa_frame_info *frames, uint32_t cap, uint32_t *n_frames, size_t *consumed);
+/* One Layer I / II frame as the kernel takes it.  cls[ch][sb], the quantisation class: 0 = nothing sent; 2 ... 16 = three (Layer I: one)
+ * codes of that many bits per granule (slot), steps = 2^bits - 1; 0x80 | 3, 5 or 9 = Layer II's grouped classes, three samples of that
+ * many steps in one code word of 5, 7 or 10 bits.  Above `bound` (joint stereo) both channels carry the class of the shared code.
+ * scf[ch][sb][part]: the scale-factor index (0 ... 63, factor 2^(1 - i/3); the standard's table ends at 62, 63 continues the closed
+ * form) of parts 0 ... 2 of the frame (Layer II: granules 0-3, 4-7, 8-11; Layer I: all three equal). */
+typedef struct sk_mpa_frame_record {
+    uint32_t byte_offset;        /* of the frame's first byte in the call's byte buffer: a multiple of 4, 8 bytes of room behind the frame */
+    uint32_t byte_len;           /* frame_bytes */
+    uint32_t sample_rate;
+    uint32_t sample_bit;         /* bit offset of the first sample code from the frame's first byte */
+    uint16_t granule_bits;       /* width of one granule (Layer II: a triple per subband and channel) or slot (Layer I) */
+    uint8_t layer, channels, sblimit, bound;
+    uint8_t granules;            /* 12 */
+    uint8_t reserved;
+    uint8_t cls[2][32];
+    uint8_t scf[2][32][3];
+} sk_mpa_frame_record;
+/* header (as sk_mpa_parse_header gave it) + the frame's bytes -> record (byte_offset left 0).  SK_MP3_NEED_MORE: len < frame_bytes;
+ * SK_MP3_INVALID: Layer I's forbidden allocation 15, or sample data that would end beyond the frame -- such a frame is consumed
+ * without output, so the kernel never reads past a frame; SK_MP3_UNSUPPORTED: a Layer III header. */
+int sk_mpa_parse_frame(const uint8_t *frame, size_t len, const sk_mpa_frame_info *header, sk_mpa_frame_record *out);
+/* Sample unpacking, requantisation and polyphase synthesis of a batch of frames in ONE launch, one wavefront per (stream, channel)
+ * walking its frames in order.  streams[i]: the open stream frame i belongs to (its channel count must be the record's).  A record
+ * that does not add up (classes, widths and bounds are checked against byte_len before anything is launched) or names no such stream
+ * gets status[i] != 0 and is dropped: no room in pcm_out, stream state untouched.  The other frames' samples (384 or 1152 x channels,
+ * interleaved, float in +-1.0 or s16 through f32_to_i16) follow one another in frame order.  Needs the synthesis window
+ * (sk_mp3_set_synthesis_window), else SK_ERR_UNSUPPORTED; *samples_written > out_cap: SK_ERR_CAPACITY, nothing synthesised. */
+int sk_mpa_decode_frames_f32(sk_engine *, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n_frames, const uint8_t *frame_bytes,
+                             size_t bytes_len, float *pcm_out, size_t out_cap, int32_t *status, size_t *samples_written);
+int sk_mpa_decode_frames_s16(sk_engine *, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n_frames, const uint8_t *frame_bytes,
+                             size_t bytes_len, int16_t *pcm_out, size_t out_cap, int32_t *status, size_t *samples_written);
+/* The same with the HIP-event time of the launch alone (uploads and the copy back excluded) in *kernel_ms.  For measurements only
+ * (tools/time_mp12.py): not part of what a binding needs, and the two calls above create no events. */
+int sk_mpa_decode_frames_timed(sk_engine *, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n_frames, const uint8_t *frame_bytes,
+                               size_t bytes_len, int16_t *pcm_out, size_t out_cap, int32_t *status, size_t *samples_written, float *kernel_ms);
 
 /* ---- sample-width / interleave conversion: soundkit::audio_bytes -------- */
 /* Elementwise ops; n = number of OUTPUT samples.  Citations: soundkit/src/audio_bytes.rs
@@ -677,7 +742,7 @@ typedef struct sk_tick_stream {
                            * from sk_tick_input's mp3_* arrays; only sk_tick_run_mixed accepts them */
     uint8_t reserved[3];
 } sk_tick_stream;
-enum { SK_TICK_AAC = 0, SK_TICK_MP3 = 1 };
+enum { SK_TICK_AAC = 0, SK_TICK_MP3 = 1, SK_TICK_MPA = 2 /* Layer I / II: sk_tick_run_mixed_mpa; n_frames counts FRAMES */ };
 
 typedef struct sk_tick_output {
     uint32_t stream_index; /* index into the tick's stream table */
@@ -742,6 +807,24 @@ typedef struct sk_tick_mp3_frames {
 int sk_tick_run_mixed_md(sk_engine *, const sk_tick_stream *streams, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md,
                          uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap, uint32_t *n_outputs,
                          size_t *out_bytes_used);
+
+/* The same with Layer I / II streams in the tick (codec SK_TICK_MPA): their units arrive as FRAMES -- records as sk_mpa_parse_frame
+ * made them and the frames' bytes, laid out as for sk_mpa_decode_frames_*, listed stream by stream in the order of `streams`; such a
+ * stream's n_frames counts its frames (a budget in whole frames).  A Layer II frame becomes two units of 576 PCM frames (18 slots
+ * each), a Layer I frame one of 384; each unit is one AudioData without resampling, exactly as a Layer III granule is, and takes the
+ * same path from there (f32_to_i16, / 32768, resampler, downmix, bytes).  The frames of one stream are of one layer.  A record that does
+ * not add up fails the call (SK_ERR_INVALID_ARG) before anything is launched: the caller's parse drops such frames.  `md` may be NULL
+ * (then `in` carries the Layer III granules, if any, as for sk_tick_run_mixed); `mpa` may be NULL or empty.  sk_tick_run_mixed and
+ * sk_tick_run_mixed_md are this call without Layer I / II frames.  sk_tick_out_bound* count two units per listed frame of such a stream. */
+typedef struct sk_tick_mpa_frames {
+    const sk_mpa_frame_record *records;
+    uint32_t n_frames;
+    const uint8_t *frame_bytes;
+    size_t bytes_len;
+} sk_tick_mpa_frames;
+int sk_tick_run_mixed_mpa(sk_engine *, const sk_tick_stream *streams, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md,
+                          const sk_tick_mpa_frames *mpa, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                          uint32_t *n_outputs, size_t *out_bytes_used);
 
 /* ---- the tick of the WAV / raw PCM streams -------------------------------------------------------------------------- */
 /* What the reference's worker does to the AudioData a WavStreamProcessor / RawPcmStreamProcessor hands it -- apply_output_options,

@@ -93,6 +93,20 @@ class Mp3FrameItem(C.Structure):
     _fields_ = [("header", Mp3FrameInfo), ("side", Mp3SideInfo), ("byte_offset", C.c_uint32), ("byte_len", C.c_uint32)]
 
 
+class MpaFrameInfo(C.Structure):
+    """sk_mpa_frame_info"""
+    _fields_ = [("offset", C.c_uint32), ("frame_bytes", C.c_uint32), ("sample_rate", C.c_uint32), ("bitrate_kbps", C.c_uint16),
+                ("samples_per_channel", C.c_uint16)] + [(n, C.c_uint8) for n in ("version", "layer", "channels", "mode", "mode_ext", "has_crc",
+                                                                                  "padding", "reserved")]
+
+
+class MpaFrameRecord(C.Structure):
+    """sk_mpa_frame_record"""
+    _fields_ = [("byte_offset", C.c_uint32), ("byte_len", C.c_uint32), ("sample_rate", C.c_uint32), ("sample_bit", C.c_uint32),
+                ("granule_bits", C.c_uint16)] + [(n, C.c_uint8) for n in ("layer", "channels", "sblimit", "bound", "granules", "reserved")] + [
+                    ("cls", (C.c_uint8 * 32) * 2), ("scf", ((C.c_uint8 * 3) * 32) * 2)]
+
+
 class TickMp3Frames(C.Structure):
     """sk_tick_mp3_frames"""
     _fields_ = [("frames", C.c_void_p), ("n_frames", C.c_uint32), ("main_bytes", C.c_void_p), ("main_len", C.c_size_t)]
@@ -319,6 +333,13 @@ _sig = {
     "sk_mp3_decode_frames_f32": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz)]),
     "sk_mp3_decode_frames_s16": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _vp, C.POINTER(_sz)]),
     "sk_mp3_decoder_set_gpu_entropy": (_i, [_vp, _i]),
+    "sk_tick_run_mixed_mpa": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_mpa_parse_header": (_i, [_vp, _sz, _vp]),
+    "sk_mpa_scan": (_i, [_vp, _sz, C.POINTER(_u32), _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_mpa_parse_frame": (_i, [_vp, _sz, _vp, _vp]),
+    "sk_mpa_decode_frames_f32": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "sk_mpa_decode_frames_s16": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz)]),
+    "sk_mpa_decode_frames_timed": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, _vp, C.POINTER(_sz), C.POINTER(C.c_float)]),
     "sk_mp3_set_band_tables": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "sk_mp3_requantize": (_i, [_vp, _vp, _vp, _vp, _u32, _vp]),
     "sk_aac_entropy_decode": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _vp, _vp]),

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "aac_entropy_tables.h"
+#include "mp12_internal.h"
 #include "sk_device.h"
 
 namespace {
@@ -257,7 +258,7 @@ struct sk_engine {
     DevBuf sinc_scratch;      // tap fragments of the matrix-core resampler (resample.hip), sized per launch
     bool sinc_exact = false;  // sk_engine_set_resampler_exact: the scalar form that keeps rubato's order of operations
     // sk_tick_run: synthesis output, resampler output, packed bytes, small-array arena (+ pinned host mirror)
-    DevBuf tick_pcm, tick_res, tick_out, tick_arena, tick_au, tick_side, tick_q, tick_mp3_in, tick_mp3_xr;
+    DevBuf tick_pcm, tick_res, tick_out, tick_arena, tick_au, tick_side, tick_q, tick_mp3_in, tick_mp3_xr, tick_mpa_in;
     DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
@@ -659,6 +660,7 @@ void sk_engine_destroy(sk_engine *e) try {
         e->tick_q.release();
         e->tick_pcm_in.release();
         e->mp3e_in.release();
+        e->tick_mpa_in.release();
         e->mp3e_out.release();
         if (e->d_mp3_cb) (void)hipFree(e->d_mp3_cb);
         if (e->h_arena) (void)hipHostFree(e->h_arena);
@@ -2138,6 +2140,7 @@ int ensure_mp3(sk_engine *e) {
     static const double c[8] = {-0.6, -0.535, -0.33, -0.185, -0.095, -0.041, -0.0142, -0.0037};  // ISO 11172-3 Table B.9
     for (int i = 0; i < 8; ++i) t.push_back((float)(1.0 / std::sqrt(1.0 + c[i] * c[i])));
     for (int i = 0; i < 8; ++i) t.push_back((float)(c[i] / std::sqrt(1.0 + c[i] * c[i])));
+    for (int i = 0; i < 64; ++i) t.push_back((float)std::pow(2.0, 1.0 - i / 3.0));  // Layer I / II scale factors (11172-3 Table B.1 in closed form)
     SK_HIP(hipMalloc((void **)&e->d_mp3_tables, t.size() * sizeof(float)), "alloc mp3 tables");
     SK_HIP(hipMemcpy(e->d_mp3_tables, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice), "upload mp3 tables");
     const size_t state_bytes = (size_t)e->max_streams * 2 * sk::kMp3StateFloats * sizeof(float);
@@ -2703,6 +2706,110 @@ int mp3_decode_frames(sk_engine *e, const sk_mp3_frame_item *frames, const uint3
     return SK_OK;
 }
 
+
+// ---- MPEG Layer I / II (mp12_synth.hip): frames' bytes and records in, PCM out, one launch ------------------------------------
+// e->in_buf: bytes | records | tasks | entries; e->out_buf: the PCM of the frames that are launched, in frame order
+int mpa_decode_frames(sk_engine *e, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t bytes_len,
+                      void *pcm_out, size_t out_cap, int32_t *status, size_t *written, bool s16, float *kernel_ms) {
+    if (!e || !written || (n && (!records || !streams || !bytes || !status)) || (out_cap && !pcm_out)) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n == 0) return SK_OK;
+    if (bytes_len > (1u << 28)) return SK_ERR_INVALID_ARG;  // bit positions are 32-bit
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e, ComputeTurn{});
+    int rc = ensure_mp3(e);
+    if (rc != SK_OK) return rc;
+    if (!e->mp3_window_set) return SK_ERR_UNSUPPORTED;  // no synthesis window: sk_mp3_set_synthesis_window first
+
+    // what may reach the kernel: a record that adds up, inside the byte buffer with its 8 bytes of room, for an open stream of its shape
+    std::vector<uint32_t> touched;
+    std::vector<uint32_t> pcm_off(n, 0);
+    uint64_t samples = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_mpa_frame_record &r = records[i];
+        int32_t st = SK_OK;
+        if (!sk_mp12::record_adds_up(r) || (r.byte_offset & 3u) || (uint64_t)r.byte_offset + r.byte_len + 8 > bytes_len) st = SK_MP3_INVALID;
+        else if (!stream_ok(e, streams[i])) st = SK_FRAME_BAD_STREAM;
+        else if (r.channels != e->streams[streams[i]].channels) st = SK_FRAME_BAD_CHANNELS;
+        status[i] = st;
+        if (st != SK_OK) continue;
+        pcm_off[i] = (uint32_t)samples;
+        samples += (uint64_t)(r.layer == 1 ? 384u : 1152u) * r.channels;
+        if (samples > 0xffffffffull) break;
+    }
+    if (samples > 0xffffffffull) return SK_ERR_INVALID_ARG;
+    if (samples > out_cap) return SK_ERR_CAPACITY;
+    if (samples == 0) return SK_OK;
+    for (uint32_t i = 0; i < n; ++i)
+        if (status[i] == SK_OK)
+            for (uint32_t c = 0; c < records[i].channels; ++c)
+                if (e->state_count[streams[i] * 2 + c]++ == 0) touched.push_back(streams[i] * 2 + c);
+    std::vector<sk::SynthTask> tasks(touched.size());
+    uint32_t n_entries = 0;
+    for (size_t t = 0; t < touched.size(); ++t) {
+        tasks[t] = sk::SynthTask{touched[t], n_entries, 0, 0};
+        n_entries += e->state_count[touched[t]];
+        e->state_task[touched[t]] = (uint32_t)t;
+    }
+    std::vector<sk::Mp12Entry> entries(n_entries);
+    for (uint32_t i = 0; i < n; ++i)
+        if (status[i] == SK_OK)
+            for (uint32_t c = 0; c < records[i].channels; ++c) {
+                sk::SynthTask &t = tasks[e->state_task[streams[i] * 2 + c]];
+                entries[t.begin + t.count++] = sk::Mp12Entry{i, pcm_off[i]};
+            }
+    for (uint32_t state : touched) e->state_count[state] = 0;
+
+    auto up256 = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t width = s16 ? sizeof(int16_t) : sizeof(float);
+    const size_t rec_at = up256(bytes_len + 16), rec_bytes = (size_t)n * sizeof(sk_mpa_frame_record);
+    const size_t tasks_at = up256(rec_at + rec_bytes), tasks_bytes = tasks.size() * sizeof(sk::SynthTask);
+    const size_t entries_at = up256(tasks_at + tasks_bytes), entries_bytes = entries.size() * sizeof(sk::Mp12Entry);
+    SK_HIP(e->in_buf.reserve(entries_at + entries_bytes + 16), "alloc mp12 input");
+    SK_HIP(e->out_buf.reserve((size_t)samples * width + 16), "alloc mp12 output");
+    uint8_t *d_in = (uint8_t *)e->in_buf.p;
+    SK_HIP(hipMemcpyAsync(d_in, bytes, bytes_len, hipMemcpyHostToDevice, e->stream), "H2D mp12 frame bytes");
+    SK_HIP(hipMemcpyAsync(d_in + rec_at, records, rec_bytes, hipMemcpyHostToDevice, e->stream), "H2D mp12 records");
+    SK_HIP(hipMemcpyAsync(d_in + tasks_at, tasks.data(), tasks_bytes, hipMemcpyHostToDevice, e->stream), "H2D mp12 tasks");
+    SK_HIP(hipMemcpyAsync(d_in + entries_at, entries.data(), entries_bytes, hipMemcpyHostToDevice, e->stream), "H2D mp12 entries");
+    SK_HIP(hipStreamSynchronize(e->stream), "mp12 upload");  // the vectors go out of scope
+    sk::Mp12Args a{};
+    a.records = (const sk_mpa_frame_record *)(d_in + rec_at);
+    a.bytes = (const uint32_t *)d_in;
+    if (s16) a.pcm16 = (int16_t *)e->out_buf.p;
+    else a.pcm = (float *)e->out_buf.p;
+    a.state = e->d_mp3_state;
+    a.tasks = (const sk::SynthTask *)(d_in + tasks_at);
+    a.entries = (const sk::Mp12Entry *)(d_in + entries_at);
+    a.n_tasks = (uint32_t)tasks.size();
+    a.matrix = e->d_mp3_tables + kMp3Imdct;
+    a.window = a.matrix + kMp3Matrix;
+    a.scf = a.window + kMp3Window + 16;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (kernel_ms) {
+        SK_HIP(hipEventCreate(&ev0), "mp12 event");
+        const hipError_t he = hipEventCreate(&ev1);
+        if (he != hipSuccess) {
+            (void)hipEventDestroy(ev0);
+            return e->hip_fail(he, "mp12 event");
+        }
+        (void)hipEventRecord(ev0, e->stream);
+    }
+    hipError_t he = sk::launch_mp12_synth(a, e->stream);
+    if (kernel_ms && he == hipSuccess) he = hipEventRecord(ev1, e->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(pcm_out, e->out_buf.p, (size_t)samples * width, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (kernel_ms) {
+        if (he == hipSuccess) he = hipEventElapsedTime(kernel_ms, ev0, ev1);
+        (void)hipEventDestroy(ev0);
+        (void)hipEventDestroy(ev1);
+    }
+    if (he != hipSuccess) return e->hip_fail(he, "mp12 synthesis");
+    *written = (size_t)samples;
+    return SK_OK;
+}
+
 }  // namespace
 
 extern "C++" {
@@ -2819,6 +2926,53 @@ int sk_mp3_decode_frames_s16(sk_engine *e, const sk_mp3_frame_item *frames, cons
     return mp3_decode_frames(e, frames, streams, n, bytes, main_len, pcm_out, out_cap, entropy_status, stage_status, written, true);
 } catch (...) {
     return sk::abi_caught("sk_mp3_decode_frames_s16");
+}
+
+// ---- MPEG Layer I / II: the host front (mp12_bitstream.cpp) and the stage call (mp12_synth.hip) ----
+int sk_mpa_parse_header(const uint8_t *d, size_t len, sk_mpa_frame_info *out) try {
+    sk::abi_enter();
+    return sk_mp12::parse_header(d, len, out);
+} catch (...) {
+    return sk::abi_caught("sk_mpa_parse_header");
+}
+
+int sk_mpa_scan(const uint8_t *d, size_t len, uint32_t *layer, sk_mpa_frame_info *frames, uint32_t cap, uint32_t *n_frames, size_t *consumed) try {
+    sk::abi_enter();
+    return sk_mp12::scan(d, len, layer, frames, cap, n_frames, consumed);
+} catch (...) {
+    return sk::abi_caught("sk_mpa_scan");
+}
+
+int sk_mpa_parse_frame(const uint8_t *frame, size_t len, const sk_mpa_frame_info *h, sk_mpa_frame_record *out) try {
+    sk::abi_enter();
+    return sk_mp12::parse_frame(frame, len, h, out);
+} catch (...) {
+    return sk::abi_caught("sk_mpa_parse_frame");
+}
+
+int sk_mpa_decode_frames_f32(sk_engine *e, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t bytes_len,
+                             float *pcm_out, size_t out_cap, int32_t *status, size_t *written) try {
+    sk::abi_enter();
+    return mpa_decode_frames(e, records, streams, n, bytes, bytes_len, pcm_out, out_cap, status, written, false, nullptr);
+} catch (...) {
+    return sk::abi_caught("sk_mpa_decode_frames_f32");
+}
+
+int sk_mpa_decode_frames_s16(sk_engine *e, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t bytes_len,
+                             int16_t *pcm_out, size_t out_cap, int32_t *status, size_t *written) try {
+    sk::abi_enter();
+    return mpa_decode_frames(e, records, streams, n, bytes, bytes_len, pcm_out, out_cap, status, written, true, nullptr);
+} catch (...) {
+    return sk::abi_caught("sk_mpa_decode_frames_s16");
+}
+
+int sk_mpa_decode_frames_timed(sk_engine *e, const sk_mpa_frame_record *records, const uint32_t *streams, uint32_t n, const uint8_t *bytes, size_t bytes_len,
+                               int16_t *pcm_out, size_t out_cap, int32_t *status, size_t *written, float *kernel_ms) try {
+    sk::abi_enter();
+    if (!kernel_ms) return SK_ERR_INVALID_ARG;
+    return mpa_decode_frames(e, records, streams, n, bytes, bytes_len, pcm_out, out_cap, status, written, true, kernel_ms);
+} catch (...) {
+    return sk::abi_caught("sk_mpa_decode_frames_timed");
 }
 
 }  // extern "C"
@@ -3370,6 +3524,18 @@ struct TickMp3 {  // the MP3 part of sk_tick_input
     const int16_t *is = nullptr;
     uint32_t n = 0;
     const TickMp3Frames *md = nullptr;  // instead of `is` (and of the granules' scale factors and preflag)
+    // Layer I / II streams (SK_TICK_MPA): the LAST n_mpa_units entries of granules / descs are their units (channels and stream filled
+    // in, nothing else), in the order of the streams; `mpa` says which frame each belongs to
+    uint32_t n_mpa_units = 0;
+    const struct TickMpa *mpa = nullptr;
+};
+struct TickMpa {
+    std::vector<sk_mpa_frame_record> records;  // checked (record_adds_up, inside the byte buffer)
+    std::vector<uint32_t> stream;              // per frame: its engine stream
+    std::vector<uint32_t> first_unit;          // per frame: its first unit among the n_mpa_units
+    std::vector<uint16_t> unit_len;            // per unit: 576 or 384
+    const uint8_t *bytes = nullptr;
+    size_t bytes_len = 0;
 };
 
 }  // namespace
@@ -3384,7 +3550,7 @@ size_t tick_out_bound(const sk_engine *e, const sk_tick_stream *ts, uint32_t n_s
     size_t bytes = 0;
     uint64_t outs = 0;
     for (uint32_t i = 0; i < n_streams; ++i) {
-        const uint64_t n = ts[i].n_frames;
+        const uint64_t n = ts[i].codec == SK_TICK_MPA ? 2ull * ts[i].n_frames : ts[i].n_frames;  // a Layer II frame is two units
         const uint64_t width = (ts[i].out_bits == 16 || ts[i].out_bits == 24 || ts[i].out_bits == 32) ? ts[i].out_bits / 8u : 4u;
         const uint64_t frame_bytes = width * ((ts[i].out_channels == 1 || ts[i].out_channels == 2) ? ts[i].out_channels : 2u);
         if (ts[i].resample) {
@@ -3544,8 +3710,8 @@ int tick_mp3_queue(sk_engine *e, const TickMp3 &mp3, float *pcm_rows, AuxArena &
     if (rc == SK_OK) rc = ensure_mp3_requant(e);
     if (rc != SK_OK) return rc;
     if (!e->mp3_window_set) return SK_ERR_UNSUPPORTED;  // no Table B.3 on this engine: sk_mp3_decoder_create / sk_mp3_set_synthesis_window first
-    const uint32_t n = mp3.n;
-    status.assign(n, 0);
+    const uint32_t n = mp3.n - mp3.n_mpa_units;  // the Layer I / II units behind them are tick_mpa_queue's
+    status.assign(mp3.n, 0);
     std::vector<sk::Mp3RequantRecord> records(n);
     std::vector<uint32_t> touched;
     uint64_t off = 0;
@@ -3638,6 +3804,54 @@ int tick_mp3_queue(sk_engine *e, const TickMp3 &mp3, float *pcm_rows, AuxArena &
     return SK_OK;
 }
 
+// The Layer I / II frames of a tick (e->mu held, device selected): one k_mp12_synth launch in its planar form, queued on e->stream with
+// no synchronisation.  Their units' channel rows follow the Layer III granules' rows in pcm_rows, in unit order.
+int tick_mpa_queue(sk_engine *e, const TickMp3 &mp3, float *pcm_rows, AuxArena &aux) {
+    int rc = ensure_mp3(e);
+    if (rc != SK_OK) return rc;
+    if (!e->mp3_window_set) return SK_ERR_UNSUPPORTED;  // no Table B.3 on this engine
+    const TickMpa &m = *mp3.mpa;
+    const uint32_t n_l3 = mp3.n - mp3.n_mpa_units, n = (uint32_t)m.records.size();
+    uint64_t l3_rows = 0;
+    for (uint32_t g = 0; g < n_l3; ++g) l3_rows += mp3.granules[g].channels;
+    std::vector<uint64_t> unit_row(mp3.n_mpa_units + 1, l3_rows);
+    for (uint32_t u = 0; u < mp3.n_mpa_units; ++u) unit_row[u + 1] = unit_row[u] + mp3.granules[n_l3 + u].channels;
+    std::vector<uint32_t> touched;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t c = 0; c < m.records[i].channels; ++c)
+            if (e->state_count[m.stream[i] * 2 + c]++ == 0) touched.push_back(m.stream[i] * 2 + c);
+    std::vector<sk::SynthTask> tasks(touched.size());
+    uint32_t n_entries = 0;
+    for (size_t t = 0; t < touched.size(); ++t) {
+        tasks[t] = sk::SynthTask{touched[t], n_entries, 0, 0};
+        n_entries += e->state_count[touched[t]];
+        e->state_task[touched[t]] = (uint32_t)t;
+    }
+    std::vector<sk::Mp12Entry> entries(n_entries);
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t c = 0; c < m.records[i].channels; ++c) {
+            sk::SynthTask &t = tasks[e->state_task[m.stream[i] * 2 + c]];
+            entries[t.begin + t.count++] = sk::Mp12Entry{i, (uint32_t)unit_row[m.first_unit[i]]};
+        }
+    for (uint32_t state : touched) e->state_count[state] = 0;
+    if (tasks.empty()) return SK_OK;
+    SK_HIP(e->tick_mpa_in.reserve(m.bytes_len + 16), "alloc tick mpa frame bytes");
+    SK_HIP(hipMemcpyAsync(e->tick_mpa_in.p, m.bytes, m.bytes_len, hipMemcpyHostToDevice, e->stream), "H2D tick mpa frame bytes");
+    sk::Mp12Args a{};
+    SK_HIP(aux.put(m.records, e->stream, &a.records), "upload tick mpa records");
+    SK_HIP(aux.put(tasks, e->stream, &a.tasks), "upload tick mpa tasks");
+    SK_HIP(aux.put(entries, e->stream, &a.entries), "upload tick mpa entries");
+    a.bytes = (const uint32_t *)e->tick_mpa_in.p;
+    a.pcm = pcm_rows;
+    a.planar_stride = 1024;
+    a.state = e->d_mp3_state;
+    a.n_tasks = (uint32_t)tasks.size();
+    a.matrix = e->d_mp3_tables + kMp3Imdct;
+    a.window = a.matrix + kMp3Matrix;
+    a.scf = a.window + kMp3Window + 16;
+    SK_HIP(sk::launch_mp12_synth(a, e->stream), "launch tick mpa synthesis");
+    return SK_OK;
+}
 
 // Queues the copy of a tick's packed output to the caller's buffer.  Into pinned memory the copy is queued like a kernel and the
 // bounded wait that follows is the tick's only wait.  A caller's pageable buffer would make hipMemcpyAsync itself wait for everything
@@ -3763,14 +3977,17 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
     if (!au_mode && !q_mode && n_frames && (!descs || !coeffs)) return SK_ERR_INVALID_ARG;
     if (q_mode && n_frames && (!descs || !q_quant)) return SK_ERR_INVALID_ARG;
     if (au_mode && n_frames && !au_bytes) return SK_ERR_INVALID_ARG;
-    if (mp3.n && (!mp3.granules || !mp3.descs || (!mp3.is && !mp3.md))) return SK_ERR_INVALID_ARG;
+    if (mp3.n_mpa_units > mp3.n || (mp3.n_mpa_units && !mp3.mpa)) return SK_ERR_INVALID_ARG;
+    const uint32_t n_l3 = mp3.n - mp3.n_mpa_units;  // the Layer III granules come first, the Layer I / II units behind them
+    if (mp3.n && (!mp3.granules || !mp3.descs)) return SK_ERR_INVALID_ARG;
+    if (n_l3 && !mp3.is && !mp3.md) return SK_ERR_INVALID_ARG;
     *n_outs = 0;
     if (out_bytes) *out_bytes = 0;
     if (n_streams == 0) return n_frames == 0 && mp3.n == 0 ? SK_OK : SK_ERR_INVALID_ARG;
     DeviceGuard guard(e);
     if (au_mode) {  // the descs are implied: every unit of a stream carries that stream's channel count
         uint64_t total = 0;
-        for (uint32_t i = 0; i < n_streams; ++i) total += ts[i].codec == SK_TICK_MP3 ? 0 : ts[i].n_frames;
+        for (uint32_t i = 0; i < n_streams; ++i) total += ts[i].codec != SK_TICK_AAC ? 0 : ts[i].n_frames;
         if (total != n_frames) return SK_ERR_INVALID_ARG;
         if (au_len > 0xffffffffull) return SK_ERR_INVALID_ARG;  // unit offsets and the bit reader count in 32 bits
         au_descs.resize(n_frames);
@@ -3778,7 +3995,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
         for (uint32_t i = 0; i < n_streams; ++i) {
             if (!stream_ok(e, ts[i].stream)) return SK_ERR_BAD_STREAM;
             if (e->streams[ts[i].stream].channels > SK_MAX_CHANNELS) return SK_ERR_INVALID_ARG;  // a wide PCM stream decodes nothing
-            if (ts[i].codec == SK_TICK_MP3) continue;
+            if (ts[i].codec != SK_TICK_AAC) continue;
             for (uint32_t f = 0; f < ts[i].n_frames; ++f, ++k) {
                 au_descs[k] = sk_aac_frame_desc{};
                 au_descs[k].stream = ts[i].stream;
@@ -3812,7 +4029,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
     std::vector<TickCall> tc(n_streams);
     {
         std::vector<uint8_t> seen(e->streams.size(), 0);
-        uint64_t total = 0, total_mp3 = 0;
+        uint64_t total = 0, total_mp3 = 0, total_mpa = 0;
         for (uint32_t i = 0; i < n_streams; ++i) {
             const sk_tick_stream &t = ts[i];
             if (!stream_ok(e, t.stream)) return SK_ERR_BAD_STREAM;
@@ -3821,8 +4038,22 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
             if (t.out_bits != 16 && t.out_bits != 24 && t.out_bits != 32) return SK_ERR_INVALID_ARG;
             if (t.out_channels == 0) return SK_ERR_INVALID_ARG;
             if (t.resample && !e->streams[t.stream].rs_open) return SK_ERR_BAD_STREAM;
+            if (t.codec == SK_TICK_MPA) {  // (n_frames counts UNITS here: the entry point made them of the stream's frames)
+                if (total_mpa + t.n_frames > mp3.n_mpa_units) return SK_ERR_INVALID_ARG;
+                tc[i].ch = e->streams[t.stream].channels;
+                for (uint32_t f = 0; f < t.n_frames; ++f) {
+                    const uint32_t g = n_l3 + (uint32_t)total_mpa + f;
+                    if (mp3.descs[g].stream != t.stream || mp3.descs[g].channels != tc[i].ch || mp3.granules[g].channels != tc[i].ch) return SK_ERR_INVALID_ARG;
+                    if (mp3.mpa->unit_len[total_mpa + f] != mp3.mpa->unit_len[total_mpa]) return SK_ERR_INVALID_ARG;  // one layer per stream
+                }
+                tc[i].first = n_l3 + (uint32_t)total_mpa;
+                tc[i].mp3 = true;
+                tc[i].ulen = t.n_frames ? mp3.mpa->unit_len[total_mpa] : 576;
+                total_mpa += t.n_frames;
+                continue;
+            }
             if (t.codec == SK_TICK_MP3) {  // its units are the next n_frames granules
-                if (total_mp3 + t.n_frames > mp3.n) return SK_ERR_INVALID_ARG;
+                if (total_mp3 + t.n_frames > n_l3) return SK_ERR_INVALID_ARG;
                 tc[i].ch = e->streams[t.stream].channels;
                 for (uint32_t f = 0; f < t.n_frames; ++f) {
                     const uint32_t g = (uint32_t)total_mp3 + f;
@@ -3842,7 +4073,7 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
             tc[i].first = (uint32_t)total;
             total += t.n_frames;
         }
-        if (total != n_frames || total_mp3 != mp3.n) return SK_ERR_INVALID_ARG;
+        if (total != n_frames || total_mp3 != n_l3 || total_mpa != mp3.n_mpa_units) return SK_ERR_INVALID_ARG;
     }
 
     // ---- synthesis of the whole batch ----
@@ -3890,7 +4121,10 @@ int tick_body(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const 
     float *d_pcm = (float *)e->tick_pcm.p;
     if (mp3.n) {  // queued in front of the AAC work: nothing below waits for it separately
         std::vector<int32_t> mp3_status;
-        rc = tick_mp3_queue(e, mp3, d_pcm + (size_t)hp.off1024 * 1024, aux, mp3_status);
+        mp3_status.assign(mp3.n, 0);
+        if (n_l3) rc = tick_mp3_queue(e, mp3, d_pcm + (size_t)hp.off1024 * 1024, aux, mp3_status);
+        if (rc != SK_OK) return rc;
+        if (mp3.n_mpa_units) rc = tick_mpa_queue(e, mp3, d_pcm + (size_t)hp.off1024 * 1024, aux);  // checked records: no unit of theirs fails
         if (rc != SK_OK) return rc;
         for (uint32_t i = 0; i < n_streams; ++i) {
             if (!tc[i].mp3) continue;
@@ -4657,8 +4891,53 @@ int tick_pcm_impl(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
 // pass of k_mp3_entropy gives every frame's verdict (one synchronisation: a dropped frame changes its stream's unit count, which the
 // tick's plan is made from); the frames that decode become the tick's granules, and the tick runs the stage a second time over them,
 // straight into its integer rows and granule records (0.35 ms per 131 072 granule-channels each time, the main data uploaded once).
+// The Layer I / II streams' frames (sk_tick_run_mixed_mpa) as the units tick_body plans with: per frame two entries (Layer I: one) for
+// the end of the granule / desc arrays, and per stream its unit count.  Every record is checked here; one that does not add up fails the call.
+struct TickMpaBuild {
+    TickMpa m;
+    std::vector<sk_mp3_requant_granule> granules;
+    std::vector<sk_mp3_granule_desc> descs;
+    std::vector<uint32_t> units_of;  // per entry of ts (0 for the other codecs)
+};
+int mpa_build(const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_mpa_frames *mpa, TickMpaBuild &b) {
+    uint64_t listed = 0;
+    for (uint32_t i = 0; i < n_streams; ++i)
+        if (ts[i].codec == SK_TICK_MPA) listed += ts[i].n_frames;
+    const uint32_t n = mpa ? mpa->n_frames : 0;
+    if (listed != n) return SK_ERR_INVALID_ARG;
+    b.units_of.assign(n_streams, 0);
+    if (n == 0) return SK_OK;
+    if (!mpa->records || !mpa->frame_bytes || mpa->bytes_len > (1u << 28)) return SK_ERR_INVALID_ARG;
+    b.m.bytes = mpa->frame_bytes, b.m.bytes_len = mpa->bytes_len;
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        if (ts[i].codec != SK_TICK_MPA) continue;
+        for (uint32_t k = 0; k < ts[i].n_frames; ++k, ++at) {
+            const sk_mpa_frame_record &r = mpa->records[at];
+            if (!sk_mp12::record_adds_up(r) || (r.byte_offset & 3u) || (uint64_t)r.byte_offset + r.byte_len + 8 > mpa->bytes_len) return SK_ERR_INVALID_ARG;
+            b.m.records.push_back(r);
+            b.m.stream.push_back(ts[i].stream);
+            b.m.first_unit.push_back((uint32_t)b.m.unit_len.size());
+            const uint32_t units = r.layer == 1 ? 1 : 2;
+            for (uint32_t u = 0; u < units; ++u) {
+                sk_mp3_requant_granule g;
+                std::memset(&g, 0, sizeof g);
+                g.sample_rate = r.sample_rate, g.channels = r.channels;
+                sk_mp3_granule_desc d;
+                std::memset(&d, 0, sizeof d);
+                d.stream = ts[i].stream, d.channels = r.channels;
+                b.granules.push_back(g);
+                b.descs.push_back(d);
+                b.m.unit_len.push_back(r.layer == 1 ? 384 : 576);
+            }
+            b.units_of[i] += units;
+        }
+    }
+    return SK_OK;
+}
+
 int tick_impl_md(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md, uint8_t *out,
-                 size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) {
+                 size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes, const TickMpaBuild *mb = nullptr) {
     if (!e || !in || !md || !n_outs || (n_streams && !ts) || (md->n_frames && (!md->frames || !md->main_bytes))) return SK_ERR_INVALID_ARG;
     if (in->n_mp3_granules || in->mp3_granules || in->mp3_is) return SK_ERR_INVALID_ARG;  // the MP3 units in ONE form
     const uint32_t n = md->n_frames;
@@ -4748,10 +5027,56 @@ int tick_impl_md(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, con
     frames_form.frames = kept.data(), frames_form.n = (uint32_t)kept.size(), frames_form.main_len = md->main_len;
     frames_form.first_row = first_row.data(), frames_form.first_record = first_record.data();
     TickMp3 mp3;
+    if (mb && !mb->granules.empty()) {  // the Layer I / II units go behind the granules
+        granules.insert(granules.end(), mb->granules.begin(), mb->granules.end());
+        descs.insert(descs.end(), mb->descs.begin(), mb->descs.end());
+        for (uint32_t i = 0; i < n_streams; ++i)
+            if (ts[i].codec == SK_TICK_MPA) kept_ts[i].n_frames = mb->units_of[i];
+        mp3.n_mpa_units = (uint32_t)mb->granules.size();
+        mp3.mpa = &mb->m;
+    }
     mp3.granules = granules.data(), mp3.descs = descs.data(), mp3.n = (uint32_t)granules.size();
     mp3.md = &frames_form;
     return tick_impl_locked(e, kept_ts.data(), n_streams, in->descs, in->coeffs, in->units, in->au_bytes, in->au_bytes_len, in->n_aac_units, out, out_cap, outs,
                             outs_cap, n_outs, out_bytes, nullptr, (const uint8_t *)in->q_sides, in->q_quant, mp3);
+}
+
+// Every mixed form of the tick: sk_tick_run_mixed (md and mpa null), sk_tick_run_mixed_md (mpa null), sk_tick_run_mixed_mpa.
+int tick_mixed(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md,
+               const sk_tick_mpa_frames *mpa, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs,
+               size_t *out_bytes) {
+    if (!in || (n_streams && !ts)) return SK_ERR_INVALID_ARG;
+    const int forms = (in->coeffs ? 1 : 0) + (in->units ? 1 : 0) + (in->q_sides ? 1 : 0);
+    if (forms > 1 || (in->n_aac_units && forms == 0)) return SK_ERR_INVALID_ARG;  // the AAC units in ONE form
+    if (in->q_sides && in->n_aac_units && (!in->q_quant || !in->descs)) return SK_ERR_INVALID_ARG;
+    TickMpaBuild mb;
+    const int rc = mpa_build(ts, n_streams, mpa, mb);
+    if (rc != SK_OK) return rc;
+    if (md) return tick_impl_md(e, ts, n_streams, in, md, out, out_cap, outs, outs_cap, n_outs, out_bytes, &mb);
+    TickMp3 mp3;
+    if (mb.granules.empty()) {  // no Layer I / II frames: the caller's arrays as they are
+        mp3.granules = in->mp3_granules, mp3.descs = in->mp3_descs, mp3.is = in->mp3_is, mp3.n = in->n_mp3_granules;
+        for (uint32_t g = 0; g < mp3.n && mp3.granules; ++g)
+            if (mp3.granules[g].channels < 1 || mp3.granules[g].channels > 2) return SK_ERR_INVALID_ARG;
+        return tick_impl(e, ts, n_streams, in->descs, in->coeffs, in->units, in->au_bytes, in->au_bytes_len, in->n_aac_units, out, out_cap, outs, outs_cap,
+                         n_outs, out_bytes, nullptr, (const uint8_t *)in->q_sides, in->q_quant, mp3);
+    }
+    // the Layer III granules as `in` brings them, the Layer I / II units behind them
+    if (in->n_mp3_granules && (!in->mp3_granules || !in->mp3_descs)) return SK_ERR_INVALID_ARG;
+    for (uint32_t g = 0; g < in->n_mp3_granules; ++g)
+        if (in->mp3_granules[g].channels < 1 || in->mp3_granules[g].channels > 2) return SK_ERR_INVALID_ARG;
+    std::vector<sk_mp3_requant_granule> granules(in->mp3_granules, in->mp3_granules + in->n_mp3_granules);
+    std::vector<sk_mp3_granule_desc> descs(in->mp3_descs, in->mp3_descs + in->n_mp3_granules);
+    granules.insert(granules.end(), mb.granules.begin(), mb.granules.end());
+    descs.insert(descs.end(), mb.descs.begin(), mb.descs.end());
+    std::vector<sk_tick_stream> units_ts(ts, ts + n_streams);  // a Layer I / II stream's units are counted from its frames
+    for (uint32_t i = 0; i < n_streams; ++i)
+        if (ts[i].codec == SK_TICK_MPA) units_ts[i].n_frames = mb.units_of[i];
+    mp3.granules = granules.data(), mp3.descs = descs.data(), mp3.is = in->mp3_is, mp3.n = (uint32_t)granules.size();
+    mp3.n_mpa_units = (uint32_t)mb.granules.size();
+    mp3.mpa = &mb.m;
+    return tick_impl(e, units_ts.data(), n_streams, in->descs, in->coeffs, in->units, in->au_bytes, in->au_bytes_len, in->n_aac_units, out, out_cap, outs,
+                     outs_cap, n_outs, out_bytes, nullptr, (const uint8_t *)in->q_sides, in->q_quant, mp3);
 }
 
 }  // namespace
@@ -4782,16 +5107,7 @@ int sk_tick_run_q(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, co
 int sk_tick_run_mixed(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, uint8_t *out, size_t out_cap,
                       sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) try {
     sk::abi_enter();
-    if (!in) return SK_ERR_INVALID_ARG;
-    const int forms = (in->coeffs ? 1 : 0) + (in->units ? 1 : 0) + (in->q_sides ? 1 : 0);
-    if (forms > 1 || (in->n_aac_units && forms == 0)) return SK_ERR_INVALID_ARG;  // the AAC units in ONE form
-    if (in->q_sides && in->n_aac_units && (!in->q_quant || !in->descs)) return SK_ERR_INVALID_ARG;
-    TickMp3 mp3;
-    mp3.granules = in->mp3_granules, mp3.descs = in->mp3_descs, mp3.is = in->mp3_is, mp3.n = in->n_mp3_granules;
-    for (uint32_t g = 0; g < mp3.n && mp3.granules; ++g)
-        if (mp3.granules[g].channels < 1 || mp3.granules[g].channels > 2) return SK_ERR_INVALID_ARG;
-    return tick_impl(e, ts, n_streams, in->descs, in->coeffs, in->units, in->au_bytes, in->au_bytes_len, in->n_aac_units, out, out_cap, outs, outs_cap,
-                     n_outs, out_bytes, nullptr, (const uint8_t *)in->q_sides, in->q_quant, mp3);
+    return tick_mixed(e, ts, n_streams, in, nullptr, nullptr, out, out_cap, outs, outs_cap, n_outs, out_bytes);
 } catch (...) {
     return sk::abi_caught("sk_tick_run_mixed");
 }
@@ -4799,13 +5115,19 @@ int sk_tick_run_mixed(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams
 int sk_tick_run_mixed_md(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md, uint8_t *out,
                          size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) try {
     sk::abi_enter();
-    if (!in) return SK_ERR_INVALID_ARG;
-    const int forms = (in->coeffs ? 1 : 0) + (in->units ? 1 : 0) + (in->q_sides ? 1 : 0);
-    if (forms > 1 || (in->n_aac_units && forms == 0)) return SK_ERR_INVALID_ARG;  // the AAC units in ONE form
-    if (in->q_sides && in->n_aac_units && (!in->q_quant || !in->descs)) return SK_ERR_INVALID_ARG;
-    return tick_impl_md(e, ts, n_streams, in, md, out, out_cap, outs, outs_cap, n_outs, out_bytes);
+    if (!md) return SK_ERR_INVALID_ARG;
+    return tick_mixed(e, ts, n_streams, in, md, nullptr, out, out_cap, outs, outs_cap, n_outs, out_bytes);
 } catch (...) {
     return sk::abi_caught("sk_tick_run_mixed_md");
+}
+
+int sk_tick_run_mixed_mpa(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, const sk_tick_input *in, const sk_tick_mp3_frames *md,
+                          const sk_tick_mpa_frames *mpa, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs,
+                          size_t *out_bytes) try {
+    sk::abi_enter();
+    return tick_mixed(e, ts, n_streams, in, md, mpa, out, out_cap, outs, outs_cap, n_outs, out_bytes);
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_mixed_mpa");
 }
 
 size_t sk_tick_pcm_out_bound_on(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,

@@ -544,6 +544,11 @@ namespace {
 
 int decode(sk_mp3_decoder *d, const uint8_t *input, size_t len, void *out, size_t out_cap, size_t *written, Out kind) {
     if (!d || !written || (len && !input) || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    if (d->mpa_layer != 3 && gpu_hooks().decode_mpa) {  // a stream of Layer I / II, or one whose layer is not known yet: mp12_decoder.cpp
+        bool handled = false;
+        const int rc = gpu_hooks().decode_mpa(d, input, len, out, out_cap, written, kind, &handled);
+        if (handled) return rc;
+    }
     if (d->gpu_entropy) return gpu_hooks().decode(d, input, len, out, out_cap, written, kind);  // mp3_decoder_gpu.cpp
     *written = 0;
     if (d->buffer.size() + len > kMaxBuffered) return SK_PIPE_CHUNK_TOO_LARGE;
@@ -748,6 +753,7 @@ int sk_mp3_decoder_reset(sk_mp3_decoder *d) try {
     d->stream_open = false;
     d->buffer.clear(), d->reservoir.clear();
     d->sample_rate = 0, d->channels = 0, d->free_format_bytes = 0;
+    d->mpa_layer = 0;
     return SK_OK;
 } catch (...) {
     return sk::abi_caught("sk_mp3_decoder_reset");

@@ -56,6 +56,10 @@ struct sk_mp3_decoder {
     std::vector<uint8_t> gpu_bytes;
     std::vector<uint32_t> gpu_streams, gpu_blob;  // gpu_blob: the decoder's code book, flattened
     std::vector<int32_t> gpu_entropy_status, gpu_stage_status;
+    // Layer I / II (mp12_decoder.cpp).  mpa_layer: 0 = the stream's layer is not known yet, else that of its first confirmed frame
+    uint8_t mpa_layer = 0;
+    std::vector<sk_mpa_frame_info> mpa_found;
+    std::vector<sk_mpa_frame_record> mpa_records;
 };
 
 namespace sk_mp3_internal {
@@ -81,6 +85,9 @@ struct GpuHooks {
     // the engine's device code book := this blob (sk_mp3_codebook_flatten); cheap when the engine holds it already
     int (*install_codebook)(sk_engine *, const uint32_t *words, size_t n_words) = nullptr;
     int (*decode)(sk_mp3_decoder *, const uint8_t *input, size_t len, void *out, size_t out_cap, size_t *written, Out kind) = nullptr;
+    // Layer I / II (mp12_decoder.cpp): finds the layer of a stream that has none yet and decodes the call if the stream is Layer I / II
+    // (or has to wait for the header that tells); *handled = false: a Layer III stream, the call is decode()'s as ever
+    int (*decode_mpa)(sk_mp3_decoder *, const uint8_t *input, size_t len, void *out, size_t out_cap, size_t *written, Out kind, bool *handled) = nullptr;
 };
 GpuHooks &gpu_hooks();  // mp3_decoder.cpp
 
@@ -103,6 +110,13 @@ struct PipelineGpuHooks {
                     sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_pcm
     size_t (*tick_pcm_out_bound)(sk_engine *, const sk_pcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
     // the engine's pool of wide PCM streams (3 ... 8 channels); with these absent such a stream is refused as before
+    // Layer I / II streams: the host front (mp12_bitstream.cpp) and the tick that takes their frames; with these absent such a stream
+    // ends with SK_ERR_UNSUPPORTED
+    int (*mpa_find_layer)(const uint8_t *, size_t) = nullptr;  // sk_mp12::find_layer
+    int (*mpa_scan)(const uint8_t *, size_t, uint32_t *, sk_mpa_frame_info *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_mpa_scan
+    int (*mpa_parse_frame)(const uint8_t *, size_t, const sk_mpa_frame_info *, sk_mpa_frame_record *) = nullptr;         // sk_mpa_parse_frame
+    int (*tick_mpa)(sk_engine *, const sk_tick_stream *, uint32_t, const sk_tick_input *, const sk_tick_mp3_frames *, const sk_tick_mpa_frames *, uint8_t *,
+                    size_t, sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_mixed_mpa
     uint32_t (*wide_pcm_streams)(const sk_engine *) = nullptr;  // sk_engine_wide_pcm_streams
     int (*enable_wide_pcm)(sk_engine *, uint32_t) = nullptr;    // sk_engine_enable_wide_pcm
 };

@@ -76,6 +76,7 @@ struct PStream {
     uint8_t codec = 0;
     std::vector<uint8_t> mp3_reservoir;  // main data of the frames seen so far (main_data_begin reaches back into it)
     uint32_t mp3_free_format = 0;        // a free-format stream's frame length once measured (sk_mp3_scan_free)
+    uint8_t mpa_layer = 0;               // an MPEG audio stream's layer: that of its first confirmed frame, 0 = not known yet
     // WAV / raw PCM streams (FormatDecoder::Wav / RawPcm, lib.rs:2292-2297): the stream processor, and what its first piece decided
     std::unique_ptr<sk_pcm::WavStream> wav;
     std::unique_ptr<sk_pcm::RawPcmStream> raw;
@@ -130,6 +131,10 @@ struct Batch {
     std::vector<sk_mp3_frame_item> mp3_frames;
     std::vector<uint32_t> mp3_frames_of;
     size_t n_mp3_frames = 0;
+    // Layer I / II streams' frames (sk_tick_run_mixed_mpa through pipeline_gpu_hooks()), in the order of their streams in ts: records and
+    // the frames' bytes (each 4-byte aligned, 8 bytes of room behind it); appended under batch_mu, they are small
+    std::vector<sk_mpa_frame_record> mpa_recs;
+    std::vector<uint8_t> mpa_bytes;
     // WAV / raw PCM streams' units (sk_tick_run_pcm through pipeline_gpu_hooks()): pieces in pcm_bytes (pinned, ensure_pcm), one table
     // row per stream with units or a flush, pcm_entry[row] = its entry
     uint8_t *pcm_bytes = nullptr;
@@ -156,6 +161,8 @@ struct Batch {
         mp3_rows = 0;
         n_mp3_frames = 0;
         mp3_frames_of.clear();
+        mpa_recs.clear();
+        mpa_bytes.clear();
         pcm_used = 0;
         pcm_ts.clear();
         pcm_units.clear();
@@ -301,6 +308,10 @@ struct Parsed {  // what one worker pass produced for one stream
     // ... or, with the Huffman stage on the device, its frames (byte_offset into mp3_bytes; n_au_bytes = mp3_bytes.size())
     std::vector<sk_mp3_frame_item> mp3_frames;
     std::vector<uint8_t> mp3_bytes;
+    // a Layer I / II stream's pass: n_frames counts FRAMES (whole frames are what such a stream is budgeted in); byte_offset into mpa_bytes
+    bool mpa = false;
+    std::vector<sk_mpa_frame_record> mpa_recs;
+    std::vector<uint8_t> mpa_bytes;
     // a WAV / raw PCM stream's pass (n_frames stays 0): pieces for the PCM tick, each at a 16-byte aligned offset of pcm_bytes, or --
     // fast path -- finished outputs; `more`: the pass stopped at a limit with input left
     bool pcm = false, more = false;
@@ -508,6 +519,96 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
     }
 }
 
+// A Layer I / II stream's pass (nanomp3 inside Mp3Decoder::decode_i16 on such a frame, up to the samples): frame sync and header, then
+// the frame's serial front -- allocation, scale-factor selection, scale factors -- read into a record on this thread, where it is
+// cheap; the samples stay in the frame's bytes and are the tick's (k_mp12_synth).  A frame the parse rejects (Layer I's allocation 15,
+// samples that would end beyond the frame) is consumed without output.  At most `limit` FRAMES per pass: a frame is never split
+// between passes or ticks.
+void parse_some_mpa(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
+    r.mpa = true;
+    auto fail = [&](int32_t st, const std::string &msg) {
+        r.failed = true;
+        r.fail_status = st;
+        r.fail_msg = msg;
+    };
+    const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+    if (!hooks.mpa_scan || !hooks.mpa_parse_frame || !hooks.tick_mpa) {
+        fail(SK_ERR_UNSUPPORTED, "Decoding failed: MPEG Layer I / II needs the device tick, which this build lacks");
+        return;
+    }
+    int rc = ensure_mp3(p);  // the synthesis window is the engine's Layer III one
+    if (rc != SK_OK) {
+        fail(rc, std::string("Decoding failed: MP3 tables: ") + sk_strerror(rc));
+        return;
+    }
+    std::vector<sk_mpa_frame_info> found(64);
+    while (r.n_frames < limit && !r.failed) {
+        const size_t avail = s.pending.size() - s.pending_pos;
+        uint32_t n_found = 0, layer = s.mpa_layer;
+        size_t scanned = 0;
+        if (avail >= 4) {
+            rc = hooks.mpa_scan(s.pending.data() + s.pending_pos, avail, &layer, found.data(), (uint32_t)found.size(), &n_found, &scanned);
+            if (rc != SK_OK) {
+                fail(rc, std::string("Decoding failed: ") + sk_strerror(rc));
+                break;
+            }
+            if (n_found > found.size()) n_found = (uint32_t)found.size();
+        }
+        if (n_found == 0) {
+            s.pending_pos += scanned;  // garbage in front of an incomplete frame goes
+            if (s.saw_eof) {
+                r.eof = true;
+                break;
+            }
+            if (pull_input(s) == 0) break;  // needs more input
+            continue;
+        }
+        size_t consumed = 0;
+        for (uint32_t k = 0; k < n_found && !r.failed; ++k) {
+            const sk_mpa_frame_info &h = found[k];
+            if (r.n_frames + 1 > limit) {
+                r.budget_stop = true;
+                break;
+            }
+            const uint8_t *frame = s.pending.data() + s.pending_pos + h.offset;
+            sk_mpa_frame_record rec;
+            if (hooks.mpa_parse_frame(frame, h.frame_bytes, &h, &rec) == SK_OK) {
+                if (s.engine_stream == kNoStream) {  // the first frame that decodes fixes rate and channels (lib.rs:203-204)
+                    s.rate = h.sample_rate;
+                    s.channels = h.channels;
+                    rc = sk_stream_open(p->engine, s.rate, s.channels, &s.engine_stream);
+                    if (rc != SK_OK) {
+                        fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
+                        break;
+                    }
+                    const uint32_t target = s.opt.output_sample_rate ? s.opt.output_sample_rate : s.rate;
+                    s.resample = target != s.rate;
+                    if (s.resample) {
+                        rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
+                        if (rc != SK_OK) {
+                            fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
+                            break;
+                        }
+                    }
+                } else if (h.channels != s.channels || h.sample_rate != s.rate) {
+                    fail(SK_MP3_UNSUPPORTED, "Decoding failed: MP3 sample rate or channel count changed mid-stream");
+                    break;
+                }
+                rec.byte_offset = (uint32_t)r.mpa_bytes.size();
+                r.mpa_bytes.insert(r.mpa_bytes.end(), frame, frame + h.frame_bytes);
+                r.mpa_bytes.resize((r.mpa_bytes.size() + 8 + 3) & ~(size_t)3, 0);  // 4-byte aligned, >= 8 zero bytes behind it
+                r.mpa_recs.push_back(rec);
+                r.n_frames += 1;
+            }
+            consumed = h.offset + h.frame_bytes;
+            if (k + 1 == n_found && n_found < found.size()) consumed = scanned;
+        }
+        s.pending_pos += consumed;
+        if (r.budget_stop) break;
+    }
+    if (r.n_frames >= limit) r.budget_stop = true;  // the pass met its frame limit: there may be more (worker_body: s.more)
+}
+
 
 // The batches' pinned buffers for PCM pieces.  Once per lane, at the first stream that needs the PCM tick.
 int ensure_pcm(sk_lane *p) {
@@ -694,6 +795,26 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         if (pull_input(s) == 0) return;  // needs more input
     }
     if (s.codec == kCodecMp3) {
+        // MPEG audio of which layer: that of the stream's first confirmed frame (two consistent headers one frame length apart)
+        const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+        if (s.mpa_layer == 0 && (s.engine_stream != kNoStream || !hooks.mpa_find_layer)) s.mpa_layer = 3;  // Layer III frames have decoded
+        while (s.mpa_layer == 0) {
+            const int layer = hooks.mpa_find_layer(s.pending.data() + s.pending_pos, s.pending.size() - s.pending_pos);
+            if (layer > 0) {
+                s.mpa_layer = (uint8_t)layer;
+                break;
+            }
+            // 0: no header in sight; -3: a Layer III candidate waits for its follower -- the Layer III pass's business, which settles
+            // nothing: the question is asked again at the next pass (Mp3Decoder does the same, mp12_decoder.cpp)
+            if (layer != -1) break;
+            if (s.saw_eof) break;                    // a lone unconfirmed frame: no frame, as the Layer III scan will find
+            if (pull_input(s) == 0) return;          // a Layer I / II candidate waits for the header behind it: needs more input
+        }
+        if (s.mpa_layer == 1 || s.mpa_layer == 2) {
+            // room counts AudioData: a Layer II frame gives two (never split: the last frame of a pass may overshoot by one)
+            parse_some_mpa(p, s, s.mpa_layer == 2 ? std::max(1u, limit / 2) : limit, r);
+            return;
+        }
         parse_some_mp3(p, s, limit, r);
         return;
     }
@@ -900,7 +1021,7 @@ void worker_body(sk_lane *p) {
         }
         {
             std::lock_guard<std::mutex> lk(s.mu);  // read by mark_schedulable and the state dump
-            s.more = (r.pcm ? r.more : (r.n_frames == limit || r.budget_stop)) && !r.eof && !r.failed;
+            s.more = (r.pcm ? r.more : (r.n_frames == limit || r.budget_stop)) && !r.eof && !r.failed;  // (a Layer I / II pass that met its frame limit: budget_stop)
         }
         p->parse_ns.fetch_add(ns_since(t0));
         p->workers_parsing.fetch_sub(1);
@@ -928,7 +1049,7 @@ void worker_body(sk_lane *p) {
             p->workers_waiting_room.fetch_add(1);
             p->room_cv.wait(lk, [&] {
                 const Batch &f = p->batches[p->filling];
-                return p->stop || (f.n_descs + f.n_mp3 + r.n_frames <= p->cfg.max_frames_per_tick &&
+                return p->stop || (f.n_descs + f.n_mp3 + f.mpa_recs.size() + r.n_frames <= p->cfg.max_frames_per_tick &&
                                    (gpu_entropy ? f.au_used + r.n_au_bytes <= f.au_cap : f.n_floats + r.n_floats <= f.coeff_cap) &&
                                    (!quant || f.au_used + r.n_au_bytes <= f.au_cap) &&
                                    (r.pcm_units.empty() || f.pcm_used + r.pcm_bytes.size() <= f.pcm_cap));
@@ -943,7 +1064,15 @@ void worker_body(sk_lane *p) {
             mp3_row_at = b->mp3_rows;
             mp3_frame_at = b->n_mp3_frames;
             b->mp3_frames_of.push_back((uint32_t)r.mp3_frames.size());
-            if (r.mp3) {
+            if (r.mpa) {  // whole frames, in claim order = the order of their streams in ts
+                const size_t at = (b->mpa_bytes.size() + 3) & ~(size_t)3;
+                b->mpa_bytes.resize(at);
+                b->mpa_bytes.insert(b->mpa_bytes.end(), r.mpa_bytes.begin(), r.mpa_bytes.end());
+                for (sk_mpa_frame_record rec : r.mpa_recs) {
+                    rec.byte_offset += (uint32_t)at;
+                    b->mpa_recs.push_back(rec);
+                }
+            } else if (r.mp3) {
                 b->n_mp3 += r.n_frames;
                 b->mp3_rows += r.mp3_is.size() / 576;
                 b->n_mp3_frames += r.mp3_frames.size();
@@ -953,7 +1082,7 @@ void worker_body(sk_lane *p) {
             b->n_floats += r.n_floats;
             b->au_used += r.n_au_bytes;
             sk_tick_stream t{};
-            t.codec = r.mp3 ? SK_TICK_MP3 : SK_TICK_AAC;
+            t.codec = r.mpa ? SK_TICK_MPA : (r.mp3 ? SK_TICK_MP3 : SK_TICK_AAC);
             t.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
             t.n_frames = r.n_frames;
             t.out_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : 16;
@@ -1004,6 +1133,7 @@ void worker_body(sk_lane *p) {
         }
         if (r.pcm) {
             if (!r.pcm_units.empty()) std::memcpy(b->pcm_bytes + pcm_at, r.pcm_bytes.data(), r.pcm_bytes.size());
+        } else if (r.mpa) {  // staged under the lock above
         } else if (r.n_frames && r.mp3 && p->mp3_gpu) {
             std::memcpy(b->au_bytes + au_at, r.mp3_bytes.data(), r.n_au_bytes);
             for (size_t k = 0; k < r.mp3_frames.size(); ++k) {
@@ -1117,7 +1247,33 @@ void submit_body(sk_lane *p) {
             }
             if (b->recs.size() < (size_t)max_out + pcm_max_out) b->recs.resize((size_t)max_out + pcm_max_out);
         }
-        if (!ts.empty()) {
+        if (!ts.empty() && b->rc == SK_OK && !b->mpa_recs.empty()) {
+            // Layer I / II frames in this tick: the tick that takes them, with everything else in the lane's form beside them
+            const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+            sk_tick_input in{};
+            in.n_aac_units = n_frames;
+            if (p->cfg.gpu_entropy == 2) in.descs = b->descs.data(), in.q_sides = b->au_bytes, in.q_quant = reinterpret_cast<const int16_t *>(b->coeffs);
+            else if (p->cfg.gpu_entropy) in.units = b->units.data(), in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
+            else in.descs = b->descs.data(), in.coeffs = b->coeffs;
+            if (n_frames == 0) in.descs = nullptr, in.coeffs = nullptr, in.units = nullptr, in.q_sides = nullptr;
+            sk_tick_mp3_frames md{b->mp3_frames.data(), (uint32_t)b->n_mp3_frames, b->au_bytes, b->au_used + 8};
+            const bool with_md = b->n_mp3 && p->mp3_gpu;
+            ts_md = ts;
+            if (with_md) {  // an MP3 stream's units are frames there
+                in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
+                for (size_t row = 0; row < ts_md.size(); ++row)
+                    if (ts_md[row].codec == SK_TICK_MP3) ts_md[row].n_frames = b->mp3_frames_of[b->row_of[row]];
+                b->rc = hooks.install_codebook(p->engine, p->mp3_blob.data(), p->mp3_blob.size());
+            } else if (b->n_mp3) {
+                in.n_mp3_granules = (uint32_t)b->n_mp3;
+                in.mp3_granules = b->mp3_gr.data(), in.mp3_descs = b->mp3_desc.data(), in.mp3_is = b->mp3_is;
+            }
+            b->mpa_bytes.resize(b->mpa_bytes.size() + 8, 0);
+            sk_tick_mpa_frames mpa{b->mpa_recs.data(), (uint32_t)b->mpa_recs.size(), b->mpa_bytes.data(), b->mpa_bytes.size()};
+            if (b->rc == SK_OK)
+                b->rc = hooks.tick_mpa(p->engine, ts_md.data(), (uint32_t)ts_md.size(), &in, with_md ? &md : nullptr, &mpa, b->out_pinned, b->out_pinned_cap,
+                                       b->recs.data(), max_out, &b->n_out, &used);
+        } else if (!ts.empty()) {
             if (b->rc == SK_OK && b->n_mp3 && p->mp3_gpu) {  // the same with the MP3 streams' Huffman stage in the tick as well
                 const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
                 sk_tick_input in{};
@@ -1178,7 +1334,7 @@ void submit_body(sk_lane *p) {
         p->submit_where = 4;
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
-        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->pcm_units.size());
+        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -1702,6 +1858,7 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.codec = 0;
     s.mp3_reservoir.clear();
     s.mp3_free_format = 0;
+    s.mpa_layer = 0;
     s.wav.reset();
     s.raw.reset();
     s.raw_format = sk_raw_pcm_format{};

@@ -3,6 +3,7 @@
 // library is loaded.  Everything else of the mode is in pipeline.cpp (parse_some_mp3 stops behind the reservoir and stages frames +
 // main data; the submission thread calls tick_md).
 #include "mp3_internal.h"
+#include "mp12_internal.h"
 
 namespace {
 
@@ -12,6 +13,10 @@ const bool g_hooked = [] {
     hooks.tick_md = sk_tick_run_mixed_md;
     hooks.tick_pcm = sk_tick_run_pcm;  // the WAV / raw PCM streams' tick comes the same way
     hooks.tick_pcm_out_bound = sk_tick_pcm_out_bound_on;
+    hooks.mpa_find_layer = sk_mp12::find_layer;  // Layer I / II streams: their host front and their tick
+    hooks.mpa_scan = sk_mpa_scan;
+    hooks.mpa_parse_frame = sk_mpa_parse_frame;
+    hooks.tick_mpa = sk_tick_run_mixed_mpa;
     hooks.wide_pcm_streams = sk_engine_wide_pcm_streams;
     hooks.enable_wide_pcm = sk_engine_enable_wide_pcm;
     return true;

@@ -342,6 +342,30 @@ struct Mp3Args {
 };
 hipError_t launch_mp3_hybrid(const Mp3Args &a, hipStream_t s);
 
+// mp12_synth.hip -- Layer I / II: sample unpacking from the frame's bytes, requantisation, polyphase synthesis; one wave per
+// (stream, channel).  The polyphase FIFO is the stream's Layer III one (ring and position inside kMp3StateFloats).
+struct Mp12Entry {
+    uint32_t record;   // index into records
+    uint32_t pcm_off;  // the frame's first sample in pcm / pcm16 (interleaved: samples_per_channel x channels from there); planar: a row
+};
+struct Mp12Args {
+    const sk_mpa_frame_record *records;  // checked on the host (sk_mp12::record_adds_up): no code ends beyond byte_offset + byte_len
+    const uint32_t *bytes;               // the frames' bytes as they arrived; byte_offset a multiple of 4, 8 bytes of room behind each
+    float *pcm;                          // interleaved f32 out ...
+    int16_t *pcm16;                      // ... or s16 (f32_to_i16); one of the two
+    uint32_t planar_stride;              // != 0 (the scheduler's tick, with pcm): Mp12Entry::pcm_off is the frame's first channel ROW; unit u
+                                         // (Layer II: slots 18 u ... 18 u + 17, Layer I: its 12 slots) of channel c goes to row
+                                         // pcm_off + u * channels + c, rows planar_stride floats apart, each sample f32_to_i16(x) / 32768
+    float *state;                        // [states][kMp3StateFloats]
+    const SynthTask *tasks;              // state = stream * 2 + channel
+    const Mp12Entry *entries;
+    uint32_t n_tasks;
+    const float *matrix;                 // [64][32]: the engine's polyphase matrixing table
+    const float *window;                 // [512]: D
+    const float *scf;                    // [64]: 2^(1 - i/3)
+};
+hipError_t launch_mp12_synth(const Mp12Args &a, hipStream_t s);
+
 // mp3_requant.hip -- Layer III requantisation + joint stereo + short-block reorder, one wave per granule
 constexpr uint32_t kMp3Rates = 9;      // 44.1 / 48 / 32 / 22.05 / 24 / 16 / 11.025 / 12 / 8 kHz: one band-table slot each
 constexpr uint32_t kMp3BandRow = 40;   // u16 per slot: 23 long offsets | 14 short offsets | padding

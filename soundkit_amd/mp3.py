@@ -8,8 +8,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (Mp3FrameInfo, Mp3FrameItem, Mp3GranuleData, Mp3GranuleDesc, Mp3RequantGranule, Mp3SideInfo, SoundkitError, check,
-                   lib)
+from ._lib import (Mp3FrameInfo, Mp3FrameItem, Mp3GranuleData, Mp3GranuleDesc, Mp3RequantGranule, Mp3SideInfo, MpaFrameInfo,
+                   MpaFrameRecord, SoundkitError, check, lib)
 from .engine import _ptr, default_engine
 
 
@@ -243,9 +243,70 @@ def decode_frames(items, streams, n, buf, engine=None, s16=False, out_cap=None):
 MAX_SAMPLES_PER_FRAME = 2304
 
 
+# ---- Layer I / II: the host front (csrc/mp12_bitstream.cpp) and the stage call (csrc/mp12_synth.hip) ---------------------------
+
+def mpa_parse_header(data):
+    """4 bytes of any layer -> (status, MpaFrameInfo)"""
+    info = MpaFrameInfo()
+    b = _bytes(data)
+    return lib.sk_mpa_parse_header(_ptr(b), len(data), C.byref(info)), info
+
+
+def mpa_scan(data, layer=0, cap=1 << 16):
+    """sk_mpa_scan: frames of one layer (0: that of the first confirmed frame) -> ([MpaFrameInfo], bytes consumed, layer)"""
+    frames = (MpaFrameInfo * cap)()
+    n, used, lay = C.c_uint32(0), C.c_size_t(0), C.c_uint32(layer)
+    b = _bytes(data)
+    check(lib.sk_mpa_scan(_ptr(b), len(data), C.byref(lay), frames, cap, C.byref(n), C.byref(used)), "sk_mpa_scan")
+    return [frames[i] for i in range(min(n.value, cap))], used.value, lay.value
+
+
+def mpa_parse_frame(frame, info):
+    """one Layer I / II frame -> (status, MpaFrameRecord): classes, scale factors, where the samples stand"""
+    rec = MpaFrameRecord()
+    b = _bytes(frame)
+    return lib.sk_mpa_parse_frame(_ptr(b), len(frame), C.byref(info), C.byref(rec)), rec
+
+
+def mpa_pack_frames(frames):
+    """frames: iterable of (MpaFrameRecord, frame bytes) -> (record array, n, uint8 buffer) laid out as sk_mpa_decode_frames_* take
+    them (offsets multiples of 4, 8 zero bytes behind each)"""
+    frames = list(frames)
+    recs = (MpaFrameRecord * max(len(frames), 1))()
+    at, chunks = 0, []
+    for i, (rec, data) in enumerate(frames):
+        data = bytes(data)
+        C.memmove(C.byref(recs[i]), C.byref(rec), C.sizeof(MpaFrameRecord))
+        recs[i].byte_offset = at
+        room = (len(data) + 8 + 3) & ~3
+        chunks.append(data + bytes(room - len(data)))
+        at += room
+    buf = np.frombuffer(b"".join(chunks) or bytes(8), np.uint8)
+    return recs, len(frames), buf
+
+
+def mpa_decode_frames(recs, streams, n, buf, engine=None, s16=False, out_cap=None, timed=False):
+    """sk_mpa_decode_frames_* -> (status, pcm[:written], status[n]) and, with timed (s16 only), the launch's HIP-event milliseconds"""
+    engine = engine or default_engine()
+    streams = np.ascontiguousarray(streams, np.uint32)
+    cap = n * MAX_SAMPLES_PER_FRAME if out_cap is None else out_cap
+    pcm = np.zeros(max(cap, 1), np.int16 if (s16 or timed) else np.float32)
+    st = np.zeros(max(n, 1), np.int32)
+    written = C.c_size_t(0)
+    if timed:
+        ms = C.c_float(0.0)
+        rc = lib.sk_mpa_decode_frames_timed(engine._h, recs, _ptr(streams), n, _ptr(buf), buf.size, _ptr(pcm), cap, _ptr(st), C.byref(written), C.byref(ms))
+        return rc, pcm[:written.value], st[:n], ms.value
+    fn = lib.sk_mpa_decode_frames_s16 if s16 else lib.sk_mpa_decode_frames_f32
+    rc = fn(engine._h, recs, _ptr(streams), n, _ptr(buf), buf.size, _ptr(pcm), cap, _ptr(st), C.byref(written))
+    return rc, pcm[:written.value], st[:n]
+
+
 class Mp3Decoder:
     """soundkit-mp3's Mp3Decoder (soundkit-mp3/src/lib.rs:147-374): new / sample_rate / channels / buffer_len / reset /
-    decode_i16 / decode_i32 / decode_f32, bytes in at any chunking, interleaved samples out; errors raise SoundkitError"""
+    decode_i16 / decode_i32 / decode_f32, bytes in at any chunking, interleaved samples out; errors raise SoundkitError.
+    All three layers, as nanomp3 behind the reference's: a stream whose first confirmed frame is Layer I or II is unpacked and
+    synthesised by csrc/mp12_synth.hip (384 / 1152 samples per channel and frame), with no switch."""
 
     def __init__(self, codebook=None, engine=None, gpu_entropy=False):
         """gpu_entropy: scale factors and Huffman decode on the GPU as well (sk_mp3_decoder_set_gpu_entropy); same results"""
