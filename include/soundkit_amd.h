@@ -996,6 +996,10 @@ typedef struct sk_raw_pcm_format {
     uint16_t reserved;
 } sk_raw_pcm_format;
 int sk_pipeline_spawn_raw_pcm(sk_pipeline *, const sk_raw_pcm_format *format, const sk_decode_options *opt /* NULL = defaults */, uint32_t *handle);
+/* DecodePipeline::spawn_aiff_with_options (lib.rs:2714-2724): an AIFF / AIFF-C stream with its decoder from the start -- nothing is
+ * detected or gathered, every received chunk is one `add` of the walker (at most one AudioData per chunk), the end of the stream is the
+ * finalising empty add.  (sk_pipeline_spawn finds such a stream by its FORM....AIFF|AIFC header too, behind the detection buffer.) */
+int sk_pipeline_spawn_aiff(sk_pipeline *, const sk_decode_options *opt /* NULL = defaults */, uint32_t *handle);
 int sk_pipeline_send(sk_pipeline *, uint32_t handle, const uint8_t *data, size_t len);   /* lib.rs:2795-2835 */
 int sk_pipeline_finish(sk_pipeline *, uint32_t handle);                                   /* lib.rs:2838-2840 */
 /* 1 = one output copied to data / info; 0 = nothing ready; SK_PIPE_CLOSED = ended and drained; SK_ERR_CAPACITY =
@@ -1035,6 +1039,76 @@ void sk_raw_pcm_framer_destroy(sk_raw_pcm_framer *);
 int sk_raw_pcm_framer_add(sk_raw_pcm_framer *, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece);
 int sk_raw_pcm_framer_flush(sk_raw_pcm_framer *); /* end of stream: SK_PCM_ERR_STREAM when a partial frame is left */
 const char *sk_raw_pcm_framer_last_error(const sk_raw_pcm_framer *);
+
+/* ---- AIFF / AIFF-C stream walker (host only) ------------------------------------------------------------------------ */
+/* AiffDecoder::add (soundkit-aiff/src/lib.rs:93-475) without its per-sample work: the FORM / COMM / SSND walk with every limit and
+ * error text of the reference.  One `add` (at most 4 MiB; an EMPTY add is the finalising one, which reports a truncated stream) gives
+ * at most one piece: whole sample groups as the file encodes them -- a sample, or for IMA4 one 34-byte packet per channel -- that
+ * sk_aiff_decode or sk_tick_run_aiff turn into the little-endian PCM of the output contract.  *piece_offset counts sound bytes. */
+enum sk_aiff_encoding {
+    SK_AIFF_U8 = 0, SK_AIFF_S8, SK_AIFF_S16BE, SK_AIFF_S16LE, SK_AIFF_S24BE, SK_AIFF_S32BE, SK_AIFF_S32LE, SK_AIFF_F32BE, SK_AIFF_F64BE,
+    SK_AIFF_ULAW, SK_AIFF_ALAW, SK_AIFF_IMA4
+};
+typedef struct sk_aiff_info { /* zeros (but buffered_bytes) until COMM has been read */
+    uint32_t sample_rate;
+    uint32_t buffered_bytes; /* AiffDecoder::buffered_bytes: held back container bytes + the incomplete sample group */
+    uint8_t channels;        /* 1 ... 32 */
+    uint8_t encoding;        /* enum sk_aiff_encoding: how the pieces are encoded */
+    uint8_t bits;            /* the output contract: 16 / 24 / 32 */
+    uint8_t is_float;        /* the output contract: 32-bit float */
+} sk_aiff_info;
+typedef struct sk_aiff_reader sk_aiff_reader;
+int sk_aiff_reader_create(sk_aiff_reader **out);
+void sk_aiff_reader_destroy(sk_aiff_reader *);
+int sk_aiff_reader_add(sk_aiff_reader *, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece);
+int sk_aiff_reader_info(const sk_aiff_reader *, sk_aiff_info *info);
+const char *sk_aiff_reader_last_error(const sk_aiff_reader *);
+
+/* ---- AIFF / AIFF-C decode stage (GPU) ------------------------------------------------------------------------------- */
+/* decode_stream_bytes (soundkit-aiff/src/lib.rs:477-560) on the GPU (csrc/aiff_decode.hip): whole sample groups in the file's encoding
+ * in, interleaved little-endian PCM of the output contract out -- u8 / s8 / mu-law / A-law / IMA4 to s16, big-endian samples
+ * reversed (f32be bit for bit), f64be rounded to f32 (nearest even; subnormals kept, overflow to infinity), sowt / 23ni copied.
+ * IMA4 (1 or 2 channels, 34-byte packets of 64 samples, channel after channel) carries {predictor, step_index} per channel from
+ * packet to packet; `state` is that carry: read on entry, written on success (AdpcmImaState::new() is all zeros), ignored (may be
+ * NULL) for the other encodings.  The carry rule is QuickTime's: a packet whose header has the carried step index and
+ * a predictor within 0x7f of the carried one continues from the carried predictor; any other packet restarts from its header.
+ * len is a whole number of groups (SK_ERR_INVALID_ARG otherwise, or when out_cap is too small); *out_len receives the decoded size:
+ * 2 bytes a sample for the 16-bit contracts, 3 for s24be, 4 for the 32-bit and float ones, 128 bytes per IMA4 packet.
+ * The _dev form takes 16-byte aligned device pointers and is queued on the engine's stream; it waits only for the state. */
+typedef struct sk_aiff_ima_state {
+    int16_t predictor;
+    uint8_t step_index; /* 0 ... 88 */
+    uint8_t reserved;
+} sk_aiff_ima_state;
+int sk_aiff_decode(sk_engine *, int encoding, uint32_t channels, const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap, size_t *out_len,
+                   sk_aiff_ima_state *state /*[2]*/);
+int sk_aiff_decode_dev(sk_engine *, int encoding, uint32_t channels, const uint8_t *d_bytes, size_t len, uint8_t *d_out, size_t out_cap,
+                       size_t *out_len, sk_aiff_ima_state *state /*[2]*/);
+
+/* The tick of the AIFF streams: every unit (= the piece of one sk_aiff_reader_add, packed at a 16-byte aligned offset) is first
+ * decoded to the contract's PCM on the device.  A stream with nothing further to change (no rate change, out_bits = the contract's,
+ * out_channels = channels) gets those bytes as its outputs, one per unit, for up to 32 channels.  Every other stream then runs
+ * exactly what sk_tick_run_pcm runs on a little-endian source of the contract's format -- same kernels, records, bounds and limits
+ * (1 or 2 channels, up to SK_MAX_PCM_CHANNELS with sk_engine_enable_wide_pcm).  The fields are sk_pcm_tick_stream's, except that
+ * `encoding` stands where `format` does, plus the IMA4 carry, which the call updates on success and leaves alone on failure.  The
+ * units of a stream chain in order. */
+typedef struct sk_aiff_tick_stream {
+    uint32_t stream;      /* engine stream (resample = 1 only) */
+    uint32_t n_units;
+    uint8_t encoding;     /* enum sk_aiff_encoding */
+    uint8_t channels;     /* 1 ... 32 */
+    uint8_t out_bits;     /* 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t reserved[2];
+    sk_aiff_ima_state ima_state[2];
+} sk_aiff_tick_stream;
+size_t sk_tick_aiff_out_bound_on(sk_engine *, const sk_aiff_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                 uint32_t *max_outputs);
+int sk_tick_run_aiff(sk_engine *, sk_aiff_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                     const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                     uint32_t *n_outputs, size_t *out_bytes_used);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,24 @@ class PcmUnit(C.Structure):
     _fields_ = [("byte_offset", C.c_uint64), ("byte_len", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AiffImaState(C.Structure):
+    """sk_aiff_ima_state"""
+    _fields_ = [("predictor", C.c_int16), ("step_index", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class AiffTickStream(C.Structure):
+    """sk_aiff_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("encoding", C.c_uint8), ("channels", C.c_uint8), ("out_bits", C.c_uint8),
+                ("out_channels", C.c_uint8), ("resample", C.c_uint8), ("flush", C.c_uint8), ("reserved", C.c_uint8 * 2),
+                ("ima_state", AiffImaState * 2)]
+
+
+class AiffInfo(C.Structure):
+    """sk_aiff_info"""
+    _fields_ = [("sample_rate", C.c_uint32), ("buffered_bytes", C.c_uint32), ("channels", C.c_uint8), ("encoding", C.c_uint8),
+                ("bits", C.c_uint8), ("is_float", C.c_uint8)]
+
+
 class RawPcmFormatC(C.Structure):
     """sk_raw_pcm_format"""
     _fields_ = [("sample_rate", C.c_uint32), ("channels", C.c_uint8), ("format", C.c_uint8), ("reserved", C.c_uint16)]
@@ -361,6 +379,7 @@ _sig = {
     "sk_tick_pcm_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "sk_tick_run_pcm": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
     "sk_pipeline_spawn_raw_pcm": (_i, [_vp, _vp, _vp, C.POINTER(_u32)]),
+    "sk_pipeline_spawn_aiff": (_i, [_vp, _vp, C.POINTER(_u32)]),
     "sk_wav_reader_create": (_i, [C.POINTER(_vp)]),
     "sk_wav_reader_destroy": (None, [_vp]),
     "sk_wav_reader_add": (_i, [_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(_sz), C.POINTER(_vp)]),
@@ -371,6 +390,15 @@ _sig = {
     "sk_raw_pcm_framer_add": (_i, [_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(_sz), C.POINTER(_vp)]),
     "sk_raw_pcm_framer_flush": (_i, [_vp]),
     "sk_raw_pcm_framer_last_error": (C.c_char_p, [_vp]),
+    "sk_aiff_reader_create": (_i, [C.POINTER(_vp)]),
+    "sk_aiff_reader_destroy": (None, [_vp]),
+    "sk_aiff_reader_add": (_i, [_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(_sz), C.POINTER(_vp)]),
+    "sk_aiff_reader_info": (_i, [_vp, C.POINTER(AiffInfo)]),
+    "sk_aiff_reader_last_error": (C.c_char_p, [_vp]),
+    "sk_aiff_decode": (_i, [_vp, _i, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_aiff_decode_dev": (_i, [_vp, _i, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_tick_aiff_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_aiff": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

@@ -28,6 +28,7 @@
 
 #include "aac_entropy_tables.h"
 #include "mp12_internal.h"
+#include "pcm_stream.h"
 #include "sk_device.h"
 
 namespace {
@@ -260,6 +261,7 @@ struct sk_engine {
     // sk_tick_run: synthesis output, resampler output, packed bytes, small-array arena (+ pinned host mirror)
     DevBuf tick_pcm, tick_res, tick_out, tick_arena, tick_au, tick_side, tick_q, tick_mp3_in, tick_mp3_xr, tick_mpa_in;
     DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
+    DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
     void *d_ec_blob = nullptr;
@@ -659,6 +661,7 @@ void sk_engine_destroy(sk_engine *e) try {
         e->tick_side.release();
         e->tick_q.release();
         e->tick_pcm_in.release();
+        e->tick_aiff.release();
         e->mp3e_in.release();
         e->tick_mpa_in.release();
         e->mp3e_out.release();
@@ -4546,12 +4549,22 @@ struct PcmCall {  // one sk_pcm_tick_stream
     std::vector<std::pair<uint32_t, uint32_t>> chunks;  // (column, frames) of each resampled AudioData
 };
 
+// sk_tick_run_aiff: what stands in front of the PCM tick's body.  The body's stream table and units describe the DECODED PCM (a
+// little-endian source of the contract's format, laid out in tick_aiff); `bytes` are the source-encoded units.
+struct AiffTick {
+    const sk_aiff_tick_stream *as = nullptr;
+    const sk_pcm_unit *src_units = nullptr;  // the caller's units, into `bytes`
+    size_t decoded_len = 0;                  // of the decoded layout
+    std::vector<uint8_t> plain;              // per stream: nothing to change behind the decode -- the decoded bytes are its outputs, one per unit
+    std::vector<uint32_t> states;            // out: 2 per stream, what k_aiff_ima4 left ((uint16_t)predictor | step_index << 16)
+};
+
 bool pcm_fmt_is_float(int fmt) { return fmt == SK_FMT_F32LE || fmt == SK_FMT_F32BE; }
 uint32_t pcm_fmt_bits(int fmt) { return fmt <= SK_FMT_S16BE ? 16 : (fmt <= SK_FMT_S24BE ? 24 : 32); }
 
 // Checks the table and fills in what follows from it.  SK_OK, or the status sk_tick_run_pcm returns.
 int pcm_tick_plan(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, size_t bytes_len,
-                  std::vector<PcmCall> &pc) {
+                  std::vector<PcmCall> &pc, const uint8_t *plain = nullptr) {
     pc.assign(n_streams, PcmCall{});
     std::vector<uint8_t> seen(e->streams.size(), 0);
     uint64_t at = 0;
@@ -4561,11 +4574,12 @@ int pcm_tick_plan(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_s
         if (t.format > SK_FMT_F32BE) return SK_ERR_INVALID_ARG;
         if (t.channels == 0 || t.out_channels == 0) return SK_ERR_INVALID_ARG;
         // 3 ... 8 channels: only an engine that reserved the slots for them (sk_engine_enable_wide_pcm) takes them
-        if (t.channels > SK_MAX_CHANNELS && (t.channels > SK_MAX_PCM_CHANNELS || !e->wide_enabled)) return SK_ERR_UNSUPPORTED;
+        const bool as_is = plain && plain[i];  // a decoded AIFF stream with nothing further to change: any channel count, no device work here
+        if (!as_is && t.channels > SK_MAX_CHANNELS && (t.channels > SK_MAX_PCM_CHANNELS || !e->wide_enabled)) return SK_ERR_UNSUPPORTED;
         if (t.out_bits != 16 && t.out_bits != 24 && t.out_bits != 32) return SK_ERR_INVALID_ARG;
         const uint32_t bits = pcm_fmt_bits(t.format);
         // the fast path (lib.rs:3339-3345) needs no device: such a stream's pieces are delivered as they are, by the caller
-        if (!t.resample && t.out_bits == bits && t.out_channels == t.channels) return SK_ERR_INVALID_ARG;
+        if (!as_is && !t.resample && t.out_bits == bits && t.out_channels == t.channels) return SK_ERR_INVALID_ARG;
         if (t.resample) {
             if (!stream_ok(e, t.stream) || !e->streams[t.stream].rs_open || e->streams[t.stream].channels != t.channels) return SK_ERR_BAD_STREAM;
             if (seen[t.stream]++) return SK_ERR_INVALID_ARG;  // a stream appears once per tick
@@ -4582,7 +4596,9 @@ int pcm_tick_plan(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_s
         uint64_t frames = 0;
         for (uint32_t u = 0; u < t.n_units; ++u) {
             const sk_pcm_unit &un = units[at + u];
-            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len > 0x7fffffffu || un.byte_len % c.frame_bytes) return SK_ERR_INVALID_ARG;
+            // (a decoded AIFF unit that is delivered as it is holds whole samples, not necessarily whole frames: the reference's decoder
+            // emits every complete sample of an `add`)
+            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len > 0x7fffffffu || (!as_is && un.byte_len % c.frame_bytes)) return SK_ERR_INVALID_ARG;
             if (un.byte_offset > bytes_len || un.byte_len > bytes_len - un.byte_offset) return SK_ERR_INVALID_ARG;
             frames += un.byte_len / c.frame_bytes;
         }
@@ -4599,10 +4615,10 @@ uint64_t pcm_chunk_out_frames(const StreamInfo &s) {
 }
 
 size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
-                          uint32_t *max_outputs) {
+                          uint32_t *max_outputs, const uint8_t *plain = nullptr) {
     std::vector<PcmCall> pc;
     if (max_outputs) *max_outputs = 0;
-    if (pcm_tick_plan(e, ts, n_streams, units, n_units, (size_t)-1, pc) != SK_OK) return 0;
+    if (pcm_tick_plan(e, ts, n_streams, units, n_units, (size_t)-1, pc, plain) != SK_OK) return 0;
     size_t bytes = 0;
     uint64_t outs = 0;
     for (uint32_t i = 0; i < n_streams; ++i) {
@@ -4613,7 +4629,8 @@ size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint
             bytes += chunks * (pcm_chunk_out_frames(s) * frame_out + 16) + 16;
             outs += chunks;
         } else {
-            bytes += (uint64_t)pc[i].total_frames * frame_out + (uint64_t)ts[i].n_units * 16 + 16;
+            // (+ a frame per unit: a decoded AIFF unit delivered as it is may end inside a frame)
+            bytes += ((uint64_t)pc[i].total_frames + (plain && plain[i] ? ts[i].n_units : 0)) * frame_out + (uint64_t)ts[i].n_units * 16 + 16;
             outs += ts[i].n_units;
         }
     }
@@ -4622,14 +4639,15 @@ size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint
 }
 
 int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
-                  size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) {
+                  size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
+                  AiffTick *aiff = nullptr) {
     if (!e || !n_outs || (n_streams && !ts) || (n_units && (!units || !bytes))) return SK_ERR_INVALID_ARG;
     *n_outs = 0;
     if (out_bytes) *out_bytes = 0;
     if (n_streams == 0) return n_units == 0 ? SK_OK : SK_ERR_INVALID_ARG;
     DeviceGuard guard(e);
     std::vector<PcmCall> pc;
-    int rc = pcm_tick_plan(e, ts, n_streams, units, n_units, bytes_len, pc);
+    int rc = pcm_tick_plan(e, ts, n_streams, units, n_units, aiff ? aiff->decoded_len : bytes_len, pc, aiff ? aiff->plain.data() : nullptr);
     if (rc != SK_OK) return rc;
 
     // from here to the tick's last wait the device belongs to this engine (see g_device_turn)
@@ -4675,6 +4693,67 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
     const uint8_t *d_in = (const uint8_t *)e->tick_pcm_in.p;
     e->where.store("tick (pcm): upload, ingest, resampler rounds");
     if (bytes_len) SK_HIP(hipMemcpyAsync(e->tick_pcm_in.p, bytes, bytes_len, hipMemcpyHostToDevice, e->stream), "H2D tick pcm bytes");
+
+    // ---- AIFF: every unit to the contract's PCM first (aiff_decode.hip).  The streams that go on through the body decode into
+    // tick_aiff, which the body then reads in the place of the uploaded bytes; the others decode straight into their output records ----
+    std::vector<std::pair<const uint32_t *, std::vector<uint32_t>>> aiff_states;  // (pinned states, AiffImaStream -> index into ts) per launch
+    auto aiff_decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of) -> int {
+        std::vector<sk::AiffElemJob> elems;
+        std::vector<sk::AiffImaStream> imas;
+        std::vector<sk::AiffImaUnit> ima_units;
+        std::vector<uint32_t> ima_of;  // AiffImaStream -> index into ts
+        uint32_t max_samples = 0;
+        const uint8_t *d_src = (const uint8_t *)e->tick_pcm_in.p;
+        for (uint32_t i = 0; i < n_streams; ++i) {
+            if ((aiff->plain[i] != 0) != as_is) continue;
+            const sk_aiff_tick_stream &a = aiff->as[i];
+            const size_t group = sk_pcm::aiff_group_bytes(a.encoding, a.channels);
+            if (a.encoding == SK_AIFF_IMA4) {
+                sk::AiffImaStream st{};
+                st.first_unit = (uint32_t)ima_units.size(), st.n_units = a.n_units, st.channels = a.channels;
+                for (int c = 0; c < 2; ++c) st.predictor[c] = a.ima_state[c].predictor, st.step_index[c] = a.ima_state[c].step_index;
+                imas.push_back(st);
+                ima_of.push_back(i);
+            }
+            for (uint32_t u = 0; u < a.n_units; ++u) {
+                const sk_pcm_unit &un = aiff->src_units[pc[i].first + u];
+                if (a.encoding == SK_AIFF_IMA4) {
+                    ima_units.push_back(sk::AiffImaUnit{d_src + un.byte_offset, dst_of(i, u), (uint32_t)(un.byte_len / group), 0});
+                } else {
+                    const uint32_t samples = (uint32_t)(un.byte_len / group);
+                    elems.push_back(sk::AiffElemJob{d_src + un.byte_offset, dst_of(i, u), samples, a.encoding});
+                    max_samples = std::max(max_samples, samples);
+                }
+            }
+        }
+        if (!elems.empty()) {
+            const sk::AiffElemJob *d_jobs = nullptr;
+            SK_HIP(aux.put(elems, e->stream, &d_jobs), "upload tick aiff jobs");
+            SK_HIP(sk::launch_aiff_elem(d_jobs, (uint32_t)elems.size(), max_samples, e->stream), "tick aiff decode");
+        }
+        if (!imas.empty()) {
+            const sk::AiffImaStream *d_streams = nullptr;
+            const sk::AiffImaUnit *d_units = nullptr;
+            uint32_t *d_states = nullptr;
+            const std::vector<uint32_t> zeros(imas.size() * 2, 0);
+            SK_HIP(aux.put(imas, e->stream, &d_streams), "upload tick aiff ima4 streams");
+            SK_HIP(aux.put(ima_units, e->stream, &d_units), "upload tick aiff ima4 units");
+            SK_HIP(aux.put_rw(zeros, e->stream, &d_states), "upload tick aiff ima4 states");
+            SK_HIP(sk::launch_aiff_ima4(d_streams, (uint32_t)imas.size(), d_units, d_states, e->stream), "tick aiff ima4 decode");
+            // the states come back through the arena's pinned mirror; they are read behind the tick's last wait
+            const uint32_t *h_states = (const uint32_t *)(aux.host + ((const uint8_t *)d_states - aux.base));
+            SK_HIP(hipMemcpyAsync((void *)h_states, d_states, zeros.size() * 4, hipMemcpyDeviceToHost, e->stream), "D2H tick aiff ima4 states");
+            aiff_states.push_back({h_states, std::move(ima_of)});
+        }
+        return SK_OK;
+    };
+    if (aiff) {
+        SK_HIP(e->tick_aiff.reserve(aiff->decoded_len + 64), "alloc tick aiff decoded");
+        uint8_t *d_dec = (uint8_t *)e->tick_aiff.p;
+        rc = aiff_decode(false, [&](uint32_t i, uint32_t u) { return d_dec + units[pc[i].first + u].byte_offset; });
+        if (rc != SK_OK) return rc;
+        d_in = d_dec;
+    }
 
     // ---- streaming resamplers: k_pcm_ingest in the place of the row copies ----
     float *d_res = nullptr;
@@ -4771,6 +4850,7 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
         cursor += ((size_t)o.bytes + 15) & ~(size_t)15;
         return &o;
     };
+    std::vector<uint64_t> aiff_out(aiff ? n_units : 0, 0);  // AIFF streams delivered as decoded: where each unit's record lies in d_out
     // first pass sizes the output, second creates the jobs (the device buffer may move when it grows)
     for (int pass = 0; pass < 2; ++pass) {
         n_rec = 0;
@@ -4791,7 +4871,16 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
                 wides[kind].push_back(j);
                 max_wide_frames[kind] = std::max(max_wide_frames[kind], frames);
             };
-            if (!t.resample) {
+            if (aiff && aiff->plain[i]) {  // the decode writes these records itself, behind the passes
+                for (uint32_t u = 0; u < t.n_units; ++u) {
+                    const uint32_t len = units[c.first + u].byte_len;
+                    sk_tick_output *o = emit(i, len / c.frame_bytes, c, t.out_bits);
+                    if (!o) return SK_ERR_INVALID_ARG;
+                    cursor += (((size_t)len + 15) & ~(size_t)15) - (((size_t)o->bytes + 15) & ~(size_t)15);  // every sample of the unit, a last incomplete frame included
+                    o->bytes = len;
+                    if (pass) aiff_out[c.first + u] = o->byte_offset;
+                }
+            } else if (!t.resample) {
                 for (uint32_t u = 0; u < t.n_units; ++u) {
                     const sk_pcm_unit &un = units[c.first + u];
                     const uint32_t frames = un.byte_len / c.frame_bytes;
@@ -4832,6 +4921,10 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
             d_out = (uint8_t *)e->tick_out.p;
         }
     }
+    if (aiff) {
+        rc = aiff_decode(true, [&](uint32_t i, uint32_t u) { return d_out + aiff_out[pc[i].first + u]; });
+        if (rc != SK_OK) return rc;
+    }
     if (!directs.empty()) {
         const sk::PcmDirectJob *d_jobs = nullptr;
         SK_HIP(aux.put(directs, e->stream, &d_jobs), "upload tick pcm direct jobs");
@@ -4861,6 +4954,9 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
     }
     rc = wait_stream(e, "tick (pcm): waiting for the device at the end of the tick");
     if (rc != SK_OK) return rc;
+    for (const auto &got : aiff_states)
+        for (size_t k = 0; k < got.second.size(); ++k)
+            aiff->states[2 * got.second[k]] = got.first[2 * k], aiff->states[2 * got.second[k] + 1] = got.first[2 * k + 1];
     if (bounce) std::memcpy(out, bounce, cursor);
     *n_outs = n_rec;
     if (out_bytes) *out_bytes = cursor;
@@ -4869,14 +4965,15 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
 
 // tick_pcm_body under the engine's lock; the resamplers' host bookkeeping is put back when it fails, as tick_impl_locked does
 int tick_pcm_impl(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
-                  size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) {
+                  size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
+                  AiffTick *aiff = nullptr) {
     if (!e) return SK_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(e->mu);
     TickWhere where(e);
     RsSaved saved;
     for (uint32_t i = 0; ts && i < n_streams; ++i)
         if (ts[i].resample) saved.add(e, ts[i].stream);
-    const int rc = tick_pcm_body(e, ts, n_streams, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes);
+    const int rc = tick_pcm_body(e, ts, n_streams, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, aiff);
     if (rc != SK_OK) {
         saved.restore(e);
         if (n_outs) *n_outs = 0;
@@ -4885,6 +4982,47 @@ int tick_pcm_impl(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
         if (rc != SK_ERR_TIMEOUT) (void)hipStreamSynchronize(e->stream);
     }
     return rc;
+}
+
+// sk_tick_run_aiff / sk_tick_aiff_out_bound_on: checks the AIFF table and derives what the PCM tick's body works on -- per stream a
+// little-endian source of the contract's format, per unit where its decoded PCM lies (16-byte aligned, unit after unit).
+struct AiffDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;
+    AiffTick tick;
+};
+int aiff_tick_derive(const sk_aiff_tick_stream *as, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, size_t bytes_len, AiffDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.assign(n_units, sk_pcm_unit{});
+    d.tick.as = as, d.tick.src_units = units;
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    uint64_t at = 0, cursor = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_aiff_tick_stream &a = as[i];
+        if (a.encoding >= sk_pcm::kAiffEncodings || a.channels == 0 || a.channels > sk_pcm::kMaxAiffChannels) return SK_ERR_INVALID_ARG;
+        if (a.encoding == SK_AIFF_IMA4 && (a.channels > 2 || a.ima_state[0].step_index > 88 || a.ima_state[1].step_index > 88)) return SK_ERR_INVALID_ARG;
+        const uint32_t bits = sk_pcm::aiff_contract_bits(a.encoding);
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = a.stream, t.n_units = a.n_units, t.channels = a.channels, t.out_bits = a.out_bits, t.out_channels = a.out_channels;
+        t.resample = a.resample, t.flush = a.flush;
+        t.format = (uint8_t)(sk_pcm::aiff_contract_float(a.encoding) ? SK_FMT_F32LE : (bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : SK_FMT_S32LE)));
+        d.tick.plain[i] = !a.resample && a.out_bits == bits && a.out_channels == a.channels;
+        if (at + a.n_units > n_units) return SK_ERR_INVALID_ARG;
+        const uint64_t group = sk_pcm::aiff_group_bytes(a.encoding, a.channels), group_out = sk_pcm::aiff_group_out_bytes(a.encoding, a.channels);
+        for (uint32_t u = 0; u < a.n_units; ++u) {
+            const sk_pcm_unit &un = units[at + u];
+            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len % group) return SK_ERR_INVALID_ARG;
+            if (un.byte_offset > bytes_len || un.byte_len > bytes_len - un.byte_offset) return SK_ERR_INVALID_ARG;
+            const uint64_t decoded = un.byte_len / group * group_out;
+            if (decoded > 0x7fffffffull) return SK_ERR_INVALID_ARG;
+            d.units[at + u] = sk_pcm_unit{cursor, (uint32_t)decoded, 0};
+            cursor += (decoded + 15) & ~15ull;
+        }
+        at += a.n_units;
+    }
+    d.tick.decoded_len = (size_t)cursor;
+    return at == n_units ? SK_OK : SK_ERR_INVALID_ARG;
 }
 
 // sk_tick_run_mixed_md: the MP3 streams' units arrive as frames with main data (ts[i].n_frames = frames of stream i).  A first
@@ -5148,6 +5286,111 @@ int sk_tick_run_pcm(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_strea
     return tick_pcm_impl(e, ts, n_streams, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes);
 } catch (...) {
     return sk::abi_caught("sk_tick_run_pcm");
+}
+
+size_t sk_tick_aiff_out_bound_on(sk_engine *e, const sk_aiff_tick_stream *as, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                 uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!as && n_streams) || (!units && n_units)) return 0;
+    AiffDerived d;
+    if (aiff_tick_derive(as, n_streams, units, n_units, (size_t)-1, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), n_units, max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_aiff_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_aiff(sk_engine *e, sk_aiff_tick_stream *as, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                     size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && !as) || (n_units && (!units || !bytes))) return SK_ERR_INVALID_ARG;
+    AiffDerived d;
+    int rc = aiff_tick_derive(as, n_streams, units, n_units, bytes_len, d);
+    if (rc != SK_OK) {
+        *n_outs = 0;
+        if (out_bytes) *out_bytes = 0;
+        return rc;
+    }
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, &d.tick);
+    if (rc != SK_OK) return rc;
+    for (uint32_t i = 0; i < n_streams; ++i) {  // a failed call leaves the states as they were
+        if (as[i].encoding != SK_AIFF_IMA4 || as[i].n_units == 0) continue;
+        for (int c = 0; c < 2; ++c) {
+            as[i].ima_state[c].predictor = (int16_t)(d.tick.states[2 * i + c] & 0xffff);
+            as[i].ima_state[c].step_index = (uint8_t)(d.tick.states[2 * i + c] >> 16);
+        }
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_aiff");
+}
+
+// one stream's bytes, one call: a table of one job in front of the same kernels
+static int aiff_decode_one(sk_engine *e, int encoding, uint32_t channels, const uint8_t *bytes, bool on_device, size_t len, uint8_t *out, size_t out_cap,
+                           size_t *out_len, sk_aiff_ima_state *state) {
+    if (!e || !out_len || encoding < 0 || encoding >= sk_pcm::kAiffEncodings || channels == 0 || channels > sk_pcm::kMaxAiffChannels) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    const bool ima = encoding == SK_AIFF_IMA4;
+    if (ima && (channels > 2 || !state || state[0].step_index > 88 || state[1].step_index > 88)) return SK_ERR_INVALID_ARG;
+    const size_t group = sk_pcm::aiff_group_bytes(encoding, channels), group_out = sk_pcm::aiff_group_out_bytes(encoding, channels);
+    if (len % group || len / group > 0x7fffffffu || (len && (!bytes || !out))) return SK_ERR_INVALID_ARG;
+    const size_t groups = len / group, need = groups * group_out;
+    if (need > out_cap) return SK_ERR_INVALID_ARG;
+    if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15)) return SK_ERR_INVALID_ARG;
+    if (groups == 0) return SK_OK;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    const size_t table_at = on_device ? 0 : (len + 15) & ~(size_t)15;
+    SK_HIP(e->in_buf.reserve(table_at + 256), "alloc staging");
+    const uint8_t *d_src = bytes;
+    uint8_t *d_dst = out;
+    if (!on_device) {
+        SK_HIP(e->out_buf.reserve(need), "alloc staging");
+        SK_HIP(hipMemcpyAsync(e->in_buf.p, bytes, len, hipMemcpyHostToDevice, e->stream), "H2D aiff");
+        d_src = (const uint8_t *)e->in_buf.p, d_dst = (uint8_t *)e->out_buf.p;
+    }
+    uint8_t *table = (uint8_t *)e->in_buf.p + table_at;
+    uint32_t got[2] = {0, 0};
+    if (ima) {
+        struct { sk::AiffImaStream st; sk::AiffImaUnit un; uint32_t states[2]; uint32_t pad[2]; } t{};
+        t.st.first_unit = 0, t.st.n_units = 1, t.st.channels = (uint8_t)channels;
+        for (int c = 0; c < 2; ++c) t.st.predictor[c] = state[c].predictor, t.st.step_index[c] = state[c].step_index;
+        t.un = sk::AiffImaUnit{d_src, d_dst, (uint32_t)groups, 0};
+        SK_HIP(hipMemcpyAsync(table, &t, sizeof t, hipMemcpyHostToDevice, e->stream), "H2D aiff ima4 table");
+        SK_HIP(hipStreamSynchronize(e->stream), "aiff table sync");  // t leaves scope with this block
+        SK_HIP(sk::launch_aiff_ima4((const sk::AiffImaStream *)table, 1, (const sk::AiffImaUnit *)(table + offsetof(decltype(t), un)),
+                                    (uint32_t *)(table + offsetof(decltype(t), states)), e->stream), "launch aiff ima4");
+        SK_HIP(hipMemcpyAsync(got, table + offsetof(decltype(t), states), sizeof got, hipMemcpyDeviceToHost, e->stream), "D2H aiff ima4 states");
+    } else {
+        const sk::AiffElemJob job{d_src, d_dst, (uint32_t)groups, (uint32_t)encoding};
+        SK_HIP(hipMemcpyAsync(table, &job, sizeof job, hipMemcpyHostToDevice, e->stream), "H2D aiff job");
+        SK_HIP(hipStreamSynchronize(e->stream), "aiff table sync");
+        SK_HIP(sk::launch_aiff_elem((const sk::AiffElemJob *)table, 1, (uint32_t)groups, e->stream), "launch aiff decode");
+    }
+    if (!on_device) SK_HIP(hipMemcpyAsync(out, d_dst, need, hipMemcpyDeviceToHost, e->stream), "D2H aiff");
+    SK_HIP(hipStreamSynchronize(e->stream), "aiff sync");
+    if (ima)
+        for (int c = 0; c < 2; ++c) state[c].predictor = (int16_t)(got[c] & 0xffff), state[c].step_index = (uint8_t)(got[c] >> 16);
+    *out_len = need;
+    return SK_OK;
+}
+
+int sk_aiff_decode(sk_engine *e, int encoding, uint32_t channels, const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap, size_t *out_len,
+                   sk_aiff_ima_state *state) try {
+    sk::abi_enter();
+    return aiff_decode_one(e, encoding, channels, bytes, false, len, out, out_cap, out_len, state);
+} catch (...) {
+    return sk::abi_caught("sk_aiff_decode");
+}
+
+int sk_aiff_decode_dev(sk_engine *e, int encoding, uint32_t channels, const uint8_t *d_bytes, size_t len, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                       sk_aiff_ima_state *state) try {
+    sk::abi_enter();
+    return aiff_decode_one(e, encoding, channels, d_bytes, true, len, d_out, out_cap, out_len, state);
+} catch (...) {
+    return sk::abi_caught("sk_aiff_decode_dev");
 }
 
 int sk_aac_entropy_decode(sk_engine *e, const uint32_t *streams, const uint32_t *units_per_stream, uint32_t n_streams,

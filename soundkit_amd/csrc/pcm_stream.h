@@ -2,6 +2,7 @@
 //
 //   WavStream     = WavStreamProcessor::add with install_fmt / install_ds64 (soundkit/src/wav.rs:95-324)
 //   RawPcmStream  = RawPcmStreamProcessor::add / flush (soundkit/src/raw_pcm.rs:150-190)
+//   AiffStream    = AiffDecoder::add without its per-sample work (soundkit-aiff/src/lib.rs:93-475); see the class
 //
 // Both take a stream's bytes in whatever chunks they arrive and give back, per call, at most one PIECE: the whole PCM frames
 // available now.  A piece is a contiguous range of the stream (the bytes buffered since the last piece plus part of this chunk), so
@@ -12,8 +13,11 @@
 // Limits: a chunk of at most 4 MiB (MAX_WAV_INPUT_CHUNK_BYTES, wav.rs:19; MAX_INPUT_CHUNK_BYTES, raw_pcm.rs), `fmt ` / `ds64`
 // chunks of at most 4096 bytes (MAX_WAV_FMT_BYTES, wav.rs:20).
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -287,6 +291,423 @@ private:
     std::vector<uint8_t> buf_;
     size_t pos_ = 0;
     uint64_t base_ = 0;
+};
+
+// AiffStream = AiffDecoder::add / parse_available / parse_stream_info / parse_extended_sample_rate (soundkit-aiff/src/lib.rs:93-475)
+// up to, and without, decode_stream_bytes: one add gives at most one piece of whole SOURCE-ENCODED sample groups (a sample; for IMA4
+// 34 bytes per channel) and the stream's description; the per-sample work is the tick's (aiff_decode.hip).  A piece may join the
+// retained incomplete group with this chunk's bytes, so it lives in a buffer of its own; its stream_offset counts sound bytes.
+// An empty add is the finalising one.  After an error every further add repeats it.
+enum AiffEncoding : uint8_t {  // = enum sk_aiff_encoding
+    kAiffU8, kAiffS8, kAiffS16BE, kAiffS16LE, kAiffS24BE, kAiffS32BE, kAiffS32LE, kAiffF32BE, kAiffF64BE, kAiffUlaw, kAiffAlaw, kAiffIma4,
+    kAiffEncodings
+};
+constexpr size_t kMaxAiffCommBytes = 4096;
+constexpr uint32_t kMaxAiffChannels = 32;
+
+// bytes of one encoded sample group, and of what it decodes to (the output contract, lib.rs:41-54)
+inline size_t aiff_group_bytes(int enc, uint32_t channels) {
+    switch (enc) {
+    case kAiffU8: case kAiffS8: case kAiffUlaw: case kAiffAlaw: return 1;
+    case kAiffS16BE: case kAiffS16LE: return 2;
+    case kAiffS24BE: return 3;
+    case kAiffS32BE: case kAiffS32LE: case kAiffF32BE: return 4;
+    case kAiffF64BE: return 8;
+    default: return (size_t)34 * channels;
+    }
+}
+inline uint32_t aiff_contract_bits(int enc) { return enc == kAiffS24BE ? 24 : (enc >= kAiffS32BE && enc <= kAiffF64BE ? 32 : 16); }
+inline bool aiff_contract_float(int enc) { return enc == kAiffF32BE || enc == kAiffF64BE; }
+inline size_t aiff_group_out_bytes(int enc, uint32_t channels) {
+    return enc == kAiffIma4 ? (size_t)128 * channels : aiff_contract_bits(enc) / 8;
+}
+
+class AiffStream {
+public:
+    bool add(const uint8_t *chunk, size_t len, Piece &piece, std::string &err) {
+        piece = Piece{};
+        if (failed_) {
+            err = error_;
+            return false;
+        }
+        if (finished_) return true;
+        if (len > kMaxInputChunkBytes) {  // (the reference's decoder stays usable after this one; so does this)
+            err = "AIFF input chunk exceeds the " + std::to_string(kMaxInputChunkBytes) + " byte streaming budget";
+            return false;
+        }
+        audio_base_ += out_.size();
+        out_.clear();
+        if (len) buf_.insert(buf_.end(), chunk, chunk + len);
+        if (!parse_available(err)) return fail(err);
+        if (len == 0) {
+            if (state_ != Done) return fail(err = "truncated AIFF stream in state " + debug_state());
+            if (!pending_.empty()) return fail(err = "AIFF sound data ends inside an encoded sample group");
+            finished_ = true;
+        }
+        if (out_.empty()) return true;
+        if (!have_info_) return fail(err = "AIFF PCM arrived before COMM metadata");
+        piece.data = out_.data();
+        piece.len = out_.size();
+        piece.stream_offset = audio_base_;
+        return true;
+    }
+
+    size_t buffered_bytes() const { return buf_.size() + pending_.size(); }
+    bool have_info() const { return have_info_; }
+    uint32_t sample_rate() const { return rate_; }
+    uint32_t channels() const { return channels_; }
+    int encoding() const { return enc_; }
+    uint32_t bits() const { return have_info_ ? aiff_contract_bits(enc_) : 0; }
+    bool is_float() const { return have_info_ && aiff_contract_float(enc_); }
+
+private:
+    enum State { FormHeader, ChunkHeader, Comm, SsndHeader, SsndOffset, Audio, Skip, Padding, Done };
+    static uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
+    static uint32_t be32(const uint8_t *p) { return (be16(p) << 16) | be16(p + 2); }
+    static std::string lossy4(const uint8_t *p) {  // String::from_utf8_lossy of four bytes
+        std::string s;
+        for (int i = 0; i < 4;) {
+            const uint8_t c = p[i];
+            int n = c < 0x80 ? 1 : (c >= 0xc2 && c <= 0xdf ? 2 : (c >= 0xe0 && c <= 0xef ? 3 : (c >= 0xf0 && c <= 0xf4 ? 4 : 0)));
+            bool ok = n > 0;
+            int have = 1;  // bytes of the maximal valid prefix of this sequence (one U+FFFD replaces it)
+            if (n > 1) {
+                for (int k = 1; k < n; ++k) {
+                    if (i + k >= 4) { ok = false; break; }
+                    const uint8_t d = p[i + k];
+                    uint8_t lo = 0x80, hi = 0xbf;
+                    if (k == 1) {
+                        if (c == 0xe0) lo = 0xa0;
+                        if (c == 0xed) hi = 0x9f;
+                        if (c == 0xf0) lo = 0x90;
+                        if (c == 0xf4) hi = 0x8f;
+                    }
+                    if (d < lo || d > hi) { ok = false; break; }
+                    have += 1;
+                }
+            }
+            if (ok) {
+                s.append((const char *)p + i, (size_t)n);
+                i += n;
+            } else {
+                s += "\xef\xbf\xbd";
+                i += have;
+            }
+        }
+        return s;
+    }
+    bool fail(const std::string &text) {
+        failed_ = true;
+        error_ = text;
+        return false;
+    }
+    static const char *tf(bool b) { return b ? "true" : "false"; }
+    std::string debug_state() const {  // {:?} of ParseState
+        const std::string pad = std::string(", padded: ") + tf(padded_) + " }";
+        switch (state_) {
+        case FormHeader: return "FormHeader";
+        case ChunkHeader: return "ChunkHeader";
+        case Comm: return "Comm { size: " + std::to_string(remaining_) + pad;
+        case SsndHeader: return "SsndHeader { remaining: " + std::to_string(remaining_) + pad;
+        case SsndOffset: return "SsndOffset { skip: " + std::to_string(skip_) + ", remaining_audio: " + std::to_string(remaining_) + pad;
+        case Audio: return "Audio { remaining: " + std::to_string(remaining_) + pad;
+        case Skip: return "Skip { remaining: " + std::to_string(remaining_) + pad;
+        case Padding: return "Padding";
+        default: return "Done";
+        }
+    }
+    bool consume_form(uint64_t n, std::string &err) {
+        if (n > form_remaining_) {
+            err = "AIFF parser crossed the FORM boundary";
+            return false;
+        }
+        form_remaining_ -= n;
+        return true;
+    }
+    State next_chunk_state() const { return form_remaining_ == 0 ? Done : ChunkHeader; }
+    void finish_chunk(bool padded) {
+        const State next = next_chunk_state();
+        if (padded) padding_next_ = next, state_ = Padding;
+        else state_ = next;
+    }
+
+    // {value} of an f64 as Rust's Display prints it: the shortest digits that read back, never an exponent
+    static std::string display_f64(double v) {
+        if (v != v) return "NaN";
+        if (v == HUGE_VAL) return "inf";
+        if (v == 0) return "0";
+        char text[40];
+        int prec = 0;
+        for (; prec < 17; ++prec) {
+            std::snprintf(text, sizeof text, "%.*e", prec, v);
+            if (std::strtod(text, nullptr) == v) break;
+        }
+        std::string digits;
+        const char *e = std::strchr(text, 'e');
+        for (const char *p = text; p < e; ++p)
+            if (*p != '.') digits += *p;
+        const int exp10 = std::atoi(e + 1);  // value = d.ddd * 10^exp10
+        while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+        std::string s;
+        if (exp10 < 0) {
+            s = "0." + std::string((size_t)(-exp10 - 1), '0') + digits;
+        } else if ((size_t)exp10 + 1 >= digits.size()) {
+            s = digits + std::string((size_t)exp10 + 1 - digits.size(), '0');
+        } else {
+            s = digits.substr(0, (size_t)exp10 + 1) + "." + digits.substr((size_t)exp10 + 1);
+        }
+        return s;
+    }
+
+    bool parse_rate(const uint8_t *d, std::string &err) {  // parse_extended_sample_rate + parse_sample_rate
+        const uint32_t exponent_word = be16(d);
+        if (exponent_word & 0x8000) {
+            err = "AIFF sample rate is negative";
+            return false;
+        }
+        const uint32_t exponent = exponent_word & 0x7fff;
+        const uint64_t mantissa = ((uint64_t)be32(d + 2) << 32) | be32(d + 6);
+        if (exponent == 0 && mantissa == 0) {
+            err = "AIFF sample rate is zero";
+            return false;
+        }
+        if (exponent == 0x7fff) {
+            err = "AIFF sample rate is not finite";
+            return false;
+        }
+        // 2f64.powi(n): exact powers of two by repeated multiplication, and 1 / 2^-n for n < 0 -- inf beyond 2^1023, so 0 below 2^-1023
+        const int n = (int)exponent - 16383 - 63;
+        const double scale = n > 1023 ? HUGE_VAL : (n < -1023 ? 0.0 : std::ldexp(1.0, n));
+        const double value = (double)mantissa * scale;
+        if (!(value == value) || value == HUGE_VAL || value <= 0.0 || value > 4294967295.0) {
+            err = "Invalid AIFF sample rate: " + display_f64(value);
+            return false;
+        }
+        rate_ = (uint32_t)std::round(value);
+        return true;
+    }
+
+    bool parse_stream_info(const uint8_t *d, size_t n, std::string &err) {
+        if (n < 18) {
+            err = "AIFF COMM is shorter than 18 bytes";
+            return false;
+        }
+        const uint32_t channels = be16(d);
+        if (channels < 1 || channels > kMaxAiffChannels) {
+            err = "invalid AIFF channel count: " + std::to_string(channels);
+            return false;
+        }
+        const uint32_t sample_size = be16(d + 6);
+        if (!parse_rate(d + 8, err)) return false;
+        int enc = -1;
+        auto signed_be = [&]() {
+            if (sample_size >= 1 && sample_size <= 8) enc = kAiffS8;
+            else if (sample_size <= 16 && sample_size >= 9) enc = kAiffS16BE;
+            else if (sample_size <= 24 && sample_size >= 17) enc = kAiffS24BE;
+            else if (sample_size <= 32 && sample_size >= 25) enc = kAiffS32BE;
+            else err = "unsupported AIFF sample size: " + std::to_string(sample_size);
+            return enc >= 0;
+        };
+        if (!aifc_) {
+            if (!signed_be()) return false;
+        } else {
+            if (n < 22) {
+                err = "AIFF-C COMM has no compression type";
+                return false;
+            }
+            static const struct { const char *tag; int enc; } tags[] = {
+                {"raw ", kAiffU8}, {"twos", kAiffS16BE}, {"sowt", kAiffS16LE}, {"in24", kAiffS24BE}, {"in32", kAiffS32BE}, {"23ni", kAiffS32LE},
+                {"FL32", kAiffF32BE}, {"fl32", kAiffF32BE}, {"FL64", kAiffF64BE}, {"fl64", kAiffF64BE}, {"ULAW", kAiffUlaw}, {"ulaw", kAiffUlaw},
+                {"ALAW", kAiffAlaw}, {"alaw", kAiffAlaw}, {"ima4", kAiffIma4}};
+            if (std::memcmp(d + 18, "NONE", 4) == 0) {
+                if (!signed_be()) return false;
+            } else {
+                for (const auto &t : tags)
+                    if (std::memcmp(d + 18, t.tag, 4) == 0) enc = t.enc;
+                if (enc < 0) {
+                    err = "unsupported AIFF-C compression type: " + lossy4(d + 18);
+                    return false;
+                }
+            }
+        }
+        if (enc == kAiffIma4 && channels > 2) {
+            err = "AIFF-C IMA4 supports at most two channels";
+            return false;
+        }
+        channels_ = channels, enc_ = enc, have_info_ = true;
+        return true;
+    }
+
+    // the sound bytes of one Audio step: whole groups go to the piece, the incomplete last one is retained
+    void take_audio(const uint8_t *p, size_t n) {
+        const size_t group = aiff_group_bytes(enc_, channels_);
+        if (!pending_.empty()) {
+            const size_t need = group - pending_.size();
+            const size_t k = n < need ? n : need;
+            pending_.insert(pending_.end(), p, p + k);
+            p += k, n -= k;
+            if (pending_.size() < group) return;
+            out_.insert(out_.end(), pending_.begin(), pending_.end());
+            pending_.clear();
+        }
+        const size_t whole = n / group * group;
+        out_.insert(out_.end(), p, p + whole);
+        pending_.assign(p + whole, p + n);
+    }
+
+    bool parse_available(std::string &err) {
+        size_t position = 0;
+        for (;;) {
+            const size_t available = buf_.size() - position;
+            const uint8_t *b = buf_.data() + position;
+            bool stop = false;
+            switch (state_) {
+            case FormHeader: {
+                if (available < 12) { stop = true; break; }
+                if (std::memcmp(b, "FORM", 4) != 0) {
+                    err = "AIFF stream does not start with FORM";
+                    return false;
+                }
+                const uint32_t form_size = be32(b + 4);
+                if (form_size < 4) {
+                    err = "AIFF FORM is shorter than its type field";
+                    return false;
+                }
+                if (std::memcmp(b + 8, "AIFF", 4) == 0) aifc_ = false;
+                else if (std::memcmp(b + 8, "AIFC", 4) == 0) aifc_ = true;
+                else {
+                    err = "unsupported FORM type " + lossy4(b + 8);
+                    return false;
+                }
+                form_remaining_ = form_size - 4;
+                position += 12;
+                state_ = next_chunk_state();
+                break;
+            }
+            case ChunkHeader: {
+                if (form_remaining_ == 0) { state_ = Done; break; }
+                if (form_remaining_ < 8) {
+                    err = "AIFF FORM ends inside a chunk header";
+                    return false;
+                }
+                if (available < 8) { stop = true; break; }
+                const uint32_t size = be32(b + 4);
+                if (!consume_form(8, err)) return false;
+                position += 8;
+                const bool padded = (size & 1) != 0;
+                if ((uint64_t)size + (padded ? 1 : 0) > form_remaining_) {
+                    err = "AIFF chunk " + lossy4(b) + " exceeds the FORM boundary";
+                    return false;
+                }
+                padded_ = padded;
+                remaining_ = size;
+                if (std::memcmp(b, "COMM", 4) == 0) {
+                    if (size > kMaxAiffCommBytes) {
+                        err = "AIFF COMM exceeds the " + std::to_string(kMaxAiffCommBytes) + " byte budget";
+                        return false;
+                    }
+                    state_ = Comm;
+                } else if (std::memcmp(b, "SSND", 4) == 0) {
+                    if (size < 8) {
+                        err = "AIFF SSND is shorter than its header";
+                        return false;
+                    }
+                    if (!have_info_) {
+                        err = "AIFF SSND appears before COMM";
+                        return false;
+                    }
+                    state_ = SsndHeader;
+                } else {
+                    state_ = Skip;
+                }
+                break;
+            }
+            case Comm: {
+                const size_t size = (size_t)remaining_;
+                if (available < size) { stop = true; break; }
+                if (!parse_stream_info(b, size, err)) return false;
+                if (!consume_form(size, err)) return false;
+                position += size;
+                finish_chunk(padded_);
+                break;
+            }
+            case SsndHeader: {
+                if (available < 8) { stop = true; break; }
+                const uint64_t offset = be32(b);
+                const uint64_t audio_and_offset = remaining_ - 8;
+                if (offset > audio_and_offset) {
+                    err = "AIFF SSND offset exceeds its chunk";
+                    return false;
+                }
+                if (!consume_form(8, err)) return false;
+                position += 8;
+                skip_ = offset;
+                remaining_ = audio_and_offset - offset;
+                state_ = SsndOffset;
+                break;
+            }
+            case SsndOffset: {
+                const size_t take = (size_t)((uint64_t)available < skip_ ? available : skip_);
+                position += take;
+                if (!consume_form(take, err)) return false;
+                skip_ -= take;
+                if (skip_ == 0) state_ = Audio;
+                else stop = true;
+                break;
+            }
+            case Audio: {
+                const size_t take = (size_t)((uint64_t)available < remaining_ ? available : remaining_);
+                take_audio(b, take);
+                position += take;
+                if (!consume_form(take, err)) return false;
+                remaining_ -= take;
+                if (remaining_ == 0) {
+                    if (!pending_.empty()) {
+                        err = "AIFF SSND ends inside an encoded sample group";
+                        return false;
+                    }
+                    finish_chunk(padded_);
+                } else {
+                    stop = true;
+                }
+                break;
+            }
+            case Skip: {
+                const size_t take = (size_t)((uint64_t)available < remaining_ ? available : remaining_);
+                position += take;
+                if (!consume_form(take, err)) return false;
+                remaining_ -= take;
+                if (remaining_ == 0) finish_chunk(padded_);
+                else stop = true;
+                break;
+            }
+            case Padding:
+                if (available == 0) { stop = true; break; }
+                position += 1;
+                if (!consume_form(1, err)) return false;
+                state_ = padding_next_;
+                break;
+            case Done:
+                if (available != 0) {
+                    err = "AIFF stream has bytes after the FORM boundary";
+                    return false;
+                }
+                stop = true;
+                break;
+            }
+            if (stop) break;
+        }
+        buf_.erase(buf_.begin(), buf_.begin() + (std::ptrdiff_t)position);
+        return true;
+    }
+
+    State state_ = FormHeader, padding_next_ = ChunkHeader;
+    std::vector<uint8_t> buf_, pending_, out_;
+    uint64_t form_remaining_ = 0, remaining_ = 0, skip_ = 0, audio_base_ = 0;
+    bool padded_ = false, aifc_ = false, have_info_ = false, finished_ = false, failed_ = false;
+    uint32_t rate_ = 0, channels_ = 0;
+    int enc_ = 0;
+    std::string error_;
 };
 
 }  // namespace sk_pcm

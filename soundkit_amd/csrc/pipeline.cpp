@@ -80,6 +80,12 @@ struct PStream {
     // WAV / raw PCM streams (FormatDecoder::Wav / RawPcm, lib.rs:2292-2297): the stream processor, and what its first piece decided
     std::unique_ptr<sk_pcm::WavStream> wav;
     std::unique_ptr<sk_pcm::RawPcmStream> raw;
+    // AIFF / AIFF-C streams (FormatDecoder::Aiff): the container walker; its pieces are source-encoded, the AIFF tick decodes them.
+    // The IMA4 carry belongs to the submission thread: it goes into the stream's row when its tick runs and comes back from it.
+    std::unique_ptr<sk_pcm::AiffStream> aiff;
+    uint8_t aiff_enc = 0;
+    bool aiff_plain = false;  // nothing to change behind the decode
+    sk_aiff_ima_state aiff_ima[2] = {};
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -87,8 +93,8 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2;
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -142,6 +148,10 @@ struct Batch {
     std::vector<sk_pcm_tick_stream> pcm_ts;
     std::vector<sk_pcm_unit> pcm_units;
     std::vector<uint32_t> pcm_entry;
+    // AIFF streams' units (sk_tick_run_aiff), staged in pcm_bytes beside the PCM streams' pieces; a table of their own
+    std::vector<sk_aiff_tick_stream> aiff_ts;
+    std::vector<sk_pcm_unit> aiff_units;
+    std::vector<uint32_t> aiff_entry;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -167,6 +177,9 @@ struct Batch {
         pcm_ts.clear();
         pcm_units.clear();
         pcm_entry.clear();
+        aiff_ts.clear();
+        aiff_units.clear();
+        aiff_entry.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -285,6 +298,7 @@ void release_device_side(sk_lane *p, PStream &s) {
         s.mp3_reservoir.shrink_to_fit();
         s.wav.reset();
         s.raw.reset();
+        s.aiff.reset();
     }
     if (engine_stream != kNoStream) (void)sk_stream_close(p->engine, engine_stream);  // also drops its resampler
     if (fe) sk_aac_decoder_destroy(fe);
@@ -366,6 +380,13 @@ uint8_t sniff_codec(const uint8_t *d, size_t n) {
         if (n < 12) return 0;
         if (std::memcmp(d + 8, "WAVE", 4) == 0) return kCodecWav;
     } else if (n > 0 && n < 4 && (std::memcmp(d, "RIFF", n) == 0 || std::memcmp(d, "RF64", n) == 0)) {
+        return 0;
+    }
+    // FORM....AIFF / FORM....AIFC -> AIFF (AudioType::Aiff, lib.rs:3099-3102); the same wait
+    if (n >= 4 && std::memcmp(d, "FORM", 4) == 0) {
+        if (n < 12) return 0;
+        if (std::memcmp(d + 8, "AIFF", 4) == 0 || std::memcmp(d + 8, "AIFC", 4) == 0) return kCodecAiff;
+    } else if (n > 0 && n < 4 && std::memcmp(d, "FORM", n) == 0) {
         return 0;
     }
     if (n >= 3 && d[0] == 'I' && d[1] == 'D' && d[2] == '3') return kCodecMp3;
@@ -641,7 +662,10 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     };
     uint32_t rate, channels, bits;
     bool is_float, big_endian = false;
-    if (s.wav) {
+    if (s.aiff) {  // what the decoder emits (the output contract), not what the file holds: apply_output_options sees only that
+        rate = s.aiff->sample_rate(), channels = s.aiff->channels(), bits = s.aiff->bits(), is_float = s.aiff->is_float();
+        s.aiff_enc = (uint8_t)s.aiff->encoding();
+    } else if (s.wav) {
         rate = s.wav->sample_rate(), channels = s.wav->channels(), bits = s.wav->bits(), is_float = s.wav->is_float();
     } else {
         const int f = s.raw_format.format;
@@ -658,8 +682,18 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     const uint32_t target_rate = s.opt.output_sample_rate ? s.opt.output_sample_rate : rate;
     const uint32_t target_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : bits;
     const uint32_t target_channels = s.opt.output_channels ? s.opt.output_channels : channels;
+    const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     if (target_rate == rate && target_bits == bits && target_channels == channels) {
-        s.pcm_route = kPcmFast;
+        // sowt / 23ni are the contract's bytes already; every other encoding has per-sample work, which is the tick's
+        if (!s.aiff || s.aiff_enc == SK_AIFF_S16LE || s.aiff_enc == SK_AIFF_S32LE) {
+            s.pcm_route = kPcmFast;
+            return true;
+        }
+        if (!hooks.tick_aiff || !hooks.tick_aiff_out_bound) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: AIFF decoding needs the device tick, which this build lacks");
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmAiffTick;
+        s.aiff_plain = true;
         return true;
     }
     // audio_data_to_f32_channels (lib.rs:3563-3617) and exact_signed_pcm_to_i16 take 16 / 24 / 32-bit samples
@@ -667,10 +701,10 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     if (bits != 16 && bits != 24 && bits != 32)
         return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
     // 3 ... 8 channels: the tick takes them on an engine whose pool of wide streams was reserved (sk_engine_enable_wide_pcm)
-    const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     if (channels > SK_MAX_CHANNELS && (channels > SK_MAX_PCM_CHANNELS || !hooks.wide_pcm_streams || hooks.wide_pcm_streams(p->engine) == 0))
         return fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
-    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
+    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound || (s.aiff && (!hooks.tick_aiff || !hooks.tick_aiff_out_bound)))
+        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
     s.pcm_fmt = (uint8_t)((bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : (is_float ? SK_FMT_F32LE : SK_FMT_S32LE))) + (big_endian ? 1 : 0));
     int rc = ensure_pcm(p);
     if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
@@ -681,7 +715,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = kPcmTick;
+    s.pcm_route = s.aiff ? kPcmAiffTick : kPcmTick;
     return true;
 }
 
@@ -701,15 +735,25 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     auto process = [&](const uint8_t *data, size_t len) -> bool {
         sk_pcm::Piece piece;
         std::string err;
-        const bool ok = s.wav ? s.wav->add(data, len, piece, err) : s.raw->add(data, len, piece, err);
+        const bool ok = s.aiff ? s.aiff->add(data, len, piece, err) : (s.wav ? s.wav->add(data, len, piece, err) : s.raw->add(data, len, piece, err));
         if (!ok) {
             fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
             return false;
         }
         if (piece.len == 0) return true;
         if (!s.pcm_route && !pcm_open(p, s, r)) return false;
+        // (an AIFF piece is source-encoded: its frames follow from its sample groups)
         const uint32_t frame_bytes = (uint32_t)s.pcm_bits / 8 * s.channels;
-        const uint32_t frames = (uint32_t)(piece.len / frame_bytes);
+        const uint32_t frames = s.aiff ? (uint32_t)(piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) * (s.aiff_enc == SK_AIFF_IMA4 ? 64 : 1) /
+                                                    (s.aiff_enc == SK_AIFF_IMA4 ? 1 : s.channels))
+                                       : (uint32_t)(piece.len / frame_bytes);
+        // the decoder emits every complete SAMPLE of an add: a piece may end inside a frame.  Delivered as it is that is what the
+        // reference delivers; its conversions refuse it (audio_data_to_f32_channels, lib.rs:3569-3574)
+        if (s.aiff && !s.aiff_plain && s.pcm_route == kPcmAiffTick && s.aiff_enc != SK_AIFF_IMA4 &&
+            piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) % s.channels != 0) {
+            fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
+            return false;
+        }
         if (s.pcm_route == kPcmFast) {
             Output o;
             o.rate = s.rate, o.frames = frames, o.bits = s.pcm_bits, o.channels = s.channels, o.flags = s.pcm_flags;
@@ -730,10 +774,11 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         }
         return true;
     };
-    if (s.codec == kCodecWav && !s.pcm_detected) {
+    if ((s.codec == kCodecWav || s.codec == kCodecAiff) && !s.pcm_detected) {
         while (s.pending.size() - s.pending_pos < kMinDetectionBytes && !s.saw_eof)
             if (pull_input(s) == 0) return;  // needs more input
-        s.wav.reset(new sk_pcm::WavStream());
+        if (s.codec == kCodecAiff) s.aiff.reset(new sk_pcm::AiffStream());
+        else s.wav.reset(new sk_pcm::WavStream());
         s.pcm_detected = true;
         const uint8_t *d = s.pending.data() + s.pending_pos;
         const size_t n = s.pending.size() - s.pending_pos, first = std::min(n, kMaxDetectionBytes);
@@ -748,6 +793,7 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         if (s.saw_eof) {  // flush_decoder (lib.rs:3139-3169): the framer's partial frame is an error, the resampler is flushed by the tick
             std::string err;
             if (s.raw && !s.raw->flush(err)) fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
+            else if (s.aiff && !process(nullptr, 0)) {}  // the finalising empty add (lib.rs:2426): a truncated stream ends with its text
             else r.eof = true;
             break;
         }
@@ -818,7 +864,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         parse_some_mp3(p, s, limit, r);
         return;
     }
-    if (s.codec == kCodecWav || s.codec == kCodecRawPcm) {
+    if (s.codec == kCodecWav || s.codec == kCodecRawPcm || s.codec == kCodecAiff) {
         parse_some_pcm(p, s, room, r);
         return;
     }
@@ -1102,7 +1148,26 @@ void worker_body(sk_lane *p) {
                 be.pre = std::move(r.pre);
                 t.n_frames = 0;
                 t.flush = 0;
-                if (s.pcm_route == kPcmTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
+                if (s.pcm_route == kPcmAiffTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
+                    pcm_at = b->pcm_used;
+                    b->pcm_used += r.pcm_bytes.size();
+                    sk_aiff_tick_stream at{};
+                    at.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
+                    at.n_units = (uint32_t)r.pcm_units.size();
+                    at.encoding = s.aiff_enc;
+                    at.channels = s.channels;
+                    at.out_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits;
+                    at.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
+                    at.resample = s.resample ? 1 : 0;
+                    at.flush = (r.eof && s.resample) ? 1 : 0;
+                    b->aiff_ts.push_back(at);
+                    be.pcm_row = true;
+                    b->aiff_entry.push_back((uint32_t)b->entries.size());
+                    for (sk_pcm_unit u : r.pcm_units) {
+                        u.byte_offset += pcm_at;
+                        b->aiff_units.push_back(u);
+                    }
+                } else if (s.pcm_route == kPcmTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
                     pcm_at = b->pcm_used;
                     b->pcm_used += r.pcm_bytes.size();
                     sk_pcm_tick_stream pt{};
@@ -1217,13 +1282,16 @@ void submit_body(sk_lane *p) {
             b->entry_row[i] = (uint32_t)b->row_of.size();
             b->row_of.push_back(i);
         }
-        uint32_t max_out = 0, pcm_max_out = 0;
+        uint32_t max_out = 0, pcm_max_out = 0, aiff_max_out = 0;
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
         const sk_mp3_internal::PipelineGpuHooks &pcm_hooks = sk_mp3_internal::pipeline_gpu_hooks();
-        if (!ts.empty() || !b->pcm_ts.empty()) {
+        if (!ts.empty() || !b->pcm_ts.empty() || !b->aiff_ts.empty()) {
             size_t bound = ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out);
+            if (!b->aiff_ts.empty())  // ... and the AIFF tick's behind those
+                bound += 16 + pcm_hooks.tick_aiff_out_bound(p->engine, b->aiff_ts.data(), (uint32_t)b->aiff_ts.size(), b->aiff_units.data(),
+                                                            (uint32_t)b->aiff_units.size(), &aiff_max_out);
             if (!b->pcm_ts.empty())  // the PCM tick's outputs follow the other tick's in the same buffer
                 bound += 16 + pcm_hooks.tick_pcm_out_bound(p->engine, b->pcm_ts.data(), (uint32_t)b->pcm_ts.size(), b->pcm_units.data(),
                                                            (uint32_t)b->pcm_units.size(), &pcm_max_out);
@@ -1245,7 +1313,7 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            if (b->recs.size() < (size_t)max_out + pcm_max_out) b->recs.resize((size_t)max_out + pcm_max_out);
+            if (b->recs.size() < (size_t)max_out + pcm_max_out + aiff_max_out) b->recs.resize((size_t)max_out + pcm_max_out + aiff_max_out);
         }
         if (!ts.empty() && b->rc == SK_OK && !b->mpa_recs.empty()) {
             // Layer I / II frames in this tick: the tick that takes them, with everything else in the lane's form beside them
@@ -1311,6 +1379,34 @@ void submit_body(sk_lane *p) {
                 b->rc = sk_tick_run(p->engine, ts.data(), (uint32_t)ts.size(), b->descs.data(), b->coeffs, n_frames, b->out_pinned,
                                     b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
         }
+        if (b->rc == SK_OK && !b->aiff_ts.empty()) {  // the AIFF streams' tick of this round, behind both
+            const uint32_t first_row = (uint32_t)b->row_of.size();
+            const size_t base = (used + 15) & ~(size_t)15;
+            uint32_t n_aiff_out = 0;
+            size_t aiff_used = 0;
+            // the IMA4 carry of each stream as the ticks before this one left it (this thread alone reads and writes it)
+            for (uint32_t row = 0; row < b->aiff_ts.size(); ++row) {
+                const PStream &s = *p->streams[b->entries[b->aiff_entry[row]].handle];
+                b->aiff_ts[row].ima_state[0] = s.aiff_ima[0], b->aiff_ts[row].ima_state[1] = s.aiff_ima[1];
+            }
+            b->rc = pcm_hooks.tick_aiff(p->engine, b->aiff_ts.data(), (uint32_t)b->aiff_ts.size(), b->aiff_units.data(), (uint32_t)b->aiff_units.size(),
+                                        b->pcm_bytes, b->pcm_used, b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, aiff_max_out,
+                                        &n_aiff_out, &aiff_used);
+            if (b->rc == SK_OK) {
+                for (uint32_t k = 0; k < n_aiff_out; ++k) {
+                    b->recs[b->n_out + k].stream_index += first_row;
+                    b->recs[b->n_out + k].byte_offset += base;
+                }
+                b->n_out += n_aiff_out;
+                for (uint32_t row = 0; row < b->aiff_entry.size(); ++row) {
+                    PStream &s = *p->streams[b->entries[b->aiff_entry[row]].handle];
+                    s.aiff_ima[0] = b->aiff_ts[row].ima_state[0], s.aiff_ima[1] = b->aiff_ts[row].ima_state[1];
+                    b->entry_row[b->aiff_entry[row]] = first_row + row;
+                    b->row_of.push_back(b->aiff_entry[row]);
+                }
+                used = base + aiff_used;
+            }
+        }
         if (b->rc == SK_OK && !b->pcm_ts.empty()) {  // the PCM streams' tick of this round, behind the other one
             const uint32_t first_row = (uint32_t)b->row_of.size();
             const size_t base = (used + 15) & ~(size_t)15;
@@ -1334,7 +1430,7 @@ void submit_body(sk_lane *p) {
         p->submit_where = 4;
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
-        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_units.size());
+        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_units.size() + (uint32_t)b->aiff_units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -1822,7 +1918,7 @@ void lane_destroy(sk_lane *p) {
     delete p;
 }
 
-int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle) {
+int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false) {
     if (!p || !handle) return SK_ERR_INVALID_ARG;
     // RawPcmFormat::validate (raw_pcm.rs:117-125), and the sample formats there are
     if (raw && (raw->sample_rate == 0 || raw->channels == 0 || raw->format > SK_FMT_F32BE)) return SK_ERR_INVALID_ARG;
@@ -1861,6 +1957,10 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.mpa_layer = 0;
     s.wav.reset();
     s.raw.reset();
+    s.aiff.reset();
+    s.aiff_enc = 0;
+    s.aiff_plain = false;
+    s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
     s.pcm_detected = false;
     s.pcm_route = 0, s.pcm_fmt = 0, s.pcm_flags = 0, s.pcm_bits = 0;
@@ -1870,6 +1970,11 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
         s.raw_format = *raw;
         const size_t width = raw->format <= SK_FMT_S16BE ? 2 : (raw->format <= SK_FMT_S24BE ? 3 : 4);
         s.raw.reset(new sk_pcm::RawPcmStream(width * raw->channels));
+    }
+    if (aiff) {  // spawn_aiff_with_options (lib.rs:2714-2724): the decoder is there from the start, nothing is detected or gathered
+        s.codec = kCodecAiff;
+        s.aiff.reset(new sk_pcm::AiffStream());
+        s.pcm_detected = true;
     }
     *handle = h;
     return SK_OK;
@@ -1986,6 +2091,10 @@ struct sk_wav_reader {
     sk_pcm::WavStream stream;
     std::string error;
 };
+struct sk_aiff_reader {
+    sk_pcm::AiffStream stream;
+    std::string error;
+};
 struct sk_raw_pcm_framer {
     explicit sk_raw_pcm_framer(uint32_t bytes_per_frame) : stream(bytes_per_frame) {}
     sk_pcm::RawPcmStream stream;
@@ -2011,7 +2120,7 @@ inline sk_lane *lane_of(sk_pipeline *p, uint32_t handle, uint32_t *inner) {
     return p->lanes[handle % n];
 }
 
-int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle) {
+int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false) {
     if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
     const uint32_t n = (uint32_t)p->lanes.size();
     const uint32_t first = p->next_lane.fetch_add(1) % n;
@@ -2019,7 +2128,7 @@ int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pc
     for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
         const uint32_t li = (first + k) % n;
         uint32_t inner = 0;
-        rc = lane_spawn(p->lanes[li], opt, raw, &inner);
+        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff);
         if (rc == SK_OK) {
             *handle = inner * n + li;
             return SK_OK;
@@ -2141,6 +2250,13 @@ int sk_pipeline_spawn_raw_pcm(sk_pipeline *p, const sk_raw_pcm_format *format, c
     return pipeline_spawn(p, opt, format, handle);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn_raw_pcm");
+}
+
+int sk_pipeline_spawn_aiff(sk_pipeline *p, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    return pipeline_spawn(p, opt, nullptr, handle, true);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_aiff");
 }
 
 int sk_pipeline_send(sk_pipeline *p, uint32_t handle, const uint8_t *data, size_t len) try {
@@ -2372,6 +2488,60 @@ const char *sk_raw_pcm_framer_last_error(const sk_raw_pcm_framer *f) try {
     return f ? f->error.c_str() : "";
 } catch (...) {
     (void)sk::abi_caught("sk_raw_pcm_framer_last_error");
+    return "";
+}
+
+int sk_aiff_reader_create(sk_aiff_reader **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_aiff_reader();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_aiff_reader_create");
+}
+
+void sk_aiff_reader_destroy(sk_aiff_reader *r) try {
+    sk::abi_enter();
+    delete r;
+} catch (...) {
+    (void)sk::abi_caught("sk_aiff_reader_destroy");
+}
+
+int sk_aiff_reader_add(sk_aiff_reader *r, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece) try {
+    sk::abi_enter();
+    if (!r || (len && !bytes) || !piece_offset || !piece_len) return SK_ERR_INVALID_ARG;
+    sk_pcm::Piece got;
+    *piece_offset = 0, *piece_len = 0;
+    if (piece) *piece = nullptr;
+    if (!r->stream.add(bytes, len, got, r->error)) return SK_PCM_ERR_STREAM;
+    *piece_offset = got.stream_offset, *piece_len = got.len;
+    if (piece) *piece = got.data;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_aiff_reader_add");
+}
+
+int sk_aiff_reader_info(const sk_aiff_reader *r, sk_aiff_info *info) try {
+    sk::abi_enter();
+    if (!r || !info) return SK_ERR_INVALID_ARG;
+    std::memset(info, 0, sizeof *info);
+    info->buffered_bytes = (uint32_t)r->stream.buffered_bytes();
+    if (!r->stream.have_info()) return SK_OK;
+    info->sample_rate = r->stream.sample_rate();
+    info->channels = (uint8_t)r->stream.channels();
+    info->encoding = (uint8_t)r->stream.encoding();
+    info->bits = (uint8_t)r->stream.bits();
+    info->is_float = r->stream.is_float() ? 1 : 0;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_aiff_reader_info");
+}
+
+const char *sk_aiff_reader_last_error(const sk_aiff_reader *r) try {
+    sk::abi_enter();
+    return r ? r->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_aiff_reader_last_error");
     return "";
 }
 

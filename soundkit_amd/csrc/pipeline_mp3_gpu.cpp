@@ -13,6 +13,8 @@ const bool g_hooked = [] {
     hooks.tick_md = sk_tick_run_mixed_md;
     hooks.tick_pcm = sk_tick_run_pcm;  // the WAV / raw PCM streams' tick comes the same way
     hooks.tick_pcm_out_bound = sk_tick_pcm_out_bound_on;
+    hooks.tick_aiff = sk_tick_run_aiff;  // ... and the AIFF streams'
+    hooks.tick_aiff_out_bound = sk_tick_aiff_out_bound_on;
     hooks.mpa_find_layer = sk_mp12::find_layer;  // Layer I / II streams: their host front and their tick
     hooks.mpa_scan = sk_mpa_scan;
     hooks.mpa_parse_frame = sk_mpa_parse_frame;

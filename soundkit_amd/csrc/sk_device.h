@@ -546,4 +546,30 @@ struct PcmWideIngestJob {
 };
 hipError_t launch_pcm_wide_ingest(const PcmWideIngestJob *jobs, uint32_t n_jobs, uint32_t max_frames, hipStream_t s);
 
+// aiff_decode.hip -- decode_stream_bytes (soundkit-aiff/src/lib.rs:477-560) for every unit of a tick: the file's sample encoding in,
+// little-endian PCM of the output contract out.  enc = enum sk_aiff_encoding.
+struct AiffElemJob {  // every encoding but IMA4: grid = (slices of kPcmSliceSamples samples, jobs), a lane = 16 samples
+    const uint8_t *src;  // 16-byte aligned
+    uint8_t *dst;        // 16-byte aligned
+    uint32_t samples;    // frames x channels
+    uint32_t enc;
+};
+hipError_t launch_aiff_elem(const AiffElemJob *jobs, uint32_t n_jobs, uint32_t max_samples, hipStream_t s);
+// IMA4: one wave per stream walks the stream's units in order, 64 packets a round, the predictor carried from packet to packet
+struct AiffImaUnit {
+    const uint8_t *src;  // 16-byte aligned: groups x channels packets of 34 bytes, channel after channel within a group
+    uint8_t *dst;        // 16-byte aligned: groups x 64 frames of interleaved s16
+    uint32_t groups;
+    uint32_t pad;
+};
+struct AiffImaStream {
+    uint32_t first_unit, n_units;  // into the unit table
+    int16_t predictor[2];          // the state the stream enters with, per channel
+    uint8_t step_index[2];
+    uint8_t channels;              // 1 or 2
+    uint8_t pad;
+};
+// states_out[2 * stream + channel] = (uint16_t)predictor | step_index << 16: what the stream leaves with
+hipError_t launch_aiff_ima4(const AiffImaStream *streams, uint32_t n_streams, const AiffImaUnit *units, uint32_t *states_out, hipStream_t s);
+
 }  // namespace sk

@@ -16,6 +16,11 @@ ONLY_LONG, LONG_START, EIGHT_SHORT, LONG_STOP = 0, 1, 2, 3
 SINE, KBD = 0, 1
 
 FMT_S16LE, FMT_S16BE, FMT_S24LE, FMT_S24BE, FMT_S32LE, FMT_S32BE, FMT_F32LE, FMT_F32BE = range(8)
+# enum sk_aiff_encoding: how an AIFF / AIFF-C file encodes its samples
+(AIFF_U8, AIFF_S8, AIFF_S16BE, AIFF_S16LE, AIFF_S24BE, AIFF_S32BE, AIFF_S32LE, AIFF_F32BE, AIFF_F64BE, AIFF_ULAW, AIFF_ALAW,
+ AIFF_IMA4) = range(12)
+AIFF_GROUP_BYTES = {AIFF_U8: 1, AIFF_S8: 1, AIFF_S16BE: 2, AIFF_S16LE: 2, AIFF_S24BE: 3, AIFF_S32BE: 4, AIFF_S32LE: 4, AIFF_F32BE: 4,
+                    AIFF_F64BE: 8, AIFF_ULAW: 1, AIFF_ALAW: 1}  # IMA4: 34 bytes per channel
 
 PCM_OPS = [
     "I16LE_TO_F32", "I16_TO_I16LE", "I16LE_TO_I16", "S24LE_TO_I32", "S24LE_TO_I16", "S24BE_TO_I16",
@@ -513,6 +518,62 @@ class Engine:
         n_out, used = C.c_uint32(), C.c_size_t()
         check(lib.sk_tick_run_pcm(self._h, ts, len(streams), table, n, _ptr(blob), total, _ptr(out), out.size, recs, max_out.value,
                                   C.byref(n_out), C.byref(used)), "sk_tick_run_pcm", self._h)
+        return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                for r in recs[:n_out.value]]
+
+    def aiff_decode(self, encoding, channels, data, ima_state=None):
+        """sk_aiff_decode: whole sample groups of an AIFF / AIFF-C stream in the file's encoding (AIFF_*) -> the little-endian PCM
+        of the output contract, as bytes.  IMA4: ima_state = [(predictor, step_index)] * 2 carried in (None: a fresh stream); the
+        return is then (bytes, state)."""
+        import ctypes as C
+        from ._lib import AiffImaState
+        data = np.frombuffer(bytes(data), np.uint8)
+        group = 34 * channels if encoding == AIFF_IMA4 else AIFF_GROUP_BYTES.get(encoding, 1)  # (an unknown encoding is the library's to refuse)
+        per_group = 128 * channels if encoding == AIFF_IMA4 else (3 if encoding == AIFF_S24BE else (4 if AIFF_S32BE <= encoding <= AIFF_F64BE else 2))
+        out = np.zeros(max(data.size // max(group, 1) * per_group, 16), np.uint8)
+        st = (AiffImaState * 2)()
+        for c, (p, i) in enumerate(ima_state or []):
+            st[c].predictor, st[c].step_index = int(p), int(i)
+        n = C.c_size_t()
+        check(lib.sk_aiff_decode(self._h, int(encoding), int(channels), _ptr(data) if data.size else None, data.size, _ptr(out), out.size,
+                                 C.byref(n), st), "sk_aiff_decode", self._h)
+        got = out[:n.value].tobytes()
+        if encoding == AIFF_IMA4:
+            return got, [(st[c].predictor, st[c].step_index) for c in range(2)]
+        return got
+
+    def tick_run_aiff(self, streams, units):
+        """One tick of AIFF streams (sk_tick_run_aiff).  As tick_run_pcm, with `encoding` (AIFF_*) in the place of `format` and, for
+        IMA4, "ima_state": [(predictor, step_index)] * 2, which is updated in the dict.  -> the same list of records."""
+        import ctypes as C
+        from ._lib import AiffTickStream, PcmUnit, TickOutput
+        ts = (AiffTickStream * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            ts[i].encoding, ts[i].channels = int(s["encoding"]), int(s["channels"])
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+            for c, (p, x) in enumerate(s.get("ima_state") or []):
+                ts[i].ima_state[c].predictor, ts[i].ima_state[c].step_index = int(p), int(x)
+        n = len(units)
+        table = (PcmUnit * max(n, 1))()
+        total = 0
+        for k, u in enumerate(units):
+            table[k].byte_offset, table[k].byte_len = total, len(u)
+            total += (len(u) + 15) & ~15
+        blob = np.zeros(max(total, 16), np.uint8)
+        for k, u in enumerate(units):
+            blob[table[k].byte_offset:table[k].byte_offset + len(u)] = np.frombuffer(bytes(u), np.uint8)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_aiff_out_bound_on(self._h, ts, len(streams), table, n, C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_aiff(self._h, ts, len(streams), table, n, _ptr(blob), total, _ptr(out), out.size, recs, max_out.value,
+                                   C.byref(n_out), C.byref(used)), "sk_tick_run_aiff", self._h)
+        for i, s in enumerate(streams):
+            if int(s["encoding"]) == AIFF_IMA4:
+                s["ima_state"] = [(ts[i].ima_state[c].predictor, ts[i].ima_state[c].step_index) for c in range(2)]
         return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
                 for r in recs[:n_out.value]]
 

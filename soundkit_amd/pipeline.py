@@ -6,7 +6,9 @@ handle feeds one shared scheduler per GPU (entropy decode on host threads, every
 Input: ADTS AAC-LC and MPEG Layer III (the stream's first bytes choose), WAV / RF64 (`RIFF....WAVE`: the walker of
 soundkit/src/wav.rs, then the reference's output stage -- sample width, mono downmix, rate -- in one batched GPU tick for all such
 streams; a stream with nothing to change is passed through as it is, any width and channel count), and headerless PCM through
-`spawn_raw_pcm[_with_options](RawPcmFormat)`.  AudioData from WAV / raw PCM streams carries the real `audio_format` and `endianness`.
+`spawn_raw_pcm[_with_options](RawPcmFormat)`, and AIFF / AIFF-C (`FORM....AIFF|AIFC`, or `spawn_aiff[_with_options]`: the walker of
+soundkit-aiff, its per-sample decode -- byte order, widening, f64, G.711, IMA4 -- and the same output stage in the batched tick).
+AudioData from WAV / raw PCM / AIFF streams carries the real `audio_format` and `endianness`.
 The reference's other formats stay with their CPU decoders (out of scope)."""
 import ctypes as C
 from dataclasses import dataclass
@@ -104,6 +106,16 @@ class BatchScheduler:
         rc = lib.sk_pipeline_spawn_raw_pcm(self._h, C.byref(f), C.byref(o), C.byref(handle))
         if rc != 0:
             raise SoundkitError(rc, "sk_pipeline_spawn_raw_pcm")
+        return DecodePipelineHandle(self, handle.value)
+
+    def spawn_aiff(self, options=None):
+        """DecodePipeline::spawn_aiff_with_options (lib.rs:2714-2724): an AIFF / AIFF-C stream, its decoder there from the start"""
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_aiff(self._h, C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_aiff")
         return DecodePipelineHandle(self, handle.value)
 
     def wait_outputs(self, timeout_ms=100, cap=256):
@@ -228,6 +240,14 @@ class DecodePipeline:
     @staticmethod
     def spawn_with_options(options):
         return default_scheduler().spawn(options)
+
+    @staticmethod
+    def spawn_aiff():
+        return default_scheduler().spawn_aiff(DecodeOptions())
+
+    @staticmethod
+    def spawn_aiff_with_options(options):
+        return default_scheduler().spawn_aiff(options)
 
     @staticmethod
     def spawn_raw_pcm(format):
