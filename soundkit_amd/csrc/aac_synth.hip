@@ -43,6 +43,9 @@ constexpr int kWavesPerBlock = SK_SYNTH_BLOCK_WAVES;
 #endif
 constexpr int kDepth = SK_PREFETCH_DEPTH;  // spectra in flight per wave
 constexpr int kWavesPerSimd = SK_WAVES_PER_SIMD;  // occupancy the register budget is held to
+#ifndef SK_SYNTH_HOLD_ONE
+#define SK_SYNTH_HOLD_ONE 1
+#endif
 constexpr int kExchange = 576;  // f2 per wave: max(8*68, 8*72)
 constexpr int kStage = 1024;    // floats per wave: rare-path staging (transition windows, eight-short output)
 
@@ -87,6 +90,10 @@ __device__ __forceinline__ void wave_sync() {
 // issued a vector load plus s_waitcnt vmcnt(0) at the top of every frame -- which also waits for the PCM stores of the
 // frame before to be acknowledged by memory: the wave drained its whole memory pipeline once (twice, with the look-up
 // for the prefetch address) per frame, and that, not bandwidth, set the launch time (profiles/r02_ab_synth_groups.md).
+// This removes that wait only.  The compiler still does not count across the frame loop's back-edge: where two
+// predecessors of the loop head leave different operations outstanding it takes the conservative merge, and a frame that
+// ends in its PCM stores made the head's wait for the prefetched spectra a wait for those stores as well.  The kernels
+// therefore hold a frame's PCM and store it in front of the next prefetch (HOLD below, profiles/synth_store_drain.md).
 typedef const __attribute__((address_space(4))) SynthEntry *const_entries;
 __device__ __forceinline__ const_entries as_constant(const SynthEntry *p) {
     return reinterpret_cast<const_entries>(reinterpret_cast<uintptr_t>(p));
@@ -277,8 +284,9 @@ __device__ __attribute__((noinline)) void synth_rare_frame(lds_f2 *ex, lds_f *st
 
 // OUT16: the PCM leaves as planar s16 (float_sample_to_i16 of every sample; same [off1024][1024] packing, two bytes
 // per sample) -- what decode_aac_access_unit hands on (soundkit-decoder lib.rs:1793-1813) before interleaving
-// ONLY_LONG: every frame of every task is OnlyLong (the host knows the windows and sorts the tasks): the loop is one
-// straight line, so the compiler can count its memory operations exactly instead of draining them at a join.
+// ONLY_LONG: every frame of every task is OnlyLong (the host knows the windows and sorts the tasks): the loop body is one
+// straight line, so the compiler can count its memory operations exactly inside a frame instead of draining them at a
+// join.  (The loop head is still a join of the pre-header and the back-edge: see HOLD.)
 template <bool OUT16, bool ONLY_LONG>
 __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? kWavesPerSimd + 1 : kWavesPerSimd) void k_aac_synth(SynthArgs a) {
     __shared__ f2 lds[kWavesPerBlock][kExchange];
@@ -342,6 +350,27 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
 #pragma unroll
         for (int r = 0; r < 8; ++r) xin[r] = SK_SYNTH_LOAD(reinterpret_cast<const f2 *>(src + 128 * r));
     };
+    // HOLD: a long frame's packed PCM (slot 2 r: first half | mirrored half) waits in registers for one frame and is stored in
+    // front of the next frame's prefetch, so that the spectrum requests are the youngest memory operations at the loop head
+    // and the wait for them is no wait for stores (see k_aac_synth_pair's frame loop, profiles/synth_store_drain.md)
+    constexpr bool HOLD = SK_SYNTH_HOLD_ONE;
+    u2 held16[HOLD && OUT16 ? 4 : 1];
+    f4 held32[HOLD && !OUT16 ? 4 : 1];
+    uint32_t held_off = 0;
+    bool holding = false;  // wave-uniform
+    auto store_held = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int j = 4 * lane + 256 * r;
+            if constexpr (OUT16) {
+                SK_SYNTH_STORE(held16[2 * r], reinterpret_cast<u2 *>(a.pcm16 + (size_t)held_off * 1024 + j));
+                SK_SYNTH_STORE(held16[2 * r + 1], reinterpret_cast<u2 *>(a.pcm16 + (size_t)held_off * 1024 + 1020 - j));
+            } else {
+                SK_SYNTH_STORE(held32[2 * r], reinterpret_cast<f4 *>(a.pcm + (size_t)held_off * 1024 + j));
+                SK_SYNTH_STORE(held32[2 * r + 1], reinterpret_cast<f4 *>(a.pcm + (size_t)held_off * 1024 + 1020 - j));
+            }
+        }
+    };
     auto frame = [&](f2 (&xin)[8], uint32_t e) __attribute__((always_inline)) {
         const uint32_t ent_off = entries[e].off1024, ent_win = entries[e].win;
         const uint32_t win = __builtin_amdgcn_readfirstlane(ent_win);
@@ -383,6 +412,11 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
                 w2f[r] = *reinterpret_cast<const f4 *>(w2 + j);
                 w2m[r] = *reinterpret_cast<const f4 *>(w2 + 1020 - j);
             }
+            if constexpr (HOLD) {
+                if (holding) store_held();
+                holding = true;
+                held_off = __builtin_amdgcn_readfirstlane(ent_off);
+            }
             // next spectrum in flight while this one is transformed.  Unconditional (the last frames re-read the task's
             // last spectrum): with a branch around these loads the compiler can no longer count what is outstanding when
             // the epilogue needs its windows, and waits for the prefetch itself before every store.
@@ -411,7 +445,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
                 // out1[508-j..511-j] = M0.im, F1.re, M1.im, F0.re (dsp.rs:517, 529)
                 m.x = M.y * W1m.x + dly[8 * r + 4]; m.y = F.z * W1m.y + dly[8 * r + 5];
                 m.z = M.w * W1m.z + dly[8 * r + 6]; m.w = F.x * W1m.w + dly[8 * r + 7];
-                if (OUT16) {
+                if constexpr (HOLD) {
+                    if constexpr (OUT16) held16[2 * r] = pack4_s16(f), held16[2 * r + 1] = pack4_s16(m);
+                    else held32[2 * r] = f, held32[2 * r + 1] = m;
+                } else if (OUT16) {
                     SK_SYNTH_STORE(pack4_s16(f), reinterpret_cast<u2 *>(out16_ptr + j));
                     SK_SYNTH_STORE(pack4_s16(m), reinterpret_cast<u2 *>(out16_ptr + 1020 - j));
                 } else {
@@ -427,6 +464,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
             }
             wave_sync();
         } else if constexpr (!ONLY_LONG) {
+            if constexpr (HOLD) {  // nothing is held across the call; this arm stores its own frame below
+                if (holding) store_held();
+                holding = false;
+            }
             // hand the frame over through LDS (see synth_rare_frame), then restart the prefetch
 #pragma unroll
             for (int r = 0; r < 8; ++r) ex[64 * r + lane] = z[r];
@@ -470,6 +511,9 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
 #pragma unroll
         for (int d = 0; d < kDepth; ++d)
             if (e0 + d < count) frame(ring[d], e0 + d);
+    }
+    if constexpr (HOLD) {  // the task's last frame: a launch leaves nothing held
+        if (holding) store_held();
     }
 
 #pragma unroll
@@ -676,6 +720,10 @@ __device__ __attribute__((noinline)) void synth_rare_pair(lds_f4 *ex, lds_f2 *st
 template <bool OUT16, bool WITH_SHORT>
 __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(SynthArgs a) {
     constexpr bool LDS_WIN = !WITH_SHORT;
+#ifndef SK_SYNTH_HOLD_SHORT
+#define SK_SYNTH_HOLD_SHORT 1
+#endif
+    constexpr bool HOLD = !WITH_SHORT || SK_SYNTH_HOLD_SHORT;
     __shared__ f4 lds[kWavesPerBlock][kPairExchange];
     __shared__ f4 win_tab[LDS_WIN ? 2048 : 1];  // a.t.win without its short windows: long [0, 4096), transition halves [4096, 8192)
     __shared__ f2 stage_lds[WITH_SHORT ? kWavesPerBlock : 1][WITH_SHORT ? kStage : 2];  // eight-short arm only: 1024 (A, B) pairs per wave
@@ -752,7 +800,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
         }
     };
     // window + overlap-add + store of one channel's half r from its four post-twiddled bins (dsp.rs:267-279, 516-531)
-    auto emit = [&](int r, f2 F0, f2 F1, f2 M0, f2 M1, const Win &w, int w1_at, int w2_at, float (&dly)[16], float *out_ptr, int16_t *out16_ptr) {
+    // HOLD: the packed PCM stays in registers (slot 4 r + 2 ch: first half | mirrored half) and store_held sends it at the top
+    // of the next frame, in front of that frame's prefetch -- see the frame loop
+    u2 held16[HOLD && OUT16 ? 8 : 1];
+    f4 held32[HOLD && !OUT16 ? 8 : 1];
+    uint32_t held_off_a = 0, held_off_b = 0;
+    auto emit = [&](int r, int ch, f2 F0, f2 F1, f2 M0, f2 M1, const Win &w, int w1_at, int w2_at, float (&dly)[16], float *out_ptr, int16_t *out16_ptr) {
         const int j = 4 * lane + 256 * r;  // = 2 q, q = 2 lane + 128 r the first of the lane's two bins
         f4 W1f, W1m, W2f, W2m;
         if constexpr (LDS_WIN) {
@@ -766,7 +819,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
         f.z = -F1.x * W1f.z + dly[8 * r + 2]; f.w = -M0.y * W1f.w + dly[8 * r + 3];
         m.x = M0.y * W1m.x + dly[8 * r + 4]; m.y = F1.x * W1m.y + dly[8 * r + 5];
         m.z = M1.y * W1m.z + dly[8 * r + 6]; m.w = F0.x * W1m.w + dly[8 * r + 7];
-        if (OUT16) {
+        if constexpr (HOLD) {
+            if constexpr (OUT16) held16[4 * r + 2 * ch] = pack4_s16(f), held16[4 * r + 2 * ch + 1] = pack4_s16(m);
+            else held32[4 * r + 2 * ch] = f, held32[4 * r + 2 * ch + 1] = m;
+        } else if (OUT16) {
             SK_SYNTH_STORE(pack4_s16(f), reinterpret_cast<u2 *>(out16_ptr + j));
             SK_SYNTH_STORE(pack4_s16(m), reinterpret_cast<u2 *>(out16_ptr + 1020 - j));
         } else {
@@ -796,6 +852,31 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
         }
     };
 
+    // the held frame, in the order emit would have stored it
+    auto store_held = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {
+                const int j = 4 * lane + 256 * r;
+                const size_t at = (size_t)(ch ? held_off_b : held_off_a) * 1024;
+                if constexpr (OUT16) {
+                    SK_SYNTH_STORE(held16[4 * r + 2 * ch], reinterpret_cast<u2 *>(a.pcm16 + at + j));
+                    SK_SYNTH_STORE(held16[4 * r + 2 * ch + 1], reinterpret_cast<u2 *>(a.pcm16 + at + 1020 - j));
+                } else {
+                    SK_SYNTH_STORE(held32[4 * r + 2 * ch], reinterpret_cast<f4 *>(a.pcm + at + j));
+                    SK_SYNTH_STORE(held32[4 * r + 2 * ch + 1], reinterpret_cast<f4 *>(a.pcm + at + 1020 - j));
+                }
+            }
+    };
+
+    // Loads and stores share one in-order counter (vmcnt), and the loop head waits for the spectra that were requested a
+    // frame ago.  Stored where emit computes it, a frame's PCM is YOUNGER than those requests, so the wait for the spectra was
+    // also a wait for every store of the frame before: the wave drained its memory pipeline once per frame
+    // (profiles/synth_store_drain.md).  HOLD keeps the PCM for one frame instead and stores it in front of the next prefetch:
+    // on the back-edge as from the pre-header the spectrum requests are the youngest operations, and the stores ahead of
+    // them are a whole transform old when the wave waits.
+    bool holding = false;  // wave-uniform: a frame's PCM waits in held16 / held32
     f2 xa[8], xb[8];
     load_spectrum(xa, ent_a, 0);
     load_spectrum(xb, ent_b, 0);
@@ -805,6 +886,10 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
         const int shape_a = (win_a >> 2) & 1, shape_b = (win_b >> 2) & 1;
         if constexpr (WITH_SHORT) {
             if ((win_a & 3u) == 2u) {  // wave-uniform; channel B's frame is EightShort too (the host pairs no others)
+                if constexpr (HOLD) {  // nothing is held across the call; this arm stores its own frame below
+                    if (holding) store_held();
+                    holding = false;
+                }
                 // both channels' EightShort frame (dsp.rs:284-338) through synth_rare_pair: pre-twiddled blocks and the two
                 // overlaps in through the wave's LDS, PCM and new overlaps back the same way
                 {
@@ -876,6 +961,12 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
             load_windows(wa, (int)(win_a & 3), prev_a, shape_a);
             load_windows(wb, (int)(win_b & 3), prev_b, shape_b);
         }
+        if constexpr (HOLD) {
+            if (holding) store_held();
+            holding = true;
+            held_off_a = off_a;
+            held_off_b = off_b;
+        }
         {
             const uint32_t ahead = e + 1 < count ? e + 1 : count - 1;  // unconditional, as in the one-channel kernel
             load_spectrum(xa, ent_a, ahead);
@@ -897,12 +988,15 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
         for (int r = 0; r < 2; ++r) {
             const int q = 2 * lane + 128 * r;
             const f4 F0 = ex[256 + q], F1 = ex[257 + q], M0 = ex[254 - q], M1 = ex[255 - q];
-            emit(r, (f2){F0.x, F0.z}, (f2){F1.x, F1.z}, (f2){M0.x, M0.z}, (f2){M1.x, M1.z}, wa, w1_a, w2_a, dly_a, out_a, out16_a);
-            emit(r, (f2){F0.y, F0.w}, (f2){F1.y, F1.w}, (f2){M0.y, M0.w}, (f2){M1.y, M1.w}, wb, w1_b, w2_b, dly_b, out_b, out16_b);
+            emit(r, 0, (f2){F0.x, F0.z}, (f2){F1.x, F1.z}, (f2){M0.x, M0.z}, (f2){M1.x, M1.z}, wa, w1_a, w2_a, dly_a, out_a, out16_a);
+            emit(r, 1, (f2){F0.y, F0.w}, (f2){F1.y, F1.w}, (f2){M0.y, M0.w}, (f2){M1.y, M1.w}, wb, w1_b, w2_b, dly_b, out_b, out16_b);
         }
         wave_sync();
         prev_a = shape_a;  // decoder.rs:371
         prev_b = shape_b;
+    }
+    if constexpr (HOLD) {  // the task's last frame: a launch leaves nothing held
+        if (holding) store_held();
     }
     auto store_state = [&](float *p, const float (&d)[16]) {
 #pragma unroll
