@@ -112,10 +112,18 @@ class TickMp3Frames(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("n_frames", C.c_uint32), ("main_bytes", C.c_void_p), ("main_len", C.c_size_t)]
 
 
+class TickMpaFrames(C.Structure):
+    """sk_tick_mpa_frames"""
+    _fields_ = [("records", C.c_void_p), ("n_frames", C.c_uint32), ("frame_bytes", C.c_void_p), ("bytes_len", C.c_size_t)]
+
+
 class TickStream(C.Structure):
     """sk_tick_stream"""
     _fields_ = [("stream", C.c_uint32), ("n_frames", C.c_uint32), ("out_bits", C.c_uint8), ("out_channels", C.c_uint8),
                 ("resample", C.c_uint8), ("flush", C.c_uint8), ("codec", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+SK_TICK_AAC, SK_TICK_MP3, SK_TICK_MPA = 0, 1, 2  # sk_tick_stream.codec
 
 
 class TickInput(C.Structure):

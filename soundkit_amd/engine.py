@@ -577,6 +577,40 @@ class Engine:
         return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
                 for r in recs[:n_out.value]]
 
+    def tick_run_mpa(self, streams, frames=None):
+        """One tick of MPEG Layer I / II streams alone (sk_tick_run_mixed_mpa with no AAC unit and no Layer III granule).  streams:
+        list of dicts {stream, channels, out_bits, out_channels (the source's `channels` when absent), resample, flush, frames};
+        a stream's frames are (MpaFrameRecord, frame bytes) pairs as mp3.mpa_parse_frame gives them.  They are packed as
+        mp3.mpa_pack_frames packs them (4-byte aligned, at least 8 zero bytes behind each), stream by stream in the order of
+        `streams`.  `frames`, when given, is that packing done by the caller -- (record array, n, uint8 buffer) -- and every
+        stream's dict then says how many of its records are its own with n_frames; nothing is checked here, so a table that does
+        not add up reaches the library, which refuses it.
+        -> list of (stream_index, status, frames, channels, bits, bytes), as tick_run."""
+        import ctypes as C
+        from . import mp3
+        from ._lib import SK_TICK_MPA, TickInput, TickMpaFrames, TickOutput, TickStream
+        if frames is None:
+            frames = mp3.mpa_pack_frames([f for s in streams for f in s["frames"]])
+        recs, n, buf = frames
+        ts = (TickStream * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_frames = int(s["stream"]), int(s["n_frames"]) if "n_frames" in s else len(s["frames"])
+            ts[i].out_bits, ts[i].out_channels = int(s.get("out_bits", 16)), int(s.get("out_channels") or s["channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+            ts[i].codec = SK_TICK_MPA
+        buf = np.ascontiguousarray(buf, np.uint8)
+        mpa = TickMpaFrames(C.cast(recs, C.c_void_p), n, _ptr(buf), buf.size if n else 0)
+        tin = TickInput()
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_out_bound_on(self._h, ts, len(streams), C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        outs = (TickOutput * max(max_out.value, 1))()
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_mixed_mpa(self._h, ts, len(streams), C.byref(tin), None, C.byref(mpa), _ptr(out), out.size, outs, max_out.value,
+                                        C.byref(n_out), C.byref(used)), "sk_tick_run_mixed_mpa", self._h)
+        return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes())
+                for r in outs[:n_out.value]]
+
     def tick_run_au(self, streams, access_units):
         """sk_tick_run_au: as tick_run, but the entropy front-end runs on the GPU.  access_units: the raw access
         units (bytes) of all streams, stream by stream in the order of `streams`."""

@@ -117,9 +117,11 @@ def build_frame(h4, h, alloc, scfsi, scf, codes, allow_overrun=False):
                                            sblimit=sblimit, bound=bound)
 
 
-def random_frame(rng, layer, lsf, rate_index, bitrate_index, mode, mode_ext=0, crc=False, padding=0, code_mode="random", fill=0.9):
+def random_frame(rng, layer, lsf, rate_index, bitrate_index, mode, mode_ext=0, crc=False, padding=0, code_mode="random", fill=0.9, scf_floor=0):
     """A frame with a random allocation that uses about `fill` of its bits, random scale factors (all four scfsi patterns) and codes:
-    code_mode "random", "zero", "max" or "middle"."""
+    code_mode "random", "zero", "max" or "middle".  The scale-factor indices are drawn from scf_floor ... 63: index 0 is a factor of
+    2.0 per subband, and with every subband at that level the decoded PCM leaves +-1 (fine for a float comparison, useless behind
+    an s16 output); from 9 on (a factor of 0.25 at the most) no stream of tests/test_mp12_cpu.py's CONFIGS does."""
     h4, h = header(layer, lsf, rate_index, bitrate_index, mode, mode_ext, crc, padding)
     rows, sblimit, bound = geometry(h)
     ch = h["channels"]
@@ -140,7 +142,7 @@ def random_frame(rng, layer, lsf, rate_index, bitrate_index, mode, mode_ext=0, c
                 alloc[c][sb] = a
                 used += per + side
     scfsi = rng.integers(0, 4, (2, 32))
-    scf = rng.integers(0, 64, (2, 32, 3))
+    scf = rng.integers(scf_floor, 64, (2, 32, 3))
     codes = np.zeros((12, 32, 2, 3), np.int64)
     for sb in range(sblimit):
         for c in range(ch if sb < bound else 1):
