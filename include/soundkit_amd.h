@@ -1110,6 +1110,134 @@ int sk_tick_run_aiff(sk_engine *, sk_aiff_tick_stream *streams, uint32_t n_strea
                      const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
                      uint32_t *n_outputs, size_t *out_bytes_used);
 
+/* ---- FLAC (RFC 9639): header parser, framer, stream reader (host only) ----------------------------------------------- */
+/* Native FLAC streams (`fLaC`).  Not built: Ogg FLAC, FLAC in MP4, decode_f32, 32-bit frames with a side channel (33-bit samples:
+ * SK_ERR_UNSUPPORTED as that frame's status), MD5 / total-sample verification at the end of a stream. */
+enum sk_flac_status {
+    SK_FLAC_NEED_MORE = -501,       /* the header is longer than the bytes given */
+    SK_FLAC_NO_SYNC = -502,         /* the bytes do not begin with 0xFFF8 / 0xFFF9 */
+    SK_FLAC_RESERVED = -503,        /* a reserved value: block-size code 0, rate code 15, depth code 3, assignment 11 ... 15, a set
+                                     * reserved bit, an invalid coded number */
+    SK_FLAC_BAD_CRC = -504,         /* the header's CRC-8 fails; sk_flac_scan: no span within the frame bound satisfies the CRC-16 */
+    SK_FLAC_NEED_STREAMINFO = -505, /* rate code 0 or depth code 0 and no STREAMINFO was given */
+    SK_FLAC_INVALID = -506,         /* a frame's status from the device stage: the subframes break the syntax or miss the frame's end */
+    SK_FLAC_ERR_STREAM = -507       /* the reader / decoder rejected the stream; *_last_error has the text */
+};
+typedef struct sk_flac_streaminfo { /* the STREAMINFO block, RFC 9639 8.2 */
+    uint32_t min_blocksize, max_blocksize, min_framesize, max_framesize; /* frame sizes: 0 = unknown */
+    uint32_t sample_rate;
+    uint8_t channels, bits_per_sample;
+    uint16_t reserved;
+    uint64_t total_samples; /* 0 = unknown */
+    uint8_t md5[16];        /* of the unencoded samples; all zeros = not computed.  Reported, never checked. */
+} sk_flac_streaminfo;
+typedef struct sk_flac_frame_info {
+    uint64_t number;         /* the coded number: the frame's (fixed block size) or its first sample's (variable) */
+    uint32_t offset;         /* sk_flac_scan / reader: position of the frame in the scanned bytes */
+    uint32_t frame_bytes;    /* sync code to the end of the CRC-16; 0 from sk_flac_parse_header */
+    uint32_t sample_rate;
+    uint32_t block_size;     /* 1 ... 65536 samples per channel */
+    uint8_t header_bytes;    /* 6 ... 16, CRC-8 included */
+    uint8_t channels;        /* 1 ... 8 */
+    uint8_t assignment;      /* 0 ... 7 independent channels; 8 left/side, 9 side/right, 10 mid/side */
+    uint8_t bits_per_sample; /* 4 ... 32 */
+    uint8_t variable_blocksize;
+    uint8_t reserved[3];
+} sk_flac_frame_info;
+/* One frame header, RFC 9639 9.1: sync, blocking strategy, the coded number (up to 36 bits), every block-size code (6 / 7 with their
+ * tail bytes), every rate code (12 / 13 / 14 with theirs; 0 = STREAMINFO's), depth codes 0 (= STREAMINFO's), 8, 12, 16, 20, 24, 32,
+ * assignments 0 ... 10, CRC-8.  `info` may be NULL: a header that needs it is SK_FLAC_NEED_STREAMINFO then. */
+int sk_flac_parse_header(const uint8_t *data, size_t len, const sk_flac_streaminfo *info, sk_flac_frame_info *out);
+/* Whole frames out of bytes that begin at a frame; stateless.  A frame ends where the next valid header (sync, parse, CRC-8) begins AND
+ * the CRC-16 of the span holds, or -- with `final` != 0 -- at the end of the data if the CRC-16 holds there.  A sync pattern inside a
+ * frame, even one with a valid CRC-8, is no boundary: the scan goes on.  The search is bounded: by STREAMINFO's max_framesize when it
+ * has one, else by 19 + ceil((block_size * channels * (bits + 1) + channels * 40) / 8) bytes (header 16, CRC-16 2, padding 1; every
+ * subframe VERBATIM at a side channel's width, with its header byte and the longest wasted-bits count).  No span within the bound:
+ * SK_FLAC_BAD_CRC -- FLAC is lossless, a lost frame is not skipped.  Bytes that are no header where a frame must begin: that header's
+ * status.  *consumed = bytes up to the first incomplete frame; frames beyond `cap` stay unconsumed. */
+int sk_flac_scan(const uint8_t *data, size_t len, const sk_flac_streaminfo *info, int final, sk_flac_frame_info *frames, uint32_t cap,
+                 uint32_t *n_frames, size_t *consumed);
+/* A stream from its `fLaC` marker on, cut anywhere: the marker, the metadata blocks (STREAMINFO first, exactly 34 bytes; PADDING,
+ * APPLICATION, SEEKTABLE, VORBIS_COMMENT, CUESHEET and PICTURE are skipped by count without being buffered; type 127 and a second
+ * STREAMINFO are rejected), then whole frames through sk_flac_scan.  One `add` gives at most `cap` frames -- the others come with the
+ * next one -- at *data + frames[i].offset, valid until the next call on the reader.  An EMPTY add is the finalising one: the last
+ * frame ends with the data, and bytes that form no frame are a truncated stream.  A frame whose channel count, depth or rate
+ * disagrees with STREAMINFO ends the stream.  SK_FLAC_ERR_STREAM: rejected, sk_flac_reader_last_error has the text; it stays so. */
+typedef struct sk_flac_info { /* zeros (but buffered_bytes) until STREAMINFO has been read */
+    sk_flac_streaminfo streaminfo;
+    uint64_t frames;         /* frames handed out so far */
+    uint32_t buffered_bytes; /* held back: an incomplete marker / block header / STREAMINFO / frame */
+    uint8_t have_streaminfo;
+    uint8_t reserved[3];
+} sk_flac_info;
+typedef struct sk_flac_reader sk_flac_reader;
+int sk_flac_reader_create(sk_flac_reader **out);
+void sk_flac_reader_destroy(sk_flac_reader *);
+int sk_flac_reader_add(sk_flac_reader *, const uint8_t *bytes, size_t len, sk_flac_frame_info *frames, uint32_t cap, uint32_t *n_frames,
+                       const uint8_t **data);
+int sk_flac_reader_info(const sk_flac_reader *, sk_flac_info *info);
+const char *sk_flac_reader_last_error(const sk_flac_reader *);
+
+/* ---- FLAC decode stage (GPU, csrc/flac_decode.hip) ------------------------------------------------------------------- */
+/* frames[i] lies at bytes + frames[i].offset (frame_bytes long, as sk_flac_scan gives them).  Output: the frames one after the other in
+ * the order given, each block_size x channels samples interleaved, little-endian, in the width of its depth: <= 8 bits one byte
+ * (sample + 128), 9 ... 16 two, 17 ... 24 three, 32 four.  status_per_frame[i]: SK_OK, SK_FLAC_INVALID (a reserved subframe type, a set
+ * padding bit, a partition order the block size does not divide by or whose first partition is shorter than the predictor order, a
+ * negative LPC shift, precision code 15, samples that end beyond the frame's bytes before its CRC or more than 7 bits short of it,
+ * assignment 8 ... 10 with other than 2 channels) or SK_ERR_UNSUPPORTED (32 bits with a side channel).  A rejected frame keeps its
+ * place in `out` and nothing is written there.  out_cap too small, or a frame_info outside 1 ... 8 channels / 4 ... 32 bits / 1 ... 65536
+ * samples: SK_ERR_INVALID_ARG, nothing decoded.  The CRC-16 is the framer's business and is not checked again.
+ * The _dev form takes 16-byte aligned device pointers and runs on the engine's stream; it waits only for the statuses. */
+int sk_flac_decode_frames(sk_engine *, const sk_flac_frame_info *frames, uint32_t n, const uint8_t *bytes, uint8_t *out, size_t out_cap,
+                          size_t *out_len, int32_t *status_per_frame);
+int sk_flac_decode_frames_dev(sk_engine *, const sk_flac_frame_info *frames, uint32_t n, const uint8_t *d_bytes, uint8_t *d_out, size_t out_cap,
+                              size_t *out_len, int32_t *status_per_frame);
+
+/* The tick of the FLAC streams, sk_tick_run_aiff's pattern: the units are whole frames (as sk_flac_scan / the reader cut them, packed at
+ * 16-byte aligned offsets: frames[k].offset into `bytes`, stream after stream), and every frame is first decoded to the contract's PCM
+ * on the device.  A stream with nothing to change (no rate change, out_bits = the contract's width in bits, out_channels = channels)
+ * gets those bytes as its outputs, one per frame, at any depth and for 1 ... 8 channels.  Every other stream then runs exactly what
+ * sk_tick_run_pcm runs on a little-endian source of that format -- same kernels, records, bounds and limits (16 / 24 / 32-bit samples,
+ * the exact 24 / 32 -> 16 path included; 3 ... 8 channels need sk_engine_enable_wide_pcm); any other depth with a conversion requested:
+ * SK_ERR_UNSUPPORTED.  A refused tick leaves every stream as it was.  status_per_frame[k] is sk_flac_decode_frames': a rejected frame
+ * writes nothing; its output record carries the status, and behind a conversion -- where the frame went in as silence -- every record
+ * of its stream in this tick does: the stream is to be ended. */
+typedef struct sk_flac_tick_stream {
+    uint32_t stream;         /* engine stream (resample = 1 only) */
+    uint32_t n_units;        /* frames */
+    uint8_t channels;        /* 1 ... 8 */
+    uint8_t bits_per_sample; /* 4 ... 32 */
+    uint8_t out_bits;        /* 8 (as decoded, depth <= 8) / 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t reserved[2];
+} sk_flac_tick_stream;
+size_t sk_tick_flac_out_bound_on(sk_engine *, const sk_flac_tick_stream *streams, uint32_t n_streams, const sk_flac_frame_info *frames,
+                                 uint32_t n_frames, uint32_t *max_outputs);
+int sk_tick_run_flac(sk_engine *, const sk_flac_tick_stream *streams, uint32_t n_streams, const sk_flac_frame_info *frames, uint32_t n_frames,
+                     const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                     uint32_t *n_outputs, size_t *out_bytes_used, int32_t *status_per_frame);
+
+/* FlacDecoder (soundkit-flac/src/lib.rs:122-219): bytes in at any chunking, interleaved samples out.  One call buffers its input and
+ * decodes every whole frame available that fits into out_cap (SK_ERR_CAPACITY when not even the next one does); *written counts
+ * interleaved samples.  A call with len = 0 fetches frames an earlier call had no room for -- in the middle of a stream as well, more
+ * input may follow -- and, once none waits, is the finalising one: 0 written = nothing is left.  decode_i16 is
+ * decode_i32 CLAMPED to the i16 range (lib.rs:192-193), not shifted.  A frame the device rejects or a stream the framer rejects:
+ * SK_FLAC_ERR_STREAM with a text (the reference returns Err(String)); the decoder stays in error until reset. */
+typedef struct sk_flac_decoder sk_flac_decoder;
+int sk_flac_decoder_create(sk_engine *, sk_flac_decoder **out);
+void sk_flac_decoder_destroy(sk_flac_decoder *);
+int sk_flac_decoder_reset(sk_flac_decoder *);
+/* sample_rate / channels / bits_per_sample are 0 until STREAMINFO has been read (Option::None) */
+int sk_flac_decoder_info(const sk_flac_decoder *, uint32_t *sample_rate, uint8_t *channels, uint8_t *bits_per_sample, uint64_t *frames_decoded);
+/* FlacDecoder::pending_samples (lib.rs:175): interleaved samples of the frames that wait for room.  While it is not 0 a call with
+ * len = 0 only fetches them; at 0 such a call finalises the stream. */
+size_t sk_flac_decoder_pending_samples(const sk_flac_decoder *);
+int sk_flac_decoder_decode_i32(sk_flac_decoder *, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written);
+int sk_flac_decoder_decode_i16(sk_flac_decoder *, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written);
+const char *sk_flac_decoder_last_error(const sk_flac_decoder *);
+
 #ifdef __cplusplus
 }
 #endif

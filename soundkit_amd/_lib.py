@@ -20,6 +20,8 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -107: "InvalidConfig", -108: "InvalidBitstream",
              -301: "Mp3NeedMore", -302: "Mp3NoSync", -303: "Mp3Unsupported", -304: "Mp3Invalid",
              -401: "PcmStreamRejected",
+             -501: "FlacNeedMore", -502: "FlacNoSync", -503: "FlacReserved", -504: "FlacBadCrc", -505: "FlacNeedStreamInfo",
+             -506: "FlacInvalid", -507: "FlacStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -166,6 +168,31 @@ class AiffInfo(C.Structure):
     """sk_aiff_info"""
     _fields_ = [("sample_rate", C.c_uint32), ("buffered_bytes", C.c_uint32), ("channels", C.c_uint8), ("encoding", C.c_uint8),
                 ("bits", C.c_uint8), ("is_float", C.c_uint8)]
+
+
+class FlacStreamInfo(C.Structure):
+    """sk_flac_streaminfo"""
+    _fields_ = [(n, C.c_uint32) for n in ("min_blocksize", "max_blocksize", "min_framesize", "max_framesize", "sample_rate")] + [
+        ("channels", C.c_uint8), ("bits_per_sample", C.c_uint8), ("reserved", C.c_uint16), ("total_samples", C.c_uint64), ("md5", C.c_uint8 * 16)]
+
+
+class FlacFrameInfo(C.Structure):
+    """sk_flac_frame_info"""
+    _fields_ = [("number", C.c_uint64), ("offset", C.c_uint32), ("frame_bytes", C.c_uint32), ("sample_rate", C.c_uint32),
+                ("block_size", C.c_uint32)] + [(n, C.c_uint8) for n in ("header_bytes", "channels", "assignment", "bits_per_sample",
+                                                                         "variable_blocksize")] + [("reserved", C.c_uint8 * 3)]
+
+
+class FlacInfo(C.Structure):
+    """sk_flac_info"""
+    _fields_ = [("streaminfo", FlacStreamInfo), ("frames", C.c_uint64), ("buffered_bytes", C.c_uint32), ("have_streaminfo", C.c_uint8),
+                ("reserved", C.c_uint8 * 3)]
+
+
+class FlacTickStream(C.Structure):
+    """sk_flac_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("channels", C.c_uint8), ("bits_per_sample", C.c_uint8), ("out_bits", C.c_uint8),
+                ("out_channels", C.c_uint8), ("resample", C.c_uint8), ("flush", C.c_uint8), ("reserved", C.c_uint8 * 2)]
 
 
 class RawPcmFormatC(C.Structure):
@@ -407,6 +434,25 @@ _sig = {
     "sk_aiff_decode_dev": (_i, [_vp, _i, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "sk_tick_aiff_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "sk_tick_run_aiff": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_flac_parse_header": (_i, [_vp, _sz, _vp, _vp]),
+    "sk_flac_scan": (_i, [_vp, _sz, _vp, _i, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
+    "sk_flac_reader_create": (_i, [C.POINTER(_vp)]),
+    "sk_flac_reader_destroy": (None, [_vp]),
+    "sk_flac_reader_add": (_i, [_vp, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_vp)]),
+    "sk_flac_reader_info": (_i, [_vp, C.POINTER(FlacInfo)]),
+    "sk_flac_reader_last_error": (C.c_char_p, [_vp]),
+    "sk_flac_decode_frames": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_flac_decode_frames_dev": (_i, [_vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_tick_flac_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_flac": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz), _vp]),
+    "sk_flac_decoder_create": (_i, [_vp, C.POINTER(_vp)]),
+    "sk_flac_decoder_destroy": (None, [_vp]),
+    "sk_flac_decoder_reset": (_i, [_vp]),
+    "sk_flac_decoder_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]),
+    "sk_flac_decoder_pending_samples": (_sz, [_vp]),
+    "sk_flac_decoder_decode_i32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_flac_decoder_decode_i16": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_flac_decoder_last_error": (C.c_char_p, [_vp]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

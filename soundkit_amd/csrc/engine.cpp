@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "aac_entropy_tables.h"
+#include "flac_stream.h"
 #include "mp12_internal.h"
 #include "pcm_stream.h"
 #include "sk_device.h"
@@ -261,6 +262,7 @@ struct sk_engine {
     // sk_tick_run: synthesis output, resampler output, packed bytes, small-array arena (+ pinned host mirror)
     DevBuf tick_pcm, tick_res, tick_out, tick_arena, tick_au, tick_side, tick_q, tick_mp3_in, tick_mp3_xr, tick_mpa_in;
     DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
+    DevBuf flac_in, flac_ws, flac_out;  // sk_flac_decode_frames: frames | tables | statuses, planar i32 workspace | subframe records, PCM
     DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
@@ -580,6 +582,13 @@ const char *sk_strerror(int status) try {
     case SK_MP3_UNSUPPORTED: return "unsupported MPEG audio layer or feature";
     case SK_MP3_INVALID: return "invalid MP3 side information";
     case SK_PCM_ERR_STREAM: return "WAV / raw PCM stream rejected";
+    case SK_FLAC_NEED_MORE: return "more FLAC input needed";
+    case SK_FLAC_NO_SYNC: return "not a FLAC frame header";
+    case SK_FLAC_RESERVED: return "reserved value in a FLAC frame header";
+    case SK_FLAC_BAD_CRC: return "FLAC CRC mismatch";
+    case SK_FLAC_NEED_STREAMINFO: return "FLAC frame header refers to a STREAMINFO that was not given";
+    case SK_FLAC_INVALID: return "invalid FLAC frame";
+    case SK_FLAC_ERR_STREAM: return "FLAC stream rejected";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -662,6 +671,9 @@ void sk_engine_destroy(sk_engine *e) try {
         e->tick_q.release();
         e->tick_pcm_in.release();
         e->tick_aiff.release();
+        e->flac_in.release();
+        e->flac_ws.release();
+        e->flac_out.release();
         e->mp3e_in.release();
         e->tick_mpa_in.release();
         e->mp3e_out.release();
@@ -4557,6 +4569,8 @@ struct AiffTick {
     size_t decoded_len = 0;                  // of the decoded layout
     std::vector<uint8_t> plain;              // per stream: nothing to change behind the decode -- the decoded bytes are its outputs, one per unit
     std::vector<uint32_t> states;            // out: 2 per stream, what k_aiff_ima4 left ((uint16_t)predictor | step_index << 16)
+    // sk_tick_run_flac: another decode in the place of the AIFF one -- the same two passes to the same destinations; d_src = the uploaded units
+    std::function<int(bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src)> decode;
 };
 
 bool pcm_fmt_is_float(int fmt) { return fmt == SK_FMT_F32LE || fmt == SK_FMT_F32BE; }
@@ -4698,6 +4712,7 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
     // tick_aiff, which the body then reads in the place of the uploaded bytes; the others decode straight into their output records ----
     std::vector<std::pair<const uint32_t *, std::vector<uint32_t>>> aiff_states;  // (pinned states, AiffImaStream -> index into ts) per launch
     auto aiff_decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of) -> int {
+        if (aiff->decode) return aiff->decode(as_is, dst_of, (const uint8_t *)e->tick_pcm_in.p);
         std::vector<sk::AiffElemJob> elems;
         std::vector<sk::AiffImaStream> imas;
         std::vector<sk::AiffImaUnit> ima_units;
@@ -5438,6 +5453,492 @@ int sk_tick_run_au(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, c
                      outs_cap, n_outs, out_bytes);
 } catch (...) {
     return sk::abi_caught("sk_tick_run_au");
+}
+
+}  // extern "C"
+
+// ---- FLAC (flac_stream.h, flac_decode.hip) ----------------------------------------------------------------------------------------
+
+namespace {
+
+inline uint32_t flac_width(uint32_t bits, uint32_t mode) {
+    return mode == sk::kFlacOutI32 ? 4u : mode == sk::kFlacOutI16Clamp ? 2u : (bits <= 8 ? 1u : bits <= 16 ? 2u : bits <= 24 ? 3u : 4u);
+}
+
+// the three launches over every frame of a call; mode = how k_flac_output writes (the contract's bytes, i32, i16 clamped)
+int flac_decode_frames(sk_engine *e, const sk_flac_frame_info *frames, uint32_t n, const uint8_t *bytes, bool on_device, uint8_t *out, size_t out_cap,
+                       size_t *out_len, int32_t *status, uint32_t mode) {
+    if (!e || !out_len || (n && (!frames || !bytes || !out || !status))) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (n == 0) return SK_OK;
+    std::vector<sk::FlacFrame> table(n);
+    uint64_t need = 0, ws_words = 0, bytes_len = 0, n_subs = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_flac_frame_info &f = frames[i];
+        if (f.channels == 0 || f.channels > 8 || f.bits_per_sample < 4 || f.bits_per_sample > 32 || f.block_size == 0 || f.block_size > 65536 ||
+            f.header_bytes < 6 || f.frame_bytes < (uint32_t)f.header_bytes + 3 || f.frame_bytes > (1u << 24))  // STREAMINFO counts a frame's bytes in 24 bits
+            return SK_ERR_INVALID_ARG;
+        sk::FlacFrame &t = table[i];
+        t.byte_offset = f.offset, t.byte_len = f.frame_bytes, t.block_size = f.block_size, t.ws_offset = (uint32_t)ws_words;
+        t.out_offset = need, t.sub0 = (uint32_t)n_subs;
+        t.header_bytes = f.header_bytes, t.channels = f.channels, t.assignment = f.assignment, t.bits = f.bits_per_sample;
+        need += (uint64_t)f.block_size * f.channels * flac_width(f.bits_per_sample, mode);
+        ws_words += (uint64_t)f.block_size * f.channels;
+        n_subs += f.channels;
+        bytes_len = std::max<uint64_t>(bytes_len, (uint64_t)f.offset + f.frame_bytes);
+        if (ws_words > 0x3fffffffu || bytes_len > 0x7fffffffu) return SK_ERR_INVALID_ARG;
+    }
+    if (need > out_cap) return SK_ERR_INVALID_ARG;
+    if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15)) return SK_ERR_INVALID_ARG;
+    std::vector<uint32_t> by_length(n);
+    for (uint32_t i = 0; i < n; ++i) by_length[i] = i;
+    std::stable_sort(by_length.begin(), by_length.end(), [&](uint32_t a, uint32_t b) { return frames[a].frame_bytes > frames[b].frame_bytes; });
+
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    // flac_in: [bytes (host form)] | frame table | order | statuses, each part 16-byte aligned
+    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t at_table = on_device ? 0 : up16((size_t)bytes_len), at_order = at_table + up16(n * sizeof(sk::FlacFrame)),
+                 at_status = at_order + up16(n * sizeof(uint32_t)), in_len = at_status + up16(n * sizeof(int32_t));
+    const size_t at_subs = up16((size_t)ws_words * 4), ws_len = at_subs + (size_t)n_subs * sizeof(sk::FlacSubframe);
+    SK_HIP(e->flac_in.reserve(in_len), "alloc flac input");
+    SK_HIP(e->flac_ws.reserve(ws_len), "alloc flac workspace");
+    uint8_t *d_in = (uint8_t *)e->flac_in.p, *d_ws = (uint8_t *)e->flac_ws.p, *d_out = out;
+    const uint8_t *d_bytes = bytes;
+    if (!on_device) {
+        SK_HIP(e->flac_out.reserve((size_t)need), "alloc flac output");
+        d_out = (uint8_t *)e->flac_out.p;
+        SK_HIP(hipMemcpyAsync(d_in, bytes, (size_t)bytes_len, hipMemcpyHostToDevice, e->stream), "H2D flac frames");
+        d_bytes = d_in;
+    }
+    SK_HIP(hipMemcpyAsync(d_in + at_table, table.data(), n * sizeof(sk::FlacFrame), hipMemcpyHostToDevice, e->stream), "H2D flac table");
+    SK_HIP(hipMemcpyAsync(d_in + at_order, by_length.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream), "H2D flac order");
+    // a record that no accepted frame wrote names no frame
+    SK_HIP(hipMemsetAsync(d_ws + at_subs, 0xff, (size_t)n_subs * sizeof(sk::FlacSubframe), e->stream), "clear flac records");
+    const sk::FlacFrame *d_table = (const sk::FlacFrame *)(d_in + at_table);
+    sk::FlacSubframe *d_subs = (sk::FlacSubframe *)(d_ws + at_subs);
+    int32_t *d_status = (int32_t *)(d_in + at_status);
+    SK_HIP(sk::launch_flac_residual(d_table, (const uint32_t *)(d_in + at_order), n, d_bytes, (uint32_t)bytes_len, (int32_t *)d_ws, d_subs, d_status,
+                                    e->stream), "launch flac residual");
+    SK_HIP(sk::launch_flac_restore(d_subs, (uint32_t)n_subs, (int32_t *)d_ws, d_status, e->stream), "launch flac restore");
+    SK_HIP(sk::launch_flac_output(d_table, n, d_subs, (const int32_t *)d_ws, d_status, d_out, mode, e->stream), "launch flac output");
+    SK_HIP(hipMemcpyAsync(status, d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H flac statuses");
+    SK_HIP(hipStreamSynchronize(e->stream), "flac sync");  // table and by_length leave scope with the call
+    if (!on_device) {
+        // a rejected frame's place in the caller's buffer stays as it was: the accepted frames are copied one run at a time
+        uint32_t i = 0;
+        while (i < n) {
+            if (status[i] != 0) {
+                ++i;
+                continue;
+            }
+            uint32_t j = i;
+            while (j < n && status[j] == 0) ++j;
+            const uint64_t from = table[i].out_offset, to = j < n ? table[j].out_offset : need;
+            SK_HIP(hipMemcpyAsync(out + from, d_out + from, (size_t)(to - from), hipMemcpyDeviceToHost, e->stream), "D2H flac");
+            i = j;
+        }
+        SK_HIP(hipStreamSynchronize(e->stream), "flac sync");
+    }
+    *out_len = (size_t)need;
+    return SK_OK;
+}
+
+// sk_tick_run_flac / sk_tick_flac_out_bound_on: checks the table and derives what the PCM tick's body works on, as aiff_tick_derive does --
+// per stream a little-endian source of the contract's format, per frame where its decoded PCM lies (16-byte aligned, frame after frame)
+// -- and the decode that stands in front of the body: the three launches of flac_decode.hip over the frames of each pass.
+struct FlacDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;   // the decoded layout
+    std::vector<uint32_t> first;      // per stream: its first frame
+    AiffTick tick;
+    // what the two passes (streams that go on through the body, streams delivered as decoded) upload and get back: alive until the
+    // tick's last wait
+    std::vector<sk::FlacFrame> table[2];
+    std::vector<uint32_t> order[2], index[2];  // index: row of the table -> frame of the call
+    std::vector<int32_t> status[2];
+};
+
+int flac_tick_derive(const sk_flac_tick_stream *fs, uint32_t n_streams, const sk_flac_frame_info *frames, uint32_t n_frames, size_t bytes_len,
+                     FlacDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.assign(n_frames, sk_pcm_unit{});
+    d.first.assign(n_streams, 0);
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    uint64_t at = 0, cursor = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_flac_tick_stream &f = fs[i];
+        if (f.channels == 0 || f.channels > 8 || f.bits_per_sample < 4 || f.bits_per_sample > 32) return SK_ERR_INVALID_ARG;
+        const uint32_t width = flac_width(f.bits_per_sample, sk::kFlacOutContract);
+        const bool plain = !f.resample && f.out_bits == width * 8 && f.out_channels == f.channels;
+        // anything to change: what sk_tick_run_pcm takes, i.e. samples that fill their 16 / 24 / 32 bits
+        if (!plain && f.bits_per_sample != 16 && f.bits_per_sample != 24 && f.bits_per_sample != 32) return SK_ERR_UNSUPPORTED;
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = f.stream, t.n_units = f.n_units, t.channels = f.channels, t.resample = f.resample, t.flush = f.flush;
+        // a stream delivered as decoded is planned as s16 whatever its width: its records are rewritten behind the body
+        t.out_bits = plain ? 16 : f.out_bits, t.out_channels = f.out_channels;
+        t.format = (uint8_t)(plain || width == 2 ? SK_FMT_S16LE : (width == 3 ? SK_FMT_S24LE : SK_FMT_S32LE));
+        d.tick.plain[i] = plain;
+        d.first[i] = (uint32_t)at;
+        if (at + f.n_units > n_frames) return SK_ERR_INVALID_ARG;
+        for (uint32_t u = 0; u < f.n_units; ++u) {
+            const sk_flac_frame_info &fr = frames[at + u];
+            if (fr.channels != f.channels || fr.bits_per_sample != f.bits_per_sample || fr.block_size == 0 || fr.block_size > 65536 || fr.header_bytes < 6 ||
+                fr.frame_bytes < (uint32_t)fr.header_bytes + 3 || fr.frame_bytes > (1u << 24) || fr.offset % 16)
+                return SK_ERR_INVALID_ARG;
+            if (fr.offset > bytes_len || fr.frame_bytes > bytes_len - fr.offset) return SK_ERR_INVALID_ARG;
+            const uint64_t decoded = (uint64_t)fr.block_size * f.channels * width;
+            d.units[at + u] = sk_pcm_unit{cursor, (uint32_t)decoded, 0};
+            cursor += (decoded + 15) & ~15ull;
+        }
+        at += f.n_units;
+    }
+    if (cursor > 0x7fffffffull || bytes_len > 0x7fffffffull) return SK_ERR_INVALID_ARG;
+    d.tick.decoded_len = (size_t)cursor;
+    return at == n_frames ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// one pass of the decode in front of the body: the frames of the streams whose `plain` is as_is, each to where dst_of puts it
+int flac_tick_decode(sk_engine *e, const sk_flac_frame_info *frames, uint32_t n_frames, size_t bytes_len, FlacDerived &d, bool as_is,
+                     const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+    const int p = as_is ? 1 : 0;
+    std::vector<sk::FlacFrame> &table = d.table[p];
+    std::vector<uint32_t> &order = d.order[p], &index = d.index[p];
+    std::vector<uint8_t *> dst;
+    for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
+        if ((d.tick.plain[i] != 0) != as_is) continue;
+        for (uint32_t u = 0; u < d.ts[i].n_units; ++u) index.push_back(d.first[i] + u), dst.push_back(dst_of(i, u));
+    }
+    const uint32_t n = (uint32_t)index.size();
+    if (n == 0) return SK_OK;
+    uint8_t *base = *std::min_element(dst.begin(), dst.end());
+    if (!as_is) {
+        // what a rejected frame leaves for the body to convert is silence, not whatever an earlier tick had there
+        size_t extent = 0;
+        for (uint32_t k = 0; k < n; ++k) extent = std::max(extent, (size_t)(dst[k] - base) + d.units[index[k]].byte_len);
+        SK_HIP(hipMemsetAsync(base, 0, extent, e->stream), "clear tick flac decoded");
+    }
+    uint64_t ws_words = 0, n_subs = 0;
+    table.resize(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        const sk_flac_frame_info &f = frames[index[k]];
+        sk::FlacFrame &t = table[k];
+        t.byte_offset = f.offset, t.byte_len = f.frame_bytes, t.block_size = f.block_size, t.ws_offset = (uint32_t)ws_words;
+        t.out_offset = (uint64_t)(dst[k] - base), t.sub0 = (uint32_t)n_subs;
+        t.header_bytes = f.header_bytes, t.channels = f.channels, t.assignment = f.assignment, t.bits = f.bits_per_sample;
+        ws_words += (uint64_t)f.block_size * f.channels;
+        n_subs += f.channels;
+    }
+    if (ws_words > 0x3fffffffu) return SK_ERR_INVALID_ARG;
+    order.resize(n);
+    for (uint32_t k = 0; k < n; ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return table[a].byte_len > table[b].byte_len; });
+    // each pass has its own part of flac_in, sized for every frame of the call: table | order | statuses
+    const auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t at_order = up16(n_frames * sizeof(sk::FlacFrame)), at_status = at_order + up16(n_frames * sizeof(uint32_t)),
+                 part = at_status + up16(n_frames * sizeof(int32_t));
+    const size_t at_subs = up16((size_t)ws_words * 4);
+    SK_HIP(e->flac_in.reserve(2 * part), "alloc tick flac tables");
+    SK_HIP(e->flac_ws.reserve(at_subs + (size_t)n_subs * sizeof(sk::FlacSubframe)), "alloc tick flac workspace");
+    uint8_t *d_in = (uint8_t *)e->flac_in.p + (size_t)p * part, *d_ws = (uint8_t *)e->flac_ws.p;
+    SK_HIP(hipMemcpyAsync(d_in, table.data(), n * sizeof(sk::FlacFrame), hipMemcpyHostToDevice, e->stream), "H2D tick flac table");
+    SK_HIP(hipMemcpyAsync(d_in + at_order, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream), "H2D tick flac order");
+    SK_HIP(hipMemsetAsync(d_ws + at_subs, 0xff, (size_t)n_subs * sizeof(sk::FlacSubframe), e->stream), "clear tick flac records");
+    const sk::FlacFrame *d_table = (const sk::FlacFrame *)d_in;
+    sk::FlacSubframe *d_subs = (sk::FlacSubframe *)(d_ws + at_subs);
+    int32_t *d_status = (int32_t *)(d_in + at_status);
+    SK_HIP(sk::launch_flac_residual(d_table, (const uint32_t *)(d_in + at_order), n, d_src, (uint32_t)bytes_len, (int32_t *)d_ws, d_subs, d_status, e->stream),
+           "tick flac residual");
+    SK_HIP(sk::launch_flac_restore(d_subs, (uint32_t)n_subs, (int32_t *)d_ws, d_status, e->stream), "tick flac restore");
+    SK_HIP(sk::launch_flac_output(d_table, n, d_subs, (const int32_t *)d_ws, d_status, base, sk::kFlacOutContract, e->stream), "tick flac output");
+    d.status[p].assign(n, 0);
+    SK_HIP(hipMemcpyAsync(d.status[p].data(), d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H tick flac statuses");
+    return SK_OK;
+}
+
+}  // namespace
+
+// FlacDecoder: the reader in front of the decode stage.  Frames wait in `pending` (their bytes packed one after the other) until a
+// call has room for them.
+struct sk_flac_decoder {
+    sk_engine *eng = nullptr;
+    sk_flac::Reader reader;
+    std::vector<sk_flac_frame_info> pending;  // offsets into pending_bytes
+    std::vector<uint8_t> pending_bytes;
+    size_t next = 0;  // first pending frame not decoded yet
+    uint64_t frames_decoded = 0;
+    bool failed = false;
+    std::string error;
+    std::vector<uint8_t> staging;
+    std::vector<int32_t> status;
+};
+
+namespace {
+
+int flac_decoder_fail(sk_flac_decoder *d, const std::string &text) {
+    d->failed = true;
+    d->error = text;
+    return SK_FLAC_ERR_STREAM;
+}
+
+int flac_decoder_decode(sk_flac_decoder *d, const uint8_t *input, size_t len, void *out, size_t out_cap, size_t *written, uint32_t mode) {
+    if (!d || !written || (len && !input) || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    if (d->failed) return SK_FLAC_ERR_STREAM;
+    // Everything the reader can cut out of its buffer and the input, a table of 256 frames at a time.  An empty input finalises the
+    // reader only when no frame waits for room: until then a call without input is the caller fetching what an earlier call could
+    // not give it, in the middle of the stream as well.
+    const bool finalise = len == 0 && d->next == d->pending.size();
+    if (len != 0 || finalise) {
+        sk_flac_frame_info got[256];
+        for (bool first = true;; first = false) {
+            uint32_t n = 0;
+            const uint8_t *data = nullptr;
+            if (!d->reader.feed(first ? input : nullptr, first ? len : 0, finalise, got, 256, &n, &data)) return flac_decoder_fail(d, d->reader.error());
+            for (uint32_t i = 0; i < n; ++i) {
+                sk_flac_frame_info f = got[i];
+                const size_t at = (d->pending_bytes.size() + 15) & ~(size_t)15;
+                d->pending_bytes.resize(at);
+                d->pending_bytes.insert(d->pending_bytes.end(), data + f.offset, data + f.offset + f.frame_bytes);
+                f.offset = (uint32_t)at;
+                d->pending.push_back(f);
+            }
+            if (n < 256) break;
+        }
+    }
+    // whole frames that fit
+    const size_t sample_bytes = mode == sk::kFlacOutI32 ? 4 : 2;
+    size_t take = 0, samples = 0;
+    while (d->next + take < d->pending.size()) {
+        const sk_flac_frame_info &f = d->pending[d->next + take];
+        const size_t more = (size_t)f.block_size * f.channels;
+        if (samples + more > out_cap) break;
+        samples += more, ++take;
+    }
+    if (take == 0) return d->next < d->pending.size() ? SK_ERR_CAPACITY : SK_OK;
+    d->status.assign(take, 0);
+    d->staging.resize(samples * sample_bytes);
+    size_t out_len = 0;
+    const int rc = flac_decode_frames(d->eng, d->pending.data() + d->next, (uint32_t)take, d->pending_bytes.data(), false, d->staging.data(),
+                                      d->staging.size(), &out_len, d->status.data(), mode);
+    if (rc != SK_OK) return rc;
+    for (size_t i = 0; i < take; ++i)
+        if (d->status[i] != 0)
+            return flac_decoder_fail(d, "FLAC frame " + std::to_string(d->frames_decoded + i) + ": " +
+                                            (d->status[i] == SK_ERR_UNSUPPORTED ? "32-bit samples with a side channel are not supported"
+                                                                                : "the subframes break the syntax or miss the frame's end"));
+    std::memcpy(out, d->staging.data(), out_len);
+    d->frames_decoded += take;
+    d->next += take;
+    if (d->next == d->pending.size()) d->pending.clear(), d->pending_bytes.clear(), d->next = 0;
+    *written = samples;
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sk_flac_parse_header(const uint8_t *data, size_t len, const sk_flac_streaminfo *info, sk_flac_frame_info *out) try {
+    sk::abi_enter();
+    if ((len && !data) || !out) return SK_ERR_INVALID_ARG;
+    return sk_flac::parse_header(data, len, info, out);
+} catch (...) {
+    return sk::abi_caught("sk_flac_parse_header");
+}
+
+int sk_flac_scan(const uint8_t *data, size_t len, const sk_flac_streaminfo *info, int final, sk_flac_frame_info *frames, uint32_t cap,
+                 uint32_t *n_frames, size_t *consumed) try {
+    sk::abi_enter();
+    if ((len && !data) || (cap && !frames) || !n_frames || !consumed || len > 0x7fffffffu) return SK_ERR_INVALID_ARG;
+    return sk_flac::scan(data, len, info, final != 0, frames, cap, n_frames, consumed);
+} catch (...) {
+    return sk::abi_caught("sk_flac_scan");
+}
+
+int sk_flac_reader_create(sk_flac_reader **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_flac_reader();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_flac_reader_create");
+}
+
+void sk_flac_reader_destroy(sk_flac_reader *r) try {
+    sk::abi_enter();
+    delete r;
+} catch (...) {
+    (void)sk::abi_caught("sk_flac_reader_destroy");
+}
+
+int sk_flac_reader_add(sk_flac_reader *r, const uint8_t *bytes, size_t len, sk_flac_frame_info *frames, uint32_t cap, uint32_t *n_frames,
+                       const uint8_t **data) try {
+    sk::abi_enter();
+    if (!r || (len && !bytes) || (cap && !frames) || !n_frames || len > 0x7fffffffu) return SK_ERR_INVALID_ARG;
+    return r->reader.add(bytes, len, frames, cap, n_frames, data) ? SK_OK : SK_FLAC_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_flac_reader_add");
+}
+
+int sk_flac_reader_info(const sk_flac_reader *r, sk_flac_info *info) try {
+    sk::abi_enter();
+    if (!r || !info) return SK_ERR_INVALID_ARG;
+    std::memset(info, 0, sizeof *info);
+    info->buffered_bytes = (uint32_t)r->reader.buffered_bytes();
+    info->frames = r->reader.frames();
+    if (r->reader.have_info()) info->streaminfo = r->reader.info(), info->have_streaminfo = 1;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_flac_reader_info");
+}
+
+const char *sk_flac_reader_last_error(const sk_flac_reader *r) try {
+    sk::abi_enter();
+    return r ? r->reader.error().c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_flac_reader_last_error");
+    return "";
+}
+
+int sk_flac_decode_frames(sk_engine *e, const sk_flac_frame_info *frames, uint32_t n, const uint8_t *bytes, uint8_t *out, size_t out_cap,
+                          size_t *out_len, int32_t *status_per_frame) try {
+    sk::abi_enter();
+    return flac_decode_frames(e, frames, n, bytes, false, out, out_cap, out_len, status_per_frame, sk::kFlacOutContract);
+} catch (...) {
+    return sk::abi_caught("sk_flac_decode_frames");
+}
+
+int sk_flac_decode_frames_dev(sk_engine *e, const sk_flac_frame_info *frames, uint32_t n, const uint8_t *d_bytes, uint8_t *d_out, size_t out_cap,
+                              size_t *out_len, int32_t *status_per_frame) try {
+    sk::abi_enter();
+    return flac_decode_frames(e, frames, n, d_bytes, true, d_out, out_cap, out_len, status_per_frame, sk::kFlacOutContract);
+} catch (...) {
+    return sk::abi_caught("sk_flac_decode_frames_dev");
+}
+
+size_t sk_tick_flac_out_bound_on(sk_engine *e, const sk_flac_tick_stream *fs, uint32_t n_streams, const sk_flac_frame_info *frames, uint32_t n_frames,
+                                 uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!fs && n_streams) || (!frames && n_frames)) return 0;
+    FlacDerived d;
+    if (flac_tick_derive(fs, n_streams, frames, n_frames, 0x7fffffffu, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), n_frames, max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_flac_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_flac(sk_engine *e, const sk_flac_tick_stream *fs, uint32_t n_streams, const sk_flac_frame_info *frames, uint32_t n_frames,
+                     const uint8_t *bytes, size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs,
+                     size_t *out_bytes, int32_t *status_per_frame) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && !fs) || (n_frames && (!frames || !bytes || !status_per_frame))) return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    FlacDerived d;
+    int rc = flac_tick_derive(fs, n_streams, frames, n_frames, bytes_len, d);
+    if (rc != SK_OK) return rc;
+    d.tick.decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+        return flac_tick_decode(e, frames, n_frames, bytes_len, d, as_is, dst_of, d_src);
+    };
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), n_frames, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, &d.tick);
+    if (rc != SK_OK) return rc;
+    for (int p = 0; p < 2; ++p)
+        for (size_t k = 0; k < d.index[p].size(); ++k) status_per_frame[d.index[p][k]] = d.status[p][k];
+    // the records of a stream delivered as decoded say what its frames are; a rejected frame marks its record, or -- behind a
+    // conversion, where records and frames do not correspond -- every record of its stream in this tick
+    std::vector<uint32_t> seen(n_streams, 0);
+    for (uint32_t k = 0; k < *n_outs; ++k) {
+        sk_tick_output &o = outs[k];
+        const uint32_t i = o.stream_index;
+        if (d.tick.plain[i]) {
+            const uint32_t g = d.first[i] + seen[i]++;
+            o.frames = frames[g].block_size, o.channels = fs[i].channels, o.status = status_per_frame[g];
+            o.bits = (uint8_t)(flac_width(fs[i].bits_per_sample, sk::kFlacOutContract) * 8);
+        } else {
+            for (uint32_t u = 0; u < fs[i].n_units && o.status == 0; ++u) o.status = status_per_frame[d.first[i] + u];
+        }
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_flac");
+}
+
+int sk_flac_decoder_create(sk_engine *e, sk_flac_decoder **out) try {
+    sk::abi_enter();
+    if (!e || !out) return SK_ERR_INVALID_ARG;
+    *out = new sk_flac_decoder();
+    (*out)->eng = e;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_flac_decoder_create");
+}
+
+void sk_flac_decoder_destroy(sk_flac_decoder *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_flac_decoder_destroy");
+}
+
+int sk_flac_decoder_reset(sk_flac_decoder *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    sk_engine *e = d->eng;
+    *d = sk_flac_decoder();
+    d->eng = e;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_flac_decoder_reset");
+}
+
+int sk_flac_decoder_info(const sk_flac_decoder *d, uint32_t *sample_rate, uint8_t *channels, uint8_t *bits_per_sample, uint64_t *frames_decoded) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    const bool have = d->reader.have_info();
+    if (sample_rate) *sample_rate = have ? d->reader.info().sample_rate : 0;
+    if (channels) *channels = have ? d->reader.info().channels : 0;
+    if (bits_per_sample) *bits_per_sample = have ? d->reader.info().bits_per_sample : 0;
+    if (frames_decoded) *frames_decoded = d->frames_decoded;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_flac_decoder_info");
+}
+
+size_t sk_flac_decoder_pending_samples(const sk_flac_decoder *d) try {
+    sk::abi_enter();
+    size_t n = 0;
+    for (size_t k = d ? d->next : 0; d && k < d->pending.size(); ++k) n += (size_t)d->pending[k].block_size * d->pending[k].channels;
+    return n;
+} catch (...) {
+    (void)sk::abi_caught("sk_flac_decoder_pending_samples");
+    return 0;
+}
+
+int sk_flac_decoder_decode_i32(sk_flac_decoder *d, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return flac_decoder_decode(d, input, len, out, out_cap, written, sk::kFlacOutI32);
+} catch (...) {
+    return sk::abi_caught("sk_flac_decoder_decode_i32");
+}
+
+int sk_flac_decoder_decode_i16(sk_flac_decoder *d, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return flac_decoder_decode(d, input, len, out, out_cap, written, sk::kFlacOutI16Clamp);
+} catch (...) {
+    return sk::abi_caught("sk_flac_decoder_decode_i16");
+}
+
+const char *sk_flac_decoder_last_error(const sk_flac_decoder *d) try {
+    sk::abi_enter();
+    return d ? d->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_flac_decoder_last_error");
+    return "";
 }
 
 }  // extern "C"

@@ -113,6 +113,10 @@ struct PipelineGpuHooks {
     int (*tick_aiff)(sk_engine *, sk_aiff_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
                      sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_aiff
     size_t (*tick_aiff_out_bound)(sk_engine *, const sk_aiff_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
+    // sk_tick_run_flac / sk_tick_flac_out_bound_on: the FLAC streams' frames
+    int (*tick_flac)(sk_engine *, const sk_flac_tick_stream *, uint32_t, const sk_flac_frame_info *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
+                     sk_tick_output *, uint32_t, uint32_t *, size_t *, int32_t *) = nullptr;
+    size_t (*tick_flac_out_bound)(sk_engine *, const sk_flac_tick_stream *, uint32_t, const sk_flac_frame_info *, uint32_t, uint32_t *) = nullptr;
     // the engine's pool of wide PCM streams (3 ... 8 channels); with these absent such a stream is refused as before
     // Layer I / II streams: the host front (mp12_bitstream.cpp) and the tick that takes their frames; with these absent such a stream
     // ends with SK_ERR_UNSUPPORTED

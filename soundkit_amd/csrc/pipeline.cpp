@@ -17,6 +17,7 @@
 #include "../../include/soundkit_amd.h"
 #include "sk_abi.h"
 #include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
+#include "flac_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
 #include <hip/hip_runtime.h>
@@ -86,6 +87,10 @@ struct PStream {
     uint8_t aiff_enc = 0;
     bool aiff_plain = false;  // nothing to change behind the decode
     sk_aiff_ima_state aiff_ima[2] = {};
+    // FLAC streams (FormatDecoder::Flac): the reader; its frames are the units of the FLAC tick, which decodes them in front of what the
+    // PCM tick would do.  flac_plain: nothing to change behind the decode (one AudioData per frame, in the depth STREAMINFO names)
+    std::unique_ptr<sk_flac::Reader> flac;
+    bool flac_plain = false;
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -93,8 +98,8 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -152,6 +157,11 @@ struct Batch {
     std::vector<sk_aiff_tick_stream> aiff_ts;
     std::vector<sk_pcm_unit> aiff_units;
     std::vector<uint32_t> aiff_entry;
+    // FLAC streams' frames (sk_tick_run_flac), staged in pcm_bytes as well; the statuses the device gives them
+    std::vector<sk_flac_tick_stream> flac_ts;
+    std::vector<sk_flac_frame_info> flac_frames;
+    std::vector<uint32_t> flac_entry;
+    std::vector<int32_t> flac_status;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -180,6 +190,9 @@ struct Batch {
         aiff_ts.clear();
         aiff_units.clear();
         aiff_entry.clear();
+        flac_ts.clear();
+        flac_frames.clear();
+        flac_entry.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -299,6 +312,7 @@ void release_device_side(sk_lane *p, PStream &s) {
         s.wav.reset();
         s.raw.reset();
         s.aiff.reset();
+        s.flac.reset();
     }
     if (engine_stream != kNoStream) (void)sk_stream_close(p->engine, engine_stream);  // also drops its resampler
     if (fe) sk_aac_decoder_destroy(fe);
@@ -331,6 +345,7 @@ struct Parsed {  // what one worker pass produced for one stream
     bool pcm = false, more = false;
     std::vector<uint8_t> pcm_bytes;
     std::vector<sk_pcm_unit> pcm_units;
+    std::vector<sk_flac_frame_info> flac_frames;  // a FLAC stream's pass: one per unit, offset into pcm_bytes
     std::vector<Output> pre;
 };
 
@@ -389,6 +404,9 @@ uint8_t sniff_codec(const uint8_t *d, size_t n) {
     } else if (n > 0 && n < 4 && std::memcmp(d, "FORM", n) == 0) {
         return 0;
     }
+    // fLaC -> native FLAC (AudioType::Flac); fewer than 4 bytes that match so far: wait
+    if (n >= 4 && std::memcmp(d, "fLaC", 4) == 0) return kCodecFlac;
+    if (n > 0 && n < 4 && std::memcmp(d, "fLaC", n) == 0) return 0;
     if (n >= 3 && d[0] == 'I' && d[1] == 'D' && d[2] == '3') return kCodecMp3;
     for (size_t i = 0; i + 1 < n; ++i)
         if (d[i] == 0xff && (d[i + 1] & 0xe0) == 0xe0) return ((d[i + 1] >> 1) & 3) == 0 ? kCodecAac : kCodecMp3;
@@ -662,7 +680,9 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     };
     uint32_t rate, channels, bits;
     bool is_float, big_endian = false;
-    if (s.aiff) {  // what the decoder emits (the output contract), not what the file holds: apply_output_options sees only that
+    if (s.flac) {  // STREAMINFO's: the AudioData of a FLAC frame carries the stream's own depth (create_audio_data_i32_with_bits, lib.rs:3191-3236)
+        rate = s.flac->info().sample_rate, channels = s.flac->info().channels, bits = s.flac->info().bits_per_sample, is_float = false;
+    } else if (s.aiff) {  // what the decoder emits (the output contract), not what the file holds: apply_output_options sees only that
         rate = s.aiff->sample_rate(), channels = s.aiff->channels(), bits = s.aiff->bits(), is_float = s.aiff->is_float();
         s.aiff_enc = (uint8_t)s.aiff->encoding();
     } else if (s.wav) {
@@ -683,6 +703,15 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     const uint32_t target_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : bits;
     const uint32_t target_channels = s.opt.output_channels ? s.opt.output_channels : channels;
     const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+    if (s.flac && (!hooks.tick_flac || !hooks.tick_flac_out_bound))
+        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: FLAC decoding needs the device tick, which this build lacks");
+    if (s.flac && target_rate == rate && target_bits == bits && target_channels == channels) {  // every frame has per-sample work: the tick's
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmFlacTick;
+        s.flac_plain = true;
+        return true;
+    }
     if (target_rate == rate && target_bits == bits && target_channels == channels) {
         // sowt / 23ni are the contract's bytes already; every other encoding has per-sample work, which is the tick's
         if (!s.aiff || s.aiff_enc == SK_AIFF_S16LE || s.aiff_enc == SK_AIFF_S32LE) {
@@ -715,8 +744,100 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.aiff ? kPcmAiffTick : kPcmTick;
+    s.pcm_route = s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick);
     return true;
+}
+
+// A FLAC stream's pass: the reader cuts whole frames out of the chunks (marker and metadata first), and whole frames are what the
+// stream is budgeted in -- `room` AudioData (one per frame, or one per completed 4096-frame chunk through the resampler) and the units
+// of one stream in a tick.  Frames the reader holds beyond that come with the next pass (r.more).  A stream the reader rejects ends
+// with its text; the frames in front of the damage have gone out with the passes before.
+void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    auto fail = [&](int32_t st, const std::string &msg) {
+        r.failed = true;
+        r.fail_status = st;
+        r.fail_msg = msg;
+    };
+    if (!s.flac) {
+        s.flac.reset(new sk_flac::Reader());
+        s.pcm_detected = true;
+    }
+    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
+    uint32_t outputs = 0;
+    std::vector<sk_flac_frame_info> got;
+    // true: go on; the frames of one feed (all of them: the reader has let go of them) are staged
+    auto feed = [&](const uint8_t *data, size_t len, bool final) -> bool {
+        const uint32_t cap = per_pass - (uint32_t)r.pcm_units.size();
+        got.resize(cap);
+        uint32_t n = 0;
+        const uint8_t *base = nullptr;
+        if (!s.flac->feed(data, len, final, got.data(), cap, &n, &base)) {
+            fail(SK_FLAC_ERR_STREAM, "Decoding failed: " + s.flac->error());
+            return false;
+        }
+        if (n && !s.pcm_route && !pcm_open(p, s, r)) return false;
+        for (uint32_t k = 0; k < n; ++k) {
+            sk_flac_frame_info f = got[k];
+            const size_t at = (r.pcm_bytes.size() + 15) & ~(size_t)15;
+            r.pcm_bytes.resize(at);
+            r.pcm_bytes.insert(r.pcm_bytes.end(), base + f.offset, base + f.offset + f.frame_bytes);
+            r.pcm_units.push_back(sk_pcm_unit{at, f.frame_bytes, 0});
+            f.offset = (uint32_t)at;
+            r.flac_frames.push_back(f);
+            if (s.resample) {
+                outputs += (s.pcm_fill + f.block_size) / 4096;
+                s.pcm_fill = (s.pcm_fill + f.block_size) % 4096;
+            } else {
+                outputs += 1;
+            }
+        }
+        if (n == cap) r.more = true;  // the reader may hold further frames
+        return true;
+    };
+    // what a feed can stage: everything the reader holds, each frame padded to 16 bytes
+    auto fits = [&](size_t next) {
+        return r.pcm_bytes.size() + s.flac->buffered_bytes() + next + 16 * (size_t)per_pass + 4096 <= kPcmTickBytes;
+    };
+    // the pending bytes of the detection (parse_some gathered them) go in first
+    if (s.pending.size() > s.pending_pos) {
+        std::vector<uint8_t> first(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
+        s.pending.clear();
+        s.pending.shrink_to_fit();
+        s.pending_pos = 0;
+        if (!feed(first.data(), first.size(), false)) return;
+    } else if (s.more && !feed(nullptr, 0, s.saw_eof && s.flac->finalised())) {  // frames left over by the pass before
+        return;
+    }
+    while (!r.failed && !r.more) {
+        if (outputs >= room || r.pcm_units.size() >= per_pass) {
+            r.more = true;
+            break;
+        }
+        if (s.saw_eof) {  // the finalising feed: the last frame ends with the data; a truncated tail ends the stream with its text
+            if (!feed(nullptr, 0, true)) break;
+            if (!r.more) r.eof = true;
+            break;
+        }
+        std::vector<uint8_t> chunk;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            if (s.in.empty()) break;
+            if (!s.in.front().empty() && !r.pcm_units.empty() && !fits(s.in.front().size())) {
+                r.more = true;
+                break;
+            }
+            chunk = std::move(s.in.front());
+            s.in.pop_front();
+        }
+        if (chunk.empty()) {
+            s.saw_eof = true;
+            continue;
+        }
+        s.queued_bytes.fetch_sub(chunk.size());
+        if (!feed(chunk.data(), chunk.size(), false)) break;
+    }
+    r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
 
 // A WAV / raw PCM stream's pass.  Unit boundaries are the reference worker's: one `process` per received chunk, each giving at most one
@@ -862,6 +983,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             return;
         }
         parse_some_mp3(p, s, limit, r);
+        return;
+    }
+    if (s.codec == kCodecFlac) {
+        parse_some_flac(p, s, room, r);
         return;
     }
     if (s.codec == kCodecWav || s.codec == kCodecRawPcm || s.codec == kCodecAiff) {
@@ -1167,6 +1292,28 @@ void worker_body(sk_lane *p) {
                         u.byte_offset += pcm_at;
                         b->aiff_units.push_back(u);
                     }
+                } else if (s.pcm_route == kPcmFlacTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
+                    pcm_at = b->pcm_used;
+                    b->pcm_used += r.pcm_bytes.size();
+                    const sk_flac_streaminfo &si = s.flac->info();
+                    const uint32_t width = si.bits_per_sample <= 8 ? 1 : (si.bits_per_sample <= 16 ? 2 : (si.bits_per_sample <= 24 ? 3 : 4));
+                    sk_flac_tick_stream ft{};
+                    ft.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
+                    ft.n_units = (uint32_t)r.flac_frames.size();
+                    ft.channels = s.channels;
+                    ft.bits_per_sample = si.bits_per_sample;
+                    // as decoded: the contract's width (the record's depth is put back at delivery); else what the options ask for
+                    ft.out_bits = (uint8_t)(s.flac_plain ? 8 * width : (s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits));
+                    ft.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
+                    ft.resample = s.resample ? 1 : 0;
+                    ft.flush = (r.eof && s.resample) ? 1 : 0;
+                    b->flac_ts.push_back(ft);
+                    be.pcm_row = true;
+                    b->flac_entry.push_back((uint32_t)b->entries.size());
+                    for (sk_flac_frame_info f : r.flac_frames) {
+                        f.offset += (uint32_t)pcm_at;
+                        b->flac_frames.push_back(f);
+                    }
                 } else if (s.pcm_route == kPcmTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
                     pcm_at = b->pcm_used;
                     b->pcm_used += r.pcm_bytes.size();
@@ -1282,16 +1429,19 @@ void submit_body(sk_lane *p) {
             b->entry_row[i] = (uint32_t)b->row_of.size();
             b->row_of.push_back(i);
         }
-        uint32_t max_out = 0, pcm_max_out = 0, aiff_max_out = 0;
+        uint32_t max_out = 0, pcm_max_out = 0, aiff_max_out = 0, flac_max_out = 0;
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
         const sk_mp3_internal::PipelineGpuHooks &pcm_hooks = sk_mp3_internal::pipeline_gpu_hooks();
-        if (!ts.empty() || !b->pcm_ts.empty() || !b->aiff_ts.empty()) {
+        if (!ts.empty() || !b->pcm_ts.empty() || !b->aiff_ts.empty() || !b->flac_ts.empty()) {
             size_t bound = ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out);
             if (!b->aiff_ts.empty())  // ... and the AIFF tick's behind those
                 bound += 16 + pcm_hooks.tick_aiff_out_bound(p->engine, b->aiff_ts.data(), (uint32_t)b->aiff_ts.size(), b->aiff_units.data(),
                                                             (uint32_t)b->aiff_units.size(), &aiff_max_out);
+            if (!b->flac_ts.empty())  // ... the FLAC tick's
+                bound += 16 + pcm_hooks.tick_flac_out_bound(p->engine, b->flac_ts.data(), (uint32_t)b->flac_ts.size(), b->flac_frames.data(),
+                                                            (uint32_t)b->flac_frames.size(), &flac_max_out);
             if (!b->pcm_ts.empty())  // the PCM tick's outputs follow the other tick's in the same buffer
                 bound += 16 + pcm_hooks.tick_pcm_out_bound(p->engine, b->pcm_ts.data(), (uint32_t)b->pcm_ts.size(), b->pcm_units.data(),
                                                            (uint32_t)b->pcm_units.size(), &pcm_max_out);
@@ -1313,7 +1463,8 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            if (b->recs.size() < (size_t)max_out + pcm_max_out + aiff_max_out) b->recs.resize((size_t)max_out + pcm_max_out + aiff_max_out);
+            if (b->recs.size() < (size_t)max_out + pcm_max_out + aiff_max_out + flac_max_out)
+                b->recs.resize((size_t)max_out + pcm_max_out + aiff_max_out + flac_max_out);
         }
         if (!ts.empty() && b->rc == SK_OK && !b->mpa_recs.empty()) {
             // Layer I / II frames in this tick: the tick that takes them, with everything else in the lane's form beside them
@@ -1407,6 +1558,28 @@ void submit_body(sk_lane *p) {
                 used = base + aiff_used;
             }
         }
+        if (b->rc == SK_OK && !b->flac_ts.empty()) {  // the FLAC streams' tick of this round
+            const uint32_t first_row = (uint32_t)b->row_of.size();
+            const size_t base = (used + 15) & ~(size_t)15;
+            uint32_t n_flac_out = 0;
+            size_t flac_used = 0;
+            b->flac_status.assign(b->flac_frames.size() + 1, 0);
+            b->rc = pcm_hooks.tick_flac(p->engine, b->flac_ts.data(), (uint32_t)b->flac_ts.size(), b->flac_frames.data(), (uint32_t)b->flac_frames.size(),
+                                        b->pcm_bytes, b->pcm_used, b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, flac_max_out,
+                                        &n_flac_out, &flac_used, b->flac_status.data());
+            if (b->rc == SK_OK) {
+                for (uint32_t k = 0; k < n_flac_out; ++k) {
+                    b->recs[b->n_out + k].stream_index += first_row;
+                    b->recs[b->n_out + k].byte_offset += base;
+                }
+                b->n_out += n_flac_out;
+                for (uint32_t row = 0; row < b->flac_entry.size(); ++row) {
+                    b->entry_row[b->flac_entry[row]] = first_row + row;
+                    b->row_of.push_back(b->flac_entry[row]);
+                }
+                used = base + flac_used;
+            }
+        }
         if (b->rc == SK_OK && !b->pcm_ts.empty()) {  // the PCM streams' tick of this round, behind the other one
             const uint32_t first_row = (uint32_t)b->row_of.size();
             const size_t base = (used + 15) & ~(size_t)15;
@@ -1430,7 +1603,8 @@ void submit_body(sk_lane *p) {
         p->submit_where = 4;
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
-        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_units.size() + (uint32_t)b->aiff_units.size());
+        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_units.size() + (uint32_t)b->aiff_units.size() +
+                              (uint32_t)b->flac_frames.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -1451,6 +1625,9 @@ void submit_body(sk_lane *p) {
 // text comes from parsing the entry's access units of this tick once more on the host (errors are rare, and an entry holds
 // at most max_stream_frames_per_tick units).
 std::string device_error_text(sk_lane *p, const Batch *b, uint32_t entry, const PStream &s, int32_t status) {
+    if (s.codec == kCodecFlac)
+        return status == SK_ERR_UNSUPPORTED ? "Decoding failed: FLAC frame rejected: 32-bit samples with a side channel are not supported"
+                                            : "Decoding failed: FLAC frame rejected: the subframes break the syntax or miss the frame's end";
     std::string msg = "Decoding failed: invalid AAC config: frame rejected by the synthesis engine";
     if (!(p->cfg.gpu_entropy && status <= -101 && status >= -108)) return msg;
     msg = std::string("Decoding failed: ") + sk_strerror(status);  // found on the device (stereo tools, TNS) or in the unit's tail
@@ -1543,7 +1720,7 @@ void deliver_body(sk_lane *p) {
                     Output o;
                     o.rate = s.opt.output_sample_rate ? s.opt.output_sample_rate : s.rate;
                     o.frames = r.frames;
-                    o.bits = r.bits;
+                    o.bits = s.flac_plain ? s.pcm_bits : r.bits;  // a FLAC frame as decoded: the stream's depth, in the contract's width
                     o.channels = r.channels;
                     o.flags = (r.reserved & SK_TICK_OUT_FLOAT) ? SK_AUDIO_FLOAT : 0;
                     o.data.assign(b->out_pinned + r.byte_offset, b->out_pinned + r.byte_offset + r.bytes);
@@ -1959,6 +2136,8 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.raw.reset();
     s.aiff.reset();
     s.aiff_enc = 0;
+    s.flac.reset();
+    s.flac_plain = false;
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};

@@ -572,4 +572,32 @@ struct AiffImaStream {
 // states_out[2 * stream + channel] = (uint16_t)predictor | step_index << 16: what the stream leaves with
 hipError_t launch_aiff_ima4(const AiffImaStream *streams, uint32_t n_streams, const AiffImaUnit *units, uint32_t *states_out, hipStream_t s);
 
+// flac_decode.hip -- FLAC frames (RFC 9639 9.2-9.3) to interleaved PCM, integer only, three launches over every frame of a call:
+// k_flac_residual (one frame per lane: subframe headers, warm-up samples and Rice residuals into a planar i32 workspace, one record
+// per subframe), k_flac_restore (one subframe per lane: the FIXED / LPC recurrence in place, 64-bit accumulate) and k_flac_output
+// (one block per frame: wasted bits, stereo decorrelation, interleave, narrow).
+struct FlacFrame {
+    uint32_t byte_offset;  // of the frame's sync code in `bytes`
+    uint32_t byte_len;     // sync code to the end of the CRC-16
+    uint32_t block_size;
+    uint32_t ws_offset;    // the frame's workspace: channel c lies at ws_offset + c * block_size
+    uint64_t out_offset;   // bytes into the output
+    uint32_t sub0;         // the frame's first subframe record
+    uint8_t header_bytes, channels, assignment, bits;
+};
+struct FlacSubframe {
+    int16_t coef[32];  // coef[j] multiplies the sample j + 1 back
+    uint8_t kind;      // kFlacConstant (the value is the workspace's first word) | kFlacVerbatim | kFlacPredict
+    uint8_t order, shift, wasted;
+    uint32_t ws_offset, block_size, frame;
+};
+enum : uint8_t { kFlacConstant = 0, kFlacVerbatim = 1, kFlacPredict = 2 };
+enum : uint32_t { kFlacOutContract = 0, kFlacOutI32 = 1, kFlacOutI16Clamp = 2 };
+// by_length: the frames' indices, longest first -- a wave runs until its slowest lane is done.  bytes is 4-byte aligned.
+hipError_t launch_flac_residual(const FlacFrame *frames, const uint32_t *by_length, uint32_t n_frames, const uint8_t *bytes, uint32_t bytes_len,
+                                int32_t *ws, FlacSubframe *subs, int32_t *status, hipStream_t s);
+hipError_t launch_flac_restore(const FlacSubframe *subs, uint32_t n_subs, int32_t *ws, const int32_t *status, hipStream_t s);
+hipError_t launch_flac_output(const FlacFrame *frames, uint32_t n_frames, const FlacSubframe *subs, const int32_t *ws, const int32_t *status,
+                              uint8_t *out, uint32_t mode, hipStream_t s);
+
 }  // namespace sk

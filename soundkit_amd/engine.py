@@ -542,6 +542,39 @@ class Engine:
             return got, [(st[c].predictor, st[c].step_index) for c in range(2)]
         return got
 
+    def flac_decode(self, frames):
+        """sk_flac_decode_frames: [(frame dict, frame bytes)] as flac.FlacReader.add / flac.scan cut them -> (the contract's interleaved
+        little-endian PCM as bytes, [status per frame])"""
+        from . import flac
+        return flac.decode_frames(frames, engine=self)
+
+    def tick_run_flac(self, streams, frames):
+        """One tick of FLAC streams (sk_tick_run_flac).  streams: list of dicts {channels, bits_per_sample, out_bits, out_channels, n_units,
+        and for a rate change: stream, resample, flush}; frames: [(frame dict, frame bytes)] of all streams, stream by stream, each
+        packed at a 16-byte aligned offset.  -> (the same list of records as tick_run_pcm, [status per frame])."""
+        import ctypes as C
+        from . import flac
+        from ._lib import FlacTickStream, TickOutput
+        ts = (FlacTickStream * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            ts[i].channels, ts[i].bits_per_sample = int(s["channels"]), int(s["bits_per_sample"])
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+        table, blob = flac.pack_frames(frames)
+        n = len(frames)
+        src = np.frombuffer(blob + bytes(16), np.uint8)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_flac_out_bound_on(self._h, ts, len(streams), table, n, C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        status = np.zeros(max(n, 1), np.int32)
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_flac(self._h, ts, len(streams), table, n, _ptr(src), len(blob), _ptr(out), out.size, recs, max_out.value,
+                                   C.byref(n_out), C.byref(used), _ptr(status)), "sk_tick_run_flac", self._h)
+        return ([(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                 for r in recs[:n_out.value]], status[:n].tolist())
+
     def tick_run_aiff(self, streams, units):
         """One tick of AIFF streams (sk_tick_run_aiff).  As tick_run_pcm, with `encoding` (AIFF_*) in the place of `format` and, for
         IMA4, "ima_state": [(predictor, step_index)] * 2, which is updated in the dict.  -> the same list of records."""
