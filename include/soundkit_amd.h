@@ -848,7 +848,9 @@ int sk_tick_run_mixed_mpa(sk_engine *, const sk_tick_stream *streams, uint32_t n
  * units: stream by stream in the order of `streams`; byte_offset is a multiple of 16 (the caller packs the pieces that
  * way: a lane then reads 16 samples with 16-byte loads), byte_len a whole number of frames, > 0.  A resampling stream names the
  * engine stream that holds its resampler (sk_stream_open with the source's rate and channels, sk_resampler_open); `stream` is
- * ignored otherwise.  Blocks until out_bytes holds the results.  On failure the resamplers' bookkeeping is as before the call. */
+ * ignored otherwise.  Blocks until out_bytes holds the results.  On failure the resamplers' bookkeeping is as before the call; a
+ * table the call refuses, or an out_cap / outputs_cap too small for what it would deliver, is refused before anything is queued: the
+ * resamplers' rows are then as before the call too, and the same units may be sent again. */
 typedef struct sk_pcm_tick_stream {
     uint32_t stream;      /* engine stream (resample = 1 only) */
     uint32_t n_units;     /* units of this stream in the tick (may be 0 with flush) */

@@ -4628,11 +4628,9 @@ uint64_t pcm_chunk_out_frames(const StreamInfo &s) {
     return (uint64_t)std::ceil((double)kRsChunk * (double)s.rs_out_hz / (double)s.rs_in_hz) + 2;
 }
 
-size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
-                          uint32_t *max_outputs, const uint8_t *plain = nullptr) {
-    std::vector<PcmCall> pc;
-    if (max_outputs) *max_outputs = 0;
-    if (pcm_tick_plan(e, ts, n_streams, units, n_units, (size_t)-1, pc, plain) != SK_OK) return 0;
+// the bound of a table pcm_tick_plan took: plain arithmetic per stream, no walk over the resamplers' chunks
+size_t pcm_planned_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const std::vector<PcmCall> &pc, uint32_t *max_outputs,
+                             const uint8_t *plain) {
     size_t bytes = 0;
     uint64_t outs = 0;
     for (uint32_t i = 0; i < n_streams; ++i) {
@@ -4652,6 +4650,14 @@ size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint
     return bytes;
 }
 
+size_t tick_pcm_out_bound(const sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                          uint32_t *max_outputs, const uint8_t *plain = nullptr) {
+    std::vector<PcmCall> pc;
+    if (max_outputs) *max_outputs = 0;
+    if (pcm_tick_plan(e, ts, n_streams, units, n_units, (size_t)-1, pc, plain) != SK_OK) return 0;
+    return pcm_planned_out_bound(e, ts, n_streams, pc, max_outputs, plain);
+}
+
 int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
                   size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
                   AiffTick *aiff = nullptr) {
@@ -4663,6 +4669,52 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
     std::vector<PcmCall> pc;
     int rc = pcm_tick_plan(e, ts, n_streams, units, n_units, aiff ? aiff->decoded_len : bytes_len, pc, aiff ? aiff->plain.data() : nullptr);
     if (rc != SK_OK) return rc;
+
+    // ---- what the tick will deliver, before anything is queued: the resampler rounds rewrite their streams' rows on the device, which
+    // the bookkeeping put back after a failure does not undo, so an output that is too small is refused here, with the rows untouched.
+    // The records are those of the passes below; a resampled chunk's frames follow from the stream's time index alone.  A caller that
+    // brings the bound of sk_tick_pcm_out_bound_on, as the scheduler does, is spared the walk ----
+    uint32_t bound_recs = 0;
+    const size_t bound_bytes = pcm_planned_out_bound(e, ts, n_streams, pc, &bound_recs, aiff ? aiff->plain.data() : nullptr);
+    if (!out || out_cap < bound_bytes || outs_cap < bound_recs) {
+        uint64_t need_bytes = 0, need_recs = 0;
+        std::vector<double> idx;
+        std::map<std::pair<int, double>, std::pair<uint64_t, double>> walked;  // (ratio table, time index) -> (frames, next time index): streams in step share it
+        auto chunk_frames = [&](int table, double &last) -> uint64_t {
+            auto w = walked.find({table, last});
+            if (w == walked.end()) {
+                double next = 0.0;
+                chunk_indices(e->ratio_tables[(size_t)table].ratio, last, kRsChunk, idx, &next);
+                w = walked.emplace(std::make_pair(table, last), std::make_pair((uint64_t)idx.size(), next)).first;
+            }
+            last = w->second.second;
+            return w->second.first;
+        };
+        auto record = [&](uint64_t bytes) { need_recs += 1, need_bytes += (bytes + 15) & ~15ull; };
+        for (uint32_t i = 0; i < n_streams; ++i) {
+            const sk_pcm_tick_stream &t = ts[i];
+            const PcmCall &c = pc[i];
+            const uint64_t frame_out = (uint64_t)(t.out_bits / 8) * c.ch_out;
+            if (aiff && aiff->plain[i]) {
+                for (uint32_t u = 0; u < t.n_units; ++u) record(units[c.first + u].byte_len);
+            } else if (!t.resample) {
+                for (uint32_t u = 0; u < t.n_units; ++u) record(units[c.first + u].byte_len / c.frame_bytes * frame_out);
+            } else {
+                const StreamInfo &s = e->streams[t.stream];
+                const uint64_t have = (uint64_t)s.rs_fill + c.total_frames;
+                double last = s.rs_last_index;
+                for (uint64_t k = 0; k < have / kRsChunk; ++k)
+                    if (const uint64_t frames = chunk_frames(s.rs_table, last)) record(frames * frame_out);
+                if (t.flush) {  // rs_run_rounds: the rest padded to a chunk, the padding's share trimmed
+                    const uint64_t remaining = have % kRsChunk, padded = kRsChunk - remaining;
+                    const uint64_t trim = remaining ? (uint64_t)std::llround(((double)padded * (double)s.rs_out_hz) / (double)s.rs_in_hz) : 0;
+                    const uint64_t frames = chunk_frames(s.rs_table, last);
+                    if (frames > trim) record((frames - trim) * frame_out);
+                }
+            }
+        }
+        if (need_bytes > out_cap || (need_bytes && !out) || need_recs > outs_cap) return SK_ERR_INVALID_ARG;
+    }
 
     // from here to the tick's last wait the device belongs to this engine (see g_device_turn)
     std::unique_lock<std::mutex> turn;
