@@ -4,6 +4,10 @@ and 24 kHz up to 48 kHz and 44.1 -> 48 kHz; depth, channel count and stereo assi
 give exactly what sk_tick_run_pcm gives for the same samples handed in as little-endian units, whichever way its frames are dealt out
 over ticks.  The two header rates the resampler does not take are refused with their status.
 
+The expected value here is another tick, which shares the resampler with this one.  What holds sk_tick_run_pcm itself to the CPU
+chain at these 20 pairs, on streams of the same eight unit sizes -- every record's size exactly, every sample within one step -- is
+tests/test_rate_pairs_gpu.py::test_pcm_tick_meets_the_cpu_chain_at_every_pair.
+
 Every built stream is first decoded by the model (tests/flac_model.py) back to its source samples, on the CPU."""
 import functools
 import random
