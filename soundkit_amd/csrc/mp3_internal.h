@@ -103,8 +103,6 @@ int mp3_install_codebook(sk_engine *, const uint32_t *words, size_t n_words);  /
 namespace sk_mp3_internal {
 struct PipelineGpuHooks {
     int (*install_codebook)(sk_engine *, const uint32_t *words, size_t n_words) = nullptr;
-    int (*tick_md)(sk_engine *, const sk_tick_stream *, uint32_t, const sk_tick_input *, const sk_tick_mp3_frames *, uint8_t *, size_t, sk_tick_output *,
-                   uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_mixed_md
     // the WAV / raw PCM streams' tick; with these absent a PCM stream that needs a conversion ends with SK_ERR_UNSUPPORTED
     int (*tick_pcm)(sk_engine *, const sk_pcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
                     sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_pcm
@@ -119,7 +117,7 @@ struct PipelineGpuHooks {
     size_t (*tick_flac_out_bound)(sk_engine *, const sk_flac_tick_stream *, uint32_t, const sk_flac_frame_info *, uint32_t, uint32_t *) = nullptr;
     // the engine's pool of wide PCM streams (3 ... 8 channels); with these absent such a stream is refused as before
     // Layer I / II streams: the host front (mp12_bitstream.cpp) and the tick that takes their frames; with these absent such a stream
-    // ends with SK_ERR_UNSUPPORTED
+    // ends with SK_ERR_UNSUPPORTED.  tick_mpa is also the tick of gpu_entropy = 3 (frames with main data; its Layer I / II table is null then)
     int (*mpa_find_layer)(const uint8_t *, size_t) = nullptr;  // sk_mp12::find_layer
     int (*mpa_scan)(const uint8_t *, size_t, uint32_t *, sk_mpa_frame_info *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_mpa_scan
     int (*mpa_parse_frame)(const uint8_t *, size_t, const sk_mpa_frame_info *, sk_mpa_frame_record *) = nullptr;         // sk_mpa_parse_frame

@@ -121,6 +121,23 @@ struct BatchEntry {  // bookkeeping beside one sk_tick_stream
     std::vector<Output> pre;
 };
 
+// The table of one PCM-family tick (WAV / raw PCM, AIFF, FLAC): a row per stream that brings units or ends a resampler, the units stream
+// after stream (their offsets into Batch::pcm_bytes), entry[row] = the row's batch entry, and -- submission thread -- the records the
+// tick's bound call allows it
+template <class Row, class Unit>
+struct TickTable {
+    std::vector<Row> rows;
+    std::vector<Unit> units;
+    std::vector<uint32_t> entry;
+    uint32_t max_out = 0;
+    void clear() {
+        rows.clear();
+        units.clear();
+        entry.clear();
+        max_out = 0;
+    }
+};
+
 struct Batch {
     float *coeffs = nullptr;  // pinned
     size_t coeff_cap = 0, n_floats = 0;
@@ -146,21 +163,13 @@ struct Batch {
     // the frames' bytes (each 4-byte aligned, 8 bytes of room behind it); appended under batch_mu, they are small
     std::vector<sk_mpa_frame_record> mpa_recs;
     std::vector<uint8_t> mpa_bytes;
-    // WAV / raw PCM streams' units (sk_tick_run_pcm through pipeline_gpu_hooks()): pieces in pcm_bytes (pinned, ensure_pcm), one table
-    // row per stream with units or a flush, pcm_entry[row] = its entry
+    // WAV / raw PCM streams' pieces (sk_tick_run_pcm through pipeline_gpu_hooks()), AIFF streams' pieces (sk_tick_run_aiff) and FLAC streams'
+    // frames (sk_tick_run_flac): all staged in pcm_bytes (pinned, ensure_pcm), a table per tick; the statuses the device gives the frames
     uint8_t *pcm_bytes = nullptr;
     size_t pcm_cap = 0, pcm_used = 0;
-    std::vector<sk_pcm_tick_stream> pcm_ts;
-    std::vector<sk_pcm_unit> pcm_units;
-    std::vector<uint32_t> pcm_entry;
-    // AIFF streams' units (sk_tick_run_aiff), staged in pcm_bytes beside the PCM streams' pieces; a table of their own
-    std::vector<sk_aiff_tick_stream> aiff_ts;
-    std::vector<sk_pcm_unit> aiff_units;
-    std::vector<uint32_t> aiff_entry;
-    // FLAC streams' frames (sk_tick_run_flac), staged in pcm_bytes as well; the statuses the device gives them
-    std::vector<sk_flac_tick_stream> flac_ts;
-    std::vector<sk_flac_frame_info> flac_frames;
-    std::vector<uint32_t> flac_entry;
+    TickTable<sk_pcm_tick_stream, sk_pcm_unit> pcm_ts;
+    TickTable<sk_aiff_tick_stream, sk_pcm_unit> aiff_ts;
+    TickTable<sk_flac_tick_stream, sk_flac_frame_info> flac_ts;
     std::vector<int32_t> flac_status;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
@@ -185,14 +194,8 @@ struct Batch {
         mpa_bytes.clear();
         pcm_used = 0;
         pcm_ts.clear();
-        pcm_units.clear();
-        pcm_entry.clear();
         aiff_ts.clear();
-        aiff_units.clear();
-        aiff_entry.clear();
         flac_ts.clear();
-        flac_frames.clear();
-        flac_entry.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -248,7 +251,7 @@ struct sk_lane {
     sk_mp3_codebook *mp3_cb = nullptr;
     std::atomic<bool> mp3_ready{false};
     // gpu_entropy = 3: the MP3 streams' passes stop behind the bit reservoir; scale factors and Huffman codes are the tick's
-    // (sk_tick_run_mixed_md, reached through pipeline_gpu_hooks()).  cfg.gpu_entropy holds 1 then: the AAC streams' mode.
+    // (sk_tick_run_mixed_mpa, reached through pipeline_gpu_hooks()).  cfg.gpu_entropy holds 1 then: the AAC streams' mode.
     bool mp3_gpu = false;
     std::vector<uint32_t> mp3_blob;  // mp3_cb flattened for the device (sk_mp3_codebook_flatten)
     // WAV / raw PCM: the batches' pinned byte buffers, made when the first stream that needs the PCM tick shows up
@@ -347,6 +350,12 @@ struct Parsed {  // what one worker pass produced for one stream
     std::vector<sk_pcm_unit> pcm_units;
     std::vector<sk_flac_frame_info> flac_frames;  // a FLAC stream's pass: one per unit, offset into pcm_bytes
     std::vector<Output> pre;
+    bool fail(int32_t st, const std::string &msg) {  // the pass ends its stream with this error; false, for a caller that returns it
+        failed = true;
+        fail_status = st;
+        fail_msg = msg;
+        return false;
+    }
 };
 
 // 1 = a chunk was appended to s.pending, 0 = nothing queued right now, -1 = the end-of-stream marker was taken (s.saw_eof set)
@@ -420,14 +429,9 @@ uint8_t sniff_codec(const uint8_t *d, size_t n) {
 // does.  At most `limit` granules per pass.
 void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
     r.mp3 = true;
-    auto fail = [&](int32_t st, const std::string &msg) {
-        r.failed = true;
-        r.fail_status = st;
-        r.fail_msg = msg;
-    };
     int rc = ensure_mp3(p);
     if (rc != SK_OK) {
-        fail(rc, std::string("Decoding failed: MP3 tables: ") + sk_strerror(rc));
+        r.fail(rc, std::string("Decoding failed: MP3 tables: ") + sk_strerror(rc));
         return;
     }
     std::vector<sk_mp3_frame_info> found(64);
@@ -444,7 +448,7 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
             free_format_scan = s.mp3_free_format;
             rc = sk_mp3_scan_free(s.pending.data() + s.pending_pos, avail, found.data(), (uint32_t)found.size(), &n_found, &scanned, &free_format_scan);
             if (rc != SK_OK) {
-                fail(rc, std::string("Decoding failed: ") + sk_strerror(rc));
+                r.fail(rc, std::string("Decoding failed: ") + sk_strerror(rc));
                 break;
             }
             if (n_found > found.size()) n_found = (uint32_t)found.size();
@@ -487,7 +491,7 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     s.channels = h.channels;
                     rc = sk_stream_open(p->engine, s.rate, s.channels, &s.engine_stream);
                     if (rc != SK_OK) {
-                        fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
+                        r.fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
                         break;
                     }
                     const uint32_t target = s.opt.output_sample_rate ? s.opt.output_sample_rate : s.rate;
@@ -495,12 +499,12 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     if (s.resample) {
                         rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
                         if (rc != SK_OK) {
-                            fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
+                            r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
                             break;
                         }
                     }
                 } else if (h.channels != s.channels || h.sample_rate != s.rate) {
-                    fail(SK_MP3_UNSUPPORTED, "Decoding failed: MP3 sample rate or channel count changed mid-stream");
+                    r.fail(SK_MP3_UNSUPPORTED, "Decoding failed: MP3 sample rate or channel count changed mid-stream");
                     break;
                 }
                 if (p->mp3_gpu) {  // the pass ends behind the reservoir: the frame and its main data go to the tick as they are
@@ -565,19 +569,14 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
 // between passes or ticks.
 void parse_some_mpa(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
     r.mpa = true;
-    auto fail = [&](int32_t st, const std::string &msg) {
-        r.failed = true;
-        r.fail_status = st;
-        r.fail_msg = msg;
-    };
     const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     if (!hooks.mpa_scan || !hooks.mpa_parse_frame || !hooks.tick_mpa) {
-        fail(SK_ERR_UNSUPPORTED, "Decoding failed: MPEG Layer I / II needs the device tick, which this build lacks");
+        r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: MPEG Layer I / II needs the device tick, which this build lacks");
         return;
     }
     int rc = ensure_mp3(p);  // the synthesis window is the engine's Layer III one
     if (rc != SK_OK) {
-        fail(rc, std::string("Decoding failed: MP3 tables: ") + sk_strerror(rc));
+        r.fail(rc, std::string("Decoding failed: MP3 tables: ") + sk_strerror(rc));
         return;
     }
     std::vector<sk_mpa_frame_info> found(64);
@@ -588,7 +587,7 @@ void parse_some_mpa(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
         if (avail >= 4) {
             rc = hooks.mpa_scan(s.pending.data() + s.pending_pos, avail, &layer, found.data(), (uint32_t)found.size(), &n_found, &scanned);
             if (rc != SK_OK) {
-                fail(rc, std::string("Decoding failed: ") + sk_strerror(rc));
+                r.fail(rc, std::string("Decoding failed: ") + sk_strerror(rc));
                 break;
             }
             if (n_found > found.size()) n_found = (uint32_t)found.size();
@@ -617,7 +616,7 @@ void parse_some_mpa(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     s.channels = h.channels;
                     rc = sk_stream_open(p->engine, s.rate, s.channels, &s.engine_stream);
                     if (rc != SK_OK) {
-                        fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
+                        r.fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
                         break;
                     }
                     const uint32_t target = s.opt.output_sample_rate ? s.opt.output_sample_rate : s.rate;
@@ -625,12 +624,12 @@ void parse_some_mpa(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     if (s.resample) {
                         rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
                         if (rc != SK_OK) {
-                            fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
+                            r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
                             break;
                         }
                     }
                 } else if (h.channels != s.channels || h.sample_rate != s.rate) {
-                    fail(SK_MP3_UNSUPPORTED, "Decoding failed: MP3 sample rate or channel count changed mid-stream");
+                    r.fail(SK_MP3_UNSUPPORTED, "Decoding failed: MP3 sample rate or channel count changed mid-stream");
                     break;
                 }
                 rec.byte_offset = (uint32_t)r.mpa_bytes.size();
@@ -672,12 +671,6 @@ int ensure_pcm(sk_lane *p) {
 // eight on an engine with the pool of wide streams) and,
 // for a rate change, an engine stream with a resampler.  false: the stream has failed (r says how).
 bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
-    auto fail = [&](int32_t st, const std::string &msg) {
-        r.failed = true;
-        r.fail_status = st;
-        r.fail_msg = msg;
-        return false;
-    };
     uint32_t rate, channels, bits;
     bool is_float, big_endian = false;
     if (s.flac) {  // STREAMINFO's: the AudioData of a FLAC frame carries the stream's own depth (create_audio_data_i32_with_bits, lib.rs:3191-3236)
@@ -694,7 +687,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         is_float = f >= SK_FMT_F32LE;
         big_endian = (f & 1) != 0;
     }
-    if (channels > 255 || bits > 255) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: WAV channel count or sample width above 255");
+    if (channels > 255 || bits > 255) return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: WAV channel count or sample width above 255");
     s.rate = rate;
     s.channels = (uint8_t)channels;
     s.pcm_bits = (uint8_t)bits;
@@ -704,10 +697,10 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     const uint32_t target_channels = s.opt.output_channels ? s.opt.output_channels : channels;
     const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     if (s.flac && (!hooks.tick_flac || !hooks.tick_flac_out_bound))
-        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: FLAC decoding needs the device tick, which this build lacks");
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: FLAC decoding needs the device tick, which this build lacks");
     if (s.flac && target_rate == rate && target_bits == bits && target_channels == channels) {  // every frame has per-sample work: the tick's
         const int rc = ensure_pcm(p);
-        if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
         s.pcm_route = kPcmFlacTick;
         s.flac_plain = true;
         return true;
@@ -718,34 +711,50 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
             s.pcm_route = kPcmFast;
             return true;
         }
-        if (!hooks.tick_aiff || !hooks.tick_aiff_out_bound) return fail(SK_ERR_UNSUPPORTED, "Decoding failed: AIFF decoding needs the device tick, which this build lacks");
+        if (!hooks.tick_aiff || !hooks.tick_aiff_out_bound) return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: AIFF decoding needs the device tick, which this build lacks");
         const int rc = ensure_pcm(p);
-        if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
         s.pcm_route = kPcmAiffTick;
         s.aiff_plain = true;
         return true;
     }
     // audio_data_to_f32_channels (lib.rs:3563-3617) and exact_signed_pcm_to_i16 take 16 / 24 / 32-bit samples
-    if (is_float && bits != 32) return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: floating-point PCM must contain 32-bit samples");
+    if (is_float && bits != 32) return r.fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: floating-point PCM must contain 32-bit samples");
     if (bits != 16 && bits != 24 && bits != 32)
-        return fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
+        return r.fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
     // 3 ... 8 channels: the tick takes them on an engine whose pool of wide streams was reserved (sk_engine_enable_wide_pcm)
     if (channels > SK_MAX_CHANNELS && (channels > SK_MAX_PCM_CHANNELS || !hooks.wide_pcm_streams || hooks.wide_pcm_streams(p->engine) == 0))
-        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
     if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound || (s.aiff && (!hooks.tick_aiff || !hooks.tick_aiff_out_bound)))
-        return fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
     s.pcm_fmt = (uint8_t)((bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : (is_float ? SK_FMT_F32LE : SK_FMT_S32LE))) + (big_endian ? 1 : 0));
     int rc = ensure_pcm(p);
-    if (rc != SK_OK) return fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+    if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
     s.resample = target_rate != rate;
     if (s.resample) {
         rc = sk_stream_open(p->engine, rate, s.channels, &s.engine_stream);
-        if (rc != SK_OK) return fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
-        if (rc != SK_OK) return fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
+        if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
     s.pcm_route = s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick);
     return true;
+}
+
+// One unit of a PCM-family pass is staged: its bytes at the next 16-byte aligned offset of r.pcm_bytes (returned), its entry in
+// r.pcm_units, and the AudioData it will give counted into `outputs` -- one, or through the resampler one per completed 4096-frame chunk
+size_t stage_unit(Parsed &r, PStream &s, const uint8_t *data, size_t len, uint32_t frames, uint32_t &outputs) {
+    const size_t at = (r.pcm_bytes.size() + 15) & ~(size_t)15;
+    r.pcm_bytes.resize(at);
+    r.pcm_bytes.insert(r.pcm_bytes.end(), data, data + len);
+    r.pcm_units.push_back(sk_pcm_unit{at, (uint32_t)len, 0});
+    if (s.resample) {
+        outputs += (s.pcm_fill + frames) / 4096;
+        s.pcm_fill = (s.pcm_fill + frames) % 4096;
+    } else {
+        outputs += 1;
+    }
+    return at;
 }
 
 // A FLAC stream's pass: the reader cuts whole frames out of the chunks (marker and metadata first), and whole frames are what the
@@ -754,11 +763,6 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
 // with its text; the frames in front of the damage have gone out with the passes before.
 void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     r.pcm = true;
-    auto fail = [&](int32_t st, const std::string &msg) {
-        r.failed = true;
-        r.fail_status = st;
-        r.fail_msg = msg;
-    };
     if (!s.flac) {
         s.flac.reset(new sk_flac::Reader());
         s.pcm_detected = true;
@@ -773,24 +777,14 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         uint32_t n = 0;
         const uint8_t *base = nullptr;
         if (!s.flac->feed(data, len, final, got.data(), cap, &n, &base)) {
-            fail(SK_FLAC_ERR_STREAM, "Decoding failed: " + s.flac->error());
+            r.fail(SK_FLAC_ERR_STREAM, "Decoding failed: " + s.flac->error());
             return false;
         }
         if (n && !s.pcm_route && !pcm_open(p, s, r)) return false;
         for (uint32_t k = 0; k < n; ++k) {
             sk_flac_frame_info f = got[k];
-            const size_t at = (r.pcm_bytes.size() + 15) & ~(size_t)15;
-            r.pcm_bytes.resize(at);
-            r.pcm_bytes.insert(r.pcm_bytes.end(), base + f.offset, base + f.offset + f.frame_bytes);
-            r.pcm_units.push_back(sk_pcm_unit{at, f.frame_bytes, 0});
-            f.offset = (uint32_t)at;
+            f.offset = (uint32_t)stage_unit(r, s, base + f.offset, f.frame_bytes, f.block_size, outputs);
             r.flac_frames.push_back(f);
-            if (s.resample) {
-                outputs += (s.pcm_fill + f.block_size) / 4096;
-                s.pcm_fill = (s.pcm_fill + f.block_size) % 4096;
-            } else {
-                outputs += 1;
-            }
         }
         if (n == cap) r.more = true;  // the reader may hold further frames
         return true;
@@ -847,18 +841,13 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
 // never split, so the last one may overshoot.
 void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     r.pcm = true;
-    auto fail = [&](int32_t st, const std::string &msg) {
-        r.failed = true;
-        r.fail_status = st;
-        r.fail_msg = msg;
-    };
     uint32_t outputs = 0;
     auto process = [&](const uint8_t *data, size_t len) -> bool {
         sk_pcm::Piece piece;
         std::string err;
         const bool ok = s.aiff ? s.aiff->add(data, len, piece, err) : (s.wav ? s.wav->add(data, len, piece, err) : s.raw->add(data, len, piece, err));
         if (!ok) {
-            fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
+            r.fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
             return false;
         }
         if (piece.len == 0) return true;
@@ -872,7 +861,7 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         // reference delivers; its conversions refuse it (audio_data_to_f32_channels, lib.rs:3569-3574)
         if (s.aiff && !s.aiff_plain && s.pcm_route == kPcmAiffTick && s.aiff_enc != SK_AIFF_IMA4 &&
             piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) % s.channels != 0) {
-            fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
+            r.fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
             return false;
         }
         if (s.pcm_route == kPcmFast) {
@@ -883,16 +872,7 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
             outputs += 1;
             return true;
         }
-        const size_t at = (r.pcm_bytes.size() + 15) & ~(size_t)15;
-        r.pcm_bytes.resize(at);
-        r.pcm_bytes.insert(r.pcm_bytes.end(), piece.data, piece.data + piece.len);
-        r.pcm_units.push_back(sk_pcm_unit{at, (uint32_t)piece.len, 0});
-        if (s.resample) {
-            outputs += (s.pcm_fill + frames) / 4096;
-            s.pcm_fill = (s.pcm_fill + frames) % 4096;
-        } else {
-            outputs += 1;
-        }
+        stage_unit(r, s, piece.data, piece.len, frames, outputs);
         return true;
     };
     if ((s.codec == kCodecWav || s.codec == kCodecAiff) && !s.pcm_detected) {
@@ -913,7 +893,7 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     while (!r.failed) {
         if (s.saw_eof) {  // flush_decoder (lib.rs:3139-3169): the framer's partial frame is an error, the resampler is flushed by the tick
             std::string err;
-            if (s.raw && !s.raw->flush(err)) fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
+            if (s.raw && !s.raw->flush(err)) r.fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
             else if (s.aiff && !process(nullptr, 0)) {}  // the finalising empty add (lib.rs:2426): a truncated stream ends with its text
             else r.eof = true;
             break;
@@ -947,11 +927,6 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
                 sk_au_item *au_items, uint32_t room, Parsed &r) {
     const bool gpu_entropy = p->cfg.gpu_entropy == 1;
     const bool quant = p->cfg.gpu_entropy == 2;  // host Huffman decode, the rest of the front-end on the device (sk_tick_run_q)
-    auto fail = [&](int32_t st, const std::string &msg) {
-        r.failed = true;
-        r.fail_status = st;
-        r.fail_msg = msg;
-    };
     while (s.codec == 0) {  // the worker's detect_and_init_decoder: the stream's first bytes choose the decoder
         s.codec = sniff_codec(s.pending.data() + s.pending_pos, s.pending.size() - s.pending_pos);
         if (s.codec) break;
@@ -1021,7 +996,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         if (!s.fe) {  // first header: AacLcDecoder::from_audio_specific_config (lib.rs:1007-1027, decoder.rs:80)
             int rc = sk_aac_decoder_create(asc, 2, &s.fe);
             if (rc != SK_OK) {
-                fail(rc, std::string("Decoding failed: AAC-LC decoder init: ") + sk_strerror(rc));
+                r.fail(rc, std::string("Decoding failed: AAC-LC decoder init: ") + sk_strerror(rc));
                 break;
             }
             s.asc[0] = asc[0];
@@ -1029,7 +1004,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             (void)sk_aac_decoder_info(s.fe, &s.rate, &s.channels);
             rc = sk_stream_open(p->engine, s.rate, s.channels, &s.engine_stream);
             if (rc != SK_OK) {
-                fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
+                r.fail(rc, std::string("Decoding failed: engine stream: ") + sk_strerror(rc));
                 break;
             }
             const uint32_t target = s.opt.output_sample_rate ? s.opt.output_sample_rate : s.rate;
@@ -1037,12 +1012,12 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             if (s.resample) {
                 rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
                 if (rc != SK_OK) {  // StreamingResampler::new failing, lib.rs:3405-3417
-                    fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
+                    r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
                     break;
                 }
             }
         } else if (asc[0] != s.asc[0] || asc[1] != s.asc[1]) {
-            fail(SK_AAC_ERR_UNSUPPORTED_FEATURE, "Decoding failed: AAC configuration changed mid-stream");
+            r.fail(SK_AAC_ERR_UNSUPPORTED_FEATURE, "Decoding failed: AAC configuration changed mid-stream");
             break;
         }
         if (gpu_entropy) {  // framing only: the access unit itself goes to the device
@@ -1064,7 +1039,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             const int rc = sk_aac_decoder_parse_q(s.fe, frame + pay_off, pay_len, reinterpret_cast<int16_t *>(coeffs) + r.n_floats,
                                                   au_stage.data() + r.n_au_bytes, &d);
             if (rc != SK_OK) {
-                fail(rc, std::string("Decoding failed: ") + sk_aac_decoder_last_error(s.fe));
+                r.fail(rc, std::string("Decoding failed: ") + sk_aac_decoder_last_error(s.fe));
                 break;
             }
             d.stream = s.engine_stream;
@@ -1075,7 +1050,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             sk_aac_frame_desc &d = descs[r.n_frames];
             const int rc = sk_aac_decoder_parse(s.fe, frame + pay_off, pay_len, coeffs + r.n_floats, &d);
             if (rc != SK_OK) {
-                fail(rc, std::string("Decoding failed: ") + sk_aac_decoder_last_error(s.fe));
+                r.fail(rc, std::string("Decoding failed: ") + sk_aac_decoder_last_error(s.fe));
                 break;
             }
             d.stream = s.engine_stream;
@@ -1139,6 +1114,35 @@ std::atomic<int> g_thread_throw_after{-1}, g_thread_throw_where{-1};
 void thread_debug_point(int where) {
     if (g_thread_throw_after.load(std::memory_order_relaxed) < 0 || g_thread_throw_where.load(std::memory_order_relaxed) != where) return;
     if (g_thread_throw_after.fetch_sub(1) == 0) throw std::bad_alloc();
+}
+
+inline void shift_unit(sk_pcm_unit &u, size_t by) { u.byte_offset += by; }
+inline void shift_unit(sk_flac_frame_info &f, size_t by) { f.offset += (uint32_t)by; }
+
+// A PCM-family pass joins the table of its tick (batch_mu held): nothing when it neither brings units nor ends a resampler; else it
+// takes its place in the batch's staged bytes (pcm_at) and a row with what the three ticks' rows share, and its units follow with
+// their offsets moved to that place.  The row comes back for the fields that are its kind's own.
+template <class Row, class Unit>
+Row *claim_tick_row(Batch *b, TickTable<Row, Unit> &t, const PStream &s, const Parsed &r, const std::vector<Unit> &units, BatchEntry &be, size_t &pcm_at) {
+    if (units.empty() && !(r.eof && s.resample)) return nullptr;
+    pcm_at = b->pcm_used;
+    b->pcm_used += r.pcm_bytes.size();
+    Row row{};
+    row.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
+    row.n_units = (uint32_t)units.size();
+    row.channels = s.channels;
+    row.out_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits;
+    row.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
+    row.resample = s.resample ? 1 : 0;
+    row.flush = (r.eof && s.resample) ? 1 : 0;
+    t.rows.push_back(row);
+    be.pcm_row = true;
+    t.entry.push_back((uint32_t)b->entries.size());
+    for (Unit u : units) {
+        shift_unit(u, pcm_at);
+        t.units.push_back(u);
+    }
+    return &t.rows.back();
 }
 
 void worker_body(sk_lane *p) {
@@ -1273,66 +1277,17 @@ void worker_body(sk_lane *p) {
                 be.pre = std::move(r.pre);
                 t.n_frames = 0;
                 t.flush = 0;
-                if (s.pcm_route == kPcmAiffTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
-                    pcm_at = b->pcm_used;
-                    b->pcm_used += r.pcm_bytes.size();
-                    sk_aiff_tick_stream at{};
-                    at.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
-                    at.n_units = (uint32_t)r.pcm_units.size();
-                    at.encoding = s.aiff_enc;
-                    at.channels = s.channels;
-                    at.out_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits;
-                    at.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
-                    at.resample = s.resample ? 1 : 0;
-                    at.flush = (r.eof && s.resample) ? 1 : 0;
-                    b->aiff_ts.push_back(at);
-                    be.pcm_row = true;
-                    b->aiff_entry.push_back((uint32_t)b->entries.size());
-                    for (sk_pcm_unit u : r.pcm_units) {
-                        u.byte_offset += pcm_at;
-                        b->aiff_units.push_back(u);
+                if (s.pcm_route == kPcmAiffTick) {
+                    if (sk_aiff_tick_stream *row = claim_tick_row(b, b->aiff_ts, s, r, r.pcm_units, be, pcm_at)) row->encoding = s.aiff_enc;
+                } else if (s.pcm_route == kPcmFlacTick) {
+                    if (sk_flac_tick_stream *row = claim_tick_row(b, b->flac_ts, s, r, r.flac_frames, be, pcm_at)) {
+                        const uint8_t depth = s.flac->info().bits_per_sample;
+                        row->bits_per_sample = depth;
+                        // as decoded: the contract's width (the record's depth is put back at delivery); else what the options ask for
+                        if (s.flac_plain) row->out_bits = depth <= 8 ? 8 : (depth <= 16 ? 16 : (depth <= 24 ? 24 : 32));
                     }
-                } else if (s.pcm_route == kPcmFlacTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
-                    pcm_at = b->pcm_used;
-                    b->pcm_used += r.pcm_bytes.size();
-                    const sk_flac_streaminfo &si = s.flac->info();
-                    const uint32_t width = si.bits_per_sample <= 8 ? 1 : (si.bits_per_sample <= 16 ? 2 : (si.bits_per_sample <= 24 ? 3 : 4));
-                    sk_flac_tick_stream ft{};
-                    ft.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
-                    ft.n_units = (uint32_t)r.flac_frames.size();
-                    ft.channels = s.channels;
-                    ft.bits_per_sample = si.bits_per_sample;
-                    // as decoded: the contract's width (the record's depth is put back at delivery); else what the options ask for
-                    ft.out_bits = (uint8_t)(s.flac_plain ? 8 * width : (s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits));
-                    ft.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
-                    ft.resample = s.resample ? 1 : 0;
-                    ft.flush = (r.eof && s.resample) ? 1 : 0;
-                    b->flac_ts.push_back(ft);
-                    be.pcm_row = true;
-                    b->flac_entry.push_back((uint32_t)b->entries.size());
-                    for (sk_flac_frame_info f : r.flac_frames) {
-                        f.offset += (uint32_t)pcm_at;
-                        b->flac_frames.push_back(f);
-                    }
-                } else if (s.pcm_route == kPcmTick && (!r.pcm_units.empty() || (r.eof && s.resample))) {
-                    pcm_at = b->pcm_used;
-                    b->pcm_used += r.pcm_bytes.size();
-                    sk_pcm_tick_stream pt{};
-                    pt.stream = s.engine_stream == kNoStream ? 0 : s.engine_stream;
-                    pt.n_units = (uint32_t)r.pcm_units.size();
-                    pt.format = s.pcm_fmt;
-                    pt.channels = s.channels;
-                    pt.out_bits = s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : s.pcm_bits;
-                    pt.out_channels = s.opt.output_channels ? s.opt.output_channels : s.channels;
-                    pt.resample = s.resample ? 1 : 0;
-                    pt.flush = (r.eof && s.resample) ? 1 : 0;
-                    b->pcm_ts.push_back(pt);
-                    be.pcm_row = true;
-                    b->pcm_entry.push_back((uint32_t)b->entries.size());
-                    for (sk_pcm_unit u : r.pcm_units) {
-                        u.byte_offset += pcm_at;
-                        b->pcm_units.push_back(u);
-                    }
+                } else if (s.pcm_route == kPcmTick) {
+                    if (sk_pcm_tick_stream *row = claim_tick_row(b, b->pcm_ts, s, r, r.pcm_units, be, pcm_at)) row->format = s.pcm_fmt;
                 }
             }
             if (s.engine_stream == kNoStream) {  // ended before a single header was seen: nothing for the device
@@ -1384,7 +1339,66 @@ void push_error(PStream &s, int32_t status, const std::string &msg) {
     s.out.push_back(std::move(o));
 }
 
+// What the main tick's mixed forms take beside the table: the AAC units in the lane's form (all null without units), the MP3 streams'
+// granules from the host's Huffman stage -- or, with that stage in the tick (with_md), the bytes their frames point into
+sk_tick_input tick_input(const sk_lane *p, const Batch *b, uint32_t n_frames, bool with_md) {
+    sk_tick_input in{};
+    in.n_aac_units = n_frames;
+    if (p->cfg.gpu_entropy == 2) in.descs = b->descs.data(), in.q_sides = b->au_bytes, in.q_quant = reinterpret_cast<const int16_t *>(b->coeffs);
+    else if (p->cfg.gpu_entropy) in.units = b->units.data(), in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
+    else in.descs = b->descs.data(), in.coeffs = b->coeffs;
+    if (n_frames == 0) in.descs = nullptr, in.coeffs = nullptr, in.units = nullptr, in.q_sides = nullptr;
+    if (with_md) {
+        in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
+    } else if (b->n_mp3) {
+        in.n_mp3_granules = (uint32_t)b->n_mp3;
+        in.mp3_granules = b->mp3_gr.data(), in.mp3_descs = b->mp3_desc.data(), in.mp3_is = b->mp3_is;
+    }
+    return in;
+}
+
+// The main tick's table with the Huffman stage in the tick: an MP3 stream's units are frames there (ts keeps counting granules: the
+// budget and the output bound are in granules)
+void frames_form(const Batch *b, const std::vector<sk_tick_stream> &ts, std::vector<sk_tick_stream> &ts_md) {
+    ts_md = ts;
+    for (size_t row = 0; row < ts_md.size(); ++row)
+        if (ts_md[row].codec == SK_TICK_MP3) ts_md[row].n_frames = b->mp3_frames_of[b->row_of[row]];
+}
+
+// A PCM-family tick's share of the output buffer: 16 bytes for the alignment of its base plus the tick's own bound; the records it may
+// write stay with the table
+template <class Table, class Bound>
+size_t follow_on_bound(sk_lane *p, Table &t, Bound out_bound) {
+    if (t.rows.empty()) return 0;
+    return 16 + out_bound(p->engine, t.rows.data(), (uint32_t)t.rows.size(), t.units.data(), (uint32_t)t.units.size(), &t.max_out);
+}
+
+// One PCM-family tick of a round, behind whatever ran before it: its outputs follow the others' in the same buffer from the next
+// 16-byte aligned offset, its records in the same array, and its rows number on from theirs.  `run` calls the hook with the place
+// for both; a failure (this tick's or an earlier one's) leaves the batch as it is, with the status in b->rc.
+template <class Table, class Run>
+void follow_on_tick(Batch *b, const Table &t, size_t &used, Run run) {
+    if (b->rc != SK_OK || t.rows.empty()) return;
+    const uint32_t first_row = (uint32_t)b->row_of.size();
+    const size_t base = (used + 15) & ~(size_t)15;
+    uint32_t n_out = 0;
+    size_t tick_used = 0;
+    b->rc = run(b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, t.max_out, &n_out, &tick_used);
+    if (b->rc != SK_OK) return;
+    for (uint32_t k = 0; k < n_out; ++k) {
+        b->recs[b->n_out + k].stream_index += first_row;
+        b->recs[b->n_out + k].byte_offset += base;
+    }
+    b->n_out += n_out;
+    for (uint32_t row = 0; row < t.entry.size(); ++row) {
+        b->entry_row[t.entry[row]] = first_row + row;
+        b->row_of.push_back(t.entry[row]);
+    }
+    used = base + tick_used;
+}
+
 void submit_body(sk_lane *p) {
+    const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     std::vector<sk_tick_stream> ts, ts_md;
     for (;;) {
         Batch *b;
@@ -1429,22 +1443,15 @@ void submit_body(sk_lane *p) {
             b->entry_row[i] = (uint32_t)b->row_of.size();
             b->row_of.push_back(i);
         }
-        uint32_t max_out = 0, pcm_max_out = 0, aiff_max_out = 0, flac_max_out = 0;
+        uint32_t max_out = 0;
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
-        const sk_mp3_internal::PipelineGpuHooks &pcm_hooks = sk_mp3_internal::pipeline_gpu_hooks();
-        if (!ts.empty() || !b->pcm_ts.empty() || !b->aiff_ts.empty() || !b->flac_ts.empty()) {
-            size_t bound = ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out);
-            if (!b->aiff_ts.empty())  // ... and the AIFF tick's behind those
-                bound += 16 + pcm_hooks.tick_aiff_out_bound(p->engine, b->aiff_ts.data(), (uint32_t)b->aiff_ts.size(), b->aiff_units.data(),
-                                                            (uint32_t)b->aiff_units.size(), &aiff_max_out);
-            if (!b->flac_ts.empty())  // ... the FLAC tick's
-                bound += 16 + pcm_hooks.tick_flac_out_bound(p->engine, b->flac_ts.data(), (uint32_t)b->flac_ts.size(), b->flac_frames.data(),
-                                                            (uint32_t)b->flac_frames.size(), &flac_max_out);
-            if (!b->pcm_ts.empty())  // the PCM tick's outputs follow the other tick's in the same buffer
-                bound += 16 + pcm_hooks.tick_pcm_out_bound(p->engine, b->pcm_ts.data(), (uint32_t)b->pcm_ts.size(), b->pcm_units.data(),
-                                                           (uint32_t)b->pcm_units.size(), &pcm_max_out);
+        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty()) {
+            // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, then the PCM tick's: one buffer
+            const size_t bound = (ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out)) +
+                                 follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
+                                 follow_on_bound(p, b->pcm_ts, hooks.tick_pcm_out_bound);
             if (bound > b->out_pinned_cap) {
                 // Pinned memory is slow to get (10 ms per 64 MB on an idle device, many times that beside a running lane): the
                 // bound is the engine's own (the streams' real ratios and widths, not the 8 -> 48 kHz stereo 32-bit case), with room
@@ -1463,148 +1470,69 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            if (b->recs.size() < (size_t)max_out + pcm_max_out + aiff_max_out + flac_max_out)
-                b->recs.resize((size_t)max_out + pcm_max_out + aiff_max_out + flac_max_out);
+            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->pcm_ts.max_out;
+            if (b->recs.size() < n_recs) b->recs.resize(n_recs);
         }
-        if (!ts.empty() && b->rc == SK_OK && !b->mpa_recs.empty()) {
-            // Layer I / II frames in this tick: the tick that takes them, with everything else in the lane's form beside them
-            const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
-            sk_tick_input in{};
-            in.n_aac_units = n_frames;
-            if (p->cfg.gpu_entropy == 2) in.descs = b->descs.data(), in.q_sides = b->au_bytes, in.q_quant = reinterpret_cast<const int16_t *>(b->coeffs);
-            else if (p->cfg.gpu_entropy) in.units = b->units.data(), in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
-            else in.descs = b->descs.data(), in.coeffs = b->coeffs;
-            if (n_frames == 0) in.descs = nullptr, in.coeffs = nullptr, in.units = nullptr, in.q_sides = nullptr;
-            sk_tick_mp3_frames md{b->mp3_frames.data(), (uint32_t)b->n_mp3_frames, b->au_bytes, b->au_used + 8};
-            const bool with_md = b->n_mp3 && p->mp3_gpu;
-            ts_md = ts;
-            if (with_md) {  // an MP3 stream's units are frames there
-                in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
-                for (size_t row = 0; row < ts_md.size(); ++row)
-                    if (ts_md[row].codec == SK_TICK_MP3) ts_md[row].n_frames = b->mp3_frames_of[b->row_of[row]];
-                b->rc = hooks.install_codebook(p->engine, p->mp3_blob.data(), p->mp3_blob.size());
-            } else if (b->n_mp3) {
-                in.n_mp3_granules = (uint32_t)b->n_mp3;
-                in.mp3_granules = b->mp3_gr.data(), in.mp3_descs = b->mp3_desc.data(), in.mp3_is = b->mp3_is;
-            }
-            b->mpa_bytes.resize(b->mpa_bytes.size() + 8, 0);
-            sk_tick_mpa_frames mpa{b->mpa_recs.data(), (uint32_t)b->mpa_recs.size(), b->mpa_bytes.data(), b->mpa_bytes.size()};
-            if (b->rc == SK_OK)
-                b->rc = hooks.tick_mpa(p->engine, ts_md.data(), (uint32_t)ts_md.size(), &in, with_md ? &md : nullptr, &mpa, b->out_pinned, b->out_pinned_cap,
-                                       b->recs.data(), max_out, &b->n_out, &used);
-        } else if (!ts.empty()) {
-            if (b->rc == SK_OK && b->n_mp3 && p->mp3_gpu) {  // the same with the MP3 streams' Huffman stage in the tick as well
-                const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
-                sk_tick_input in{};
-                in.n_aac_units = n_frames;
-                if (n_frames) in.units = b->units.data();
-                in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
-                ts_md = ts;  // an MP3 stream's units are frames there
-                for (size_t row = 0; row < ts_md.size(); ++row)
-                    if (ts_md[row].codec == SK_TICK_MP3) ts_md[row].n_frames = b->mp3_frames_of[b->row_of[row]];
-                sk_tick_mp3_frames md{b->mp3_frames.data(), (uint32_t)b->n_mp3_frames, b->au_bytes, b->au_used + 8};
+        const bool with_md = b->n_mp3 && p->mp3_gpu;  // the MP3 streams' Huffman stage is the tick's as well
+        if (ts.empty() || b->rc != SK_OK) {  // no row for the main tick, or no buffer for its outputs
+        } else if (with_md || !b->mpa_recs.empty()) {
+            // frames with main data or Layer I / II frames in this tick: the tick that takes them, with everything else in the lane's form
+            const sk_tick_input in = tick_input(p, b, n_frames, with_md);
+            const sk_tick_mp3_frames md{b->mp3_frames.data(), (uint32_t)b->n_mp3_frames, b->au_bytes, b->au_used + 8};
+            if (with_md) {
+                frames_form(b, ts, ts_md);
                 // (the lane's first engine is the caller's: something else may have put its own code book there since)
                 b->rc = hooks.install_codebook(p->engine, p->mp3_blob.data(), p->mp3_blob.size());
-                if (b->rc == SK_OK)
-                    b->rc = hooks.tick_md(p->engine, ts_md.data(), (uint32_t)ts_md.size(), &in, &md, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out,
-                                          &b->n_out, &used);
-            } else if (b->rc == SK_OK && b->n_mp3) {  // streams of both codecs in this tick: the AAC units in the lane's form, the MP3 granules beside them
-                sk_tick_input in{};
-                in.n_aac_units = n_frames;
-                if (p->cfg.gpu_entropy == 2) in.descs = b->descs.data(), in.q_sides = b->au_bytes, in.q_quant = reinterpret_cast<const int16_t *>(b->coeffs);
-                else if (p->cfg.gpu_entropy) in.units = b->units.data(), in.au_bytes = b->au_bytes, in.au_bytes_len = b->au_used + 8;
-                else in.descs = b->descs.data(), in.coeffs = b->coeffs;
-                if (n_frames == 0) in.descs = nullptr, in.coeffs = nullptr, in.units = nullptr, in.q_sides = nullptr;
-                in.n_mp3_granules = (uint32_t)b->n_mp3;
-                in.mp3_granules = b->mp3_gr.data(), in.mp3_descs = b->mp3_desc.data(), in.mp3_is = b->mp3_is;
-                b->rc = sk_tick_run_mixed(p->engine, ts.data(), (uint32_t)ts.size(), &in, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out,
-                                          &b->n_out, &used);
-            } else if (b->rc == SK_OK && p->cfg.gpu_entropy == 2)
-                b->rc = sk_tick_run_q(p->engine, ts.data(), (uint32_t)ts.size(), b->descs.data(), b->au_bytes,
-                                      reinterpret_cast<const int16_t *>(b->coeffs), n_frames, b->out_pinned, b->out_pinned_cap, b->recs.data(),
-                                      max_out, &b->n_out, &used);
-            else if (b->rc == SK_OK && p->cfg.gpu_entropy)
-                b->rc = sk_tick_run_au(p->engine, ts.data(), (uint32_t)ts.size(), b->units.data(), n_frames, b->au_bytes,
-                                       b->au_used + 8, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
-            else if (b->rc == SK_OK)
-                b->rc = sk_tick_run(p->engine, ts.data(), (uint32_t)ts.size(), b->descs.data(), b->coeffs, n_frames, b->out_pinned,
-                                    b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
+            }
+            const bool with_mpa = !b->mpa_recs.empty();
+            if (with_mpa) b->mpa_bytes.resize(b->mpa_bytes.size() + 8, 0);
+            const sk_tick_mpa_frames mpa{b->mpa_recs.data(), (uint32_t)b->mpa_recs.size(), b->mpa_bytes.data(), b->mpa_bytes.size()};
+            if (b->rc == SK_OK)
+                b->rc = hooks.tick_mpa(p->engine, with_md ? ts_md.data() : ts.data(), (uint32_t)ts.size(), &in, with_md ? &md : nullptr,
+                                       with_mpa ? &mpa : nullptr, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
+        } else if (b->n_mp3) {  // streams of both codecs: the AAC units in the lane's form, the MP3 granules beside them
+            const sk_tick_input in = tick_input(p, b, n_frames, false);
+            b->rc = sk_tick_run_mixed(p->engine, ts.data(), (uint32_t)ts.size(), &in, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out, &b->n_out,
+                                      &used);
+        } else if (p->cfg.gpu_entropy == 2) {
+            b->rc = sk_tick_run_q(p->engine, ts.data(), (uint32_t)ts.size(), b->descs.data(), b->au_bytes, reinterpret_cast<const int16_t *>(b->coeffs),
+                                  n_frames, b->out_pinned, b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
+        } else if (p->cfg.gpu_entropy) {
+            b->rc = sk_tick_run_au(p->engine, ts.data(), (uint32_t)ts.size(), b->units.data(), n_frames, b->au_bytes, b->au_used + 8, b->out_pinned,
+                                   b->out_pinned_cap, b->recs.data(), max_out, &b->n_out, &used);
+        } else {
+            b->rc = sk_tick_run(p->engine, ts.data(), (uint32_t)ts.size(), b->descs.data(), b->coeffs, n_frames, b->out_pinned, b->out_pinned_cap,
+                                b->recs.data(), max_out, &b->n_out, &used);
         }
-        if (b->rc == SK_OK && !b->aiff_ts.empty()) {  // the AIFF streams' tick of this round, behind both
-            const uint32_t first_row = (uint32_t)b->row_of.size();
-            const size_t base = (used + 15) & ~(size_t)15;
-            uint32_t n_aiff_out = 0;
-            size_t aiff_used = 0;
+        // the PCM-family ticks of this round, behind it: AIFF, FLAC, PCM
+        follow_on_tick(b, b->aiff_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
             // the IMA4 carry of each stream as the ticks before this one left it (this thread alone reads and writes it)
-            for (uint32_t row = 0; row < b->aiff_ts.size(); ++row) {
-                const PStream &s = *p->streams[b->entries[b->aiff_entry[row]].handle];
-                b->aiff_ts[row].ima_state[0] = s.aiff_ima[0], b->aiff_ts[row].ima_state[1] = s.aiff_ima[1];
+            for (uint32_t row = 0; row < b->aiff_ts.rows.size(); ++row) {
+                const PStream &s = *p->streams[b->entries[b->aiff_ts.entry[row]].handle];
+                b->aiff_ts.rows[row].ima_state[0] = s.aiff_ima[0], b->aiff_ts.rows[row].ima_state[1] = s.aiff_ima[1];
             }
-            b->rc = pcm_hooks.tick_aiff(p->engine, b->aiff_ts.data(), (uint32_t)b->aiff_ts.size(), b->aiff_units.data(), (uint32_t)b->aiff_units.size(),
-                                        b->pcm_bytes, b->pcm_used, b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, aiff_max_out,
-                                        &n_aiff_out, &aiff_used);
-            if (b->rc == SK_OK) {
-                for (uint32_t k = 0; k < n_aiff_out; ++k) {
-                    b->recs[b->n_out + k].stream_index += first_row;
-                    b->recs[b->n_out + k].byte_offset += base;
-                }
-                b->n_out += n_aiff_out;
-                for (uint32_t row = 0; row < b->aiff_entry.size(); ++row) {
-                    PStream &s = *p->streams[b->entries[b->aiff_entry[row]].handle];
-                    s.aiff_ima[0] = b->aiff_ts[row].ima_state[0], s.aiff_ima[1] = b->aiff_ts[row].ima_state[1];
-                    b->entry_row[b->aiff_entry[row]] = first_row + row;
-                    b->row_of.push_back(b->aiff_entry[row]);
-                }
-                used = base + aiff_used;
-            }
+            return hooks.tick_aiff(p->engine, b->aiff_ts.rows.data(), (uint32_t)b->aiff_ts.rows.size(), b->aiff_ts.units.data(),
+                                   (uint32_t)b->aiff_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used);
+        });
+        for (uint32_t row = 0; b->rc == SK_OK && row < b->aiff_ts.rows.size(); ++row) {  // ... and as this one leaves it
+            PStream &s = *p->streams[b->entries[b->aiff_ts.entry[row]].handle];
+            s.aiff_ima[0] = b->aiff_ts.rows[row].ima_state[0], s.aiff_ima[1] = b->aiff_ts.rows[row].ima_state[1];
         }
-        if (b->rc == SK_OK && !b->flac_ts.empty()) {  // the FLAC streams' tick of this round
-            const uint32_t first_row = (uint32_t)b->row_of.size();
-            const size_t base = (used + 15) & ~(size_t)15;
-            uint32_t n_flac_out = 0;
-            size_t flac_used = 0;
-            b->flac_status.assign(b->flac_frames.size() + 1, 0);
-            b->rc = pcm_hooks.tick_flac(p->engine, b->flac_ts.data(), (uint32_t)b->flac_ts.size(), b->flac_frames.data(), (uint32_t)b->flac_frames.size(),
-                                        b->pcm_bytes, b->pcm_used, b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, flac_max_out,
-                                        &n_flac_out, &flac_used, b->flac_status.data());
-            if (b->rc == SK_OK) {
-                for (uint32_t k = 0; k < n_flac_out; ++k) {
-                    b->recs[b->n_out + k].stream_index += first_row;
-                    b->recs[b->n_out + k].byte_offset += base;
-                }
-                b->n_out += n_flac_out;
-                for (uint32_t row = 0; row < b->flac_entry.size(); ++row) {
-                    b->entry_row[b->flac_entry[row]] = first_row + row;
-                    b->row_of.push_back(b->flac_entry[row]);
-                }
-                used = base + flac_used;
-            }
-        }
-        if (b->rc == SK_OK && !b->pcm_ts.empty()) {  // the PCM streams' tick of this round, behind the other one
-            const uint32_t first_row = (uint32_t)b->row_of.size();
-            const size_t base = (used + 15) & ~(size_t)15;
-            uint32_t n_pcm_out = 0;
-            size_t pcm_used = 0;
-            b->rc = pcm_hooks.tick_pcm(p->engine, b->pcm_ts.data(), (uint32_t)b->pcm_ts.size(), b->pcm_units.data(), (uint32_t)b->pcm_units.size(),
-                                       b->pcm_bytes, b->pcm_used, b->out_pinned + base, b->out_pinned_cap - base, b->recs.data() + b->n_out, pcm_max_out,
-                                       &n_pcm_out, &pcm_used);
-            if (b->rc == SK_OK) {
-                for (uint32_t k = 0; k < n_pcm_out; ++k) {
-                    b->recs[b->n_out + k].stream_index += first_row;
-                    b->recs[b->n_out + k].byte_offset += base;
-                }
-                b->n_out += n_pcm_out;
-                for (uint32_t row = 0; row < b->pcm_entry.size(); ++row) {
-                    b->entry_row[b->pcm_entry[row]] = first_row + row;
-                    b->row_of.push_back(b->pcm_entry[row]);
-                }
-            }
-        }
+        follow_on_tick(b, b->flac_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            b->flac_status.assign(b->flac_ts.units.size() + 1, 0);
+            return hooks.tick_flac(p->engine, b->flac_ts.rows.data(), (uint32_t)b->flac_ts.rows.size(), b->flac_ts.units.data(),
+                                   (uint32_t)b->flac_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used,
+                                   b->flac_status.data());
+        });
+        follow_on_tick(b, b->pcm_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            return hooks.tick_pcm(p->engine, b->pcm_ts.rows.data(), (uint32_t)b->pcm_ts.rows.size(), b->pcm_ts.units.data(),
+                                  (uint32_t)b->pcm_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used);
+        });
         p->submit_where = 4;
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
-        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_units.size() + (uint32_t)b->aiff_units.size() +
-                              (uint32_t)b->flac_frames.size());
+        p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_ts.units.size() +
+                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -2335,7 +2263,7 @@ int sk_pipeline_create(sk_engine *e, const sk_pipeline_config *cfg, sk_pipeline 
     const bool mp3_gpu = c.gpu_entropy == 3 || (c.gpu_entropy == 1 && mp3_gpu_env);
     if (mp3_gpu) {
         const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
-        if (!hooks.tick_md || !hooks.install_codebook) return SK_ERR_UNSUPPORTED;  // built without the device stage
+        if (!hooks.tick_mpa || !hooks.install_codebook) return SK_ERR_UNSUPPORTED;  // built without the device stage
         c.gpu_entropy = 1;
     }
     // A stream hands a tick at most `max_stream_frames_per_tick` units and is not scheduled again until that tick has been delivered, so

@@ -1,7 +1,7 @@
 // pipeline_mp3_gpu.cpp -- what lets the batch scheduler run its MP3 streams' Huffman stage in the tick (sk_pipeline_config::gpu_entropy
-// = 3): the two engine entry points pipeline.cpp must not name itself (mp3_internal.h says why), put into its table when the
-// library is loaded.  Everything else of the mode is in pipeline.cpp (parse_some_mp3 stops behind the reservoir and stages frames +
-// main data; the submission thread calls tick_md).
+// = 3) and its PCM-family and Layer I / II streams in theirs: the engine entry points pipeline.cpp must not name itself (mp3_internal.h
+// says why), put into its table when the library is loaded.  Everything else of the mode is in pipeline.cpp (parse_some_mp3 stops behind
+// the reservoir and stages frames + main data; the submission thread calls tick_mpa, sk_tick_run_mixed_mpa, with them).
 #include "mp3_internal.h"
 #include "mp12_internal.h"
 
@@ -10,7 +10,6 @@ namespace {
 const bool g_hooked = [] {
     sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
     hooks.install_codebook = sk::mp3_install_codebook;
-    hooks.tick_md = sk_tick_run_mixed_md;
     hooks.tick_pcm = sk_tick_run_pcm;  // the WAV / raw PCM streams' tick comes the same way
     hooks.tick_pcm_out_bound = sk_tick_pcm_out_bound_on;
     hooks.tick_aiff = sk_tick_run_aiff;  // ... and the AIFF streams'

@@ -2,13 +2,15 @@
 // tests/test_scheduler_cpu.py.  The real AAC front-end parses the real fixture; only the device side is replaced:
 // sk_tick_run here emits, per access unit, an "AudioData" whose bytes carry the stream id, the access unit's
 // running number within the stream and a checksum of its spectra, so ordering, completeness and isolation can be
-// checked without a GPU.  (Test infrastructure: the product library never contains this file.)
+// checked without a GPU.  The ticks of the WAV / raw PCM, AIFF and FLAC streams, which the scheduler reaches through its hook table, get
+// stand-ins of the same kind for scenario_pcm_family.  (Test infrastructure: the product library never contains this file.)
 #include "../soundkit_amd/csrc/pipeline.cpp"
 #include "../soundkit_amd/csrc/aac_frontend.cpp"
 #include "../soundkit_amd/csrc/mp3_bitstream.cpp"  // MP3 streams: the real framing, reservoir and Huffman stage (the standard's tables)
 #include "../soundkit_amd/csrc/mp3_decoder.cpp"
 #include "../soundkit_amd/csrc/load_gen.cpp"  // the bench's load generator: its feeder / consumer loops run under the sanitizers too
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <map>
@@ -247,6 +249,141 @@ int sk_tick_run(sk_engine *e, const sk_tick_stream *ts, uint32_t n_streams, cons
     return SK_OK;
 }
 }
+
+// ---- stand-ins for the PCM-family ticks (WAV / raw PCM, AIFF, FLAC), installed into pipeline_gpu_hooks() by scenario_pcm_family ----
+// One record per unit: (tag, the stream's running unit number, the unit's byte_len, the sum of its bytes, magic).  A stream without a
+// resampler names engine stream 0, so the tag is made of what its table row says plus the unit's first byte, which the scenario's
+// payloads keep constant per stream.
+static constexpr uint32_t kFamilyMagic = 0xfa3117e5u;
+static constexpr uint32_t kFamPcm = 1, kFamAiff = 2, kFamFlac = 3;
+static uint32_t family_tag(uint32_t kind, uint32_t fmt, uint32_t channels, uint32_t out_bits, uint32_t out_channels, uint8_t first) {
+    return (kind << 28) | (fmt << 20) | (channels << 16) | (out_bits << 10) | (out_channels << 8) | first;
+}
+struct FamilyState {
+    std::mutex mu;
+    std::map<uint32_t, uint32_t> next_unit;              // tag -> the stream's running unit number
+    std::map<uint32_t, sk_aiff_ima_state> ima_left;      // tag -> channel 0's carry as the last AIFF tick left it
+    int bad = 0, armed_ticks = 0;                        // tables the engine would have refused, carries that did not come back
+    std::atomic<uint32_t> arm_fail{0};                   // kFam*: the next tick of that kind sets fail_ticks = 1 on its engine
+    sk_pipeline *pipe = nullptr;
+    bool failed = false;                                 // the armed tick has failed; the public handles of its batch:
+    std::vector<uint32_t> failed_rows, failed_fast;      // entries that end with the tick's error / fast-path entries it must not touch
+    void reset(sk_pipeline *p) {
+        std::lock_guard<std::mutex> lk(mu);
+        next_unit.clear(), ima_left.clear(), failed_rows.clear(), failed_fast.clear();
+        bad = 0, armed_ticks = 0, failed = false, pipe = p;
+        arm_fail.store(0);
+    }
+};
+static FamilyState g_fam;
+
+static uint64_t fam_at(const sk_pcm_unit &u) { return u.byte_offset; }
+static uint32_t fam_len(const sk_pcm_unit &u) { return u.byte_len; }
+static uint64_t fam_at(const sk_flac_frame_info &f) { return f.offset; }
+static uint32_t fam_len(const sk_flac_frame_info &f) { return f.frame_bytes; }
+static uint32_t fam_fmt(const sk_pcm_tick_stream &t) { return t.format; }
+static uint32_t fam_fmt(const sk_aiff_tick_stream &t) { return t.encoding; }
+static uint32_t fam_fmt(const sk_flac_tick_stream &t) { return t.bits_per_sample; }
+static void fam_carry(const sk_pcm_tick_stream &, uint32_t) {}
+static void fam_carry(const sk_flac_tick_stream &, uint32_t) {}
+// the IMA4 carry advances deterministically; what arrives must be what the tick before left (zeros at the stream's start).  g_fam.mu held.
+static void fam_carry(sk_aiff_tick_stream &t, uint32_t tag) {
+    const sk_aiff_ima_state want = g_fam.ima_left.count(tag) ? g_fam.ima_left[tag] : sk_aiff_ima_state{};
+    if (t.ima_state[0].predictor != want.predictor || t.ima_state[0].step_index != want.step_index ||
+        t.ima_state[1].predictor != (int16_t)-want.predictor) {
+        std::fprintf(stderr, "AIFF carry of tag %08x: got %d / %u, the last tick left %d / %u\n", tag, t.ima_state[0].predictor,
+                     t.ima_state[0].step_index, want.predictor, want.step_index);
+        g_fam.bad += 1;
+    }
+    t.ima_state[0].predictor = (int16_t)(want.predictor + (int16_t)t.n_units);
+    t.ima_state[0].step_index = (uint8_t)((want.step_index + 1) % 89);
+    t.ima_state[1].predictor = (int16_t)-t.ima_state[0].predictor;
+    g_fam.ima_left[tag] = t.ima_state[0];
+}
+// The tick that is armed to fail: it waits (for a while) for a batch that also holds a fast-path entry, then notes which of the batch's
+// entries the scheduler must end with the error and which it must leave alone.  true: this is the tick that fails.  g_fam.mu held.
+static bool fam_fail_this_batch(sk_engine *e, const uint8_t *bytes) {
+    for (sk_lane *l : g_fam.pipe->lanes) {
+        if (l->engine != e) continue;
+        for (const Batch &b : l->batches) {
+            if (b.pcm_bytes != bytes) continue;
+            bool fast = false;
+            for (const BatchEntry &be : b.entries) fast = fast || (be.pcm && !be.pcm_row);
+            if (!fast && ++g_fam.armed_ticks < 4) return false;
+            for (const BatchEntry &be : b.entries)
+                (be.pcm && !be.pcm_row ? g_fam.failed_fast : g_fam.failed_rows).push_back(be.handle * l->n_lanes + l->lane_index);
+            return g_fam.failed = true;
+        }
+    }
+    return false;
+}
+
+template <class Row, class Unit>
+static size_t family_out_bound(const Row *, uint32_t n, const Unit *, uint32_t n_units, uint32_t *max_outputs) {
+    *max_outputs = n_units + n;
+    return (size_t)(n_units + n) * 64;
+}
+template <class Row, class Unit>
+static int family_tick(uint32_t kind, sk_engine *e, Row *ts, uint32_t n, const Unit *units, uint32_t n_units, const uint8_t *bytes, size_t bytes_len,
+                       uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *used) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    tick_delay();
+    std::lock_guard<std::mutex> fl(g_fam.mu);
+    if (g_fam.arm_fail.load() == kind && fam_fail_this_batch(e, bytes)) {
+        g_fam.arm_fail.store(0);
+        e->fail_ticks.store(1);
+    }
+    if (e->fail_ticks.load() > 0 && e->fail_ticks.fetch_sub(1) > 0) return SK_ERR_HIP;
+    auto refuse = [&](const char *why) {
+        std::fprintf(stderr, "tick of kind %u refused: %s\n", kind, why);
+        g_fam.bad += 1;
+        return SK_ERR_INVALID_ARG;
+    };
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) total += ts[i].n_units;
+    if (n == 0 || total != n_units) return refuse("the rows' unit counts do not add up");
+    uint32_t k = 0, u = 0;
+    size_t cursor = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (ts[i].n_units == 0 && !ts[i].flush) return refuse("a row without units or a flush");
+        if (ts[i].n_units == 0) continue;
+        if (fam_at(units[u]) >= bytes_len) return refuse("a unit outside the staged bytes");
+        const uint32_t tag = family_tag(kind, fam_fmt(ts[i]), ts[i].channels, ts[i].out_bits, ts[i].out_channels, bytes[fam_at(units[u])]);
+        fam_carry(ts[i], tag);
+        for (uint32_t j = 0; j < ts[i].n_units; ++j, ++u) {
+            const uint64_t at = fam_at(units[u]);
+            const uint32_t len = fam_len(units[u]);
+            if (at % 16 || len == 0 || at + len > bytes_len) return refuse("a unit that is misaligned, empty or outside the staged bytes");
+            if (k >= outs_cap || cursor + 64 > out_cap) return refuse("outputs beyond the bound");
+            uint32_t sum = 0;
+            for (uint32_t c = 0; c < len; ++c) sum += bytes[at + c];
+            const uint32_t words[8] = {tag, g_fam.next_unit[tag]++, len, sum, kFamilyMagic, 0, 0, 0};
+            std::memcpy(out + cursor, words, 32);
+            outs[k++] = sk_tick_output{i, 1, cursor, 32, 0, ts[i].out_channels, ts[i].out_bits, 0};
+            cursor += 64;
+        }
+    }
+    *n_outs = k;
+    if (used) *used = cursor;
+    return SK_OK;
+}
+static int stub_tick_pcm(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                         size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *used) {
+    return family_tick(kFamPcm, e, ts, n, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, used);
+}
+static int stub_tick_aiff(sk_engine *e, sk_aiff_tick_stream *ts, uint32_t n, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                          size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *used) {
+    return family_tick(kFamAiff, e, ts, n, units, n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, used);
+}
+static int stub_tick_flac(sk_engine *e, const sk_flac_tick_stream *ts, uint32_t n, const sk_flac_frame_info *frames, uint32_t n_frames,
+                          const uint8_t *bytes, size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap,
+                          uint32_t *n_outs, size_t *used, int32_t *status_per_frame) {
+    for (uint32_t k = 0; k < n_frames; ++k) status_per_frame[k] = 0;
+    return family_tick(kFamFlac, e, ts, n, frames, n_frames, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, used);
+}
+static size_t stub_pcm_bound(sk_engine *, const sk_pcm_tick_stream *ts, uint32_t n, const sk_pcm_unit *u, uint32_t nu, uint32_t *mo) { return family_out_bound(ts, n, u, nu, mo); }
+static size_t stub_aiff_bound(sk_engine *, const sk_aiff_tick_stream *ts, uint32_t n, const sk_pcm_unit *u, uint32_t nu, uint32_t *mo) { return family_out_bound(ts, n, u, nu, mo); }
+static size_t stub_flac_bound(sk_engine *, const sk_flac_tick_stream *ts, uint32_t n, const sk_flac_frame_info *u, uint32_t nu, uint32_t *mo) { return family_out_bound(ts, n, u, nu, mo); }
 
 // ---- scenarios -------------------------------------------------------------------------------------------
 static std::vector<uint8_t> clip;
@@ -770,6 +907,273 @@ static int scenario_mixed_codecs(sk_engine *e) {
     return 0;
 }
 
+// The PCM-family ticks behind one scheduler with the AAC tick: raw PCM and WAV streams that need a conversion (the PCM tick), AIFF and
+// AIFF-C IMA4 streams (the AIFF tick, with its carry), FLAC streams as decoded and with a depth change (the FLAC tick), a WAV stream with
+// nothing to change (delivered as it is, an entry without a row) and ADTS streams, all fed at once in ragged chunks from two threads.
+// Every unit must come back once, in order, under its own stream's handle, whatever the cut; with fail_kind != 0 one tick of that
+// kind fails, and exactly the streams with a row in its batch end with one error.
+struct FamilyStream {
+    std::vector<uint8_t> bytes;         // what is sent
+    uint32_t tag = 0;                   // 0: an ADTS stream or the fast-path one
+    uint64_t want_len = 0, want_sum = 0;  // over the stream's payload
+    bool adts = false, fast = false;
+    uint32_t handle = 0;
+    // what arrived
+    std::vector<Got> got;               // ADTS
+    uint32_t units = 0, errors = 0, after_error = 0;
+    uint64_t len = 0, sum = 0;
+    bool foreign = false, out_of_order = false;
+};
+static void put_be(std::vector<uint8_t> &v, uint64_t x, int n) { for (int k = n - 1; k >= 0; --k) v.push_back((uint8_t)(x >> (8 * k))); }
+static void put_le(std::vector<uint8_t> &v, uint64_t x, int n) { for (int k = 0; k < n; ++k) v.push_back((uint8_t)(x >> (8 * k))); }
+static void put_str(std::vector<uint8_t> &v, const char *s) { v.insert(v.end(), s, s + 4); }
+// `groups` sample groups of `group` bytes each: the first byte is the stream's constant, the others are drawn
+static std::vector<uint8_t> family_payload(uint8_t first, size_t group, size_t groups, FamilyStream &st) {
+    std::vector<uint8_t> v(group * groups);
+    for (size_t i = 0; i < v.size(); ++i) v[i] = i % group == 0 ? first : (uint8_t)rnd();
+    st.want_len = v.size();
+    st.want_sum = 0;
+    for (uint8_t b : v) st.want_sum += b;
+    return v;
+}
+static std::vector<uint8_t> family_wav(uint32_t channels, uint32_t bits, const std::vector<uint8_t> &data) {
+    std::vector<uint8_t> v;
+    put_str(v, "RIFF"), put_le(v, 36 + data.size(), 4), put_str(v, "WAVE"), put_str(v, "fmt "), put_le(v, 16, 4);
+    put_le(v, 1, 2), put_le(v, channels, 2), put_le(v, 44100, 4), put_le(v, 44100 * channels * bits / 8, 4), put_le(v, channels * bits / 8, 2), put_le(v, bits, 2);
+    put_str(v, "data"), put_le(v, data.size(), 4);
+    v.insert(v.end(), data.begin(), data.end());
+    return v;
+}
+static std::vector<uint8_t> family_aiff(bool ima4, uint32_t frames, const std::vector<uint8_t> &data) {
+    std::vector<uint8_t> comm;
+    put_be(comm, 1, 2), put_be(comm, frames, 4), put_be(comm, 16, 2), put_be(comm, 0x400e, 2), put_be(comm, 0xac44000000000000ull, 8);  // mono, 44100 Hz
+    if (ima4) put_str(comm, "ima4"), put_be(comm, 0, 2);
+    std::vector<uint8_t> v;
+    put_str(v, "FORM"), put_be(v, 4 + 8 + comm.size() + 8 + 8 + data.size(), 4), put_str(v, ima4 ? "AIFC" : "AIFF");
+    put_str(v, "COMM"), put_be(v, comm.size(), 4);
+    v.insert(v.end(), comm.begin(), comm.end());
+    put_str(v, "SSND"), put_be(v, 8 + data.size(), 4), put_be(v, 0, 8);
+    v.insert(v.end(), data.begin(), data.end());
+    return v;
+}
+
+static std::vector<uint8_t> flac_clip;  // the fixture's frames behind a marker and a STREAMINFO made here (the file has neither)
+static int scenario_pcm_family(sk_engine *e, uint32_t fail_kind) {
+    sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
+    hooks.tick_pcm = stub_tick_pcm, hooks.tick_pcm_out_bound = stub_pcm_bound;
+    hooks.tick_aiff = stub_tick_aiff, hooks.tick_aiff_out_bound = stub_aiff_bound;
+    hooks.tick_flac = stub_tick_flac, hooks.tick_flac_out_bound = stub_flac_bound;
+    sk_pipeline_config cfg{};
+    cfg.entropy_threads = 3;
+    cfg.max_streams = 20;
+    cfg.max_frames_per_tick = 40;
+    cfg.max_stream_frames_per_tick = 5;
+    cfg.tick_wait_us = 50;
+    cfg.lanes = g_lanes;
+    sk_pipeline *p = nullptr;
+    CHECK(sk_pipeline_create(e, &cfg, &p) == SK_OK);
+    g_fam.reset(p);
+    const uint32_t adts_loops = 2;
+    std::vector<FamilyStream> st(16);
+    size_t n = 0;
+    sk_decode_options to16{}, to24{};
+    to16.output_bits_per_sample = 16;
+    to24.output_bits_per_sample = 24;
+    for (uint32_t i = 0; i < 4; ++i, ++n) {  // ADTS
+        st[n].adts = true;
+        for (uint32_t l = 0; l < adts_loops; ++l) st[n].bytes.insert(st[n].bytes.end(), clip.begin(), clip.end());
+        CHECK(sk_pipeline_spawn(p, nullptr, &st[n].handle) == SK_OK);
+    }
+    for (uint32_t i = 0; i < 3; ++i, ++n) {  // raw PCM, s16le stereo to 24 bits: the PCM tick
+        st[n].bytes = family_payload((uint8_t)(0x10 + i), 4, 6000, st[n]);
+        st[n].tag = family_tag(kFamPcm, SK_FMT_S16LE, 2, 24, 2, (uint8_t)(0x10 + i));
+        const sk_raw_pcm_format f{44100, 2, SK_FMT_S16LE, 0};
+        CHECK(sk_pipeline_spawn_raw_pcm(p, &f, &to24, &st[n].handle) == SK_OK);
+    }
+    for (uint32_t i = 0; i < 2; ++i, ++n) {  // WAV, s24 mono to 16 bits: the PCM tick behind the detection
+        st[n].bytes = family_wav(1, 24, family_payload((uint8_t)(0x20 + i), 3, 5000, st[n]));
+        st[n].tag = family_tag(kFamPcm, SK_FMT_S24LE, 1, 16, 1, (uint8_t)(0x20 + i));
+        CHECK(sk_pipeline_spawn(p, &to16, &st[n].handle) == SK_OK);
+    }
+    for (uint32_t i = 0; i < 3; ++i, ++n) {  // AIFF, big-endian s16 mono, no options: the AIFF tick, as decoded
+        st[n].bytes = family_aiff(false, 5000, family_payload((uint8_t)(0x30 + i), 2, 5000, st[n]));
+        st[n].tag = family_tag(kFamAiff, SK_AIFF_S16BE, 1, 16, 1, (uint8_t)(0x30 + i));
+        // found by its FORM header behind the detection buffer, or (the last one) spawned as AIFF: every chunk is one add from the start
+        CHECK((i < 2 ? sk_pipeline_spawn(p, nullptr, &st[n].handle) : sk_pipeline_spawn_aiff(p, nullptr, &st[n].handle)) == SK_OK);
+    }
+    {  // AIFF-C IMA4 mono, 40 packets: the carry
+        st[n].bytes = family_aiff(true, 40 * 64, family_payload(0x40, 34, 40, st[n]));
+        st[n].tag = family_tag(kFamAiff, SK_AIFF_IMA4, 1, 16, 1, 0x40);
+        CHECK(sk_pipeline_spawn_aiff(p, nullptr, &st[n].handle) == SK_OK);  // (no detection buffer: the stream is shorter than one)
+        ++n;
+    }
+    for (uint32_t i = 0; i < 2; ++i, ++n) {  // FLAC, 16-bit stereo: as decoded, and to 24 bits; the sums are those of the frames a reader finds
+        st[n].bytes = flac_clip;
+        st[n].tag = family_tag(kFamFlac, 16, 2, i ? 24 : 16, 2, 0xff);
+        sk_flac::Reader reader;
+        std::vector<sk_flac_frame_info> frames(64);
+        for (int pass = 0; pass < 2; ++pass) {
+            uint32_t found = 0;
+            const uint8_t *base = nullptr;
+            CHECK(reader.feed(pass ? nullptr : flac_clip.data(), pass ? 0 : flac_clip.size(), pass == 1, frames.data(), 64, &found, &base));
+            CHECK(found < 64);
+            for (uint32_t k = 0; k < found; ++k) {
+                st[n].want_len += frames[k].frame_bytes;
+                for (uint32_t c = 0; c < frames[k].frame_bytes; ++c) st[n].want_sum += base[frames[k].offset + c];
+            }
+        }
+        CHECK(reader.frames() == 11 && st[n].want_len > 30000);
+        CHECK(sk_pipeline_spawn(p, i ? &to24 : nullptr, &st[n].handle) == SK_OK);
+    }
+    {  // WAV, s16 mono, nothing to change: delivered as it is, an entry without a row between the others'
+        st[n].fast = true;
+        st[n].bytes = family_wav(1, 16, family_payload(0x50, 2, 20000, st[n]));
+        CHECK(sk_pipeline_spawn(p, nullptr, &st[n].handle) == SK_OK);
+        ++n;
+    }
+    CHECK(n == st.size());
+    std::vector<std::thread> feeders;
+    for (uint32_t t = 0; t < 2; ++t)
+        feeders.emplace_back([&, t] {
+            std::vector<size_t> sent(st.size(), 0);
+            std::vector<char> done(st.size(), 0);
+            uint32_t seed = 777 + t;
+            size_t live = 0, total = 0, total_sent = 0;
+            for (size_t i = t; i < st.size(); i += 2) ++live, total += st[i].bytes.size();
+            bool armed = false;
+            while (live) {
+                if (t == 0 && fail_kind && !armed && total_sent * 4 >= total) g_fam.arm_fail.store(fail_kind), armed = true;
+                bool moved = false;
+                for (size_t i = t; i < st.size(); i += 2) {
+                    if (done[i]) continue;
+                    int rc;
+                    if (sent[i] == st[i].bytes.size()) {
+                        rc = sk_pipeline_finish(p, st[i].handle);
+                        if (rc == SK_OK || rc == SK_PIPE_CLOSED) done[i] = 1, --live, moved = true;
+                        else if (rc != SK_PIPE_INPUT_FULL) std::abort();
+                        continue;
+                    }
+                    seed = seed * 1664525u + 1013904223u;
+                    // paced by the scheduler itself, so that the streams go through many ticks side by side: mostly one chunk at a
+                    // time (a pass of one unit), now and then a second and third behind it (a row of several units)
+                    if (sk_pipeline_queued_input_bytes(p, st[i].handle) > 0 && (seed >> 12) % 4) continue;
+                    const size_t most = (seed >> 28) == 0 ? 1 : st[i].bytes.size() / 12 + 1;  // 1 byte ... a few KiB, about two dozen chunks a stream
+                    const size_t len = std::min(st[i].bytes.size() - sent[i], 1 + (size_t)(seed >> 8) % most);
+                    rc = sk_pipeline_send(p, st[i].handle, st[i].bytes.data() + sent[i], len);
+                    if (rc == SK_OK) sent[i] += len, total_sent += len, moved = true;
+                    else if (rc == SK_PIPE_CLOSED) done[i] = 1, --live, moved = true;  // ended by the failed tick
+                    else if (rc != SK_PIPE_INPUT_FULL) std::abort();
+                }
+                if (!moved) std::this_thread::sleep_for(std::chrono::microseconds(100));
+            }
+        });
+    {
+        std::vector<uint8_t> buf(1 << 16);
+        std::vector<char> ended(st.size(), 0);
+        size_t live = st.size();
+        const auto t0 = std::chrono::steady_clock::now();
+        while (live) {
+            CHECK(std::chrono::steady_clock::now() - t0 < std::chrono::seconds(120));
+            for (size_t i = 0; i < st.size(); ++i) {
+                if (ended[i]) continue;
+                FamilyStream &s = st[i];
+                sk_audio_info info;
+                const int rc = sk_pipeline_try_recv(p, s.handle, buf.data(), buf.size(), &info);
+                if (rc == SK_PIPE_CLOSED) {
+                    CHECK(!ended[i]);
+                    ended[i] = 1;
+                    --live;
+                    continue;
+                }
+                if (rc != 1) continue;
+                if (s.errors) s.after_error += 1;
+                if (info.is_error) {
+                    s.errors += 1;
+                } else if (s.fast) {
+                    s.len += info.bytes;
+                    for (uint32_t c = 0; c < info.bytes; ++c) s.sum += buf[c];
+                } else if (s.adts) {
+                    uint32_t w[4];
+                    std::memcpy(w, buf.data(), 16);
+                    CHECK(w[3] == 0xabcd1234u && info.frames == 1024);
+                    s.got.push_back(Got{w[0], w[1], w[2]});
+                } else {
+                    uint32_t w[8];
+                    CHECK(info.bytes == 32);
+                    std::memcpy(w, buf.data(), 32);
+                    CHECK(w[4] == kFamilyMagic);
+                    if (w[0] != s.tag) s.foreign = true;
+                    if (w[1] != s.units) s.out_of_order = true;
+                    s.units += 1;
+                    s.len += w[2];
+                    s.sum += w[3];
+                }
+            }
+            std::this_thread::sleep_for(std::chrono::microseconds(200));
+        }
+    }
+    for (auto &th : feeders) th.join();
+    std::vector<uint32_t> failed_rows, failed_fast;
+    {
+        std::lock_guard<std::mutex> lk(g_fam.mu);
+        CHECK(g_fam.bad == 0);
+        CHECK(g_fam.failed == (fail_kind != 0));
+        failed_rows = g_fam.failed_rows, failed_fast = g_fam.failed_fast;
+    }
+    CHECK(!fail_kind || !failed_rows.empty());
+    uint64_t want_errors = 0;
+    const FamilyStream *adts0 = nullptr;
+    for (const FamilyStream &s : st) {
+        const bool hit = std::find(failed_rows.begin(), failed_rows.end(), s.handle) != failed_rows.end();
+        CHECK(!(hit && s.fast));
+        CHECK(!s.foreign && !s.out_of_order);     // only its own records; unit numbers 0, 1, 2, ... none missing, none repeated
+        CHECK(s.after_error == 0);                // an error is the last thing a stream receives
+        CHECK(s.errors == (hit ? 1u : 0u));       // with a row in the failed batch: one error; every other stream: none
+        want_errors += s.errors;
+        for (size_t k = 0; k < s.got.size(); ++k) {
+            CHECK(s.got[k].unit == k);
+            CHECK(s.got[k].stream_tag == s.got[0].stream_tag);
+        }
+        if (hit) {  // what it already had, and no more than the whole
+            CHECK(s.len <= s.want_len && s.sum <= s.want_sum && s.got.size() <= (size_t)48 * adts_loops);
+            continue;
+        }
+        if (s.adts) {
+            CHECK(s.got.size() == (size_t)48 * adts_loops);
+            if (!adts0) adts0 = &s;
+            for (size_t k = 0; k < s.got.size(); ++k) CHECK(s.got[k].sum == adts0->got[k % 48].sum);  // same clip -> same checksums per position
+        } else {
+            CHECK(s.len == s.want_len && s.sum == s.want_sum);  // every byte of the payload, once, whatever the cut into units
+            CHECK(s.fast || s.units > 0);
+            if (s.tag == family_tag(kFamAiff, SK_AIFF_IMA4, 1, 16, 1, 0x40)) CHECK(s.units >= 4);  // the carry went through several ticks
+        }
+    }
+    sk_pipeline_stats stats;
+    CHECK(sk_pipeline_get_stats(p, &stats) == SK_OK && stats.errors == want_errors);
+    for (const FamilyStream &s : st) CHECK(sk_pipeline_cancel(p, s.handle) == SK_OK);
+    {   // every handle and every engine stream came back
+        const auto t0 = std::chrono::steady_clock::now();
+        for (;;) {
+            size_t free_now = 0, slots = 0;
+            for (sk_lane *l : p->lanes) {
+                std::lock_guard<std::mutex> lk(l->handles_mu);
+                free_now += l->free_handles.size();
+                slots += l->streams.size();
+            }
+            if (free_now == slots) break;
+            CHECK(std::chrono::steady_clock::now() - t0 < std::chrono::seconds(20));
+            std::this_thread::sleep_for(std::chrono::microseconds(100));
+        }
+        for (sk_lane *l : p->lanes) {
+            std::lock_guard<std::mutex> lk(l->engine->mu);
+            for (uint8_t o : l->engine->open) CHECK(o == 0);
+        }
+    }
+    sk_pipeline_destroy(p);
+    g_fam.reset(nullptr);
+    return 0;
+}
+
 static int scenario_cancel_churn(sk_engine *e);
 static int scenario_cancel_churn(sk_engine *e) {
     sk_pipeline_config cfg{};
@@ -871,6 +1275,34 @@ static int slow_tick_main(int argc, char **argv) {
     return 0;
 }
 
+// scenario_pcm_family on one and two lanes, with one and three delivery threads; a second pass each in which one follow-on tick fails
+static int pcm_family_main(sk_engine *ep, const char *clip_path) {
+    sk_engine &e = *ep;
+    {   // the reference's 16-bit FLAC frames; the file has no marker and no STREAMINFO, which a stream needs: both are made here
+        std::string path = clip_path;
+        path = path.substr(0, path.rfind("/aac/")) + "/flac/A_Tusk_is_used_to_make_costly_gifts_16bit.flac";
+        FILE *m = std::fopen(path.c_str(), "rb");
+        if (!m) return 68;
+        std::vector<uint8_t> frames(1 << 20);
+        frames.resize(std::fread(frames.data(), 1, frames.size(), m));
+        std::fclose(m);
+        put_str(flac_clip, "fLaC"), put_be(flac_clip, 0x80000022u, 4);  // the last metadata block: STREAMINFO, 34 bytes
+        put_be(flac_clip, 4096, 2), put_be(flac_clip, 4096, 2), put_be(flac_clip, 0, 3), put_be(flac_clip, 0, 3);
+        put_be(flac_clip, ((uint64_t)16000 << 44) | ((uint64_t)(2 - 1) << 41) | ((uint64_t)(16 - 1) << 36), 8);  // 16 kHz, stereo, 16 bits, length unknown
+        flac_clip.resize(flac_clip.size() + 16, 0);  // no MD5
+        flac_clip.insert(flac_clip.end(), frames.begin(), frames.end());
+    }
+    for (uint32_t config = 0; config < 4; ++config) {
+        g_lanes = 1 + config % 2;
+        if (config >= 2) setenv("SK_PIPELINE_DELIVER_THREADS", "3", 1);
+        if (int rc = scenario_pcm_family(&e, 0)) return rc;
+        const uint32_t fail_kind[4] = {kFamFlac, kFamPcm, kFamAiff, kFamFlac};  // the follow-on tick that fails once in the second pass
+        if (int rc = scenario_pcm_family(&e, fail_kind[config])) return rc;
+    }
+    unsetenv("SK_PIPELINE_DELIVER_THREADS");
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) return 64;
     FILE *f = std::fopen(argv[1], "rb");
@@ -884,6 +1316,7 @@ int main(int argc, char **argv) {
     e.next_unit.assign(64, 0);
     e.rs_fill.assign(64, 0);
     if (argc > 2 && std::string(argv[2]) == "slow") return slow_tick_main(argc, argv);
+    if (argc > 2 && std::string(argv[2]) == "family") return pcm_family_main(&e, argv[1]);  // that scenario alone
     if (int rc = scenario_many_streams(&e)) return rc;
     setenv("SK_PIPELINE_DELIVER_THREADS", "3", 1);  // the sliced delivery path, as the GPU front-end mode uses it
     if (int rc = scenario_many_streams(&e)) return rc;
@@ -933,6 +1366,7 @@ int main(int argc, char **argv) {
     if (int rc = scenario_max_length_frames(&e)) return rc;
     g_lanes = 2;
     if (int rc = scenario_max_length_frames(&e)) return rc;
+    if (int rc = pcm_family_main(&e, argv[1])) return rc;
     std::puts("scheduler scenarios ok");
     return 0;
 }
