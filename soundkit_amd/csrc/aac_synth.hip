@@ -68,14 +68,17 @@ __device__ __forceinline__ void dft8(f2 (&x)[8]) {
     f2 u0 = cadd(x[1], x[5]), u1 = csub(x[1], x[5]);
     f2 u2 = cadd(x[3], x[7]), u3 = mul_mi(csub(x[3], x[7]));
     f2 o0 = cadd(u0, u2), o2 = csub(u0, u2), o1 = cadd(u1, u3), o3 = csub(u1, u3);
-    // twiddles W8^k
-    f2 w1 = (f2){(o1.x + o1.y) * h, (o1.y - o1.x) * h};   // o1 * (1-i)/sqrt2
-    f2 w2 = mul_mi(o2);                                          // o2 * (-i)
-    f2 w3 = (f2){(o3.y - o3.x) * h, -(o3.x + o3.y) * h};  // o3 * (-1-i)/sqrt2
+    // twiddles W8^k.  The two rotations by odd eighths are (s, d) * h with s = re + im, d = im - re: h rides in the last
+    // butterfly's fused multiply-add (e +- (s, d) * h rounded once), so the products are never instructions of their own
+    const float s1 = o1.x + o1.y, d1 = o1.y - o1.x;  // o1 * (1-i)/sqrt2  = ( s1,  d1) * h
+    const float s3 = o3.x + o3.y, d3 = o3.y - o3.x;  // o3 * (-1-i)/sqrt2 = ( d3, -s3) * h
+    f2 w2 = mul_mi(o2);                               // o2 * (-i)
     x[0] = cadd(e0, o0); x[4] = csub(e0, o0);
-    x[1] = cadd(e1, w1); x[5] = csub(e1, w1);
+    x[1] = (f2){__builtin_fmaf(s1, h, e1.x), __builtin_fmaf(d1, h, e1.y)};
+    x[5] = (f2){__builtin_fmaf(-s1, h, e1.x), __builtin_fmaf(-d1, h, e1.y)};
     x[2] = cadd(e2, w2); x[6] = csub(e2, w2);
-    x[3] = cadd(e3, w3); x[7] = csub(e3, w3);
+    x[3] = (f2){__builtin_fmaf(d3, h, e3.x), __builtin_fmaf(-s3, h, e3.y)};
+    x[7] = (f2){__builtin_fmaf(-d3, h, e3.x), __builtin_fmaf(s3, h, e3.y)};
 }
 
 __device__ __forceinline__ void wave_sync() {
@@ -141,21 +144,38 @@ __device__ __forceinline__ void write_positions(lds_f *buf, int lane, const floa
     }
 }
 
+// Stage-1 twiddles of fft512: lane l multiplies its register k (1..7) by W512^{l k} = w512[l k].  A kernel keeps the seven either in
+// registers for the whole launch (stage1_twiddles from the table in memory, once) or, where the registers are not to be had, in a
+// per-workgroup LDS table laid out [k - 1][lane] (fill_stage1_table; 7 x 64 f2 = 3584 B, consecutive lanes on consecutive
+// 8-byte slots: no bank conflict) and reads them in front of every transform.  The same seven numbers either way.
+constexpr int kStage1Tab = 7 * 64;
+__device__ __forceinline__ void fill_stage1_table(f2 *tab, const float2 *w512, int tid, int n_threads) {
+    for (int i = tid; i < kStage1Tab; i += n_threads) tab[i] = reinterpret_cast<const f2 *>(w512)[(i & 63) * ((i >> 6) + 1)];
+}
+__device__ __forceinline__ void stage1_twiddles(f2 (&tw1)[7], const float2 *w512, int lane) {
+#pragma unroll
+    for (int k = 1; k < 8; ++k) tw1[k - 1] = reinterpret_cast<const f2 *>(w512)[lane * k];
+}
+__device__ __forceinline__ void stage1_twiddles(f2 (&tw1)[7], const lds_f2 *tab, int lane) {
+#pragma unroll
+    for (int k = 1; k < 8; ++k) tw1[k - 1] = tab[64 * (k - 1) + lane];
+}
+
 // 512-point forward FFT of z (z[r] = element 64 r + lane) through two LDS exchanges:
 // n = 64 n1 + 8 n2 + n3, k = k1 + 8 k2 + 64 k3; on return z[j] = Z[lane + 64 j].
-// Stage 1 (lane = 8 n2 + n3) needs W64^{n2 k1}; stage 2 (lane = 8 n3 + k1) needs
-// W512^{n3 (k1 + 8 k2)} = W512^{n3 k1} * W64^{n3 k2}: both W64 factors are W64^{(lane>>3) k}, so one
-// 8 x 8 table (t64[k][lane>>3], in LDS) serves both stages and stage 2 adds one per-lane constant.
-__device__ __forceinline__ void fft512(f2 (&z)[8], lds_f2 *ex, const lds_f2 *t64, f2 base2, int lane) {
+// Stage 1 (lane = 8 n2 + n3) owes output k1 the factors W64^{n2 k1} and W512^{n3 k1}: their product is
+// W512^{(8 n2 + n3) k1} = W512^{lane k1}, ONE root of the 512 (lane k1 <= 441: no wrap), each rounded once from f64 -- tw1[k1 - 1],
+// seven constants per lane (stage1_twiddles).  Stage 2 (lane = 8 n3 + k1) needs W64^{n3 k2} = t64[k2][lane >> 3], in LDS.
+__device__ __forceinline__ void fft512(f2 (&z)[8], lds_f2 *ex, const lds_f2 *t64, const f2 (&tw1)[7], int lane) {
     const int hi3 = lane >> 3, lo3 = lane & 7;
     dft8(z);  // over n1 -> k1
 #pragma unroll
-    for (int k = 1; k < 8; ++k) z[k] = cmul(z[k], t64[8 * k + hi3]);
+    for (int k = 1; k < 8; ++k) z[k] = cmul(z[k], tw1[k - 1]);
 #pragma unroll
     for (int k = 0; k < 8; ++k) ex[k * 68 + lane] = z[k];
     wave_sync();
 #pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) z[n2] = cmul(ex[lo3 * 68 + 8 * n2 + hi3], base2);
+    for (int n2 = 0; n2 < 8; ++n2) z[n2] = ex[lo3 * 68 + 8 * n2 + hi3];
     wave_sync();
     dft8(z);  // over n2 -> k2
 #pragma unroll
@@ -178,12 +198,12 @@ __device__ __forceinline__ void fft512(f2 (&z)[8], lds_f2 *ex, const lds_f2 *t64
 //        `lane` of block r); stage = overlap delay at this lane's 16 positions (write_positions)
 //   out: PCM written to out_ptr; stage = new delay at this lane's 16 positions
 __device__ __attribute__((noinline)) void synth_rare_frame(lds_f2 *ex, lds_f *stage, const lds_f2 *tw_lds,
-                                                            const lds_f2 *t64, float base2_re, float base2_im,
+                                                            const lds_f2 *t64,
                                                             const lds_f *short_win, const lds_f2 *w64, const lds_f2 *tw_short,
                                                             float *out_ptr, int16_t *out16_ptr, int seq, int prev_shape,
                                                             int shape, int lane) {
     const int hi3 = lane >> 3, lo3 = lane & 7;
-    (void)base2_re, (void)base2_im, (void)t64, (void)tw_lds, (void)seq;  // only the short transform is left here
+    (void)t64, (void)tw_lds, (void)seq;  // only the short transform is left here
     // short_win (the sine and the KBD short window), w64, tw_short: LDS copies made once per workgroup -- from global memory
     // they were three trips to memory in the middle of every EightShort frame
     const lds_f *prev_short = short_win + 256 * prev_shape;
@@ -295,9 +315,13 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
     __shared__ f2 t64_tab[64];  // t64[k][n] = W64^{n k}
     __shared__ float short_win_tab[ONLY_LONG ? 2 : 512];  // the sine and the KBD short window (eight-short frames only)
     __shared__ f2 short_tw_tab[ONLY_LONG ? 1 : 128];       // w64[64] | tw_short[64]
+    // stage-1 twiddles from LDS in every instantiation: fourteen more registers would cost the long-only form its fourth wave
+    // per SIMD, and in the other one they would be live across the call of the rare arm
+    __shared__ f2 tw1_tab[kStage1Tab];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    fill_stage1_table(tw1_tab, a.t.w512, threadIdx.x, kWavesPerBlock * 64);
     for (int i = threadIdx.x; i < 512; i += kWavesPerBlock * 64) tw_tab[i] = reinterpret_cast<const f2 *>(a.t.tw_long)[i];
     if (threadIdx.x < 64) t64_tab[threadIdx.x] = reinterpret_cast<const f2 *>(a.t.w64)[((threadIdx.x >> 3) * (threadIdx.x & 7)) & 63];
     if (!ONLY_LONG) {
@@ -321,9 +345,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
     const uint32_t state = __builtin_amdgcn_readfirstlane(task_v.state);
     if (count == 0) return;
     const const_entries entries = as_constant(a.entries + __builtin_amdgcn_readfirstlane(task_v.begin));
-
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const f2 base2 = reinterpret_cast<const f2 *>(a.t.w512)[hi3 * lo3];
 
     // carried state ---------------------------------------------------------------
     float *delay_ptr = a.delay + (size_t)state * 1024;
@@ -387,7 +408,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
                 const float even = xin[r].x;
                 const float odd = -__shfl(xin[7 - r].y, 63 - lane);  // X[1023 - 2 i]
                 const f2 t = tw_lds[lane + 64 * r];
-                z[r] = (f2){odd * t.y - even * t.x, odd * t.x + even * t.y};
+                z[r] = (f2){__builtin_fmaf(odd, t.y, -(even * t.x)), __builtin_fmaf(odd, t.x, even * t.y)};
             }
         } else {
             const f2 tws = short_tw_tab[ONLY_LONG ? 0 : 64 + lane];
@@ -395,7 +416,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
             for (int w = 0; w < 8; ++w) {  // z_w[lane] of short block w
                 const float even = xin[w].x;
                 const float odd = -__shfl(xin[w].y, 63 - lane);  // X_w[127 - 2 lane]
-                z[w] = (f2){odd * tws.y - even * tws.x, odd * tws.x + even * tws.y};
+                z[w] = (f2){__builtin_fmaf(odd, tws.y, -(even * tws.x)), __builtin_fmaf(odd, tws.x, even * tws.y)};
             }
         }
         if (ONLY_LONG || seq != 2) {
@@ -426,7 +447,9 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
 #pragma unroll
                 for (int r = 0; r < 8; ++r) xin[r] = SK_SYNTH_LOAD(reinterpret_cast<const f2 *>(src + 128 * r));
             }
-            fft512(z, ex, t64, base2, lane);
+            f2 tw1[7];
+            stage1_twiddles(tw1, (const lds_f2 *)tw1_tab, lane);
+            fft512(z, ex, t64, tw1, lane);
             // ---- post-twiddle: value = twiddle * conj(fft) (dsp.rs:512, 523) --------
 #pragma unroll
             for (int j = 0; j < 8; ++j) ex[lane + 64 * j] = cmul(tw_lds[lane + 64 * j], (f2){z[j].x, -z[j].y});
@@ -440,11 +463,11 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
                 const f4 W1f = w1f[r], W1m = w1m[r], W2f = w2f[r], W2m = w2m[r];
                 f4 f, m;
                 // out0[j..j+3] = -F0.re, -M1.im, -F1.re, -M0.im   (dsp.rs:516, 528)
-                f.x = -F.x * W1f.x + dly[8 * r + 0]; f.y = -M.w * W1f.y + dly[8 * r + 1];
-                f.z = -F.z * W1f.z + dly[8 * r + 2]; f.w = -M.y * W1f.w + dly[8 * r + 3];
+                f.x = __builtin_fmaf(-F.x, W1f.x, dly[8 * r + 0]); f.y = __builtin_fmaf(-M.w, W1f.y, dly[8 * r + 1]);
+                f.z = __builtin_fmaf(-F.z, W1f.z, dly[8 * r + 2]); f.w = __builtin_fmaf(-M.y, W1f.w, dly[8 * r + 3]);
                 // out1[508-j..511-j] = M0.im, F1.re, M1.im, F0.re (dsp.rs:517, 529)
-                m.x = M.y * W1m.x + dly[8 * r + 4]; m.y = F.z * W1m.y + dly[8 * r + 5];
-                m.z = M.w * W1m.z + dly[8 * r + 6]; m.w = F.x * W1m.w + dly[8 * r + 7];
+                m.x = __builtin_fmaf(M.y, W1m.x, dly[8 * r + 4]); m.y = __builtin_fmaf(F.z, W1m.y, dly[8 * r + 5]);
+                m.z = __builtin_fmaf(M.w, W1m.z, dly[8 * r + 6]); m.w = __builtin_fmaf(F.x, W1m.w, dly[8 * r + 7]);
                 if constexpr (HOLD) {
                     if constexpr (OUT16) held16[2 * r] = pack4_s16(f), held16[2 * r + 1] = pack4_s16(m);
                     else held32[2 * r] = f, held32[2 * r + 1] = m;
@@ -473,7 +496,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, (ONLY_LONG && kDepth == 1) ? k
             for (int r = 0; r < 8; ++r) ex[64 * r + lane] = z[r];
             write_positions(stage, lane, dly);
             wave_sync();
-            synth_rare_frame(ex, stage, tw_lds, t64, base2.x, base2.y, (const lds_f *)short_win_tab, (const lds_f2 *)short_tw_tab,
+            synth_rare_frame(ex, stage, tw_lds, t64, (const lds_f *)short_win_tab, (const lds_f2 *)short_tw_tab,
                              (const lds_f2 *)short_tw_tab + 64, out_ptr, out16_ptr, seq, prev_shape, shape, lane);
             read_positions(stage, lane, dly);
             float pcm[16];
@@ -557,29 +580,31 @@ __device__ __forceinline__ void dft8(c2 (&x)[8]) {
     c2 u0 = cadd(x[1], x[5]), u1 = csub(x[1], x[5]);
     c2 u2 = cadd(x[3], x[7]), u3 = mul_mi(csub(x[3], x[7]));
     c2 o0 = cadd(u0, u2), o2 = csub(u0, u2), o1 = cadd(u1, u3), o3 = csub(u1, u3);
-    c2 w1 = {(o1.re + o1.im) * h, (o1.im - o1.re) * h};
+    const f2 s1 = o1.re + o1.im, d1 = o1.im - o1.re;  // h folded into the last butterfly, as in the one-channel dft8
+    const f2 s3 = o3.re + o3.im, d3 = o3.im - o3.re;
     c2 w2 = mul_mi(o2);
-    c2 w3 = {(o3.im - o3.re) * h, -((o3.re + o3.im) * h)};
     x[0] = cadd(e0, o0); x[4] = csub(e0, o0);
-    x[1] = cadd(e1, w1); x[5] = csub(e1, w1);
+    x[1] = {fma2(s1, h, e1.re), fma2(d1, h, e1.im)};
+    x[5] = {fma2(-s1, h, e1.re), fma2(-d1, h, e1.im)};
     x[2] = cadd(e2, w2); x[6] = csub(e2, w2);
-    x[3] = cadd(e3, w3); x[7] = csub(e3, w3);
+    x[3] = {fma2(d3, h, e3.re), fma2(-s3, h, e3.im)};
+    x[7] = {fma2(-d3, h, e3.re), fma2(s3, h, e3.im)};
 }
 // exchange slots hold (re A, re B, im A, im B); strides are in 16-byte slots: 66 and 72 keep both transposes free of bank
 // conflicts (16 lanes of a ds_*_b128 land on 16 different slots modulo 16)
 constexpr int kPairExchange = 576;
 __device__ __forceinline__ f4 as_slot(c2 v) { return (f4){v.re.x, v.re.y, v.im.x, v.im.y}; }
 __device__ __forceinline__ c2 from_slot(f4 v) { return {(f2){v.x, v.y}, (f2){v.z, v.w}}; }
-__device__ __forceinline__ void fft512(c2 (&z)[8], lds_f4 *ex, const lds_f2 *t64, f2 base2, int lane) {
+__device__ __forceinline__ void fft512(c2 (&z)[8], lds_f4 *ex, const lds_f2 *t64, const f2 (&tw1)[7], int lane) {
     const int hi3 = lane >> 3, lo3 = lane & 7;
     dft8(z);
 #pragma unroll
-    for (int k = 1; k < 8; ++k) z[k] = cmul_w(z[k], t64[8 * k + hi3]);
+    for (int k = 1; k < 8; ++k) z[k] = cmul_w(z[k], tw1[k - 1]);
 #pragma unroll
     for (int k = 0; k < 8; ++k) ex[k * 66 + lane] = as_slot(z[k]);
     wave_sync();
 #pragma unroll
-    for (int n2 = 0; n2 < 8; ++n2) z[n2] = cmul_w(from_slot(ex[lo3 * 66 + 8 * n2 + hi3]), base2);
+    for (int n2 = 0; n2 < 8; ++n2) z[n2] = from_slot(ex[lo3 * 66 + 8 * n2 + hi3]);
     wave_sync();
     dft8(z);
 #pragma unroll
@@ -731,9 +756,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
     __shared__ f2 t64_tab[64];
     __shared__ float short_win_tab[WITH_SHORT ? 512 : 2];  // the sine and the KBD short window (eight-short arm only)
     __shared__ f2 short_tw_tab[WITH_SHORT ? 128 : 1];       // w64[64] | tw_short[64] (eight-short arm only)
+    // stage-1 twiddles: the long-only form has the fourteen registers to keep them for the whole launch; the eight-short form sits
+    // at 250 / 254 and would carry them across its call, so it reads them from LDS (3.5 KB: 80 896 B, two workgroups still fit)
+    constexpr bool TW1_LDS = WITH_SHORT;
+    __shared__ f2 tw1_tab[TW1_LDS ? kStage1Tab : 1];
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (TW1_LDS) fill_stage1_table(tw1_tab, a.t.w512, threadIdx.x, kWavesPerBlock * 64);
     for (int i = threadIdx.x; i < 512; i += kWavesPerBlock * 64) tw_tab[i] = reinterpret_cast<const f2 *>(a.t.tw_long)[i];
     if (threadIdx.x < 64) t64_tab[threadIdx.x] = reinterpret_cast<const f2 *>(a.t.w64)[((threadIdx.x >> 3) * (threadIdx.x & 7)) & 63];
     if (WITH_SHORT) {
@@ -759,8 +789,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
     const const_entries ent_a = as_constant(a.entries + __builtin_amdgcn_readfirstlane(task_a.begin));
     const const_entries ent_b = as_constant(a.entries + __builtin_amdgcn_readfirstlane(task_b.begin));
 
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const f2 base2 = reinterpret_cast<const f2 *>(a.t.w512)[hi3 * lo3];
+    f2 tw1[7];
+    if constexpr (!TW1_LDS) stage1_twiddles(tw1, a.t.w512, lane);
 
     float *delay_a = a.delay + (size_t)state_a * 1024, *delay_b = a.delay + (size_t)state_b * 1024;
     int prev_a = __builtin_amdgcn_readfirstlane((int)a.prev_shape[state_a]);
@@ -815,10 +845,18 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
             W1f = w.w1f[r], W1m = w.w1m[r], W2f = w.w2f[r], W2m = w.w2m[r];
         }
         f4 f, m;
-        f.x = -F0.x * W1f.x + dly[8 * r + 0]; f.y = -M1.y * W1f.y + dly[8 * r + 1];
-        f.z = -F1.x * W1f.z + dly[8 * r + 2]; f.w = -M0.y * W1f.w + dly[8 * r + 3];
-        m.x = M0.y * W1m.x + dly[8 * r + 4]; m.y = F1.x * W1m.y + dly[8 * r + 5];
-        m.z = M1.y * W1m.z + dly[8 * r + 6]; m.w = F0.x * W1m.w + dly[8 * r + 7];
+        f.x = __builtin_fmaf(-F0.x, W1f.x, dly[8 * r + 0]); f.y = __builtin_fmaf(-M1.y, W1f.y, dly[8 * r + 1]);
+        f.z = __builtin_fmaf(-F1.x, W1f.z, dly[8 * r + 2]); f.w = __builtin_fmaf(-M0.y, W1f.w, dly[8 * r + 3]);
+        m.x = __builtin_fmaf(M0.y, W1m.x, dly[8 * r + 4]); m.y = __builtin_fmaf(F1.x, W1m.y, dly[8 * r + 5]);
+        m.z = __builtin_fmaf(M1.y, W1m.z, dly[8 * r + 6]); m.w = __builtin_fmaf(F0.x, W1m.w, dly[8 * r + 7]);
+        if constexpr (HOLD && !OUT16) {
+            // Held as f32 the four sums above are a register quadruple that lives to the next frame's store.  Without a negated
+            // operand the compiler picks the two-address multiply-add, whose result must lie in the register of its addend, and
+            // then copies each overlap value into the quadruple first: sixteen v_mov per pair-frame.  An overlap value that is
+            // still wanted after its sum (by nothing: the statement is empty) makes it take the three-address form instead.
+#pragma unroll
+            for (int i = 4; i < 8; ++i) __asm__ volatile("" : : "v"(m[i - 4]), "v"(dly[8 * r + i]));
+        }
         if constexpr (HOLD) {
             if constexpr (OUT16) held16[4 * r + 2 * ch] = pack4_s16(f), held16[4 * r + 2 * ch + 1] = pack4_s16(m);
             else held32[4 * r + 2 * ch] = f, held32[4 * r + 2 * ch + 1] = m;
@@ -899,7 +937,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
                     for (int w = 0; w < 8; ++w) {  // z_w[lane] of short block w (dsp.rs:495-503 with input_len 128)
                         const f2 even = (f2){xa[w].x, xb[w].x};
                         const f2 odd = (f2){-__shfl(xa[w].y, 63 - lane), -__shfl(xb[w].y, 63 - lane)};
-                        const c2 zw = {odd * ty - even * tx, odd * tx + even * ty};
+                        const c2 zw = {fma2(odd, ty, -(even * tx)), fma2(odd, tx, even * ty)};
                         ex[64 * w + lane] = as_slot(zw);
                     }
                     f2 both[16];
@@ -949,7 +987,7 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
             const f2 odd = (f2){-__shfl(xa[7 - r].y, 63 - lane), -__shfl(xb[7 - r].y, 63 - lane)};
             const f2 t = tw_lds[lane + 64 * r];
             const f2 tx = splat(t.x), ty = splat(t.y);
-            z[r] = {odd * ty - even * tx, odd * tx + even * ty};
+            z[r] = {fma2(odd, ty, -(even * tx)), fma2(odd, tx, even * ty)};
         }
         Win wa, wb;  // (global form) before the prefetch: vector-memory results return in issue order
         int w1_a = 0, w2_a = 0, w1_b = 0, w2_b = 0;  // LDS_WIN: where the frame's two window halves start in win_tab (wave-uniform)
@@ -972,7 +1010,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, 2) void k_aac_synth_pair(Synth
             load_spectrum(xa, ent_a, ahead);
             load_spectrum(xb, ent_b, ahead);
         }
-        fft512(z, ex, t64, base2, lane);
+        if constexpr (TW1_LDS) stage1_twiddles(tw1, (const lds_f2 *)tw1_tab, lane);
+        fft512(z, ex, t64, tw1, lane);
         // ---- post-twiddle: value = twiddle * conj(fft) (dsp.rs:512, 523): cmul(tw, conj z) per channel ----
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -1069,8 +1108,8 @@ __global__ __launch_bounds__(128, 2) void k_aac_tail(TailArgs ta) {
     uint32_t *dst32 = reinterpret_cast<uint32_t *>(ta.out16 + (size_t)out_row * ta.out_stride * 2);  // stereo rows
     int16_t *dst16 = ta.out16 + (size_t)out_row * ta.out_stride;                                      // mono rows
 
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const f2 base2 = reinterpret_cast<const f2 *>(a.t.w512)[hi3 * lo3];
+    f2 tw1[7];  // stage-1 twiddles, in registers for the whole launch
+    stage1_twiddles(tw1, a.t.w512, lane);
 
     // the FIR's tap fragments (fir_bf16.hip: window s, plane k, this lane), held in registers for the whole launch: 68 VGPRs
     // that cost the third wave per SIMD -- fetched from the CU's L1 for every tile instead (168 VGPRs, three waves) the launch
@@ -1172,7 +1211,7 @@ __global__ __launch_bounds__(128, 2) void k_aac_tail(TailArgs ta) {
             const float even = xin[r].x;
             const float odd = -__shfl(xin[7 - r].y, 63 - lane);
             const f2 t = tw_lds[lane + 64 * r];
-            z[r] = (f2){odd * t.y - even * t.x, odd * t.x + even * t.y};
+            z[r] = (f2){__builtin_fmaf(odd, t.y, -(even * t.x)), __builtin_fmaf(odd, t.x, even * t.y)};
         }
         const float *w1 = first_half_window(a.t.win, seq, prev_shape);
         const float *w2 = second_half_window(a.t.win, seq, shape);
@@ -1186,7 +1225,7 @@ __global__ __launch_bounds__(128, 2) void k_aac_tail(TailArgs ta) {
             w2m[r] = *reinterpret_cast<const f4 *>(w2 + 1020 - j);
         }
         load_spectrum(xin, e + kTailDepth < count ? e + kTailDepth : count - 1);
-        fft512(z, ex, t64, base2, lane);
+        fft512(z, ex, t64, tw1, lane);
 #pragma unroll
         for (int j = 0; j < 8; ++j) ex[lane + 64 * j] = cmul(tw_lds[lane + 64 * j], (f2){z[j].x, -z[j].y});
         wave_sync();
@@ -1198,10 +1237,10 @@ __global__ __launch_bounds__(128, 2) void k_aac_tail(TailArgs ta) {
             const f4 M = *reinterpret_cast<const lds_f4 *>(&ex[254 - q]);
             const f4 W1f = w1f[r], W1m = w1m[r], W2f = w2f[r], W2m = w2m[r];
             f4 f, m;
-            f.x = -F.x * W1f.x + dly[8 * r + 0]; f.y = -M.w * W1f.y + dly[8 * r + 1];
-            f.z = -F.z * W1f.z + dly[8 * r + 2]; f.w = -M.y * W1f.w + dly[8 * r + 3];
-            m.x = M.y * W1m.x + dly[8 * r + 4]; m.y = F.z * W1m.y + dly[8 * r + 5];
-            m.z = M.w * W1m.z + dly[8 * r + 6]; m.w = F.x * W1m.w + dly[8 * r + 7];
+            f.x = __builtin_fmaf(-F.x, W1f.x, dly[8 * r + 0]); f.y = __builtin_fmaf(-M.w, W1f.y, dly[8 * r + 1]);
+            f.z = __builtin_fmaf(-F.z, W1f.z, dly[8 * r + 2]); f.w = __builtin_fmaf(-M.y, W1f.w, dly[8 * r + 3]);
+            m.x = __builtin_fmaf(M.y, W1m.x, dly[8 * r + 4]); m.y = __builtin_fmaf(F.z, W1m.y, dly[8 * r + 5]);
+            m.z = __builtin_fmaf(M.w, W1m.z, dly[8 * r + 6]); m.w = __builtin_fmaf(F.x, W1m.w, dly[8 * r + 7]);
             to_ring(f, frame_at + j);
             to_ring(m, frame_at + 1020 - j);
             dly[8 * r + 0] = F.y * W2f.x; dly[8 * r + 1] = M.z * W2f.y;
