@@ -1240,6 +1240,128 @@ int sk_flac_decoder_decode_i32(sk_flac_decoder *, const uint8_t *input, size_t l
 int sk_flac_decoder_decode_i16(sk_flac_decoder *, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written);
 const char *sk_flac_decoder_last_error(const sk_flac_decoder *);
 
+/* ---- Apple Lossless (ALAC): cookie, packet header, CAF packet index (host only, csrc/alac_stream.h) ----------------------- */
+/* ALAC arrives as packets that a container (CAF, MP4) has already cut, with the ALACSpecificConfig as its magic cookie.  Not built:
+ * the MP4 side of the container (an MP4 demuxer hands its packets and cookie to the same calls). */
+enum sk_alac_status {
+    SK_ALAC_INVALID = -601,     /* a packet breaks the syntax: a prediction type other than 0 / 15, a zero run past the element's end, a
+                                   frame count of 0 or above the cookie's, elements whose counts differ, more or fewer channels than the
+                                   cookie's, bits that end beyond the packet or 8 and more bits short of it */
+    SK_ALAC_ERR_STREAM = -602,  /* a cookie, a CAF file or a packet was rejected with a text */
+    SK_ALAC_UNSUPPORTED = -603  /* a CCE or PCE element (tags 2 and 5) */
+};
+typedef struct sk_alac_config { /* the 24-byte big-endian ALACSpecificConfig */
+    uint32_t frame_length;      /* 1 ... 65536 */
+    uint32_t sample_rate;       /* > 0 */
+    uint32_t max_frame_bytes, avg_bit_rate;
+    uint16_t max_run;
+    uint8_t compatible_version;
+    uint8_t bit_depth;          /* 16, 24 or 32 */
+    uint8_t pb, mb, kb;         /* history multiplier, initial history, Rice limit */
+    uint8_t channels;           /* 1 ... 8 */
+} sk_alac_config;
+/* The bare config, the MP4 `alac` FullBox payload (four zero bytes, then the config) or the QuickTime form (a 12-byte `frma` atom, then an
+ * `alac` atom).  Refused with SK_ALAC_ERR_STREAM and a text in `error` (NUL-terminated, cut to error_cap; may be NULL): fewer than 24
+ * bytes of config, rate 0, channels outside 1 ... 8, a depth other than 16 / 24 / 32, frame_length outside 1 ... 65536. */
+int sk_alac_parse_cookie(const uint8_t *cookie, size_t len, sk_alac_config *out, char *error, size_t error_cap);
+/* The frame count of a packet as its first audio element states it (DSE and FIL in front are stepped over): the size field, or
+ * frame_length without one.  SK_ALAC_INVALID: no audio element, a count of 0 or above frame_length, a header beyond the packet;
+ * SK_ALAC_UNSUPPORTED: a CCE or PCE comes first. */
+int sk_alac_packet_frames(const sk_alac_config *, const uint8_t *packet, size_t len, uint32_t *frames);
+
+/* CafAlacPacketIndex (soundkit-alac/src/lib.rs:38-215): `desc` (exactly 32 bytes, format `alac`), the cookie, the `pakt` table (24 bytes
+ * of counts, then one big-endian base-128 size of at most 10 bytes per packet, nothing behind them; not read when desc gives a constant
+ * bytes-per-packet) and where the `data` chunk's payload lies (its first 4 bytes are the edit count).  desc and cookie must agree on
+ * rate, channels and -- where desc states one -- depth; the sizes must add up to the payload; no packet is empty or above 16 MiB.
+ * A refusal is SK_ALAC_ERR_STREAM with its text in `error`. */
+typedef struct sk_caf_alac_index sk_caf_alac_index;
+typedef struct sk_caf_alac_info {
+    sk_alac_config config;
+    uint64_t valid_frames;
+    uint32_t priming_frames, remainder_frames;
+    uint32_t frames_per_packet; /* desc's: packet k begins at frame k * frames_per_packet of the timeline that priming / valid trim */
+    uint32_t n_packets;
+} sk_caf_alac_info;
+int sk_caf_alac_index_create(const uint8_t *desc, size_t desc_len, const uint8_t *cookie, size_t cookie_len, const uint8_t *pakt, size_t pakt_len,
+                             uint64_t data_offset, uint64_t data_size, sk_caf_alac_index **out, char *error, size_t error_cap);
+/* the same from a whole CAF file: finds desc, kuki, pakt and data (a data chunk of size -1 runs to the end of the file) */
+int sk_caf_alac_index_from_file(const uint8_t *file, size_t len, sk_caf_alac_index **out, char *error, size_t error_cap);
+void sk_caf_alac_index_destroy(sk_caf_alac_index *);
+int sk_caf_alac_index_info(const sk_caf_alac_index *, sk_caf_alac_info *info);
+/* the packets' absolute offsets and sizes; cap < n_packets: SK_ERR_CAPACITY */
+int sk_caf_alac_index_packets(const sk_caf_alac_index *, uint64_t *offsets, uint32_t *sizes, uint32_t cap);
+
+/* ---- ALAC decode stage (GPU, csrc/alac_decode.hip) -------------------------------------------------------------------- */
+/* packets[i] lies at bytes + packets[i].offset, a multiple of 16.  Output: the packets one after the other in the order given, each
+ * frames x channels samples interleaved in bitstream channel order, little-endian in bit_depth / 8 bytes.  frames_per_packet[i] is what
+ * sk_alac_packet_frames reads (0 where it refuses: such a packet has no place in `out`); status_per_packet[i]: SK_OK, SK_ALAC_INVALID,
+ * SK_ALAC_UNSUPPORTED or SK_ERR_UNSUPPORTED (an element whose working width exceeds 32 bits: a pair at 32 bits without extra bytes).
+ * A rejected packet keeps its place in `out` and nothing is written there.  An empty packet, one above 16 MiB, an offset that is no
+ * multiple of 16, a config outside sk_alac_parse_cookie's limits or an out_cap too small: SK_ERR_INVALID_ARG, nothing decoded.
+ * The _dev form takes 16-byte aligned device pointers, runs on the engine's stream and waits only for the statuses; there
+ * frames_per_packet is an INPUT (the caller read the counts when it had the bytes; the device rejects a packet that disagrees). */
+typedef struct sk_alac_packet {
+    uint32_t offset, size;
+} sk_alac_packet;
+int sk_alac_decode_packets(sk_engine *, const sk_alac_config *, const sk_alac_packet *packets, uint32_t n, const uint8_t *bytes, uint8_t *out,
+                           size_t out_cap, size_t *out_len, int32_t *status_per_packet, uint32_t *frames_per_packet);
+int sk_alac_decode_packets_dev(sk_engine *, const sk_alac_config *, const sk_alac_packet *packets, uint32_t n, const uint8_t *d_bytes,
+                               size_t bytes_len, uint8_t *d_out, size_t out_cap, size_t *out_len, int32_t *status_per_packet,
+                               const uint32_t *frames_per_packet);
+
+/* The tick of the ALAC streams, sk_tick_run_flac's pattern with packets as units: packets[k] lies at bytes + packets[k].offset (a
+ * multiple of 16), stream after stream, packets[k].frames is what sk_alac_packet_frames read from it (the scheduler reads it when the
+ * packet arrives; 0 or above the cookie's frame_length: SK_ERR_INVALID_ARG), and every packet is first decoded to PCM on the device.
+ * Each stream carries its own cookie's parameters.  A stream with nothing to change (no rate change, out_bits = bit_depth, out_channels = channels)
+ * gets those bytes as its outputs, one per packet, for 1 ... 8 channels.  Every other stream then runs exactly what sk_tick_run_pcm runs
+ * on a little-endian source of that format -- same kernels, records, bounds and limits (the exact 24 / 32 -> 16 path included; 3 ... 8
+ * channels need sk_engine_enable_wide_pcm).  A refused tick leaves every stream as it was.  status_per_packet[k] is
+ * sk_alac_decode_packets': a rejected packet writes nothing; its output record carries the status, and behind a conversion -- where the
+ * packet went in as silence -- every record of its stream in this tick does: the stream is to be ended. */
+typedef struct sk_alac_tick_stream {
+    uint32_t stream;       /* engine stream (resample = 1 only) */
+    uint32_t n_units;      /* packets */
+    uint32_t frame_length; /* the cookie's: frame_length, channels, bit_depth, pb, mb, kb */
+    uint8_t channels;      /* 1 ... 8 */
+    uint8_t bit_depth;     /* 16 / 24 / 32 */
+    uint8_t pb, mb, kb;
+    uint8_t out_bits;      /* 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t reserved[3];
+} sk_alac_tick_stream;
+typedef struct sk_alac_tick_packet {
+    uint32_t offset, size;
+    uint32_t frames; /* sk_alac_packet_frames' */
+    uint32_t reserved;
+} sk_alac_tick_packet;
+size_t sk_tick_alac_out_bound_on(sk_engine *, const sk_alac_tick_stream *streams, uint32_t n_streams, const sk_alac_tick_packet *packets,
+                                 uint32_t n_packets, uint32_t *max_outputs);
+int sk_tick_run_alac(sk_engine *, const sk_alac_tick_stream *streams, uint32_t n_streams, const sk_alac_tick_packet *packets, uint32_t n_packets,
+                     const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                     uint32_t *n_outputs, size_t *out_bytes_used, int32_t *status_per_packet);
+
+/* A scheduler stream of ALAC packets (the reference's sequential pipeline refuses ALAC containers, SEEKABLE_ALAC_REQUIRED, so nothing is
+ * sniffed: the caller has the container's index and hands over the cookie -- in any of sk_alac_parse_cookie's forms -- and the packets).
+ * Every sk_pipeline_send is exactly one packet; the empty send ends the stream and flushes the resampler.  One AudioData per packet, or
+ * what the output options make of them (the PCM-family tick).  A packet the host or the device rejects ends its stream with
+ * `Decoding failed: ALAC packet rejected: ...` and leaves its neighbours untouched.  A cookie that is refused: SK_ALAC_ERR_STREAM. */
+int sk_pipeline_spawn_alac_packets(sk_pipeline *, const uint8_t *cookie, size_t cookie_len, const sk_decode_options *opt, uint32_t *handle);
+
+/* AlacPacketDecoder (soundkit-alac/src/lib.rs:217-300): a cookie once, then one packet per call -> one AudioData's bytes (signed
+ * little-endian, bit_depth / 8 bytes a sample).  An empty packet, one above 16 MiB, a packet the device rejects: SK_ALAC_ERR_STREAM with
+ * a text in last_error; the decoder goes on with the next packet (packets are independent).  out_cap too small: SK_ERR_CAPACITY. */
+typedef struct sk_alac_packet_decoder sk_alac_packet_decoder;
+int sk_alac_packet_decoder_create(sk_engine *, const uint8_t *cookie, size_t cookie_len, sk_alac_packet_decoder **out, char *error,
+                                  size_t error_cap);
+void sk_alac_packet_decoder_destroy(sk_alac_packet_decoder *);
+/* maximum_pcm_samples = frame_length x channels */
+int sk_alac_packet_decoder_info(const sk_alac_packet_decoder *, uint32_t *sample_rate, uint8_t *channels, uint8_t *bit_depth,
+                                size_t *maximum_pcm_samples);
+int sk_alac_packet_decoder_decode_packet(sk_alac_packet_decoder *, const uint8_t *packet, size_t len, uint8_t *out, size_t out_cap, size_t *out_len);
+const char *sk_alac_packet_decoder_last_error(const sk_alac_packet_decoder *);
+
 #ifdef __cplusplus
 }
 #endif

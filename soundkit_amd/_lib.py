@@ -22,6 +22,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -401: "PcmStreamRejected",
              -501: "FlacNeedMore", -502: "FlacNoSync", -503: "FlacReserved", -504: "FlacBadCrc", -505: "FlacNeedStreamInfo",
              -506: "FlacInvalid", -507: "FlacStreamRejected",
+             -601: "AlacInvalid", -602: "AlacStreamRejected", -603: "AlacUnsupportedElement",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -187,6 +188,34 @@ class FlacInfo(C.Structure):
     """sk_flac_info"""
     _fields_ = [("streaminfo", FlacStreamInfo), ("frames", C.c_uint64), ("buffered_bytes", C.c_uint32), ("have_streaminfo", C.c_uint8),
                 ("reserved", C.c_uint8 * 3)]
+
+
+class AlacConfig(C.Structure):
+    """sk_alac_config"""
+    _fields_ = [(n, C.c_uint32) for n in ("frame_length", "sample_rate", "max_frame_bytes", "avg_bit_rate")] + [("max_run", C.c_uint16)] + [
+        (n, C.c_uint8) for n in ("compatible_version", "bit_depth", "pb", "mb", "kb", "channels")]
+
+
+class CafAlacInfo(C.Structure):
+    """sk_caf_alac_info"""
+    _fields_ = [("config", AlacConfig), ("valid_frames", C.c_uint64), ("priming_frames", C.c_uint32), ("remainder_frames", C.c_uint32),
+                ("frames_per_packet", C.c_uint32), ("n_packets", C.c_uint32)]
+
+
+class AlacTickStream(C.Structure):
+    """sk_alac_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("frame_length", C.c_uint32)] + [
+        (n, C.c_uint8) for n in ("channels", "bit_depth", "pb", "mb", "kb", "out_bits", "out_channels", "resample", "flush")] + [("reserved", C.c_uint8 * 3)]
+
+
+class AlacTickPacket(C.Structure):
+    """sk_alac_tick_packet"""
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32), ("frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AlacPacket(C.Structure):
+    """sk_alac_packet"""
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32)]
 
 
 class FlacTickStream(C.Structure):
@@ -453,6 +482,23 @@ _sig = {
     "sk_flac_decoder_decode_i32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "sk_flac_decoder_decode_i16": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "sk_flac_decoder_last_error": (C.c_char_p, [_vp]),
+    "sk_alac_parse_cookie": (_i, [_vp, _sz, _vp, _vp, _sz]),
+    "sk_alac_packet_frames": (_i, [_vp, _vp, _sz, C.POINTER(_u32)]),
+    "sk_caf_alac_index_create": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint64, C.c_uint64, C.POINTER(_vp), _vp, _sz]),
+    "sk_caf_alac_index_from_file": (_i, [_vp, _sz, C.POINTER(_vp), _vp, _sz]),
+    "sk_caf_alac_index_destroy": (None, [_vp]),
+    "sk_caf_alac_index_info": (_i, [_vp, C.POINTER(CafAlacInfo)]),
+    "sk_caf_alac_index_packets": (_i, [_vp, _vp, _vp, _u32]),
+    "sk_alac_decode_packets": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
+    "sk_alac_decode_packets_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
+    "sk_tick_alac_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_alac": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz), _vp]),
+    "sk_pipeline_spawn_alac_packets": (_i, [_vp, _vp, _sz, _vp, C.POINTER(_u32)]),
+    "sk_alac_packet_decoder_create": (_i, [_vp, _vp, _sz, C.POINTER(_vp), _vp, _sz]),
+    "sk_alac_packet_decoder_destroy": (None, [_vp]),
+    "sk_alac_packet_decoder_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(_sz)]),
+    "sk_alac_packet_decoder_decode_packet": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_alac_packet_decoder_last_error": (C.c_char_p, [_vp]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "aac_entropy_tables.h"
+#include "alac_stream.h"
 #include "flac_stream.h"
 #include "mp12_internal.h"
 #include "pcm_stream.h"
@@ -263,6 +264,7 @@ struct sk_engine {
     DevBuf tick_pcm, tick_res, tick_out, tick_arena, tick_au, tick_side, tick_q, tick_mp3_in, tick_mp3_xr, tick_mpa_in;
     DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
     DevBuf flac_in, flac_ws, flac_out;  // sk_flac_decode_frames: frames | tables | statuses, planar i32 workspace | subframe records, PCM
+    DevBuf alac_in, alac_ws, alac_out;  // sk_alac_decode_packets: packets | tables | statuses, planar i32 workspace | channel records, PCM
     DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
@@ -589,6 +591,9 @@ const char *sk_strerror(int status) try {
     case SK_FLAC_NEED_STREAMINFO: return "FLAC frame header refers to a STREAMINFO that was not given";
     case SK_FLAC_INVALID: return "invalid FLAC frame";
     case SK_FLAC_ERR_STREAM: return "FLAC stream rejected";
+    case SK_ALAC_INVALID: return "invalid ALAC packet";
+    case SK_ALAC_ERR_STREAM: return "ALAC stream rejected";
+    case SK_ALAC_UNSUPPORTED: return "unsupported ALAC element";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -674,6 +679,9 @@ void sk_engine_destroy(sk_engine *e) try {
         e->flac_in.release();
         e->flac_ws.release();
         e->flac_out.release();
+        e->alac_in.release();
+        e->alac_ws.release();
+        e->alac_out.release();
         e->mp3e_in.release();
         e->tick_mpa_in.release();
         e->mp3e_out.release();
@@ -5990,6 +5998,503 @@ const char *sk_flac_decoder_last_error(const sk_flac_decoder *d) try {
     return d ? d->error.c_str() : "";
 } catch (...) {
     (void)sk::abi_caught("sk_flac_decoder_last_error");
+    return "";
+}
+
+}  // extern "C"
+
+// ---- ALAC (alac_stream.h, alac_decode.hip) ----------------------------------------------------------------------------------------
+
+struct sk_caf_alac_index {
+    sk_alac::CafIndex index;
+};
+
+struct sk_alac_packet_decoder {
+    sk_engine *eng = nullptr;
+    sk_alac_config config{};
+    std::string error;
+};
+
+namespace {
+
+void alac_text(char *error, size_t cap, const std::string &text) {
+    if (!error || cap == 0) return;
+    const size_t n = std::min(cap - 1, text.size());
+    std::memcpy(error, text.data(), n);
+    error[n] = 0;
+}
+
+// what one run of the three kernels works on: packets of any number of cookies, each with its place in the bytes, the workspace and
+// the output.  add() is called per packet in the order of the output; the statuses start as what the host said (a packet whose frame
+// count it could not read is not handed to a lane) and come back as the device's.
+struct AlacBatch {
+    std::vector<sk::AlacParams> cfgs;
+    std::vector<sk::AlacPacket> table;
+    std::vector<uint32_t> order, lanes;
+    std::vector<int32_t> status;
+    uint64_t ws_words = 0;
+    uint32_t n_recs = 0;
+
+    uint32_t add_config(const sk_alac_config &c) {
+        sk::AlacParams p{};
+        p.frame_length = c.frame_length, p.bit_depth = c.bit_depth, p.pb = c.pb, p.mb = c.mb, p.kb = c.kb, p.channels = c.channels;
+        for (uint32_t i = 0; i < cfgs.size(); ++i)
+            if (std::memcmp(&cfgs[i], &p, sizeof p) == 0) return i;
+        cfgs.push_back(p);
+        return (uint32_t)cfgs.size() - 1;
+    }
+    // frames = 0: refused by the host with host_status
+    void add(uint32_t cfg, uint32_t offset, uint32_t size, uint32_t frames, uint64_t out_offset, int32_t host_status) {
+        const uint32_t ch = cfgs[cfg].channels, k = (uint32_t)table.size();
+        sk::AlacPacket t{};
+        t.byte_offset = offset, t.byte_len = size, t.frames = frames, t.ws_offset = (uint32_t)ws_words, t.rec0 = n_recs, t.cfg = cfg;
+        t.out_offset = out_offset;
+        table.push_back(t);
+        status.push_back(frames ? (int32_t)SK_ALAC_INVALID : host_status);
+        if (!frames) return;
+        order.push_back(k);
+        for (uint32_t c = 0; c < ch; ++c) lanes.push_back(k << 3 | c);
+        ws_words += (uint64_t)frames * ch;
+        n_recs += ch;
+    }
+    static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+    // the tables' device form: configs | packet table | order | lanes | statuses
+    size_t tables_len() const {
+        return up16(cfgs.size() * sizeof(sk::AlacParams)) + up16(table.size() * sizeof(sk::AlacPacket)) + up16(order.size() * 4) + up16(lanes.size() * 4) +
+               up16(status.size() * 4);
+    }
+    size_t ws_len() const { return up16((size_t)ws_words * 4) + (size_t)n_recs * sizeof(sk::AlacChannel); }
+};
+
+// uploads the tables to d_tables (tables_len() bytes), runs the three launches with the workspace at d_ws (ws_len() bytes) and asks for
+// the statuses back into b.status; everything on e->stream, nothing waited for.  b must live until the stream has been waited for.
+int alac_launch(sk_engine *e, AlacBatch &b, uint8_t *d_tables, uint8_t *d_ws, const uint8_t *d_bytes, uint32_t bytes_len, uint8_t *d_out) {
+    const uint32_t n = (uint32_t)b.table.size();
+    if (n == 0) return SK_OK;
+    if (b.ws_words > 0x3fffffffu || n > (1u << 28)) return SK_ERR_INVALID_ARG;
+    std::stable_sort(b.order.begin(), b.order.end(), [&](uint32_t x, uint32_t y) { return b.table[x].byte_len > b.table[y].byte_len; });
+    const size_t at_table = AlacBatch::up16(b.cfgs.size() * sizeof(sk::AlacParams)), at_order = at_table + AlacBatch::up16(n * sizeof(sk::AlacPacket)),
+                 at_lanes = at_order + AlacBatch::up16(b.order.size() * 4), at_status = at_lanes + AlacBatch::up16(b.lanes.size() * 4);
+    SK_HIP(hipMemcpyAsync(d_tables, b.cfgs.data(), b.cfgs.size() * sizeof(sk::AlacParams), hipMemcpyHostToDevice, e->stream), "H2D alac configs");
+    SK_HIP(hipMemcpyAsync(d_tables + at_table, b.table.data(), n * sizeof(sk::AlacPacket), hipMemcpyHostToDevice, e->stream), "H2D alac table");
+    if (!b.order.empty()) {
+        SK_HIP(hipMemcpyAsync(d_tables + at_order, b.order.data(), b.order.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D alac order");
+        SK_HIP(hipMemcpyAsync(d_tables + at_lanes, b.lanes.data(), b.lanes.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D alac lanes");
+    }
+    SK_HIP(hipMemcpyAsync(d_tables + at_status, b.status.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, e->stream), "H2D alac statuses");
+    const sk::AlacParams *d_cfgs = (const sk::AlacParams *)d_tables;
+    const sk::AlacPacket *d_table = (const sk::AlacPacket *)(d_tables + at_table);
+    sk::AlacChannel *d_recs = (sk::AlacChannel *)(d_ws + AlacBatch::up16((size_t)b.ws_words * 4));
+    int32_t *d_status = (int32_t *)(d_tables + at_status);
+    SK_HIP(sk::launch_alac_entropy(d_cfgs, d_table, (const uint32_t *)(d_tables + at_order), (uint32_t)b.order.size(), d_bytes, bytes_len, (int32_t *)d_ws,
+                                   d_recs, d_status, e->stream), "launch alac entropy");
+    SK_HIP(sk::launch_alac_predict(d_table, (const uint32_t *)(d_tables + at_lanes), (uint32_t)b.lanes.size(), d_recs, (int32_t *)d_ws, d_status, e->stream),
+           "launch alac predict");
+    SK_HIP(sk::launch_alac_output(d_cfgs, d_table, n, d_recs, (const int32_t *)d_ws, d_status, d_bytes, d_out, e->stream), "launch alac output");
+    SK_HIP(hipMemcpyAsync(b.status.data(), d_status, n * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H alac statuses");
+    return SK_OK;
+}
+
+// sk_alac_decode_packets[_dev].  Host form: `frames_out` is written (sk_alac_packet_frames per packet); device form: `frames_in` is read.
+int alac_decode_packets(sk_engine *e, const sk_alac_config *cfg, const sk_alac_packet *packets, uint32_t n, const uint8_t *bytes, size_t dev_bytes_len,
+                        bool on_device, uint8_t *out, size_t out_cap, size_t *out_len, int32_t *status, uint32_t *frames_out, const uint32_t *frames_in) {
+    if (!e || !cfg || !out_len || (n && (!packets || !bytes || !out || !status || !(on_device ? (const void *)frames_in : (const void *)frames_out))))
+        return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    std::string text;
+    if (!sk_alac::validate(*cfg, &text)) return SK_ERR_INVALID_ARG;
+    if (n == 0) return SK_OK;
+    const uint32_t ch = cfg->channels, width = cfg->bit_depth / 8u;
+    AlacBatch b;
+    const uint32_t c0 = b.add_config(*cfg);
+    std::vector<uint32_t> frames(n);
+    uint64_t need = 0, bytes_len = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        const sk_alac_packet &p = packets[i];
+        if (p.size == 0 || p.size > sk_alac::kMaxPacketBytes || (p.offset & 15u)) return SK_ERR_INVALID_ARG;
+        bytes_len = std::max<uint64_t>(bytes_len, (uint64_t)p.offset + p.size);
+        if (bytes_len > 0x7fffffffu || (on_device && bytes_len > dev_bytes_len)) return SK_ERR_INVALID_ARG;
+        uint32_t f = 0;
+        int32_t host = SK_ALAC_INVALID;
+        if (on_device) {
+            f = frames_in[i];
+            if (f > cfg->frame_length) return SK_ERR_INVALID_ARG;
+        } else if ((host = sk_alac::packet_frames(*cfg, bytes + p.offset, p.size, &f)) != SK_OK) {
+            f = 0;
+        }
+        frames[i] = f;
+        b.add(c0, p.offset, p.size, f, need, host);
+        need += (uint64_t)f * ch * width;
+        if (b.ws_words > 0x3fffffffu) return SK_ERR_INVALID_ARG;
+    }
+    if (need > out_cap) return SK_ERR_INVALID_ARG;
+    if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15)) return SK_ERR_INVALID_ARG;
+
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    // alac_in: [bytes (host form)] | the batch's tables
+    const size_t at_tables = on_device ? 0 : AlacBatch::up16((size_t)bytes_len);
+    SK_HIP(e->alac_in.reserve(at_tables + b.tables_len()), "alloc alac input");
+    SK_HIP(e->alac_ws.reserve(b.ws_len()), "alloc alac workspace");
+    uint8_t *d_in = (uint8_t *)e->alac_in.p, *d_out = out;
+    const uint8_t *d_bytes = bytes;
+    if (!on_device) {
+        SK_HIP(e->alac_out.reserve(std::max<size_t>((size_t)need, 16)), "alloc alac output");
+        d_out = (uint8_t *)e->alac_out.p;
+        SK_HIP(hipMemcpyAsync(d_in, bytes, (size_t)bytes_len, hipMemcpyHostToDevice, e->stream), "H2D alac packets");
+        d_bytes = d_in;
+    }
+    const int rc = alac_launch(e, b, d_in + at_tables, (uint8_t *)e->alac_ws.p, d_bytes, (uint32_t)(on_device ? dev_bytes_len : bytes_len), d_out);
+    if (rc != SK_OK) return rc;
+    SK_HIP(hipStreamSynchronize(e->stream), "alac sync");  // the tables leave scope with the call
+    for (uint32_t i = 0; i < n; ++i) status[i] = b.status[i];
+    if (!on_device) {
+        // a rejected packet's place in the caller's buffer stays as it was: the accepted packets are copied one run at a time
+        uint32_t i = 0;
+        while (i < n) {
+            if (status[i] != 0) {
+                ++i;
+                continue;
+            }
+            uint32_t j = i;
+            while (j < n && status[j] == 0) ++j;
+            const uint64_t from = b.table[i].out_offset, to = j < n ? b.table[j].out_offset : need;
+            SK_HIP(hipMemcpyAsync(out + from, d_out + from, (size_t)(to - from), hipMemcpyDeviceToHost, e->stream), "D2H alac");
+            i = j;
+        }
+        SK_HIP(hipStreamSynchronize(e->stream), "alac sync");
+        for (uint32_t k = 0; k < n; ++k) frames_out[k] = frames[k];
+    }
+    *out_len = (size_t)need;
+    return SK_OK;
+}
+
+// sk_tick_run_alac / sk_tick_alac_out_bound_on: checks the table and derives what the PCM tick's body works on, as flac_tick_derive does --
+// per stream a little-endian source of the cookie's format, per packet where its decoded PCM lies (16-byte aligned, packet after packet)
+// -- and the decode that stands in front of the body: the three launches of alac_decode.hip over the packets of each pass.
+struct AlacDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;  // the decoded layout
+    std::vector<uint32_t> first;     // per stream: its first packet
+    AiffTick tick;
+    // what the two passes (streams that go on through the body, streams delivered as decoded) upload and get back: alive until the
+    // tick's last wait
+    AlacBatch batch[2];
+    std::vector<uint32_t> index[2];  // row of the batch -> packet of the call
+    size_t part = 0, ws_len = 0;     // of alac_in per pass, of alac_ws: sized for every packet of the call
+};
+
+sk_alac_config alac_row_config(const sk_alac_tick_stream &a) {
+    sk_alac_config c{};
+    c.frame_length = a.frame_length, c.sample_rate = 1, c.bit_depth = a.bit_depth, c.pb = a.pb, c.mb = a.mb, c.kb = a.kb, c.channels = a.channels;
+    return c;
+}
+
+int alac_tick_derive(const sk_alac_tick_stream *as, uint32_t n_streams, const sk_alac_tick_packet *packets, uint32_t n_packets, size_t bytes_len,
+                     AlacDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.assign(n_packets, sk_pcm_unit{});
+    d.first.assign(n_streams, 0);
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    uint64_t at = 0, cursor = 0, ws_words = 0, recs = 0;
+    std::string text;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_alac_tick_stream &a = as[i];
+        if (!sk_alac::validate(alac_row_config(a), &text)) return SK_ERR_INVALID_ARG;
+        const uint32_t width = a.bit_depth / 8u, ch = a.channels;
+        const bool plain = !a.resample && a.out_bits == a.bit_depth && a.out_channels == ch;
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = a.stream, t.n_units = a.n_units, t.channels = (uint8_t)ch, t.resample = a.resample, t.flush = a.flush;
+        // a stream delivered as decoded is planned as s16 whatever its width: its records are rewritten behind the body
+        t.out_bits = plain ? 16 : a.out_bits, t.out_channels = a.out_channels;
+        t.format = (uint8_t)(plain || width == 2 ? SK_FMT_S16LE : (width == 3 ? SK_FMT_S24LE : SK_FMT_S32LE));
+        d.tick.plain[i] = plain;
+        d.first[i] = (uint32_t)at;
+        if (at + a.n_units > n_packets) return SK_ERR_INVALID_ARG;
+        for (uint32_t u = 0; u < a.n_units; ++u) {
+            const sk_alac_tick_packet &p = packets[at + u];
+            const uint32_t f = p.frames;
+            if (p.size == 0 || p.size > sk_alac::kMaxPacketBytes || p.offset % 16 || f == 0 || f > a.frame_length) return SK_ERR_INVALID_ARG;
+            if (p.offset > bytes_len || p.size > bytes_len - p.offset) return SK_ERR_INVALID_ARG;
+            const uint64_t decoded = (uint64_t)f * ch * width;
+            d.units[at + u] = sk_pcm_unit{cursor, (uint32_t)decoded, 0};
+            cursor += (decoded + 15) & ~15ull;
+            ws_words += (uint64_t)f * ch;
+            recs += ch;
+        }
+        at += a.n_units;
+    }
+    if (cursor > 0x7fffffffull || bytes_len > 0x7fffffffull || ws_words > 0x3fffffffull) return SK_ERR_INVALID_ARG;
+    d.tick.decoded_len = (size_t)cursor;
+    d.part = AlacBatch::up16(n_streams * sizeof(sk::AlacParams)) + AlacBatch::up16(n_packets * sizeof(sk::AlacPacket)) + 2 * AlacBatch::up16(n_packets * 4) +
+             AlacBatch::up16((size_t)recs * 4);
+    d.ws_len = AlacBatch::up16((size_t)ws_words * 4) + (size_t)recs * sizeof(sk::AlacChannel);
+    return at == n_packets ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// one pass of the decode in front of the body: the packets of the streams whose `plain` is as_is, each to where dst_of puts it
+int alac_tick_decode(sk_engine *e, const sk_alac_tick_stream *as, const sk_alac_tick_packet *packets, size_t bytes_len, AlacDerived &d, bool as_is,
+                     const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+    const int p = as_is ? 1 : 0;
+    AlacBatch &b = d.batch[p];
+    std::vector<uint32_t> &index = d.index[p];
+    std::vector<uint8_t *> dst;
+    std::vector<uint32_t> cfg_of;
+    for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
+        if ((d.tick.plain[i] != 0) != as_is || d.ts[i].n_units == 0) continue;
+        const uint32_t c = b.add_config(alac_row_config(as[i]));
+        for (uint32_t u = 0; u < d.ts[i].n_units; ++u) index.push_back(d.first[i] + u), dst.push_back(dst_of(i, u)), cfg_of.push_back(c);
+    }
+    const uint32_t n = (uint32_t)index.size();
+    if (n == 0) return SK_OK;
+    uint8_t *base = *std::min_element(dst.begin(), dst.end());
+    if (!as_is) {
+        // what a rejected packet leaves for the body to convert is silence, not whatever an earlier tick had there
+        size_t extent = 0;
+        for (uint32_t k = 0; k < n; ++k) extent = std::max(extent, (size_t)(dst[k] - base) + d.units[index[k]].byte_len);
+        SK_HIP(hipMemsetAsync(base, 0, extent, e->stream), "clear tick alac decoded");
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const sk_alac_tick_packet &pk = packets[index[k]];
+        b.add(cfg_of[k], pk.offset, pk.size, pk.frames, (uint64_t)(dst[k] - base), SK_ALAC_INVALID);
+    }
+    // both passes' tables have their own part of alac_in; the workspace is shared, the passes follow each other on the stream
+    SK_HIP(e->alac_in.reserve(2 * d.part), "alloc tick alac tables");
+    SK_HIP(e->alac_ws.reserve(d.ws_len), "alloc tick alac workspace");
+    return alac_launch(e, b, (uint8_t *)e->alac_in.p + (size_t)p * d.part, (uint8_t *)e->alac_ws.p, d_src, (uint32_t)bytes_len, base);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sk_alac_parse_cookie(const uint8_t *cookie, size_t len, sk_alac_config *out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !cookie) || !out) return SK_ERR_INVALID_ARG;
+    std::string text;
+    alac_text(error, error_cap, "");
+    if (sk_alac::parse_cookie(cookie, len, out, &text)) return SK_OK;
+    alac_text(error, error_cap, text);
+    return SK_ALAC_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_alac_parse_cookie");
+}
+
+int sk_alac_packet_frames(const sk_alac_config *cfg, const uint8_t *packet, size_t len, uint32_t *frames) try {
+    sk::abi_enter();
+    if (!cfg || (len && !packet) || !frames) return SK_ERR_INVALID_ARG;
+    *frames = 0;
+    return sk_alac::packet_frames(*cfg, packet, len, frames);
+} catch (...) {
+    return sk::abi_caught("sk_alac_packet_frames");
+}
+
+int sk_caf_alac_index_create(const uint8_t *desc, size_t desc_len, const uint8_t *cookie, size_t cookie_len, const uint8_t *pakt, size_t pakt_len,
+                             uint64_t data_offset, uint64_t data_size, sk_caf_alac_index **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((desc_len && !desc) || (cookie_len && !cookie) || (pakt_len && !pakt) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    alac_text(error, error_cap, "");
+    std::unique_ptr<sk_caf_alac_index> ix(new sk_caf_alac_index());
+    std::string text;
+    if (!sk_alac::caf_index(desc, desc_len, cookie, cookie_len, pakt, pakt_len, data_offset, data_size, &ix->index, &text)) {
+        alac_text(error, error_cap, text);
+        return SK_ALAC_ERR_STREAM;
+    }
+    *out = ix.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_alac_index_create");
+}
+
+int sk_caf_alac_index_from_file(const uint8_t *file, size_t len, sk_caf_alac_index **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !file) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    alac_text(error, error_cap, "");
+    std::unique_ptr<sk_caf_alac_index> ix(new sk_caf_alac_index());
+    std::string text;
+    if (!sk_alac::caf_index_from_file(file, len, &ix->index, &text)) {
+        alac_text(error, error_cap, text);
+        return SK_ALAC_ERR_STREAM;
+    }
+    *out = ix.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_alac_index_from_file");
+}
+
+void sk_caf_alac_index_destroy(sk_caf_alac_index *ix) try {
+    sk::abi_enter();
+    delete ix;
+} catch (...) {
+    (void)sk::abi_caught("sk_caf_alac_index_destroy");
+}
+
+int sk_caf_alac_index_info(const sk_caf_alac_index *ix, sk_caf_alac_info *info) try {
+    sk::abi_enter();
+    if (!ix || !info) return SK_ERR_INVALID_ARG;
+    std::memset(info, 0, sizeof *info);
+    info->config = ix->index.config;
+    info->valid_frames = ix->index.valid_frames;
+    info->priming_frames = ix->index.priming_frames, info->remainder_frames = ix->index.remainder_frames;
+    info->frames_per_packet = ix->index.frames_per_packet;
+    info->n_packets = (uint32_t)ix->index.packets.size();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_alac_index_info");
+}
+
+int sk_caf_alac_index_packets(const sk_caf_alac_index *ix, uint64_t *offsets, uint32_t *sizes, uint32_t cap) try {
+    sk::abi_enter();
+    if (!ix || (cap && (!offsets || !sizes))) return SK_ERR_INVALID_ARG;
+    if (cap < ix->index.packets.size()) return SK_ERR_CAPACITY;
+    for (size_t i = 0; i < ix->index.packets.size(); ++i) offsets[i] = ix->index.packets[i].offset, sizes[i] = ix->index.packets[i].size;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_alac_index_packets");
+}
+
+int sk_alac_decode_packets(sk_engine *e, const sk_alac_config *cfg, const sk_alac_packet *packets, uint32_t n, const uint8_t *bytes, uint8_t *out,
+                           size_t out_cap, size_t *out_len, int32_t *status_per_packet, uint32_t *frames_per_packet) try {
+    sk::abi_enter();
+    return alac_decode_packets(e, cfg, packets, n, bytes, 0, false, out, out_cap, out_len, status_per_packet, frames_per_packet, nullptr);
+} catch (...) {
+    return sk::abi_caught("sk_alac_decode_packets");
+}
+
+int sk_alac_decode_packets_dev(sk_engine *e, const sk_alac_config *cfg, const sk_alac_packet *packets, uint32_t n, const uint8_t *d_bytes,
+                               size_t bytes_len, uint8_t *d_out, size_t out_cap, size_t *out_len, int32_t *status_per_packet,
+                               const uint32_t *frames_per_packet) try {
+    sk::abi_enter();
+    return alac_decode_packets(e, cfg, packets, n, d_bytes, bytes_len, true, d_out, out_cap, out_len, status_per_packet, nullptr, frames_per_packet);
+} catch (...) {
+    return sk::abi_caught("sk_alac_decode_packets_dev");
+}
+
+size_t sk_tick_alac_out_bound_on(sk_engine *e, const sk_alac_tick_stream *as, uint32_t n_streams, const sk_alac_tick_packet *packets, uint32_t n_packets,
+                                 uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!as && n_streams) || (!packets && n_packets)) return 0;
+    AlacDerived d;
+    if (alac_tick_derive(as, n_streams, packets, n_packets, 0x7fffffffu, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), n_packets, max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_alac_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_alac(sk_engine *e, const sk_alac_tick_stream *as, uint32_t n_streams, const sk_alac_tick_packet *packets, uint32_t n_packets,
+                     const uint8_t *bytes, size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs,
+                     size_t *out_bytes, int32_t *status_per_packet) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && !as) || (n_packets && (!packets || !bytes || !status_per_packet))) return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    AlacDerived d;
+    int rc = alac_tick_derive(as, n_streams, packets, n_packets, bytes_len, d);
+    if (rc != SK_OK) return rc;
+    d.tick.decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+        return alac_tick_decode(e, as, packets, bytes_len, d, as_is, dst_of, d_src);
+    };
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), n_packets, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, &d.tick);
+    if (rc != SK_OK) return rc;
+    for (int p = 0; p < 2; ++p)
+        for (size_t k = 0; k < d.index[p].size(); ++k) status_per_packet[d.index[p][k]] = d.batch[p].status[k];
+    // the records of a stream delivered as decoded say what its packets are; a rejected packet marks its record, or -- behind a
+    // conversion, where records and packets do not correspond -- every record of its stream in this tick
+    std::vector<uint32_t> seen(n_streams, 0);
+    for (uint32_t k = 0; k < *n_outs; ++k) {
+        sk_tick_output &o = outs[k];
+        const uint32_t i = o.stream_index;
+        if (d.tick.plain[i]) {
+            const uint32_t g = d.first[i] + seen[i]++;
+            o.frames = packets[g].frames, o.channels = as[i].channels, o.status = status_per_packet[g];
+            o.bits = as[i].bit_depth;
+        } else {
+            for (uint32_t u = 0; u < as[i].n_units && o.status == 0; ++u) o.status = status_per_packet[d.first[i] + u];
+        }
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_alac");
+}
+
+int sk_alac_packet_decoder_create(sk_engine *e, const uint8_t *cookie, size_t cookie_len, sk_alac_packet_decoder **out, char *error,
+                                  size_t error_cap) try {
+    sk::abi_enter();
+    if (!e || (cookie_len && !cookie) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    alac_text(error, error_cap, "");
+    std::unique_ptr<sk_alac_packet_decoder> d(new sk_alac_packet_decoder());
+    std::string text;
+    if (!sk_alac::parse_cookie(cookie, cookie_len, &d->config, &text)) {
+        alac_text(error, error_cap, text);
+        return SK_ALAC_ERR_STREAM;
+    }
+    d->eng = e;
+    *out = d.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_alac_packet_decoder_create");
+}
+
+void sk_alac_packet_decoder_destroy(sk_alac_packet_decoder *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_alac_packet_decoder_destroy");
+}
+
+int sk_alac_packet_decoder_info(const sk_alac_packet_decoder *d, uint32_t *sample_rate, uint8_t *channels, uint8_t *bit_depth,
+                                size_t *maximum_pcm_samples) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (sample_rate) *sample_rate = d->config.sample_rate;
+    if (channels) *channels = d->config.channels;
+    if (bit_depth) *bit_depth = d->config.bit_depth;
+    if (maximum_pcm_samples) *maximum_pcm_samples = (size_t)d->config.frame_length * d->config.channels;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_alac_packet_decoder_info");
+}
+
+int sk_alac_packet_decoder_decode_packet(sk_alac_packet_decoder *d, const uint8_t *packet, size_t len, uint8_t *out, size_t out_cap,
+                                         size_t *out_len) try {
+    sk::abi_enter();
+    if (!d || (len && !packet) || !out_len || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    const auto fail = [&](const std::string &text) {
+        d->error = text;
+        return (int)SK_ALAC_ERR_STREAM;
+    };
+    if (len == 0) return fail("ALAC packet is empty");
+    if (len > sk_alac::kMaxPacketBytes) return fail("ALAC packet exceeds the " + std::to_string(sk_alac::kMaxPacketBytes) + " byte budget");
+    uint32_t frames = 0;
+    if (const int rc = sk_alac::packet_frames(d->config, packet, len, &frames)) return fail("ALAC packet: " + std::string(sk_strerror(rc)));
+    if ((size_t)frames * d->config.channels * (d->config.bit_depth / 8u) > out_cap) return SK_ERR_CAPACITY;
+    const sk_alac_packet one{0, (uint32_t)len};
+    int32_t status = 0;
+    uint32_t got = 0;
+    const int rc = alac_decode_packets(d->eng, &d->config, &one, 1, packet, 0, false, out, out_cap, out_len, &status, &got, nullptr);
+    if (rc != SK_OK) return rc;
+    if (status != SK_OK) {
+        *out_len = 0;
+        return fail("ALAC packet: " + std::string(sk_strerror(status)));
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_alac_packet_decoder_decode_packet");
+}
+
+const char *sk_alac_packet_decoder_last_error(const sk_alac_packet_decoder *d) try {
+    sk::abi_enter();
+    return d ? d->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_alac_packet_decoder_last_error");
     return "";
 }
 

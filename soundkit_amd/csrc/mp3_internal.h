@@ -123,6 +123,10 @@ struct PipelineGpuHooks {
     int (*mpa_parse_frame)(const uint8_t *, size_t, const sk_mpa_frame_info *, sk_mpa_frame_record *) = nullptr;         // sk_mpa_parse_frame
     int (*tick_mpa)(sk_engine *, const sk_tick_stream *, uint32_t, const sk_tick_input *, const sk_tick_mp3_frames *, const sk_tick_mpa_frames *, uint8_t *,
                     size_t, sk_tick_output *, uint32_t, uint32_t *, size_t *) = nullptr;  // sk_tick_run_mixed_mpa
+    // sk_tick_run_alac / sk_tick_alac_out_bound_on: the ALAC streams' packets
+    int (*tick_alac)(sk_engine *, const sk_alac_tick_stream *, uint32_t, const sk_alac_tick_packet *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
+                     sk_tick_output *, uint32_t, uint32_t *, size_t *, int32_t *) = nullptr;
+    size_t (*tick_alac_out_bound)(sk_engine *, const sk_alac_tick_stream *, uint32_t, const sk_alac_tick_packet *, uint32_t, uint32_t *) = nullptr;
     uint32_t (*wide_pcm_streams)(const sk_engine *) = nullptr;  // sk_engine_wide_pcm_streams
     int (*enable_wide_pcm)(sk_engine *, uint32_t) = nullptr;    // sk_engine_enable_wide_pcm
 };

@@ -17,6 +17,7 @@
 #include "../../include/soundkit_amd.h"
 #include "sk_abi.h"
 #include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
+#include "alac_stream.h"
 #include "flac_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
@@ -91,6 +92,10 @@ struct PStream {
     // PCM tick would do.  flac_plain: nothing to change behind the decode (one AudioData per frame, in the depth STREAMINFO names)
     std::unique_ptr<sk_flac::Reader> flac;
     bool flac_plain = false;
+    // ALAC packet streams (sk_pipeline_spawn_alac_packets): the cookie; every chunk is one packet, the unit of the ALAC tick, which decodes
+    // it in front of what the PCM tick would do.  alac_plain: nothing to change behind the decode (one AudioData per packet)
+    bool alac = false, alac_plain = false;
+    sk_alac_config alac_cfg{};
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -98,8 +103,8 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -171,6 +176,8 @@ struct Batch {
     TickTable<sk_aiff_tick_stream, sk_pcm_unit> aiff_ts;
     TickTable<sk_flac_tick_stream, sk_flac_frame_info> flac_ts;
     std::vector<int32_t> flac_status;
+    TickTable<sk_alac_tick_stream, sk_alac_tick_packet> alac_ts;  // ALAC streams' packets (sk_tick_run_alac)
+    std::vector<int32_t> alac_status;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -196,6 +203,7 @@ struct Batch {
         pcm_ts.clear();
         aiff_ts.clear();
         flac_ts.clear();
+        alac_ts.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -349,6 +357,7 @@ struct Parsed {  // what one worker pass produced for one stream
     std::vector<uint8_t> pcm_bytes;
     std::vector<sk_pcm_unit> pcm_units;
     std::vector<sk_flac_frame_info> flac_frames;  // a FLAC stream's pass: one per unit, offset into pcm_bytes
+    std::vector<sk_alac_tick_packet> alac_packets;  // an ALAC stream's pass: one per unit, offset into pcm_bytes
     std::vector<Output> pre;
     bool fail(int32_t st, const std::string &msg) {  // the pass ends its stream with this error; false, for a caller that returns it
         failed = true;
@@ -673,7 +682,9 @@ int ensure_pcm(sk_lane *p) {
 bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     uint32_t rate, channels, bits;
     bool is_float, big_endian = false;
-    if (s.flac) {  // STREAMINFO's: the AudioData of a FLAC frame carries the stream's own depth (create_audio_data_i32_with_bits, lib.rs:3191-3236)
+    if (s.alac) {  // the cookie's
+        rate = s.alac_cfg.sample_rate, channels = s.alac_cfg.channels, bits = s.alac_cfg.bit_depth, is_float = false;
+    } else if (s.flac) {  // STREAMINFO's: the AudioData of a FLAC frame carries the stream's own depth (create_audio_data_i32_with_bits, lib.rs:3191-3236)
         rate = s.flac->info().sample_rate, channels = s.flac->info().channels, bits = s.flac->info().bits_per_sample, is_float = false;
     } else if (s.aiff) {  // what the decoder emits (the output contract), not what the file holds: apply_output_options sees only that
         rate = s.aiff->sample_rate(), channels = s.aiff->channels(), bits = s.aiff->bits(), is_float = s.aiff->is_float();
@@ -703,6 +714,15 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
         s.pcm_route = kPcmFlacTick;
         s.flac_plain = true;
+        return true;
+    }
+    if (s.alac && (!hooks.tick_alac || !hooks.tick_alac_out_bound))
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: ALAC decoding needs the device tick, which this build lacks");
+    if (s.alac && target_rate == rate && target_bits == bits && target_channels == channels) {  // every packet has per-sample work: the tick's
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmAlacTick;
+        s.alac_plain = true;
         return true;
     }
     if (target_rate == rate && target_bits == bits && target_channels == channels) {
@@ -737,7 +757,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick);
+    s.pcm_route = s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
     return true;
 }
 
@@ -755,6 +775,54 @@ size_t stage_unit(Parsed &r, PStream &s, const uint8_t *data, size_t len, uint32
         outputs += 1;
     }
     return at;
+}
+
+// An ALAC stream's pass: every chunk is one packet (sk_pipeline_spawn_alac_packets), and whole packets are what the stream is budgeted in
+// -- `room` AudioData (one per packet, or one per completed 4096-frame chunk through the resampler), the units of one stream in a tick and
+// the bytes one tick takes.  The host reads the packet's frame count (alac_stream.h) so that its place in the tick is known; a packet it
+// cannot read one from, an empty one behind which more follows or one above 16 MiB ends the stream with its text.
+void parse_some_alac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
+    uint32_t outputs = 0;
+    if (!s.pcm_route && !pcm_open(p, s, r)) return;
+    while (!r.failed) {
+        if (s.saw_eof) {
+            r.eof = true;
+            break;
+        }
+        std::vector<uint8_t> chunk;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            if (s.in.empty()) break;
+            const size_t next = s.in.front().size();
+            if (next && (outputs >= room || r.pcm_units.size() >= per_pass || (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes))) {
+                r.more = true;
+                break;
+            }
+            chunk = std::move(s.in.front());
+            s.in.pop_front();
+        }
+        if (chunk.empty()) {
+            s.saw_eof = true;
+            continue;
+        }
+        s.queued_bytes.fetch_sub(chunk.size());
+        if (chunk.size() > sk_alac::kMaxPacketBytes) {
+            r.fail(SK_ALAC_ERR_STREAM, "Decoding failed: ALAC packet exceeds the " + std::to_string(sk_alac::kMaxPacketBytes) + " byte budget");
+            break;
+        }
+        uint32_t frames = 0;
+        const int rc = sk_alac::packet_frames(s.alac_cfg, chunk.data(), chunk.size(), &frames);
+        if (rc != SK_OK) {
+            r.fail(rc, rc == SK_ALAC_UNSUPPORTED ? "Decoding failed: ALAC packet rejected: a CCE or PCE element is not supported"
+                                                 : "Decoding failed: ALAC packet rejected: the elements break the syntax or miss the packet's end");
+            break;
+        }
+        const size_t at = stage_unit(r, s, chunk.data(), chunk.size(), frames, outputs);
+        r.alac_packets.push_back(sk_alac_tick_packet{(uint32_t)at, (uint32_t)chunk.size(), frames, 0});
+    }
+    r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
 
 // A FLAC stream's pass: the reader cuts whole frames out of the chunks (marker and metadata first), and whole frames are what the
@@ -964,6 +1032,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         parse_some_flac(p, s, room, r);
         return;
     }
+    if (s.codec == kCodecAlac) {
+        parse_some_alac(p, s, room, r);
+        return;
+    }
     if (s.codec == kCodecWav || s.codec == kCodecRawPcm || s.codec == kCodecAiff) {
         parse_some_pcm(p, s, room, r);
         return;
@@ -1118,6 +1190,7 @@ void thread_debug_point(int where) {
 
 inline void shift_unit(sk_pcm_unit &u, size_t by) { u.byte_offset += by; }
 inline void shift_unit(sk_flac_frame_info &f, size_t by) { f.offset += (uint32_t)by; }
+inline void shift_unit(sk_alac_tick_packet &k, size_t by) { k.offset += (uint32_t)by; }
 
 // A PCM-family pass joins the table of its tick (batch_mu held): nothing when it neither brings units nor ends a resampler; else it
 // takes its place in the batch's staged bytes (pcm_at) and a row with what the three ticks' rows share, and its units follow with
@@ -1286,6 +1359,11 @@ void worker_body(sk_lane *p) {
                         // as decoded: the contract's width (the record's depth is put back at delivery); else what the options ask for
                         if (s.flac_plain) row->out_bits = depth <= 8 ? 8 : (depth <= 16 ? 16 : (depth <= 24 ? 24 : 32));
                     }
+                } else if (s.pcm_route == kPcmAlacTick) {
+                    if (sk_alac_tick_stream *row = claim_tick_row(b, b->alac_ts, s, r, r.alac_packets, be, pcm_at)) {
+                        const sk_alac_config &c = s.alac_cfg;
+                        row->frame_length = c.frame_length, row->bit_depth = c.bit_depth, row->pb = c.pb, row->mb = c.mb, row->kb = c.kb;
+                    }
                 } else if (s.pcm_route == kPcmTick) {
                     if (sk_pcm_tick_stream *row = claim_tick_row(b, b->pcm_ts, s, r, r.pcm_units, be, pcm_at)) row->format = s.pcm_fmt;
                 }
@@ -1447,10 +1525,11 @@ void submit_body(sk_lane *p) {
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
-        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty()) {
-            // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, then the PCM tick's: one buffer
+        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty()) {
+            // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, the ALAC tick's, then the PCM tick's: one buffer
             const size_t bound = (ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out)) +
                                  follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
+                                 follow_on_bound(p, b->alac_ts, hooks.tick_alac_out_bound) +
                                  follow_on_bound(p, b->pcm_ts, hooks.tick_pcm_out_bound);
             if (bound > b->out_pinned_cap) {
                 // Pinned memory is slow to get (10 ms per 64 MB on an idle device, many times that beside a running lane): the
@@ -1470,7 +1549,7 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->pcm_ts.max_out;
+            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->pcm_ts.max_out;
             if (b->recs.size() < n_recs) b->recs.resize(n_recs);
         }
         const bool with_md = b->n_mp3 && p->mp3_gpu;  // the MP3 streams' Huffman stage is the tick's as well
@@ -1524,6 +1603,12 @@ void submit_body(sk_lane *p) {
                                    (uint32_t)b->flac_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used,
                                    b->flac_status.data());
         });
+        follow_on_tick(b, b->alac_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            b->alac_status.assign(b->alac_ts.units.size() + 1, 0);
+            return hooks.tick_alac(p->engine, b->alac_ts.rows.data(), (uint32_t)b->alac_ts.rows.size(), b->alac_ts.units.data(),
+                                   (uint32_t)b->alac_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used,
+                                   b->alac_status.data());
+        });
         follow_on_tick(b, b->pcm_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
             return hooks.tick_pcm(p->engine, b->pcm_ts.rows.data(), (uint32_t)b->pcm_ts.rows.size(), b->pcm_ts.units.data(),
                                   (uint32_t)b->pcm_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used);
@@ -1532,7 +1617,7 @@ void submit_body(sk_lane *p) {
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
         p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_ts.units.size() +
-                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size());
+                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -1553,6 +1638,10 @@ void submit_body(sk_lane *p) {
 // text comes from parsing the entry's access units of this tick once more on the host (errors are rare, and an entry holds
 // at most max_stream_frames_per_tick units).
 std::string device_error_text(sk_lane *p, const Batch *b, uint32_t entry, const PStream &s, int32_t status) {
+    if (s.codec == kCodecAlac)
+        return status == SK_ERR_UNSUPPORTED ? "Decoding failed: ALAC packet rejected: a channel pair at 32 bits without extra bytes is not supported"
+               : status == SK_ALAC_UNSUPPORTED ? "Decoding failed: ALAC packet rejected: a CCE or PCE element is not supported"
+                                               : "Decoding failed: ALAC packet rejected: the elements break the syntax or miss the packet's end";
     if (s.codec == kCodecFlac)
         return status == SK_ERR_UNSUPPORTED ? "Decoding failed: FLAC frame rejected: 32-bit samples with a side channel are not supported"
                                             : "Decoding failed: FLAC frame rejected: the subframes break the syntax or miss the frame's end";
@@ -2023,7 +2112,8 @@ void lane_destroy(sk_lane *p) {
     delete p;
 }
 
-int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false) {
+int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
+               const sk_alac_config *alac = nullptr) {
     if (!p || !handle) return SK_ERR_INVALID_ARG;
     // RawPcmFormat::validate (raw_pcm.rs:117-125), and the sample formats there are
     if (raw && (raw->sample_rate == 0 || raw->channels == 0 || raw->format > SK_FMT_F32BE)) return SK_ERR_INVALID_ARG;
@@ -2066,6 +2156,8 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.aiff_enc = 0;
     s.flac.reset();
     s.flac_plain = false;
+    s.alac = s.alac_plain = false;
+    s.alac_cfg = sk_alac_config{};
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
@@ -2081,6 +2173,12 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     if (aiff) {  // spawn_aiff_with_options (lib.rs:2714-2724): the decoder is there from the start, nothing is detected or gathered
         s.codec = kCodecAiff;
         s.aiff.reset(new sk_pcm::AiffStream());
+        s.pcm_detected = true;
+    }
+    if (alac) {  // sk_pipeline_spawn_alac_packets: the cookie is the decoder, nothing is detected or gathered
+        s.codec = kCodecAlac;
+        s.alac = true;
+        s.alac_cfg = *alac;
         s.pcm_detected = true;
     }
     *handle = h;
@@ -2227,7 +2325,8 @@ inline sk_lane *lane_of(sk_pipeline *p, uint32_t handle, uint32_t *inner) {
     return p->lanes[handle % n];
 }
 
-int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false) {
+int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
+                   const sk_alac_config *alac = nullptr) {
     if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
     const uint32_t n = (uint32_t)p->lanes.size();
     const uint32_t first = p->next_lane.fetch_add(1) % n;
@@ -2235,7 +2334,7 @@ int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pc
     for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
         const uint32_t li = (first + k) % n;
         uint32_t inner = 0;
-        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff);
+        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac);
         if (rc == SK_OK) {
             *handle = inner * n + li;
             return SK_OK;
@@ -2364,6 +2463,17 @@ int sk_pipeline_spawn_aiff(sk_pipeline *p, const sk_decode_options *opt, uint32_
     return pipeline_spawn(p, opt, nullptr, handle, true);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn_aiff");
+}
+
+int sk_pipeline_spawn_alac_packets(sk_pipeline *p, const uint8_t *cookie, size_t cookie_len, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    if (cookie_len && !cookie) return SK_ERR_INVALID_ARG;
+    sk_alac_config cfg{};
+    std::string text;
+    if (!sk_alac::parse_cookie(cookie, cookie_len, &cfg, &text)) return SK_ALAC_ERR_STREAM;
+    return pipeline_spawn(p, opt, nullptr, handle, false, &cfg);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_alac_packets");
 }
 
 int sk_pipeline_send(sk_pipeline *p, uint32_t handle, const uint8_t *data, size_t len) try {

@@ -16,6 +16,8 @@ const bool g_hooked = [] {
     hooks.tick_aiff_out_bound = sk_tick_aiff_out_bound_on;
     hooks.tick_flac = sk_tick_run_flac;  // ... and the FLAC streams'
     hooks.tick_flac_out_bound = sk_tick_flac_out_bound_on;
+    hooks.tick_alac = sk_tick_run_alac;  // ... and the ALAC streams'
+    hooks.tick_alac_out_bound = sk_tick_alac_out_bound_on;
     hooks.mpa_find_layer = sk_mp12::find_layer;  // Layer I / II streams: their host front and their tick
     hooks.mpa_scan = sk_mpa_scan;
     hooks.mpa_parse_frame = sk_mpa_parse_frame;

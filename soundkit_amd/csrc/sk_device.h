@@ -600,4 +600,39 @@ hipError_t launch_flac_restore(const FlacSubframe *subs, uint32_t n_subs, int32_
 hipError_t launch_flac_output(const FlacFrame *frames, uint32_t n_frames, const FlacSubframe *subs, const int32_t *ws, const int32_t *status,
                               uint8_t *out, uint32_t mode, hipStream_t s);
 
+// alac_decode.hip -- Apple Lossless packets to interleaved PCM, integer only, three launches over every packet of a call:
+// k_alac_entropy (one packet per lane: the element walk, headers, adaptive Golomb residuals into a planar i32 workspace, one record
+// per channel), k_alac_predict (one channel of one packet per lane: the recurrence with its adapting coefficients, in place) and
+// k_alac_output (one block per packet: pair unmix, extra bits from their recorded position, interleave, width).
+struct AlacParams {  // of a cookie; the packets of one call may belong to streams with different ones
+    uint32_t frame_length;
+    uint8_t bit_depth, pb, mb, kb, channels;
+    uint8_t pad[3];
+};
+struct AlacPacket {
+    uint32_t byte_offset;  // in `bytes`, a multiple of 16
+    uint32_t byte_len;
+    uint32_t frames;       // as the host read them from the first element; every element must agree
+    uint32_t ws_offset;    // in words: the packet's channels x frames part of the workspace, planar
+    uint32_t rec0;         // the packet's first channel record
+    uint32_t cfg;          // its cookie's AlacParams
+    uint64_t out_offset;   // in bytes
+};
+struct AlacChannel {   // record rec0 + channel, complete when the packet's status is 0
+    int16_t coef[32];  // coef[j] multiplies out[i - order + j] - out[i - order - 1]: the last one read is coef[0]
+    uint32_t extra_pos;  // bit position in the packet of the element's extra fields (frames x el_channels fields of extra_bits)
+    uint8_t bps, order, shift, ptype;
+    uint8_t mix_shift, mix_weight, extra_bits;
+    uint8_t role;      // 0 a single channel, 1 / 2 first / second of a pair
+    uint8_t raw;       // an uncompressed element: the workspace holds the samples
+    uint8_t pad[3];
+};
+// by_length: the packets' indices, longest first.  bytes is 4-byte aligned.  lanes: packet << 3 | channel, one per channel record.
+hipError_t launch_alac_entropy(const AlacParams *cfgs, const AlacPacket *packets, const uint32_t *by_length, uint32_t n_packets, const uint8_t *bytes,
+                               uint32_t bytes_len, int32_t *ws, AlacChannel *recs, int32_t *status, hipStream_t s);
+hipError_t launch_alac_predict(const AlacPacket *packets, const uint32_t *lanes, uint32_t n_lanes, const AlacChannel *recs, int32_t *ws,
+                               const int32_t *status, hipStream_t s);
+hipError_t launch_alac_output(const AlacParams *cfgs, const AlacPacket *packets, uint32_t n_packets, const AlacChannel *recs, const int32_t *ws,
+                              const int32_t *status, const uint8_t *bytes, uint8_t *out, hipStream_t s);
+
 }  // namespace sk

@@ -575,6 +575,42 @@ class Engine:
         return ([(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
                  for r in recs[:n_out.value]], status[:n].tolist())
 
+    def tick_run_alac(self, streams, packets):
+        """One tick of ALAC streams (sk_tick_run_alac).  streams: list of dicts {config (the cookie as alac.parse_cookie gives it), out_bits,
+        out_channels, n_units, and for a rate change: stream, resample, flush}; packets: [packet bytes] of all streams, stream by stream,
+        each packed at a 16-byte aligned offset; their frame counts are read with sk_alac_packet_frames, as the scheduler does it.
+        -> (the same list of records as tick_run_pcm, [status per packet])."""
+        import ctypes as C
+        from . import alac
+        from ._lib import AlacTickPacket, AlacTickStream, TickOutput
+        ts = (AlacTickStream * max(len(streams), 1))()
+        counts, at = [], 0
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            for name in ("frame_length", "channels", "bit_depth", "pb", "mb", "kb"):
+                setattr(ts[i], name, int(s["config"][name]))
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+            counts += [alac.packet_frames(s["config"], p)[1] for p in packets[at:at + int(s["n_units"])]]
+            at += int(s["n_units"])
+        counts += [0] * (len(packets) - len(counts))
+        placed, blob = alac.pack_packets(packets)
+        n = len(packets)
+        table = (AlacTickPacket * max(n, 1))()
+        for k in range(n):
+            table[k].offset, table[k].size, table[k].frames = placed[k].offset, placed[k].size, counts[k]
+        src = np.frombuffer(blob + bytes(16), np.uint8)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_alac_out_bound_on(self._h, ts, len(streams), table, n, C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        status = np.zeros(max(n, 1), np.int32)
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_alac(self._h, ts, len(streams), table, n, _ptr(src), len(blob), _ptr(out), out.size, recs, max_out.value,
+                                   C.byref(n_out), C.byref(used), _ptr(status)), "sk_tick_run_alac", self._h)
+        return ([(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                 for r in recs[:n_out.value]], status[:n].tolist())
+
     def tick_run_aiff(self, streams, units):
         """One tick of AIFF streams (sk_tick_run_aiff).  As tick_run_pcm, with `encoding` (AIFF_*) in the place of `format` and, for
         IMA4, "ima_state": [(predictor, step_index)] * 2, which is updated in the dict.  -> the same list of records."""

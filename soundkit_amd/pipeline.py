@@ -118,6 +118,18 @@ class BatchScheduler:
             raise SoundkitError(rc, "sk_pipeline_spawn_aiff")
         return DecodePipelineHandle(self, handle.value)
 
+    def spawn_alac_packets(self, magic_cookie, options=None):
+        """a stream of ALAC packets (sk_pipeline_spawn_alac_packets): the cookie once, then every `send` is exactly one packet; the
+        empty send ends the stream and flushes the resampler"""
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        cookie = bytes(magic_cookie)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_alac_packets(self._h, cookie, len(cookie), C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_alac_packets")
+        return DecodePipelineHandle(self, handle.value)
+
     def wait_outputs(self, timeout_ms=100, cap=256):
         """Handles (as spawned: `handle.id`) that have outputs or have ended; blocks up to timeout_ms.  For callers that
         serve many streams from one thread."""
@@ -248,6 +260,10 @@ class DecodePipeline:
     @staticmethod
     def spawn_aiff_with_options(options):
         return default_scheduler().spawn_aiff(options)
+
+    @staticmethod
+    def spawn_alac_packets(magic_cookie, options=None):
+        return default_scheduler().spawn_alac_packets(magic_cookie, options)
 
     @staticmethod
     def spawn_raw_pcm(format):
