@@ -1362,6 +1362,145 @@ int sk_alac_packet_decoder_info(const sk_alac_packet_decoder *, uint32_t *sample
 int sk_alac_packet_decoder_decode_packet(sk_alac_packet_decoder *, const uint8_t *packet, size_t len, uint8_t *out, size_t out_cap, size_t *out_len);
 const char *sk_alac_packet_decoder_last_error(const sk_alac_packet_decoder *);
 
+/* ---- Telephony: headerless G.711, G.722 and G.726 streams (GPU, csrc/g72x_decode.hip; host arithmetic in csrc/g72x_stream.h) -- */
+/* The streams of DecodePipeline::spawn_g711 / spawn_g722 / spawn_g726* (soundkit-decoder/src/lib.rs:2512-2610): no header, nothing to
+ * detect -- the caller knows the codec from its transport.  Everything decodes to s16le, bit for bit what the reference's decoders
+ * give.  G.711: mu-law or A-law, one byte a sample, any rate and channel count (the samples interleaved as they arrive).  G.722: the
+ * 64 kbit/s mode, mono 16 kHz, two samples a byte.  G.726: 16 / 24 / 32 / 40 kbit/s, mono 8 kHz, codes packed left (MSB first, `ffmpeg
+ * -f g726`) or right (LSB first, `-f g726le`) in groups of 1 / 3 / 1 / 5 bytes that give 4 / 8 / 2 / 8 samples.  Not built: G.722 at
+ * 56 / 48 kbit/s or with packed codes, GSM, AMR-NB, G.729 and Speex (the reference reaches them through foreign codecs), the encoders. */
+enum sk_g72x_codec { SK_G711_ULAW = 0, SK_G711_ALAW = 1, SK_G722 = 2, SK_G726 = 3 };
+enum sk_g726_packing { SK_G726_LEFT = 0, SK_G726_RIGHT = 1 };
+enum sk_g72x_status {
+    SK_G72X_ERR_STREAM = -701 /* a send or a stream was rejected with a text */
+};
+#define SK_G72X_MAX_SEND_SAMPLES 262144 /* the reference's scratch (lib.rs:82): what one send -- one unit -- may decode to */
+/* The carry of a G.726 stream from call to call: G726Core (soundkit-g726/src/lib.rs:182-212), 24 words of plain data in the caller's
+ * memory.  A new stream starts from sk_g726_state_init: yl 34816, yu 544, dq[] and sr[] 32, everything else 0. */
+typedef struct sk_g726_state {
+    int32_t yl, yu, dms, dml, ap;
+    int32_t a[2], b[6], pk[2], dq[6], sr[2];
+    int32_t td;
+} sk_g726_state;
+/* The carry of a G.722 stream: per band (low, high) the predictor of the standard's block 4 -- s, sz, r[1..2], p[1..2], a[1..2],
+ * b[1..6], d[1..6] -- with the log scale factor nb and the scale factor det, then the receive QMF's 22 history entries (oldest first,
+ * alternating rlow + rhigh and rlow - rhigh).  66 words.  A new stream starts from ALL ZEROS (sk_g722_state_init), both det included:
+ * that is what the reference's recording pins (the C code this decoder descends from starts det at 32 / 8). */
+typedef struct sk_g722_band {
+    int32_t s, sz, r[2], p[2], a[2], b[6], d[6], nb, det;
+} sk_g722_band;
+typedef struct sk_g722_state {
+    sk_g722_band band[2];
+    int32_t x[22];
+} sk_g722_state;
+void sk_g726_state_init(sk_g726_state *);
+void sk_g722_state_init(sk_g722_state *);
+
+/* One stream's bytes, one call.  g726_rate (16000 / 24000 / 32000 / 40000) and g726_packing are read for SK_G726 only; `state` is a
+ * sk_g726_state for SK_G726, a sk_g722_state for SK_G722 and unused (may be NULL) for G.711.  G.726 takes whole groups: a len that is
+ * none is SK_ERR_INVALID_ARG (sk_g726_decoder_* holds the partial group back).  out receives len x 2 (G.711), len x 4 (G.722) or
+ * groups x samples x 2 (G.726) bytes of s16le; an out_cap below that is SK_ERR_INVALID_ARG and nothing is written.  A call that decodes
+ * to more than SK_G72X_MAX_SEND_SAMPLES samples is SK_G72X_ERR_STREAM with the reference's text in `error` (NUL-terminated, cut to
+ * error_cap; may be NULL): `Output buffer too small for G.726 decode: need N, have 262144`, with the codec's own name.  The state is
+ * read on entry and written on success; any failure leaves it as it was.  The _dev form takes 16-byte aligned device pointers (the
+ * input is read in whole dwords up to the one that holds its last byte) and runs on the engine's stream. */
+int sk_g72x_decode(sk_engine *, int codec, uint32_t g726_rate, int g726_packing, const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap,
+                   size_t *out_len, void *state, char *error, size_t error_cap);
+int sk_g72x_decode_dev(sk_engine *, int codec, uint32_t g726_rate, int g726_packing, const uint8_t *d_bytes, size_t len, uint8_t *d_out,
+                       size_t out_cap, size_t *out_len, void *state, char *error, size_t error_cap);
+
+/* Many streams, one launch sequence (k_g726 over the G.726 streams, k_g722_adpcm + k_g722_qmf over the G.722 streams, the G.711
+ * expansion over the G.711 units).  The units are listed stream by stream in the order of `streams`; units[k] lies at bytes +
+ * units[k].offset, a multiple of 16, and a stream's units are decoded in order, the state carried from one into the next.  A unit may be
+ * empty; a G.726 unit holds whole groups; no unit decodes to more than SK_G72X_MAX_SEND_SAMPLES samples.  Every unit's s16le is written
+ * at the next multiple of 16 bytes of `out`, in table order, and the call sets units[k].out_offset and .out_len.  streams[i].state names
+ * the stream's record in g726_states (SK_G726) or g722_states (SK_G722); a record may be named by one stream only.  Anything that does
+ * not add up, or an out_cap too small: SK_ERR_INVALID_ARG, nothing decoded.  The states are written on success only. */
+typedef struct sk_g72x_stream {
+    uint8_t codec;        /* enum sk_g72x_codec */
+    uint8_t g726_packing; /* enum sk_g726_packing */
+    uint8_t reserved[2];
+    uint32_t g726_rate;   /* 16000 / 24000 / 32000 / 40000 */
+    uint32_t n_units;
+    uint32_t state;
+} sk_g72x_stream;
+typedef struct sk_g72x_unit {
+    uint32_t offset, size;
+    uint32_t out_len;    /* out: bytes */
+    uint32_t reserved;
+    uint64_t out_offset; /* out */
+} sk_g72x_unit;
+int sk_g72x_decode_batch(sk_engine *, const sk_g72x_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *bytes,
+                         size_t bytes_len, uint8_t *out, size_t out_cap, size_t *out_len, sk_g726_state *g726_states, uint32_t n_g726_states,
+                         sk_g722_state *g722_states, uint32_t n_g722_states);
+int sk_g72x_decode_batch_dev(sk_engine *, const sk_g72x_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units,
+                             const uint8_t *d_bytes, size_t bytes_len, uint8_t *d_out, size_t out_cap, size_t *out_len, sk_g726_state *g726_states,
+                             uint32_t n_g726_states, sk_g722_state *g722_states, uint32_t n_g722_states);
+
+/* The tick of the telephony streams, sk_tick_run_aiff's pattern: every unit (= what one send decodes now, packed at a 16-byte aligned
+ * offset; never empty, G.726 in whole groups, at most SK_G72X_MAX_SEND_SAMPLES samples) is first decoded to s16le on the device.  A
+ * stream with nothing further to change (no rate change, out_bits = 16, out_channels = channels) gets those bytes as its outputs, one
+ * per unit.  Every other stream then runs exactly what sk_tick_run_pcm runs on an s16le source of that channel count -- same kernels,
+ * records, bounds and limits; there a G.711 unit holds whole frames.  channels is read for G.711 (G.722 and G.726 are mono: 1).  The
+ * streams' carries are named as in sk_g72x_decode_batch.  On failure, or when the tick is refused, the carries and the resamplers are
+ * as they were before the call. */
+typedef struct sk_g72x_tick_stream {
+    uint32_t stream;      /* engine stream (resample = 1 only) */
+    uint32_t n_units;
+    uint32_t g726_rate;
+    uint32_t state;
+    uint8_t codec;        /* enum sk_g72x_codec */
+    uint8_t g726_packing;
+    uint8_t channels;
+    uint8_t out_bits;     /* 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t reserved;
+} sk_g72x_tick_stream;
+size_t sk_tick_g72x_out_bound_on(sk_engine *, const sk_g72x_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                 uint32_t *max_outputs);
+int sk_tick_run_g72x(sk_engine *, const sk_g72x_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                     const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                     uint32_t *n_outputs, size_t *out_bytes_used, sk_g726_state *g726_states, uint32_t n_g726_states, sk_g722_state *g722_states,
+                     uint32_t n_g722_states);
+
+/* Scheduler streams of headerless telephony audio (DecodePipeline::spawn_g711 / spawn_g722 / spawn_g726*, lib.rs:2512-2610): the stream
+ * has its decoder from the spawn and detects nothing.  Every non-empty sk_pipeline_send is one decode and gives one AudioData -- 16 bits;
+ * G.711 at the spawn's rate and channel count, G.722 16 kHz mono, G.726 8 kHz mono -- or what the output options make of it (the
+ * PCM-family tick); a G.726 send that completes no group delivers nothing.  The empty send ends the stream: G.726 with a partial group
+ * left ends alone with `Decoding failed: G.726 stream ended with N trailing partial-packet byte(s)`, G.711 and G.722 end with nothing
+ * more.  A send that decodes to more than SK_G72X_MAX_SEND_SAMPLES samples ends its stream with `Decoding failed: Output buffer too small
+ * for ... decode: need N, have 262144`.  G.711 of several channels: as decoded the samples leave as they came; behind a conversion a
+ * send that splits a frame ends the stream with the reference's `Decoding failed: Output conversion failed: PCM data is unsupported or
+ * contains a partial frame`.  sk_pipeline_spawn_g711 with a rate or a channel count of 0: SK_G72X_ERR_STREAM and the reference's text
+ * (`G.711 sample rate must be > 0`, `G.711 channel count must be > 0`) in `error` (NUL-terminated, cut to error_cap; may be NULL).  A
+ * rate that is no G.726 rate, a packing or a law that is none: SK_ERR_INVALID_ARG. */
+int sk_pipeline_spawn_g711(sk_pipeline *, int law, uint32_t sample_rate, uint32_t channels, const sk_decode_options *opt, uint32_t *handle,
+                           char *error, size_t error_cap);
+int sk_pipeline_spawn_g722(sk_pipeline *, const sk_decode_options *opt, uint32_t *handle);
+int sk_pipeline_spawn_g726(sk_pipeline *, uint32_t g726_rate, int g726_packing, const sk_decode_options *opt, uint32_t *handle);
+
+/* The reference's Decoder objects (soundkit-g711 / -g722 / -g726): decode_i16, decode_i32 (= the s16 sample << 16), decode_f32 (= / 32768),
+ * sample_rate / channels through _info.  `written` counts samples; an out_cap (in samples) below what the input decodes to is
+ * SK_ERR_CAPACITY with `Output buffer too small for ... decode: need N, have M` in last_error and nothing consumed.  The G.726 decoder
+ * holds a partial group back for the next call, and sk_g726_decoder_flush at the end of the stream is SK_G72X_ERR_STREAM with `G.726
+ * stream ended with N trailing partial-packet byte(s)` when one is left.  sk_g711_decoder_create refuses a rate or a channel count of 0
+ * with the reference's text in `error`.  kind: 0 = i16, 1 = i32, 2 = f32. */
+typedef struct sk_g72x_decoder sk_g72x_decoder;
+int sk_g711_decoder_create(sk_engine *, int law /* SK_G711_ULAW / SK_G711_ALAW */, uint32_t sample_rate, uint32_t channels, sk_g72x_decoder **out,
+                           char *error, size_t error_cap);
+int sk_g722_decoder_create(sk_engine *, sk_g72x_decoder **out);
+int sk_g726_decoder_create(sk_engine *, uint32_t g726_rate, int g726_packing, sk_g72x_decoder **out);
+void sk_g72x_decoder_destroy(sk_g72x_decoder *);
+int sk_g72x_decoder_info(const sk_g72x_decoder *, int *codec, uint32_t *sample_rate, uint32_t *channels);
+int sk_g72x_decoder_decode_i16(sk_g72x_decoder *, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written);
+int sk_g72x_decoder_decode_i32(sk_g72x_decoder *, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written);
+int sk_g72x_decoder_decode_f32(sk_g72x_decoder *, const uint8_t *input, size_t len, float *out, size_t out_cap, size_t *written);
+int sk_g726_decoder_flush(sk_g72x_decoder *);
+int sk_g72x_decoder_reset(sk_g72x_decoder *);
+const char *sk_g72x_decoder_last_error(const sk_g72x_decoder *);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -501: "FlacNeedMore", -502: "FlacNoSync", -503: "FlacReserved", -504: "FlacBadCrc", -505: "FlacNeedStreamInfo",
              -506: "FlacInvalid", -507: "FlacStreamRejected",
              -601: "AlacInvalid", -602: "AlacStreamRejected", -603: "AlacUnsupportedElement",
+             -701: "TelephonyStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -216,6 +217,40 @@ class AlacTickPacket(C.Structure):
 class AlacPacket(C.Structure):
     """sk_alac_packet"""
     _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32)]
+
+
+class G726State(C.Structure):
+    """sk_g726_state"""
+    _fields_ = [(n, C.c_int32) for n in ("yl", "yu", "dms", "dml", "ap")] + [("a", C.c_int32 * 2), ("b", C.c_int32 * 6), ("pk", C.c_int32 * 2),
+                                                                              ("dq", C.c_int32 * 6), ("sr", C.c_int32 * 2), ("td", C.c_int32)]
+
+
+class G722Band(C.Structure):
+    """sk_g722_band"""
+    _fields_ = [("s", C.c_int32), ("sz", C.c_int32), ("r", C.c_int32 * 2), ("p", C.c_int32 * 2), ("a", C.c_int32 * 2), ("b", C.c_int32 * 6),
+                ("d", C.c_int32 * 6), ("nb", C.c_int32), ("det", C.c_int32)]
+
+
+class G722State(C.Structure):
+    """sk_g722_state"""
+    _fields_ = [("band", G722Band * 2), ("x", C.c_int32 * 22)]
+
+
+class G72xStream(C.Structure):
+    """sk_g72x_stream"""
+    _fields_ = [("codec", C.c_uint8), ("g726_packing", C.c_uint8), ("reserved", C.c_uint8 * 2), ("g726_rate", C.c_uint32), ("n_units", C.c_uint32),
+                ("state", C.c_uint32)]
+
+
+class G72xUnit(C.Structure):
+    """sk_g72x_unit"""
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32), ("out_len", C.c_uint32), ("reserved", C.c_uint32), ("out_offset", C.c_uint64)]
+
+
+class G72xTickStream(C.Structure):
+    """sk_g72x_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("g726_rate", C.c_uint32), ("state", C.c_uint32)] + [
+        (n, C.c_uint8) for n in ("codec", "g726_packing", "channels", "out_bits", "out_channels", "resample", "flush", "reserved")]
 
 
 class FlacTickStream(C.Structure):
@@ -499,6 +534,28 @@ _sig = {
     "sk_alac_packet_decoder_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(_sz)]),
     "sk_alac_packet_decoder_decode_packet": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     "sk_alac_packet_decoder_last_error": (C.c_char_p, [_vp]),
+    "sk_g726_state_init": (None, [_vp]),
+    "sk_g722_state_init": (None, [_vp]),
+    "sk_g72x_decode": (_i, [_vp, _i, _u32, _i, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "sk_g72x_decode_dev": (_i, [_vp, _i, _u32, _i, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "sk_g72x_decode_batch": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _u32, _vp, _u32]),
+    "sk_g72x_decode_batch_dev": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _u32, _vp, _u32]),
+    "sk_tick_g72x_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_g72x": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz), _vp, _u32, _vp, _u32]),
+    "sk_pipeline_spawn_g711": (_i, [_vp, _i, _u32, _u32, _vp, C.POINTER(_u32), _vp, _sz]),
+    "sk_pipeline_spawn_g722": (_i, [_vp, _vp, C.POINTER(_u32)]),
+    "sk_pipeline_spawn_g726": (_i, [_vp, _u32, _i, _vp, C.POINTER(_u32)]),
+    "sk_g711_decoder_create": (_i, [_vp, _i, _u32, _u32, C.POINTER(_vp), _vp, _sz]),
+    "sk_g722_decoder_create": (_i, [_vp, C.POINTER(_vp)]),
+    "sk_g726_decoder_create": (_i, [_vp, _u32, _i, C.POINTER(_vp)]),
+    "sk_g72x_decoder_destroy": (None, [_vp]),
+    "sk_g72x_decoder_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32), C.POINTER(_u32)]),
+    "sk_g72x_decoder_decode_i16": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_g72x_decoder_decode_i32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_g72x_decoder_decode_f32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_g726_decoder_flush": (_i, [_vp]),
+    "sk_g72x_decoder_reset": (_i, [_vp]),
+    "sk_g72x_decoder_last_error": (C.c_char_p, [_vp]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

@@ -28,6 +28,7 @@
 
 #include "aac_entropy_tables.h"
 #include "alac_stream.h"
+#include "g72x_stream.h"
 #include "flac_stream.h"
 #include "mp12_internal.h"
 #include "pcm_stream.h"
@@ -265,6 +266,7 @@ struct sk_engine {
     DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
     DevBuf flac_in, flac_ws, flac_out;  // sk_flac_decode_frames: frames | tables | statuses, planar i32 workspace | subframe records, PCM
     DevBuf alac_in, alac_ws, alac_out;  // sk_alac_decode_packets: packets | tables | statuses, planar i32 workspace | channel records, PCM
+    DevBuf g72x_tab, g72x_ws;  // the telephony decode stage: stream / unit tables and state records, one word per G.722 byte
     DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
@@ -594,6 +596,7 @@ const char *sk_strerror(int status) try {
     case SK_ALAC_INVALID: return "invalid ALAC packet";
     case SK_ALAC_ERR_STREAM: return "ALAC stream rejected";
     case SK_ALAC_UNSUPPORTED: return "unsupported ALAC element";
+    case SK_G72X_ERR_STREAM: return "telephony stream rejected";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -682,6 +685,8 @@ void sk_engine_destroy(sk_engine *e) try {
         e->alac_in.release();
         e->alac_ws.release();
         e->alac_out.release();
+        e->g72x_tab.release();
+        e->g72x_ws.release();
         e->mp3e_in.release();
         e->tick_mpa_in.release();
         e->mp3e_out.release();
@@ -6495,6 +6500,564 @@ const char *sk_alac_packet_decoder_last_error(const sk_alac_packet_decoder *d) t
     return d ? d->error.c_str() : "";
 } catch (...) {
     (void)sk::abi_caught("sk_alac_packet_decoder_last_error");
+    return "";
+}
+
+}  // extern "C"
+
+// ---- Telephony: G.711, G.722, G.726 (g72x_stream.h, g72x_decode.hip) --------------------------------------------------------------
+
+struct sk_g72x_decoder {
+    sk_engine *eng = nullptr;
+    int codec = SK_G726;
+    uint32_t sample_rate = 8000, channels = 1, g726_rate = 32000;
+    int packing = SK_G726_LEFT;
+    sk_g726_state s726{};
+    sk_g722_state s722{};
+    sk_g72x::G726Framer framer;
+    std::vector<uint8_t> bytes;  // what a call decodes
+    std::vector<int16_t> pcm;    // decode_i32 / decode_f32: the s16 they follow from
+    std::string error;
+};
+
+namespace {
+
+static_assert(sizeof(sk_g726_state) == sk::kG726StateWords * 4 && sizeof(sk_g722_state) == sk::kG722StateWords * 4, "the states are the device records");
+
+size_t g72x_up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// What one launch sequence of the stage works on.  begin() a stream, then unit() for each of its units in order.  The state records go
+// in with the streams and come back into the same vectors; the batch must live until the stream has been waited for.
+struct G72xBatch {
+    std::vector<sk::G72xStream> s726, s722;
+    std::vector<sk::G72xUnit> units;
+    std::vector<sk::AiffElemJob> g711;
+    std::vector<int32_t> st726, st722;
+    uint32_t g711_max = 0, g722_max = 0;
+    uint64_t ws_words = 0;
+    int codec = 0;
+
+    void begin(int c, int bits, int packing, const void *state) {
+        codec = c;
+        if (c != SK_G722 && c != SK_G726) return;
+        sk::G72xStream s{};
+        s.first_unit = (uint32_t)units.size(), s.bits = (uint8_t)bits, s.packing = (uint8_t)packing;
+        const int32_t *w = (const int32_t *)state;
+        if (c == SK_G726) {
+            s.state = (uint32_t)s726.size();
+            s726.push_back(s);
+            st726.insert(st726.end(), w, w + sk::kG726StateWords);
+        } else {
+            s.state = (uint32_t)s722.size(), s.ws_offset = (uint32_t)ws_words;
+            s722.push_back(s);
+            st722.insert(st722.end(), w, w + sk::kG722StateWords);
+        }
+    }
+    void unit(const uint8_t *src, uint8_t *dst, uint32_t bytes) {
+        if (codec == SK_G711_ULAW || codec == SK_G711_ALAW) {
+            if (bytes == 0) return;
+            g711.push_back(sk::AiffElemJob{src, dst, bytes, (uint32_t)(codec == SK_G711_ULAW ? SK_AIFF_ULAW : SK_AIFF_ALAW)});
+            g711_max = std::max(g711_max, bytes);
+            return;
+        }
+        units.push_back(sk::G72xUnit{src, dst, bytes, 0});
+        sk::G72xStream &s = codec == SK_G726 ? s726.back() : s722.back();
+        s.n_units += 1;
+        if (codec == SK_G722) s.total_bytes += bytes, ws_words += bytes, g722_max = std::max(g722_max, s.total_bytes);
+    }
+    // the device form of the tables: streams | units | G.711 jobs | records in | records out
+    static size_t tables_bound(size_t n_streams, size_t n_units) {
+        return 2 * g72x_up16(n_streams * sizeof(sk::G72xStream)) + g72x_up16(n_units * sizeof(sk::G72xUnit)) + g72x_up16(n_units * sizeof(sk::AiffElemJob)) +
+               4 * g72x_up16(n_streams * sk::kG722StateWords * 4);
+    }
+};
+
+// uploads the tables to d_tab (tables_bound of the batch's counts), runs the launches with the workspace at d_ws (ws_words words) and
+// asks for the records back; everything on e->stream, nothing waited for
+int g72x_launch(sk_engine *e, G72xBatch &b, uint8_t *d_tab, uint32_t *d_ws) {
+    size_t at = 0;
+    const auto place = [&](size_t bytes) {
+        uint8_t *d = d_tab + at;
+        at += g72x_up16(bytes);
+        return d;
+    };
+    uint8_t *d_units = place(b.units.size() * sizeof(sk::G72xUnit));
+    if (!b.units.empty())
+        SK_HIP(hipMemcpyAsync(d_units, b.units.data(), b.units.size() * sizeof(sk::G72xUnit), hipMemcpyHostToDevice, e->stream), "H2D g72x units");
+    if (!b.g711.empty()) {
+        uint8_t *d_jobs = place(b.g711.size() * sizeof(sk::AiffElemJob));
+        SK_HIP(hipMemcpyAsync(d_jobs, b.g711.data(), b.g711.size() * sizeof(sk::AiffElemJob), hipMemcpyHostToDevice, e->stream), "H2D g711 jobs");
+        SK_HIP(sk::launch_aiff_elem((const sk::AiffElemJob *)d_jobs, (uint32_t)b.g711.size(), b.g711_max, e->stream), "launch g711 expand");
+    }
+    for (int pass = 0; pass < 2; ++pass) {
+        std::vector<sk::G72xStream> &streams = pass ? b.s722 : b.s726;
+        std::vector<int32_t> &records = pass ? b.st722 : b.st726;
+        if (streams.empty()) continue;
+        uint8_t *d_streams = place(streams.size() * sizeof(sk::G72xStream));
+        int32_t *d_in = (int32_t *)place(records.size() * 4), *d_out = (int32_t *)place(records.size() * 4);
+        SK_HIP(hipMemcpyAsync(d_streams, streams.data(), streams.size() * sizeof(sk::G72xStream), hipMemcpyHostToDevice, e->stream), "H2D g72x streams");
+        SK_HIP(hipMemcpyAsync(d_in, records.data(), records.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D g72x states");
+        if (pass)
+            SK_HIP(sk::launch_g722((const sk::G72xStream *)d_streams, (uint32_t)streams.size(), (const sk::G72xUnit *)d_units, d_in, d_out, d_ws, b.g722_max,
+                                   e->stream), "launch g722");
+        else
+            SK_HIP(sk::launch_g726((const sk::G72xStream *)d_streams, (uint32_t)streams.size(), (const sk::G72xUnit *)d_units, d_in, d_out, e->stream),
+                   "launch g726");
+        SK_HIP(hipMemcpyAsync(records.data(), d_out, records.size() * 4, hipMemcpyDeviceToHost, e->stream), "D2H g72x states");
+    }
+    return SK_OK;
+}
+
+void g72x_text(char *error, size_t cap, const std::string &text) {
+    if (!error || cap == 0) return;
+    const size_t n = std::min(cap - 1, text.size());
+    std::memcpy(error, text.data(), n);
+    error[n] = 0;
+}
+
+// the stream rows' checks shared by the batch and the tick; bits = 0 for the codecs without a rate
+bool g72x_row_ok(int codec, uint32_t g726_rate, int packing, int *bits) {
+    *bits = 0;
+    if (codec < 0 || codec >= sk_g72x::kCodecs) return false;
+    if (codec != SK_G726) return true;
+    *bits = sk_g72x::g726_bits(g726_rate);
+    return *bits != 0 && (packing == SK_G726_LEFT || packing == SK_G726_RIGHT);
+}
+
+// sk_g72x_decode_batch[_dev]
+int g72x_decode_batch(sk_engine *e, const sk_g72x_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *bytes,
+                      size_t bytes_len, bool on_device, uint8_t *out, size_t out_cap, size_t *out_len, sk_g726_state *s726, uint32_t n726, sk_g722_state *s722,
+                      uint32_t n722) {
+    if (!e || !out_len || (n_streams && !streams) || (n_units && !units) || (bytes_len && !bytes) || (n726 && !s726) || (n722 && !s722)) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (bytes_len > 0x7fffffffull) return SK_ERR_INVALID_ARG;
+    if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15)) return SK_ERR_INVALID_ARG;
+    // ---- the table, and where every unit's samples go ----
+    std::vector<uint8_t> named726(n726, 0), named722(n722, 0);
+    std::vector<int> bits_of(n_streams, 0);
+    std::vector<uint64_t> out_at(n_units, 0);
+    std::vector<uint32_t> out_bytes(n_units, 0);
+    uint64_t at = 0, cursor = 0, need = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_g72x_stream &s = streams[i];
+        if (!g72x_row_ok(s.codec, s.g726_rate, s.g726_packing, &bits_of[i])) return SK_ERR_INVALID_ARG;
+        if (s.codec == SK_G726 && (s.state >= n726 || named726[s.state]++)) return SK_ERR_INVALID_ARG;
+        if (s.codec == SK_G722 && (s.state >= n722 || named722[s.state]++)) return SK_ERR_INVALID_ARG;
+        if (at + s.n_units > n_units) return SK_ERR_INVALID_ARG;
+        const uint32_t group = sk_g72x::group_bytes(s.codec, bits_of[i]);
+        for (uint32_t u = 0; u < s.n_units; ++u) {
+            const sk_g72x_unit &un = units[at + u];
+            if (un.offset % 16 || un.size % group || un.offset > bytes_len || un.size > bytes_len - un.offset) return SK_ERR_INVALID_ARG;
+            const uint64_t samples = sk_g72x::samples_of(s.codec, bits_of[i], un.size);
+            if (samples > sk_g72x::kScratchSamples) return SK_ERR_INVALID_ARG;
+            out_at[at + u] = cursor, out_bytes[at + u] = (uint32_t)(samples * 2);
+            if (samples) need = cursor + samples * 2;
+            cursor += g72x_up16((size_t)samples * 2);
+        }
+        at += s.n_units;
+    }
+    if (at != n_units || need > out_cap || (need && !out)) return SK_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    const uint8_t *d_src = bytes;
+    uint8_t *d_dst = out;
+    if (!on_device) {
+        SK_HIP(e->in_buf.reserve(bytes_len + 64), "alloc staging");
+        SK_HIP(e->out_buf.reserve((size_t)cursor + 64), "alloc staging");
+        if (bytes_len) SK_HIP(hipMemcpyAsync(e->in_buf.p, bytes, bytes_len, hipMemcpyHostToDevice, e->stream), "H2D g72x bytes");
+        if (n_units > 1 && need) SK_HIP(hipMemsetAsync(e->out_buf.p, 0, (size_t)need, e->stream), "clear g72x staging");
+        d_src = (const uint8_t *)e->in_buf.p, d_dst = (uint8_t *)e->out_buf.p;
+    }
+    G72xBatch b;
+    at = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_g72x_stream &s = streams[i];
+        b.begin(s.codec, bits_of[i], s.g726_packing, s.codec == SK_G726 ? (const void *)&s726[s.state] : (s.codec == SK_G722 ? (const void *)&s722[s.state] : nullptr));
+        for (uint32_t u = 0; u < s.n_units; ++u) b.unit(d_src + units[at + u].offset, d_dst + out_at[at + u], units[at + u].size);
+        at += s.n_units;
+    }
+    SK_HIP(e->g72x_tab.reserve(G72xBatch::tables_bound(n_streams, n_units) + 64), "alloc g72x tables");
+    SK_HIP(e->g72x_ws.reserve((size_t)b.ws_words * 4 + 64), "alloc g72x workspace");
+    int rc = g72x_launch(e, b, (uint8_t *)e->g72x_tab.p, (uint32_t *)e->g72x_ws.p);
+    if (rc == SK_OK && !on_device && need) {
+        // one copy up to the end of the last unit's samples (a copy per unit costs 12 us each: 50 ms at 4096 units); the alignment
+        // gaps between the units were cleared with the staging buffer
+        const hipError_t err = hipMemcpyAsync(out, d_dst, (size_t)need, hipMemcpyDeviceToHost, e->stream);
+        if (err != hipSuccess) rc = e->hip_fail(err, "D2H g72x");
+    }
+    const hipError_t waited = hipStreamSynchronize(e->stream);  // the tables leave scope with the call
+    if (rc != SK_OK) return rc;
+    SK_HIP(waited, "g72x sync");
+    for (uint32_t i = 0, k6 = 0, k2 = 0; i < n_streams; ++i) {
+        if (streams[i].codec == SK_G726) std::memcpy(&s726[streams[i].state], &b.st726[(size_t)k6++ * sk::kG726StateWords], sizeof(sk_g726_state));
+        if (streams[i].codec == SK_G722) std::memcpy(&s722[streams[i].state], &b.st722[(size_t)k2++ * sk::kG722StateWords], sizeof(sk_g722_state));
+    }
+    for (uint32_t k = 0; k < n_units; ++k) units[k].out_offset = out_at[k], units[k].out_len = out_bytes[k];
+    *out_len = (size_t)need;
+    return SK_OK;
+}
+
+// sk_g72x_decode[_dev]: a table of one stream with one unit
+int g72x_decode_one(sk_engine *e, int codec, uint32_t rate, int packing, const uint8_t *bytes, size_t len, bool on_device, uint8_t *out, size_t out_cap,
+                    size_t *out_len, void *state, char *error, size_t error_cap) {
+    g72x_text(error, error_cap, "");
+    int bits = 0;
+    if (!e || !out_len || !g72x_row_ok(codec, rate, packing, &bits) || (len && !bytes) || ((codec == SK_G726 || codec == SK_G722) && !state)) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (len > 0x7fffffffull || len % sk_g72x::group_bytes(codec, bits)) return SK_ERR_INVALID_ARG;
+    std::string text;
+    if (!sk_g72x::fits_scratch(codec, sk_g72x::samples_of(codec, bits, len), &text)) {
+        g72x_text(error, error_cap, text);
+        return SK_G72X_ERR_STREAM;
+    }
+    sk_g72x_stream s{};
+    s.codec = (uint8_t)codec, s.g726_packing = (uint8_t)packing, s.g726_rate = rate, s.n_units = 1, s.state = 0;
+    sk_g72x_unit u{};
+    u.size = (uint32_t)len;
+    return g72x_decode_batch(e, &s, 1, &u, 1, bytes, len, on_device, out, out_cap, out_len, (sk_g726_state *)state, codec == SK_G726 ? 1 : 0,
+                             (sk_g722_state *)state, codec == SK_G722 ? 1 : 0);
+}
+
+// sk_tick_run_g72x / sk_tick_g72x_out_bound_on: checks the table and derives what the PCM tick's body works on, as aiff_tick_derive does --
+// per stream an s16le source, per unit where its decoded samples lie (16-byte aligned, unit after unit) -- and the decode that stands in
+// front of the body: one launch sequence of the stage over the units of each pass.
+struct G72xDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;  // the decoded layout
+    std::vector<uint32_t> first;     // per stream: its first unit
+    std::vector<int> bits;
+    AiffTick tick;
+    G72xBatch batch[2];              // streams that go on through the body, streams delivered as decoded: alive until the tick's last wait
+    std::vector<uint32_t> of[2][2];  // [pass][0: G.726, 1: G.722]: record of the batch -> index into the stream table
+    size_t part = 0;                 // of g72x_tab per pass
+    uint64_t ws_words = 0;
+};
+
+int g72x_tick_derive(const sk_g72x_tick_stream *gs, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, size_t bytes_len, bool records,
+                     uint32_t n726, uint32_t n722, G72xDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.assign(n_units, sk_pcm_unit{});
+    d.first.assign(n_streams, 0);
+    d.bits.assign(n_streams, 0);
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    // (the bound is asked for without the records: nothing is named then)
+    std::vector<uint8_t> named726(records ? n726 : 0, 0), named722(records ? n722 : 0, 0);
+    uint64_t at = 0, cursor = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_g72x_tick_stream &g = gs[i];
+        if (!g72x_row_ok(g.codec, g.g726_rate, g.g726_packing, &d.bits[i])) return SK_ERR_INVALID_ARG;
+        const bool g711 = g.codec == SK_G711_ULAW || g.codec == SK_G711_ALAW;
+        if (g.channels == 0 || (!g711 && g.channels != 1)) return SK_ERR_INVALID_ARG;
+        if (records && g.codec == SK_G726 && (g.state >= n726 || named726[g.state]++)) return SK_ERR_INVALID_ARG;
+        if (records && g.codec == SK_G722 && (g.state >= n722 || named722[g.state]++)) return SK_ERR_INVALID_ARG;
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = g.stream, t.n_units = g.n_units, t.channels = g.channels, t.out_bits = g.out_bits, t.out_channels = g.out_channels;
+        t.resample = g.resample, t.flush = g.flush, t.format = SK_FMT_S16LE;
+        d.tick.plain[i] = !g.resample && g.out_bits == 16 && g.out_channels == g.channels;
+        d.first[i] = (uint32_t)at;
+        if (at + g.n_units > n_units) return SK_ERR_INVALID_ARG;
+        const uint32_t group = sk_g72x::group_bytes(g.codec, d.bits[i]);
+        for (uint32_t u = 0; u < g.n_units; ++u) {
+            const sk_pcm_unit &un = units[at + u];
+            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len % group) return SK_ERR_INVALID_ARG;
+            if (un.byte_offset > bytes_len || un.byte_len > bytes_len - un.byte_offset) return SK_ERR_INVALID_ARG;
+            const uint64_t samples = sk_g72x::samples_of(g.codec, d.bits[i], un.byte_len);
+            if (samples > sk_g72x::kScratchSamples) return SK_ERR_INVALID_ARG;
+            d.units[at + u] = sk_pcm_unit{cursor, (uint32_t)(samples * 2), 0};
+            cursor += g72x_up16((size_t)samples * 2);
+            if (g.codec == SK_G722) d.ws_words += un.byte_len;
+        }
+        at += g.n_units;
+    }
+    if (cursor > 0x7fffffffull || (bytes_len > 0x7fffffffull && bytes_len != (size_t)-1)) return SK_ERR_INVALID_ARG;
+    d.tick.decoded_len = (size_t)cursor;
+    d.part = G72xBatch::tables_bound(n_streams, n_units) + 64;
+    return at == n_units ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// one pass of the decode in front of the body: the units of the streams whose `plain` is as_is, each to where dst_of puts it
+int g72x_tick_decode(sk_engine *e, const sk_g72x_tick_stream *gs, const sk_pcm_unit *units, const sk_g726_state *s726, const sk_g722_state *s722,
+                     G72xDerived &d, bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+    const int p = as_is ? 1 : 0;
+    G72xBatch &b = d.batch[p];
+    for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
+        if ((d.tick.plain[i] != 0) != as_is || d.ts[i].n_units == 0) continue;
+        const sk_g72x_tick_stream &g = gs[i];
+        b.begin(g.codec, d.bits[i], g.g726_packing, g.codec == SK_G726 ? (const void *)&s726[g.state] : (g.codec == SK_G722 ? (const void *)&s722[g.state] : nullptr));
+        if (g.codec == SK_G726) d.of[p][0].push_back(i);
+        if (g.codec == SK_G722) d.of[p][1].push_back(i);
+        for (uint32_t u = 0; u < g.n_units; ++u) b.unit(d_src + units[d.first[i] + u].byte_offset, dst_of(i, u), units[d.first[i] + u].byte_len);
+    }
+    if (b.units.empty() && b.g711.empty()) return SK_OK;
+    // both passes' tables have their own part of g72x_tab; the workspace is shared, the passes follow each other on the stream
+    SK_HIP(e->g72x_tab.reserve(2 * d.part), "alloc tick g72x tables");
+    SK_HIP(e->g72x_ws.reserve((size_t)d.ws_words * 4 + 64), "alloc tick g72x workspace");
+    return g72x_launch(e, b, (uint8_t *)e->g72x_tab.p + (size_t)p * d.part, (uint32_t *)e->g72x_ws.p);
+}
+
+int g72x_decoder_fail(sk_g72x_decoder *d, int rc, const std::string &text) {
+    d->error = text;
+    return rc;
+}
+
+// decode_i16 of the three Decoder objects: `written` samples into out (cap samples)
+int g72x_decoder_decode(sk_g72x_decoder *d, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written) {
+    if (!d || (len && !input) || !written || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    const int bits = d->codec == SK_G726 ? sk_g72x::g726_bits(d->g726_rate) : 0;
+    const size_t take = d->codec == SK_G726 ? d->framer.ready(len) : len;
+    const uint64_t samples = sk_g72x::samples_of(d->codec, bits, take);
+    if (samples > out_cap)
+        return g72x_decoder_fail(d, SK_ERR_CAPACITY, std::string("Output buffer too small for ") + sk_g72x::codec_name(d->codec) + " decode: need " +
+                                                         std::to_string(samples) + ", have " + std::to_string(out_cap));
+    if (samples > 0x3fffffffull) return SK_ERR_INVALID_ARG;
+    const uint8_t *src = input;
+    sk_g72x::G726Framer after = d->framer;  // the framer moves on only when the decode succeeds
+    if (d->codec == SK_G726) {
+        d->bytes.clear();
+        after.add(input, len, d->bytes);  // nothing completes a group: the bytes wait, nothing is decoded
+        src = d->bytes.data();
+    }
+    // a Decoder object is not the pipeline: its output is the caller's, so a call may exceed the pipeline's scratch -- in pieces of
+    // whole groups, the carry handed from piece to piece and kept only when all of them decoded
+    sk_g72x_stream s{};
+    s.codec = (uint8_t)d->codec, s.g726_packing = (uint8_t)d->packing, s.g726_rate = d->g726_rate, s.n_units = 1;
+    sk_g726_state st726 = d->s726;
+    sk_g722_state st722 = d->s722;
+    const size_t piece = sk_g72x::kScratchSamples / sk_g72x::group_samples(d->codec, bits) * sk_g72x::group_bytes(d->codec, bits);
+    size_t done = 0, got = 0;
+    while (done < take) {
+        const size_t n = std::min(piece, take - done);
+        sk_g72x_unit u{};
+        u.size = (uint32_t)n;
+        size_t out_len = 0;
+        const int rc = g72x_decode_batch(d->eng, &s, 1, &u, 1, src + done, n, false, (uint8_t *)(out + got), (out_cap - got) * 2, &out_len,
+                                         d->codec == SK_G726 ? &st726 : nullptr, d->codec == SK_G726 ? 1 : 0, d->codec == SK_G722 ? &st722 : nullptr,
+                                         d->codec == SK_G722 ? 1 : 0);
+        if (rc != SK_OK) return rc;
+        done += n, got += out_len / 2;
+    }
+    d->s726 = st726, d->s722 = st722, d->framer = after;
+    *written = got;
+    return SK_OK;
+}
+
+// decode_i32 / decode_f32: the s16 decode into the decoder's own buffer, then `widen` sample for sample
+template <typename T, typename F>
+int g72x_decoder_decode_as(sk_g72x_decoder *d, const uint8_t *input, size_t len, T *out, size_t out_cap, size_t *written, F widen) {
+    if (!d || !written || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    d->pcm.resize(out_cap);
+    const int rc = g72x_decoder_decode(d, input, len, d->pcm.data(), out_cap, written);
+    if (rc != SK_OK) return rc;
+    for (size_t i = 0; i < *written; ++i) out[i] = widen(d->pcm[i]);
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sk_g726_state_init(sk_g726_state *s) try {
+    sk::abi_enter();
+    if (s) sk_g72x::init_state(s);
+} catch (...) {
+    (void)sk::abi_caught("sk_g726_state_init");
+}
+
+void sk_g722_state_init(sk_g722_state *s) try {
+    sk::abi_enter();
+    if (s) sk_g72x::init_state(s);
+} catch (...) {
+    (void)sk::abi_caught("sk_g722_state_init");
+}
+
+int sk_g72x_decode(sk_engine *e, int codec, uint32_t g726_rate, int g726_packing, const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap,
+                   size_t *out_len, void *state, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    return g72x_decode_one(e, codec, g726_rate, g726_packing, bytes, len, false, out, out_cap, out_len, state, error, error_cap);
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decode");
+}
+
+int sk_g72x_decode_dev(sk_engine *e, int codec, uint32_t g726_rate, int g726_packing, const uint8_t *d_bytes, size_t len, uint8_t *d_out, size_t out_cap,
+                       size_t *out_len, void *state, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    return g72x_decode_one(e, codec, g726_rate, g726_packing, d_bytes, len, true, d_out, out_cap, out_len, state, error, error_cap);
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decode_dev");
+}
+
+int sk_g72x_decode_batch(sk_engine *e, const sk_g72x_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *bytes,
+                         size_t bytes_len, uint8_t *out, size_t out_cap, size_t *out_len, sk_g726_state *g726_states, uint32_t n_g726_states,
+                         sk_g722_state *g722_states, uint32_t n_g722_states) try {
+    sk::abi_enter();
+    return g72x_decode_batch(e, streams, n_streams, units, n_units, bytes, bytes_len, false, out, out_cap, out_len, g726_states, n_g726_states, g722_states,
+                             n_g722_states);
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decode_batch");
+}
+
+int sk_g72x_decode_batch_dev(sk_engine *e, const sk_g72x_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *d_bytes,
+                             size_t bytes_len, uint8_t *d_out, size_t out_cap, size_t *out_len, sk_g726_state *g726_states, uint32_t n_g726_states,
+                             sk_g722_state *g722_states, uint32_t n_g722_states) try {
+    sk::abi_enter();
+    return g72x_decode_batch(e, streams, n_streams, units, n_units, d_bytes, bytes_len, true, d_out, out_cap, out_len, g726_states, n_g726_states, g722_states,
+                             n_g722_states);
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decode_batch_dev");
+}
+
+size_t sk_tick_g72x_out_bound_on(sk_engine *e, const sk_g72x_tick_stream *gs, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                 uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!gs && n_streams) || (!units && n_units)) return 0;
+    G72xDerived d;
+    if (g72x_tick_derive(gs, n_streams, units, n_units, (size_t)-1, false, 0, 0, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), n_units, max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_g72x_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_g72x(sk_engine *e, const sk_g72x_tick_stream *gs, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                     size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
+                     sk_g726_state *g726_states, uint32_t n_g726_states, sk_g722_state *g722_states, uint32_t n_g722_states) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && !gs) || (n_units && (!units || !bytes)) || (n_g726_states && !g726_states) || (n_g722_states && !g722_states))
+        return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    G72xDerived d;
+    int rc = g72x_tick_derive(gs, n_streams, units, n_units, bytes_len, true, n_g726_states, n_g722_states, d);
+    if (rc != SK_OK) return rc;
+    d.tick.decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+        return g72x_tick_decode(e, gs, units, g726_states, g722_states, d, as_is, dst_of, d_src);
+    };
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, &d.tick);
+    if (rc != SK_OK) return rc;  // the carries are the caller's records: untouched
+    for (int p = 0; p < 2; ++p) {
+        for (size_t k = 0; k < d.of[p][0].size(); ++k)
+            std::memcpy(&g726_states[gs[d.of[p][0][k]].state], &d.batch[p].st726[k * sk::kG726StateWords], sizeof(sk_g726_state));
+        for (size_t k = 0; k < d.of[p][1].size(); ++k)
+            std::memcpy(&g722_states[gs[d.of[p][1][k]].state], &d.batch[p].st722[k * sk::kG722StateWords], sizeof(sk_g722_state));
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_g72x");
+}
+
+int sk_g711_decoder_create(sk_engine *e, int law, uint32_t sample_rate, uint32_t channels, sk_g72x_decoder **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if (!e || !out || (law != SK_G711_ULAW && law != SK_G711_ALAW)) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    g72x_text(error, error_cap, "");
+    std::string text;
+    if (!sk_g72x::check_g711(sample_rate, channels, &text)) {
+        g72x_text(error, error_cap, text);
+        return SK_G72X_ERR_STREAM;
+    }
+    std::unique_ptr<sk_g72x_decoder> d(new sk_g72x_decoder());
+    d->eng = e, d->codec = law, d->sample_rate = sample_rate, d->channels = channels;
+    *out = d.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_g711_decoder_create");
+}
+
+int sk_g722_decoder_create(sk_engine *e, sk_g72x_decoder **out) try {
+    sk::abi_enter();
+    if (!e || !out) return SK_ERR_INVALID_ARG;
+    std::unique_ptr<sk_g72x_decoder> d(new sk_g72x_decoder());
+    d->eng = e, d->codec = SK_G722, d->sample_rate = 16000, d->channels = 1;
+    *out = d.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_g722_decoder_create");
+}
+
+int sk_g726_decoder_create(sk_engine *e, uint32_t g726_rate, int g726_packing, sk_g72x_decoder **out) try {
+    sk::abi_enter();
+    int bits = 0;
+    if (!e || !out || !g72x_row_ok(SK_G726, g726_rate, g726_packing, &bits)) return SK_ERR_INVALID_ARG;
+    std::unique_ptr<sk_g72x_decoder> d(new sk_g72x_decoder());
+    d->eng = e, d->codec = SK_G726, d->sample_rate = 8000, d->channels = 1, d->g726_rate = g726_rate, d->packing = g726_packing;
+    d->framer = sk_g72x::G726Framer(bits);
+    sk_g726_state_init(&d->s726);
+    *out = d.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_g726_decoder_create");
+}
+
+void sk_g72x_decoder_destroy(sk_g72x_decoder *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_g72x_decoder_destroy");
+}
+
+int sk_g72x_decoder_info(const sk_g72x_decoder *d, int *codec, uint32_t *sample_rate, uint32_t *channels) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (codec) *codec = d->codec;
+    if (sample_rate) *sample_rate = d->sample_rate;
+    if (channels) *channels = d->channels;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decoder_info");
+}
+
+int sk_g72x_decoder_decode_i16(sk_g72x_decoder *d, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return g72x_decoder_decode(d, input, len, out, out_cap, written);
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decoder_decode_i16");
+}
+
+int sk_g72x_decoder_decode_i32(sk_g72x_decoder *d, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return g72x_decoder_decode_as(d, input, len, out, out_cap, written, [](int16_t v) { return (int32_t)((uint32_t)(int32_t)v << 16); });
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decoder_decode_i32");
+}
+
+int sk_g72x_decoder_decode_f32(sk_g72x_decoder *d, const uint8_t *input, size_t len, float *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return g72x_decoder_decode_as(d, input, len, out, out_cap, written, [](int16_t v) { return (float)v / 32768.0f; });
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decoder_decode_f32");
+}
+
+int sk_g726_decoder_flush(sk_g72x_decoder *d) try {
+    sk::abi_enter();
+    if (!d || d->codec != SK_G726) return SK_ERR_INVALID_ARG;
+    std::string text;
+    if (d->framer.flush(&text)) return SK_OK;
+    return g72x_decoder_fail(d, SK_G72X_ERR_STREAM, text);
+} catch (...) {
+    return sk::abi_caught("sk_g726_decoder_flush");
+}
+
+int sk_g72x_decoder_reset(sk_g72x_decoder *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    sk_g726_state_init(&d->s726);
+    sk_g722_state_init(&d->s722);
+    d->framer.pending.clear();
+    d->error.clear();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_g72x_decoder_reset");
+}
+
+const char *sk_g72x_decoder_last_error(const sk_g72x_decoder *d) try {
+    sk::abi_enter();
+    return d ? d->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_g72x_decoder_last_error");
     return "";
 }
 

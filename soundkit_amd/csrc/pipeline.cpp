@@ -18,6 +18,7 @@
 #include "sk_abi.h"
 #include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
 #include "alac_stream.h"
+#include "g72x_stream.h"
 #include "flac_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
@@ -96,6 +97,16 @@ struct PStream {
     // it in front of what the PCM tick would do.  alac_plain: nothing to change behind the decode (one AudioData per packet)
     bool alac = false, alac_plain = false;
     sk_alac_config alac_cfg{};
+    // headerless telephony streams (sk_pipeline_spawn_g711 / _g722 / _g726): the decoder's parameters come with the spawn; what a send
+    // decodes now is one unit of the telephony tick, which decodes it in front of what the PCM tick would do.  The G.726 framer holds a
+    // partial group back (worker thread); the codec's carry goes into every tick and comes back from it (submission thread)
+    bool g72x = false;
+    uint8_t g72x_codec = 0, g726_packing = 0;
+    uint32_t g72x_rate = 0, g726_rate = 0;  // g72x_rate: the AudioData's sample rate
+    uint8_t g72x_channels = 1;
+    sk_g72x::G726Framer g726_framer;
+    sk_g726_state g726_state{};
+    sk_g722_state g722_state{};
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -103,8 +114,8 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -178,6 +189,9 @@ struct Batch {
     std::vector<int32_t> flac_status;
     TickTable<sk_alac_tick_stream, sk_alac_tick_packet> alac_ts;  // ALAC streams' packets (sk_tick_run_alac)
     std::vector<int32_t> alac_status;
+    TickTable<sk_g72x_tick_stream, sk_pcm_unit> g72x_ts;  // telephony streams' units (sk_tick_run_g72x); row k's carry is record k of both arrays
+    std::vector<sk_g726_state> g726_states;
+    std::vector<sk_g722_state> g722_states;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -204,6 +218,7 @@ struct Batch {
         aiff_ts.clear();
         flac_ts.clear();
         alac_ts.clear();
+        g72x_ts.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -682,7 +697,9 @@ int ensure_pcm(sk_lane *p) {
 bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     uint32_t rate, channels, bits;
     bool is_float, big_endian = false;
-    if (s.alac) {  // the cookie's
+    if (s.g72x) {  // the spawn's: create_audio_data_i16(d.sample_rate(), d.channels(), ...), always 16 bits
+        rate = s.g72x_rate, channels = s.g72x_channels, bits = 16, is_float = false;
+    } else if (s.alac) {  // the cookie's
         rate = s.alac_cfg.sample_rate, channels = s.alac_cfg.channels, bits = s.alac_cfg.bit_depth, is_float = false;
     } else if (s.flac) {  // STREAMINFO's: the AudioData of a FLAC frame carries the stream's own depth (create_audio_data_i32_with_bits, lib.rs:3191-3236)
         rate = s.flac->info().sample_rate, channels = s.flac->info().channels, bits = s.flac->info().bits_per_sample, is_float = false;
@@ -714,6 +731,14 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
         s.pcm_route = kPcmFlacTick;
         s.flac_plain = true;
+        return true;
+    }
+    if (s.g72x && (!hooks.tick_g72x || !hooks.tick_g72x_out_bound))
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: telephony decoding needs the device tick, which this build lacks");
+    if (s.g72x && target_rate == rate && target_bits == bits && target_channels == channels) {  // every byte has per-sample work: the tick's
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmG72xTick;
         return true;
     }
     if (s.alac && (!hooks.tick_alac || !hooks.tick_alac_out_bound))
@@ -757,7 +782,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
+    s.pcm_route = s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
     return true;
 }
 
@@ -775,6 +800,72 @@ size_t stage_unit(Parsed &r, PStream &s, const uint8_t *data, size_t len, uint32
         outputs += 1;
     }
     return at;
+}
+
+// A telephony stream's pass (sk_pipeline_spawn_g711 / _g722 / _g726): decode_i16_with_drain's shape (lib.rs:2150-2181, 2310-2345) --
+// every non-empty send is one decode and gives one AudioData, or nothing where a G.726 send completes no group.  What a send decodes
+// now is one unit of the telephony tick.  A send above the reference's scratch ends the stream with the decoder's text; the end of
+// the stream is G726Decoder::flush (a partial group left: its text) or, for G.711 and G.722, an empty decode that gives nothing.
+void parse_some_g72x(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
+    const int bits = s.g72x_codec == SK_G726 ? sk_g72x::g726_bits(s.g726_rate) : 0;
+    uint32_t outputs = 0;
+    if (!s.pcm_route && !pcm_open(p, s, r)) return;
+    const bool plain = !s.resample && (s.opt.output_bits_per_sample ? s.opt.output_bits_per_sample : 16u) == 16u &&
+                       (s.opt.output_channels ? s.opt.output_channels : s.channels) == s.channels;
+    std::vector<uint8_t> whole;
+    while (!r.failed) {
+        if (s.saw_eof) {
+            std::string text;
+            if (s.g72x_codec == SK_G726 && !s.g726_framer.flush(&text)) r.fail(SK_G72X_ERR_STREAM, "Decoding failed: " + text);
+            else r.eof = true;
+            break;
+        }
+        std::vector<uint8_t> chunk;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            if (s.in.empty()) break;
+            const size_t next = s.in.front().size();
+            if (next && (outputs >= room || r.pcm_units.size() >= per_pass || (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes))) {
+                r.more = true;
+                break;
+            }
+            chunk = std::move(s.in.front());
+            s.in.pop_front();
+        }
+        if (chunk.empty()) {
+            s.saw_eof = true;
+            continue;
+        }
+        s.queued_bytes.fetch_sub(chunk.size());
+        const uint8_t *data = chunk.data();
+        size_t len = chunk.size();
+        std::string text;
+        if (s.g72x_codec == SK_G726) {
+            // the scratch is checked before anything is taken: the reference's decoder returns its error with the pending bytes as they were
+            if (!sk_g72x::fits_scratch(SK_G726, sk_g72x::samples_of(SK_G726, bits, s.g726_framer.ready(len)), &text)) {
+                r.fail(SK_G72X_ERR_STREAM, "Decoding failed: " + text);
+                break;
+            }
+            whole.clear();
+            len = s.g726_framer.add(data, len, whole);
+            data = whole.data();
+            if (len == 0) continue;  // no group completed: nothing is delivered for this send
+        } else if (!sk_g72x::fits_scratch(s.g72x_codec, sk_g72x::samples_of(s.g72x_codec, 0, len), &text)) {
+            r.fail(SK_G72X_ERR_STREAM, "Decoding failed: " + text);
+            break;
+        }
+        const uint64_t samples = sk_g72x::samples_of(s.g72x_codec, bits, len);
+        // G.711 of several channels: as decoded the samples leave as they came (create_audio_data_i16 checks nothing); a conversion
+        // refuses a send that splits a frame, with audio_data_to_f32_channels' text (lib.rs:3569-3574)
+        if (!plain && samples % s.channels != 0) {
+            r.fail(SK_PCM_ERR_STREAM, "Decoding failed: Output conversion failed: PCM data is unsupported or contains a partial frame");
+            break;
+        }
+        stage_unit(r, s, data, len, (uint32_t)(samples / s.channels), outputs);
+    }
+    r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
 
 // An ALAC stream's pass: every chunk is one packet (sk_pipeline_spawn_alac_packets), and whole packets are what the stream is budgeted in
@@ -1034,6 +1125,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
     }
     if (s.codec == kCodecAlac) {
         parse_some_alac(p, s, room, r);
+        return;
+    }
+    if (s.codec == kCodecG72x) {
+        parse_some_g72x(p, s, room, r);
         return;
     }
     if (s.codec == kCodecWav || s.codec == kCodecRawPcm || s.codec == kCodecAiff) {
@@ -1364,6 +1459,9 @@ void worker_body(sk_lane *p) {
                         const sk_alac_config &c = s.alac_cfg;
                         row->frame_length = c.frame_length, row->bit_depth = c.bit_depth, row->pb = c.pb, row->mb = c.mb, row->kb = c.kb;
                     }
+                } else if (s.pcm_route == kPcmG72xTick) {
+                    if (sk_g72x_tick_stream *row = claim_tick_row(b, b->g72x_ts, s, r, r.pcm_units, be, pcm_at))
+                        row->codec = s.g72x_codec, row->g726_rate = s.g726_rate, row->g726_packing = s.g726_packing;
                 } else if (s.pcm_route == kPcmTick) {
                     if (sk_pcm_tick_stream *row = claim_tick_row(b, b->pcm_ts, s, r, r.pcm_units, be, pcm_at)) row->format = s.pcm_fmt;
                 }
@@ -1525,11 +1623,13 @@ void submit_body(sk_lane *p) {
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
-        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty()) {
+        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty() ||
+            !b->g72x_ts.rows.empty()) {
             // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, the ALAC tick's, then the PCM tick's: one buffer
             const size_t bound = (ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out)) +
                                  follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
                                  follow_on_bound(p, b->alac_ts, hooks.tick_alac_out_bound) +
+                                 follow_on_bound(p, b->g72x_ts, hooks.tick_g72x_out_bound) +
                                  follow_on_bound(p, b->pcm_ts, hooks.tick_pcm_out_bound);
             if (bound > b->out_pinned_cap) {
                 // Pinned memory is slow to get (10 ms per 64 MB on an idle device, many times that beside a running lane): the
@@ -1549,7 +1649,7 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->pcm_ts.max_out;
+            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->pcm_ts.max_out;
             if (b->recs.size() < n_recs) b->recs.resize(n_recs);
         }
         const bool with_md = b->n_mp3 && p->mp3_gpu;  // the MP3 streams' Huffman stage is the tick's as well
@@ -1609,6 +1709,24 @@ void submit_body(sk_lane *p) {
                                    (uint32_t)b->alac_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used,
                                    b->alac_status.data());
         });
+        follow_on_tick(b, b->g72x_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            // the codec's carry of each stream as the ticks before this one left it (this thread alone reads and writes it): row k names record k
+            const uint32_t rows = (uint32_t)b->g72x_ts.rows.size();
+            b->g726_states.resize(rows);
+            b->g722_states.resize(rows);
+            for (uint32_t row = 0; row < rows; ++row) {
+                const PStream &s = *p->streams[b->entries[b->g72x_ts.entry[row]].handle];
+                b->g72x_ts.rows[row].state = row;
+                b->g726_states[row] = s.g726_state, b->g722_states[row] = s.g722_state;
+            }
+            return hooks.tick_g72x(p->engine, b->g72x_ts.rows.data(), rows, b->g72x_ts.units.data(), (uint32_t)b->g72x_ts.units.size(), b->pcm_bytes, b->pcm_used,
+                                   out, out_cap, recs, recs_cap, n_out, out_used, b->g726_states.data(), rows, b->g722_states.data(), rows);
+        });
+        for (uint32_t row = 0; b->rc == SK_OK && row < b->g72x_ts.rows.size(); ++row) {  // ... and as this one leaves it
+            PStream &s = *p->streams[b->entries[b->g72x_ts.entry[row]].handle];
+            if (s.g72x_codec == SK_G726) s.g726_state = b->g726_states[row];
+            if (s.g72x_codec == SK_G722) s.g722_state = b->g722_states[row];
+        }
         follow_on_tick(b, b->pcm_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
             return hooks.tick_pcm(p->engine, b->pcm_ts.rows.data(), (uint32_t)b->pcm_ts.rows.size(), b->pcm_ts.units.data(),
                                   (uint32_t)b->pcm_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used);
@@ -1617,7 +1735,7 @@ void submit_body(sk_lane *p) {
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
         p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_ts.units.size() +
-                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size());
+                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -2112,8 +2230,14 @@ void lane_destroy(sk_lane *p) {
     delete p;
 }
 
+struct G72xSpawn {  // sk_pipeline_spawn_g711 / _g722 / _g726
+    int codec;
+    uint32_t sample_rate, channels, g726_rate;
+    int g726_packing;
+};
+
 int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
-               const sk_alac_config *alac = nullptr) {
+               const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr) {
     if (!p || !handle) return SK_ERR_INVALID_ARG;
     // RawPcmFormat::validate (raw_pcm.rs:117-125), and the sample formats there are
     if (raw && (raw->sample_rate == 0 || raw->channels == 0 || raw->format > SK_FMT_F32BE)) return SK_ERR_INVALID_ARG;
@@ -2161,6 +2285,11 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
+    s.g72x = false;
+    s.g72x_codec = 0, s.g726_packing = 0, s.g72x_rate = 0, s.g726_rate = 0, s.g72x_channels = 1;
+    s.g726_framer = sk_g72x::G726Framer();
+    sk_g72x::init_state(&s.g726_state);
+    sk_g72x::init_state(&s.g722_state);
     s.pcm_detected = false;
     s.pcm_route = 0, s.pcm_fmt = 0, s.pcm_flags = 0, s.pcm_bits = 0;
     s.pcm_fill = 0;
@@ -2179,6 +2308,14 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
         s.codec = kCodecAlac;
         s.alac = true;
         s.alac_cfg = *alac;
+        s.pcm_detected = true;
+    }
+    if (g72x) {  // spawn_g711 / spawn_g722 / spawn_g726*: the decoder is there from the start, nothing is detected or gathered
+        s.codec = kCodecG72x;
+        s.g72x = true;
+        s.g72x_codec = (uint8_t)g72x->codec, s.g72x_rate = g72x->sample_rate, s.g72x_channels = (uint8_t)g72x->channels;
+        s.g726_rate = g72x->g726_rate, s.g726_packing = (uint8_t)g72x->g726_packing;
+        s.g726_framer = sk_g72x::G726Framer(sk_g72x::g726_bits(g72x->g726_rate));
         s.pcm_detected = true;
     }
     *handle = h;
@@ -2326,7 +2463,7 @@ inline sk_lane *lane_of(sk_pipeline *p, uint32_t handle, uint32_t *inner) {
 }
 
 int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
-                   const sk_alac_config *alac = nullptr) {
+                   const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr) {
     if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
     const uint32_t n = (uint32_t)p->lanes.size();
     const uint32_t first = p->next_lane.fetch_add(1) % n;
@@ -2334,7 +2471,7 @@ int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pc
     for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
         const uint32_t li = (first + k) % n;
         uint32_t inner = 0;
-        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac);
+        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac, g72x);
         if (rc == SK_OK) {
             *handle = inner * n + li;
             return SK_OK;
@@ -2474,6 +2611,44 @@ int sk_pipeline_spawn_alac_packets(sk_pipeline *p, const uint8_t *cookie, size_t
     return pipeline_spawn(p, opt, nullptr, handle, false, &cfg);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn_alac_packets");
+}
+
+int sk_pipeline_spawn_g711(sk_pipeline *p, int law, uint32_t sample_rate, uint32_t channels, const sk_decode_options *opt, uint32_t *handle, char *error,
+                           size_t error_cap) try {
+    sk::abi_enter();
+    if (error && error_cap) error[0] = 0;
+    if (law != SK_G711_ULAW && law != SK_G711_ALAW) return SK_ERR_INVALID_ARG;
+    std::string text;
+    if (!sk_g72x::check_g711(sample_rate, channels, &text)) {  // DecodeError::InvalidInputFormat
+        if (error && error_cap) {
+            const size_t n = std::min(error_cap - 1, text.size());
+            std::memcpy(error, text.data(), n);
+            error[n] = 0;
+        }
+        return SK_G72X_ERR_STREAM;
+    }
+    if (channels > 255) return SK_ERR_INVALID_ARG;  // the reference's channel count is a u8
+    const G72xSpawn g{law, sample_rate, channels, 0, 0};
+    return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, &g);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_g711");
+}
+
+int sk_pipeline_spawn_g722(sk_pipeline *p, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    const G72xSpawn g{SK_G722, 16000, 1, 0, 0};
+    return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, &g);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_g722");
+}
+
+int sk_pipeline_spawn_g726(sk_pipeline *p, uint32_t g726_rate, int g726_packing, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    if (!sk_g72x::g726_bits(g726_rate) || (g726_packing != SK_G726_LEFT && g726_packing != SK_G726_RIGHT)) return SK_ERR_INVALID_ARG;
+    const G72xSpawn g{SK_G726, 8000, 1, g726_rate, g726_packing};
+    return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, &g);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_g726");
 }
 
 int sk_pipeline_send(sk_pipeline *p, uint32_t handle, const uint8_t *data, size_t len) try {

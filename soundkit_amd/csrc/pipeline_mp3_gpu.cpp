@@ -18,6 +18,8 @@ const bool g_hooked = [] {
     hooks.tick_flac_out_bound = sk_tick_flac_out_bound_on;
     hooks.tick_alac = sk_tick_run_alac;  // ... and the ALAC streams'
     hooks.tick_alac_out_bound = sk_tick_alac_out_bound_on;
+    hooks.tick_g72x = sk_tick_run_g72x;  // ... and the telephony streams'
+    hooks.tick_g72x_out_bound = sk_tick_g72x_out_bound_on;
     hooks.mpa_find_layer = sk_mp12::find_layer;  // Layer I / II streams: their host front and their tick
     hooks.mpa_scan = sk_mpa_scan;
     hooks.mpa_parse_frame = sk_mpa_parse_frame;

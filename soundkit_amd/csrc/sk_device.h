@@ -635,4 +635,29 @@ hipError_t launch_alac_predict(const AlacPacket *packets, const uint32_t *lanes,
 hipError_t launch_alac_output(const AlacParams *cfgs, const AlacPacket *packets, uint32_t n_packets, const AlacChannel *recs, const int32_t *ws,
                               const int32_t *status, const uint8_t *bytes, uint8_t *out, hipStream_t s);
 
+// g72x_decode.hip -- headerless G.726 and G.722 bytes to s16le, one stream per lane, the state carried in the caller's records.
+// (G.711 is launch_aiff_elem with the mu-law / A-law encodings: the expansions live in aiff_decode.hip.)
+constexpr uint32_t kG726StateWords = 24;  // sk_g726_state
+constexpr uint32_t kG722StateWords = 66;  // sk_g722_state
+struct G72xUnit {
+    const uint8_t *src;  // 16-byte aligned; read in whole dwords up to the one that holds the last byte
+    uint8_t *dst;        // 16-byte aligned
+    uint32_t bytes;      // G.726: whole groups
+    uint32_t pad;
+};
+struct G72xStream {
+    uint32_t first_unit, n_units;  // into the unit table; a stream's units are decoded in order
+    uint32_t state;                // its record in states_in / states_out
+    uint32_t ws_offset;            // G.722: its first word of the workspace (one word per byte)
+    uint32_t total_bytes;          // G.722: of all its units
+    uint8_t bits;                  // G.726: 2 ... 5 bits a code
+    uint8_t packing;               // G.726: 0 left (MSB first), 1 right (LSB first)
+    uint8_t pad[2];
+};
+// states_in and states_out are different arrays of kG726StateWords / kG722StateWords words per record; a record belongs to one stream
+hipError_t launch_g726(const G72xStream *streams, uint32_t n_streams, const G72xUnit *units, const int32_t *states_in, int32_t *states_out, hipStream_t s);
+// k_g722_adpcm, then k_g722_qmf over (max_bytes pairs, streams); ws holds one word per byte of the call
+hipError_t launch_g722(const G72xStream *streams, uint32_t n_streams, const G72xUnit *units, const int32_t *states_in, int32_t *states_out, uint32_t *ws,
+                       uint32_t max_bytes, hipStream_t s);
+
 }  // namespace sk

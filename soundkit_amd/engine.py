@@ -611,6 +611,115 @@ class Engine:
         return ([(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
                  for r in recs[:n_out.value]], status[:n].tolist())
 
+    def g72x_decode(self, codec, data, state=None, rate=32000, packing=0):
+        """sk_g72x_decode: one telephony stream's bytes (telephony.ULAW / ALAW / G722 / G726; G.726 in whole groups) -> s16le bytes.
+        state: a telephony.new_state(codec) record carried from call to call and updated in place (None: a fresh stream)."""
+        import ctypes as C
+        from . import telephony
+        data = np.frombuffer(bytes(data), np.uint8)
+        st = state if state is not None else telephony.new_state(codec)
+        out = np.zeros(max(telephony.decoded_samples(codec, data.size, rate) * 2, 16), np.uint8)
+        n = C.c_size_t()
+        text = C.create_string_buffer(256)
+        rc = lib.sk_g72x_decode(self._h, int(codec), int(rate), int(packing), _ptr(data) if data.size else None, data.size, _ptr(out), out.size, C.byref(n),
+                                C.byref(st) if st is not None else None, text, 256)
+        if rc == telephony.ERR_STREAM:
+            raise telephony.TelephonyError(text.value.decode())
+        check(rc, "sk_g72x_decode", self._h)
+        return out[:n.value].tobytes()
+
+    def g72x_decode_batch(self, streams, units):
+        """sk_g72x_decode_batch.  streams: list of dicts {codec, n_units, and for G.726: rate, packing; for G.722 / G.726: state (a
+        telephony.new_state record, updated in place)}; units: the pieces (bytes) of all streams, stream by stream, each packed at a
+        16-byte aligned offset.  -> [s16le bytes per unit]."""
+        import ctypes as C
+        from . import telephony
+        from ._lib import G722State, G726State, G72xStream, G72xUnit
+        ts = (G72xStream * max(len(streams), 1))()
+        of726, of722 = [], []
+        for i, s in enumerate(streams):
+            ts[i].codec, ts[i].n_units = int(s["codec"]), int(s["n_units"])
+            ts[i].g726_rate, ts[i].g726_packing = int(s.get("rate", 32000)), int(s.get("packing", 0))
+            if ts[i].codec == telephony.G726:
+                ts[i].state = len(of726)
+                of726.append(s)
+            elif ts[i].codec == telephony.G722:
+                ts[i].state = len(of722)
+                of722.append(s)
+        s726, s722 = (G726State * max(len(of726), 1))(), (G722State * max(len(of722), 1))()
+        for k, s in enumerate(of726):
+            s726[k] = s["state"]
+        for k, s in enumerate(of722):
+            s722[k] = s["state"]
+        n = len(units)
+        table = (G72xUnit * max(n, 1))()
+        total, need = 0, 0
+        for k, u in enumerate(units):
+            table[k].offset, table[k].size = total, len(u)
+            total += (len(u) + 15) & ~15
+            need += (len(u) * 16 + 15) & ~15  # no codec gives more than 8 samples a byte
+        blob = np.zeros(max(total, 16), np.uint8)
+        for k, u in enumerate(units):
+            blob[table[k].offset:table[k].offset + len(u)] = np.frombuffer(bytes(u), np.uint8)
+        out = np.zeros(max(need, 16), np.uint8)
+        used = C.c_size_t()
+        check(lib.sk_g72x_decode_batch(self._h, ts, len(streams), table, n, _ptr(blob), total, _ptr(out), out.size, C.byref(used), s726, len(of726),
+                                       s722, len(of722)), "sk_g72x_decode_batch", self._h)
+        for k, s in enumerate(of726):
+            C.memmove(C.byref(s["state"]), C.byref(s726[k]), C.sizeof(G726State))
+        for k, s in enumerate(of722):
+            C.memmove(C.byref(s["state"]), C.byref(s722[k]), C.sizeof(G722State))
+        return [out[table[k].out_offset:table[k].out_offset + table[k].out_len].tobytes() for k in range(n)]
+
+    def tick_run_g72x(self, streams, units):
+        """One tick of telephony streams (sk_tick_run_g72x).  As tick_run_pcm, with `codec` (telephony.ULAW / ALAW / G722 / G726) in
+        the place of `format`, `rate` and `packing` for G.726, `channels` for G.711 (1 when absent) and "state": a telephony.new_state
+        record for G.722 / G.726, which is updated in place.  -> the same list of records."""
+        import ctypes as C
+        from . import telephony
+        from ._lib import G722State, G726State, G72xTickStream, PcmUnit, TickOutput
+        ts = (G72xTickStream * max(len(streams), 1))()
+        of726, of722 = [], []
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            ts[i].codec, ts[i].channels = int(s["codec"]), int(s.get("channels", 1))
+            ts[i].g726_rate, ts[i].g726_packing = int(s.get("rate", 32000)), int(s.get("packing", 0))
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+            if ts[i].codec == telephony.G726:
+                ts[i].state = len(of726)
+                of726.append(s)
+            elif ts[i].codec == telephony.G722:
+                ts[i].state = len(of722)
+                of722.append(s)
+        s726, s722 = (G726State * max(len(of726), 1))(), (G722State * max(len(of722), 1))()
+        for k, s in enumerate(of726):
+            s726[k] = s["state"]
+        for k, s in enumerate(of722):
+            s722[k] = s["state"]
+        n = len(units)
+        table = (PcmUnit * max(n, 1))()
+        total = 0
+        for k, u in enumerate(units):
+            table[k].byte_offset, table[k].byte_len = total, len(u)
+            total += (len(u) + 15) & ~15
+        blob = np.zeros(max(total, 16), np.uint8)
+        for k, u in enumerate(units):
+            blob[table[k].byte_offset:table[k].byte_offset + len(u)] = np.frombuffer(bytes(u), np.uint8)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_g72x_out_bound_on(self._h, ts, len(streams), table, n, C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_g72x(self._h, ts, len(streams), table, n, _ptr(blob), total, _ptr(out), out.size, recs, max_out.value,
+                                   C.byref(n_out), C.byref(used), s726, len(of726), s722, len(of722)), "sk_tick_run_g72x", self._h)
+        for k, s in enumerate(of726):
+            C.memmove(C.byref(s["state"]), C.byref(s726[k]), C.sizeof(G726State))
+        for k, s in enumerate(of722):
+            C.memmove(C.byref(s["state"]), C.byref(s722[k]), C.sizeof(G722State))
+        return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                for r in recs[:n_out.value]]
+
     def tick_run_aiff(self, streams, units):
         """One tick of AIFF streams (sk_tick_run_aiff).  As tick_run_pcm, with `encoding` (AIFF_*) in the place of `format` and, for
         IMA4, "ima_state": [(predictor, step_index)] * 2, which is updated in the dict.  -> the same list of records."""

@@ -130,6 +130,44 @@ class BatchScheduler:
             raise SoundkitError(rc, "sk_pipeline_spawn_alac_packets")
         return DecodePipelineHandle(self, handle.value)
 
+    def spawn_g711(self, law, sample_rate, channels, options=None):
+        """a headerless G.711 stream (sk_pipeline_spawn_g711): law = telephony.ULAW / ALAW; every non-empty `send` gives one AudioData"""
+        from . import telephony
+        if law not in (telephony.ULAW, telephony.ALAW):
+            raise ValueError("law must be telephony.ULAW or telephony.ALAW, not %r" % (law,))
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        handle, text = C.c_uint32(), C.create_string_buffer(128)
+        rc = lib.sk_pipeline_spawn_g711(self._h, int(law), int(sample_rate), int(channels), C.byref(o), C.byref(handle), text, 128)
+        if rc == telephony.ERR_STREAM:
+            raise telephony.TelephonyError(text.value.decode())
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_g711")
+        return DecodePipelineHandle(self, handle.value)
+
+    def spawn_g722(self, options=None):
+        """a headerless G.722 stream at 64 kbit/s, 16 kHz mono (sk_pipeline_spawn_g722)"""
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_g722(self._h, C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_g722")
+        return DecodePipelineHandle(self, handle.value)
+
+    def spawn_g726(self, rate=32000, packing=0, options=None):
+        """a headerless G.726 stream, 8 kHz mono (sk_pipeline_spawn_g726): rate 16000 / 24000 / 32000 / 40000, packing telephony.LEFT /
+        RIGHT; a `send` that completes no group gives nothing, a partial group at the end is the stream's error"""
+        from . import telephony
+        telephony._check_codec(telephony.G726, rate, packing)
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_g726(self._h, int(rate), int(packing), C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_g726")
+        return DecodePipelineHandle(self, handle.value)
+
     def wait_outputs(self, timeout_ms=100, cap=256):
         """Handles (as spawned: `handle.id`) that have outputs or have ended; blocks up to timeout_ms.  For callers that
         serve many streams from one thread."""
@@ -264,6 +302,18 @@ class DecodePipeline:
     @staticmethod
     def spawn_alac_packets(magic_cookie, options=None):
         return default_scheduler().spawn_alac_packets(magic_cookie, options)
+
+    @staticmethod
+    def spawn_g711(law, sample_rate, channels, options=None):
+        return default_scheduler().spawn_g711(law, sample_rate, channels, options)
+
+    @staticmethod
+    def spawn_g722(options=None):
+        return default_scheduler().spawn_g722(options)
+
+    @staticmethod
+    def spawn_g726(rate=32000, packing=0, options=None):
+        return default_scheduler().spawn_g726(rate, packing, options)
 
     @staticmethod
     def spawn_raw_pcm(format):
