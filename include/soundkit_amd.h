@@ -1368,7 +1368,8 @@ const char *sk_alac_packet_decoder_last_error(const sk_alac_packet_decoder *);
  * give.  G.711: mu-law or A-law, one byte a sample, any rate and channel count (the samples interleaved as they arrive).  G.722: the
  * 64 kbit/s mode, mono 16 kHz, two samples a byte.  G.726: 16 / 24 / 32 / 40 kbit/s, mono 8 kHz, codes packed left (MSB first, `ffmpeg
  * -f g726`) or right (LSB first, `-f g726le`) in groups of 1 / 3 / 1 / 5 bytes that give 4 / 8 / 2 / 8 samples.  Not built: G.722 at
- * 56 / 48 kbit/s or with packed codes, GSM, AMR-NB, G.729 and Speex (the reference reaches them through foreign codecs), the encoders. */
+ * 56 / 48 kbit/s or with packed codes, AMR-NB, G.729 and Speex (the reference reaches them through foreign codecs), the encoders.  GSM 06.10
+ * full rate has its own block below (sk_gsm_*). */
 enum sk_g72x_codec { SK_G711_ULAW = 0, SK_G711_ALAW = 1, SK_G722 = 2, SK_G726 = 3 };
 enum sk_g726_packing { SK_G726_LEFT = 0, SK_G726_RIGHT = 1 };
 enum sk_g72x_status {
@@ -1500,6 +1501,107 @@ int sk_g72x_decoder_decode_f32(sk_g72x_decoder *, const uint8_t *input, size_t l
 int sk_g726_decoder_flush(sk_g72x_decoder *);
 int sk_g72x_decoder_reset(sk_g72x_decoder *);
 const char *sk_g72x_decoder_last_error(const sk_g72x_decoder *);
+
+/* ---- Telephony: GSM 06.10 full-rate streams (GPU, csrc/gsm_decode.hip; host arithmetic in csrc/gsm_stream.h) --------------------- */
+/* The streams of DecodePipeline::spawn_gsm (soundkit-decoder/src/lib.rs:2358) and the reference's GsmDecoder (soundkit-gsm): 13 kbit/s
+ * RPE-LTP, 8 kHz mono, decoded to s16le bit for bit what libgsm's gsm_decode gives.  SK_GSM_STANDARD: packets of 33 bytes (a 0xD nibble,
+ * then 260 parameter bits) that give 160 samples.  SK_GSM_MICROSOFT: packets of 65 bytes that give 320 -- the reference's framing, two
+ * runs of 260 bits MSB first (unpack_ms_pair), which is NOT libgsm's LSB-first WAV-49 layout.  A standard frame whose first nibble is
+ * not 0xD is refused with `GSM decoder rejected frame`; Microsoft packets carry no magic.  Shares SK_G72X_ERR_STREAM,
+ * SK_G72X_MAX_SEND_SAMPLES and sk_g72x_unit with the block above.  Not built: the encoder, libgsm's WAV-49 layout, AMR-NB, G.729, Speex. */
+enum sk_gsm_variant { SK_GSM_STANDARD = 0, SK_GSM_MICROSOFT = 1 };
+/* The carry of a GSM stream from call to call, 138 words of plain data in the caller's memory: the long-term history (the last 120
+ * reconstructed short-term residual samples, oldest first), the synthesis lattice's memory, the de-emphasis memory, the last valid lag
+ * and the previous frame's decoded log-area ratios.  A new stream starts from sk_gsm_state_init: all zeros, except nrp = 40. */
+typedef struct sk_gsm_state {
+    int32_t dp[120];
+    int32_t v[8];
+    int32_t msr;
+    int32_t nrp;
+    int32_t larpp[8];
+} sk_gsm_state;
+void sk_gsm_state_init(sk_gsm_state *);
+
+/* One stream's whole packets, one call.  A len that is no multiple of the packet size is SK_ERR_INVALID_ARG (sk_gsm_decoder_* holds the
+ * partial packet back).  out receives packets x samples x 2 bytes of s16le; an out_cap below that is SK_ERR_INVALID_ARG and nothing is
+ * written.  A call that decodes to more than SK_G72X_MAX_SEND_SAMPLES samples (checked first), or a standard frame without the magic
+ * nibble (every frame is checked before anything is launched), is SK_G72X_ERR_STREAM with the reference's text in `error`
+ * (NUL-terminated, cut to error_cap; may be NULL): `Output buffer too small for GSM decode: need N, have 262144`, `GSM decoder rejected
+ * frame`.  The state is read on entry and written on success; any failure leaves it as it was and decodes nothing (the reference's
+ * object has by then advanced through the frames before a rejected one; its stream ends either way).  The _dev form takes 16-byte
+ * aligned device pointers (the input is read in whole dwords up to the one that holds its last byte) and runs on the engine's stream;
+ * it cannot see the bytes, so the magic check is the caller's. */
+int sk_gsm_decode(sk_engine *, int variant, const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap, size_t *out_len, sk_gsm_state *state,
+                  char *error, size_t error_cap);
+int sk_gsm_decode_dev(sk_engine *, int variant, const uint8_t *d_bytes, size_t len, uint8_t *d_out, size_t out_cap, size_t *out_len,
+                      sk_gsm_state *state, char *error, size_t error_cap);
+
+/* Many streams, one launch sequence (k_gsm_excite, then k_gsm_synth, over all streams).  The units are listed stream by stream in the
+ * order of `streams`; units[k] lies at bytes + units[k].offset, a multiple of 16, and a stream's units are decoded in order, the state
+ * carried from one into the next.  A unit may be empty; otherwise it holds whole packets and decodes to at most
+ * SK_G72X_MAX_SEND_SAMPLES samples.  Every unit's s16le is written at the next multiple of 16 bytes of `out`, in table order, and the
+ * call sets units[k].out_offset and .out_len.  streams[i].state names the stream's record in `states`; a record may be named by one
+ * stream only.  Anything that does not add up, or an out_cap too small: SK_ERR_INVALID_ARG; a standard frame without the magic nibble
+ * (host form; every frame is checked before anything is launched): SK_G72X_ERR_STREAM.  Either way nothing is decoded.  The states are
+ * written on success only. */
+typedef struct sk_gsm_stream {
+    uint32_t variant; /* enum sk_gsm_variant */
+    uint32_t n_units;
+    uint32_t state;
+} sk_gsm_stream;
+int sk_gsm_decode_batch(sk_engine *, const sk_gsm_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *bytes,
+                        size_t bytes_len, uint8_t *out, size_t out_cap, size_t *out_len, sk_gsm_state *states, uint32_t n_states);
+int sk_gsm_decode_batch_dev(sk_engine *, const sk_gsm_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units,
+                            const uint8_t *d_bytes, size_t bytes_len, uint8_t *d_out, size_t out_cap, size_t *out_len, sk_gsm_state *states,
+                            uint32_t n_states);
+
+/* The tick of the GSM streams, sk_tick_run_g72x's contract: every unit (= what one send decodes now, packed at a 16-byte aligned
+ * offset; never empty, whole packets, standard frames with their magic nibble, at most SK_G72X_MAX_SEND_SAMPLES samples) is first
+ * decoded to s16le on the device.  A stream with nothing further to change (no rate change, out_bits = 16, out_channels = 1) gets those
+ * bytes as its outputs, one per unit.  Every other stream then runs exactly what sk_tick_run_pcm runs on an 8 kHz mono s16le source --
+ * same kernels, records, bounds and limits.  The carries are named as in sk_gsm_decode_batch.  On failure, or when the tick is refused,
+ * the carries and the resamplers are as they were before the call. */
+typedef struct sk_gsm_tick_stream {
+    uint32_t stream;      /* engine stream (resample = 1 only) */
+    uint32_t n_units;
+    uint32_t state;
+    uint8_t variant;      /* enum sk_gsm_variant */
+    uint8_t channels;     /* 1 */
+    uint8_t out_bits;     /* 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t reserved[2];
+} sk_gsm_tick_stream;
+size_t sk_tick_gsm_out_bound_on(sk_engine *, const sk_gsm_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                uint32_t *max_outputs);
+int sk_tick_run_gsm(sk_engine *, const sk_gsm_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                    const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                    uint32_t *n_outputs, size_t *out_bytes_used, sk_gsm_state *states, uint32_t n_states);
+
+/* A scheduler stream of GSM packets (DecodePipeline::spawn_gsm): the stream has its decoder from the spawn and detects nothing.  A
+ * sk_pipeline_send that completes at least one packet (with what an earlier send left) is one decode and gives one AudioData -- 8 kHz,
+ * mono, 16 bits -- or what the output options make of it (the PCM-family tick); a send that completes none delivers nothing.  The empty
+ * send ends the stream; with bytes left it ends alone with `Decoding failed: GSM stream ended with N trailing partial-frame byte(s)`.
+ * A rejected frame or a send that decodes to more than SK_G72X_MAX_SEND_SAMPLES samples ends its stream alone with `Decoding failed: ` and
+ * the decoder's text.  A variant that is neither of the two: SK_ERR_INVALID_ARG. */
+int sk_pipeline_spawn_gsm(sk_pipeline *, int variant, const sk_decode_options *opt, uint32_t *handle);
+
+/* The reference's GsmDecoder: decode_i16, decode_i32 (= the s16 sample << 16), decode_f32 (= / 32768); 8 kHz mono through _info.
+ * `written` counts samples; an out_cap (in samples) below what pending + input decodes to is SK_ERR_CAPACITY with `Output buffer too
+ * small for GSM decode: need N, have M` in last_error and nothing consumed.  A partial packet is held back for the next call, and
+ * sk_gsm_decoder_flush at the end of the stream is SK_G72X_ERR_STREAM with `GSM stream ended with N trailing partial-frame byte(s)` when
+ * one is left.  A rejected frame is SK_G72X_ERR_STREAM with its text; the call consumes nothing. */
+typedef struct sk_gsm_decoder sk_gsm_decoder;
+int sk_gsm_decoder_create(sk_engine *, int variant, sk_gsm_decoder **out);
+void sk_gsm_decoder_destroy(sk_gsm_decoder *);
+int sk_gsm_decoder_info(const sk_gsm_decoder *, int *variant, uint32_t *sample_rate, uint32_t *channels);
+int sk_gsm_decoder_decode_i16(sk_gsm_decoder *, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written);
+int sk_gsm_decoder_decode_i32(sk_gsm_decoder *, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written);
+int sk_gsm_decoder_decode_f32(sk_gsm_decoder *, const uint8_t *input, size_t len, float *out, size_t out_cap, size_t *written);
+int sk_gsm_decoder_flush(sk_gsm_decoder *);
+int sk_gsm_decoder_reset(sk_gsm_decoder *);
+const char *sk_gsm_decoder_last_error(const sk_gsm_decoder *);
 
 #ifdef __cplusplus
 }

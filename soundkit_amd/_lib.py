@@ -253,6 +253,22 @@ class G72xTickStream(C.Structure):
         (n, C.c_uint8) for n in ("codec", "g726_packing", "channels", "out_bits", "out_channels", "resample", "flush", "reserved")]
 
 
+class GsmState(C.Structure):
+    """sk_gsm_state"""
+    _fields_ = [("dp", C.c_int32 * 120), ("v", C.c_int32 * 8), ("msr", C.c_int32), ("nrp", C.c_int32), ("larpp", C.c_int32 * 8)]
+
+
+class GsmStream(C.Structure):
+    """sk_gsm_stream"""
+    _fields_ = [("variant", C.c_uint32), ("n_units", C.c_uint32), ("state", C.c_uint32)]
+
+
+class GsmTickStream(C.Structure):
+    """sk_gsm_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("state", C.c_uint32)] + [
+        (n, C.c_uint8) for n in ("variant", "channels", "out_bits", "out_channels", "resample", "flush")] + [("reserved", C.c_uint8 * 2)]
+
+
 class FlacTickStream(C.Structure):
     """sk_flac_tick_stream"""
     _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("channels", C.c_uint8), ("bits_per_sample", C.c_uint8), ("out_bits", C.c_uint8),
@@ -556,6 +572,23 @@ _sig = {
     "sk_g726_decoder_flush": (_i, [_vp]),
     "sk_g72x_decoder_reset": (_i, [_vp]),
     "sk_g72x_decoder_last_error": (C.c_char_p, [_vp]),
+    "sk_gsm_state_init": (None, [_vp]),
+    "sk_gsm_decode": (_i, [_vp, _i, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "sk_gsm_decode_dev": (_i, [_vp, _i, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp, _sz]),
+    "sk_gsm_decode_batch": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _u32]),
+    "sk_gsm_decode_batch_dev": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _u32]),
+    "sk_tick_gsm_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_gsm": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz), _vp, _u32]),
+    "sk_pipeline_spawn_gsm": (_i, [_vp, _i, _vp, C.POINTER(_u32)]),
+    "sk_gsm_decoder_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "sk_gsm_decoder_destroy": (None, [_vp]),
+    "sk_gsm_decoder_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32), C.POINTER(_u32)]),
+    "sk_gsm_decoder_decode_i16": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_gsm_decoder_decode_i32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_gsm_decoder_decode_f32": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_gsm_decoder_flush": (_i, [_vp]),
+    "sk_gsm_decoder_reset": (_i, [_vp]),
+    "sk_gsm_decoder_last_error": (C.c_char_p, [_vp]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

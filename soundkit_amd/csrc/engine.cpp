@@ -29,6 +29,7 @@
 #include "aac_entropy_tables.h"
 #include "alac_stream.h"
 #include "g72x_stream.h"
+#include "gsm_stream.h"
 #include "flac_stream.h"
 #include "mp12_internal.h"
 #include "pcm_stream.h"
@@ -267,6 +268,7 @@ struct sk_engine {
     DevBuf flac_in, flac_ws, flac_out;  // sk_flac_decode_frames: frames | tables | statuses, planar i32 workspace | subframe records, PCM
     DevBuf alac_in, alac_ws, alac_out;  // sk_alac_decode_packets: packets | tables | statuses, planar i32 workspace | channel records, PCM
     DevBuf g72x_tab, g72x_ws;  // the telephony decode stage: stream / unit tables and state records, one word per G.722 byte
+    DevBuf gsm_tab, gsm_ws;    // the GSM decode stage: stream / unit tables and state records, one s16 of short-term residual per sample
     DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
     // entropy decode on the device (sk_tick_run_au): per-stream PNS generator state and the front-end's tables
     uint32_t *d_pns = nullptr;
@@ -687,6 +689,8 @@ void sk_engine_destroy(sk_engine *e) try {
         e->alac_out.release();
         e->g72x_tab.release();
         e->g72x_ws.release();
+        e->gsm_tab.release();
+        e->gsm_ws.release();
         e->mp3e_in.release();
         e->tick_mpa_in.release();
         e->mp3e_out.release();
@@ -7058,6 +7062,443 @@ const char *sk_g72x_decoder_last_error(const sk_g72x_decoder *d) try {
     return d ? d->error.c_str() : "";
 } catch (...) {
     (void)sk::abi_caught("sk_g72x_decoder_last_error");
+    return "";
+}
+
+}  // extern "C"
+
+// ---- Telephony: GSM 06.10 full rate (gsm_stream.h, gsm_decode.hip) -----------------------------------------------------------------
+
+struct sk_gsm_decoder {
+    sk_engine *eng = nullptr;
+    int variant = SK_GSM_STANDARD;
+    sk_gsm_state state{};
+    sk_gsm::Framer framer;
+    std::vector<uint8_t> bytes;  // what a call decodes
+    std::vector<int16_t> pcm;    // decode_i32 / decode_f32: the s16 they follow from
+    std::string error;
+};
+
+namespace {
+
+static_assert(sizeof(sk_gsm_state) == sk::kGsmStateWords * 4, "the state is the device record");
+
+// What one launch sequence of the stage works on.  begin() a stream, then unit() for each of its units in order.  The state records go
+// in with the streams and come back into the same vector; the batch must live until the stream has been waited for.
+struct GsmBatch {
+    std::vector<sk::GsmStream> streams;
+    std::vector<sk::GsmUnit> units;
+    std::vector<int32_t> states;
+    uint64_t ws_samples = 0;
+
+    void begin(int variant, const sk_gsm_state *state) {
+        sk::GsmStream s{};
+        s.first_unit = (uint32_t)units.size(), s.state = (uint32_t)streams.size(), s.ws_offset = (uint32_t)ws_samples;
+        s.base_bit = sk_gsm::base_bit(variant), s.stride_bits = sk_gsm::stride_bits(variant);
+        streams.push_back(s);
+        const int32_t *w = (const int32_t *)state;
+        states.insert(states.end(), w, w + sk::kGsmStateWords);
+    }
+    void unit(int variant, const uint8_t *src, uint8_t *dst, uint32_t bytes) {
+        const uint32_t frames = (uint32_t)(sk_gsm::samples_of(variant, bytes) / sk_gsm::kFrameSamples);
+        units.push_back(sk::GsmUnit{src, dst, bytes, frames});
+        streams.back().n_units += 1;
+        ws_samples += (uint64_t)frames * sk_gsm::kFrameSamples;
+    }
+    // the device form of the tables: streams | units | records in | records out
+    static size_t tables_bound(size_t n_streams, size_t n_units) {
+        return g72x_up16(n_streams * sizeof(sk::GsmStream)) + g72x_up16(n_units * sizeof(sk::GsmUnit)) + 2 * g72x_up16(n_streams * sk::kGsmStateWords * 4);
+    }
+};
+
+// uploads the tables to d_tab (tables_bound of the batch's counts), runs the two kernels with the workspace at d_ws (ws_samples s16)
+// and asks for the records back; everything on e->stream, nothing waited for
+int gsm_launch(sk_engine *e, GsmBatch &b, uint8_t *d_tab, int16_t *d_ws) {
+    if (b.streams.empty()) return SK_OK;
+    size_t at = 0;
+    const auto place = [&](size_t bytes) {
+        uint8_t *d = d_tab + at;
+        at += g72x_up16(bytes);
+        return d;
+    };
+    uint8_t *d_streams = place(b.streams.size() * sizeof(sk::GsmStream));
+    uint8_t *d_units = place(b.units.size() * sizeof(sk::GsmUnit));
+    int32_t *d_in = (int32_t *)place(b.states.size() * 4), *d_out = (int32_t *)place(b.states.size() * 4);
+    SK_HIP(hipMemcpyAsync(d_streams, b.streams.data(), b.streams.size() * sizeof(sk::GsmStream), hipMemcpyHostToDevice, e->stream), "H2D gsm streams");
+    if (!b.units.empty())
+        SK_HIP(hipMemcpyAsync(d_units, b.units.data(), b.units.size() * sizeof(sk::GsmUnit), hipMemcpyHostToDevice, e->stream), "H2D gsm units");
+    SK_HIP(hipMemcpyAsync(d_in, b.states.data(), b.states.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D gsm states");
+    SK_HIP(sk::launch_gsm((const sk::GsmStream *)d_streams, (uint32_t)b.streams.size(), (const sk::GsmUnit *)d_units, d_in, d_out, d_ws, e->stream), "launch gsm");
+    SK_HIP(hipMemcpyAsync(b.states.data(), d_out, b.states.size() * 4, hipMemcpyDeviceToHost, e->stream), "D2H gsm states");
+    return SK_OK;
+}
+
+// sk_gsm_decode_batch[_dev]
+int gsm_decode_batch(sk_engine *e, const sk_gsm_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *bytes,
+                     size_t bytes_len, bool on_device, uint8_t *out, size_t out_cap, size_t *out_len, sk_gsm_state *states, uint32_t n_states) {
+    if (!e || !out_len || (n_streams && (!streams || !states)) || (n_units && !units) || (bytes_len && !bytes)) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (bytes_len > 0x7fffffffull) return SK_ERR_INVALID_ARG;
+    if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15)) return SK_ERR_INVALID_ARG;
+    // ---- the table, and where every unit's samples go ----
+    std::vector<uint8_t> named(n_states, 0);
+    std::vector<uint64_t> out_at(n_units, 0);
+    std::vector<uint32_t> out_bytes(n_units, 0);
+    uint64_t at = 0, cursor = 0, need = 0;
+    bool rejected = false;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_gsm_stream &s = streams[i];
+        if (!sk_gsm::variant_ok((int)s.variant) || s.state >= n_states || named[s.state]++) return SK_ERR_INVALID_ARG;
+        if (at + s.n_units > n_units) return SK_ERR_INVALID_ARG;
+        for (uint32_t u = 0; u < s.n_units; ++u) {
+            const sk_g72x_unit &un = units[at + u];
+            if (un.offset % 16 || un.size % sk_gsm::packet_bytes((int)s.variant) || un.offset > bytes_len || un.size > bytes_len - un.offset) return SK_ERR_INVALID_ARG;
+            const uint64_t samples = sk_gsm::samples_of((int)s.variant, un.size);
+            if (samples > sk_gsm::kScratchSamples) return SK_ERR_INVALID_ARG;
+            if (!on_device && !sk_gsm::frames_accepted((int)s.variant, bytes + un.offset, un.size, nullptr)) rejected = true;
+            out_at[at + u] = cursor, out_bytes[at + u] = (uint32_t)(samples * 2);
+            if (samples) need = cursor + samples * 2;
+            cursor += g72x_up16((size_t)samples * 2);
+        }
+        at += s.n_units;
+    }
+    if (at != n_units || need > out_cap || (need && !out)) return SK_ERR_INVALID_ARG;
+    if (rejected) return SK_G72X_ERR_STREAM;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    const uint8_t *d_src = bytes;
+    uint8_t *d_dst = out;
+    if (!on_device) {
+        SK_HIP(e->in_buf.reserve(bytes_len + 64), "alloc staging");
+        SK_HIP(e->out_buf.reserve((size_t)cursor + 64), "alloc staging");
+        if (bytes_len) SK_HIP(hipMemcpyAsync(e->in_buf.p, bytes, bytes_len, hipMemcpyHostToDevice, e->stream), "H2D gsm bytes");
+        d_src = (const uint8_t *)e->in_buf.p, d_dst = (uint8_t *)e->out_buf.p;
+    }
+    GsmBatch b;
+    at = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_gsm_stream &s = streams[i];
+        b.begin((int)s.variant, &states[s.state]);
+        for (uint32_t u = 0; u < s.n_units; ++u) b.unit((int)s.variant, d_src + units[at + u].offset, d_dst + out_at[at + u], units[at + u].size);
+        at += s.n_units;
+    }
+    SK_HIP(e->gsm_tab.reserve(GsmBatch::tables_bound(n_streams, n_units) + 64), "alloc gsm tables");
+    SK_HIP(e->gsm_ws.reserve((size_t)b.ws_samples * 2 + 64), "alloc gsm workspace");
+    int rc = gsm_launch(e, b, (uint8_t *)e->gsm_tab.p, (int16_t *)e->gsm_ws.p);
+    if (rc == SK_OK && !on_device && need) {
+        // one copy up to the end of the last unit's samples; every unit is whole frames of 320 bytes, so there are no gaps between them
+        const hipError_t err = hipMemcpyAsync(out, d_dst, (size_t)need, hipMemcpyDeviceToHost, e->stream);
+        if (err != hipSuccess) rc = e->hip_fail(err, "D2H gsm");
+    }
+    const hipError_t waited = hipStreamSynchronize(e->stream);  // the tables leave scope with the call
+    if (rc != SK_OK) return rc;
+    SK_HIP(waited, "gsm sync");
+    for (uint32_t i = 0; i < n_streams; ++i) std::memcpy(&states[streams[i].state], &b.states[(size_t)i * sk::kGsmStateWords], sizeof(sk_gsm_state));
+    for (uint32_t k = 0; k < n_units; ++k) units[k].out_offset = out_at[k], units[k].out_len = out_bytes[k];
+    *out_len = (size_t)need;
+    return SK_OK;
+}
+
+// sk_gsm_decode[_dev]: a table of one stream with one unit
+int gsm_decode_one(sk_engine *e, int variant, const uint8_t *bytes, size_t len, bool on_device, uint8_t *out, size_t out_cap, size_t *out_len,
+                   sk_gsm_state *state, char *error, size_t error_cap) {
+    g72x_text(error, error_cap, "");
+    if (!e || !out_len) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (!sk_gsm::variant_ok(variant) || (len && !bytes) || !state) return SK_ERR_INVALID_ARG;
+    if (len > 0x7fffffffull || len % sk_gsm::packet_bytes(variant)) return SK_ERR_INVALID_ARG;
+    std::string text;
+    if (!sk_gsm::fits_scratch(sk_gsm::samples_of(variant, len), &text) || (!on_device && !sk_gsm::frames_accepted(variant, bytes, len, &text))) {
+        g72x_text(error, error_cap, text);
+        return SK_G72X_ERR_STREAM;
+    }
+    sk_gsm_stream s{};
+    s.variant = (uint32_t)variant, s.n_units = 1, s.state = 0;
+    sk_g72x_unit u{};
+    u.size = (uint32_t)len;
+    return gsm_decode_batch(e, &s, 1, &u, 1, bytes, len, on_device, out, out_cap, out_len, state, 1);
+}
+
+// sk_tick_run_gsm / sk_tick_gsm_out_bound_on: checks the table and derives what the PCM tick's body works on, as g72x_tick_derive does --
+// per stream an 8 kHz mono s16le source, per unit where its decoded samples lie (16-byte aligned, unit after unit) -- and the decode
+// that stands in front of the body: one launch sequence of the stage over the units of each pass.
+struct GsmDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;  // the decoded layout
+    std::vector<uint32_t> first;     // per stream: its first unit
+    AiffTick tick;
+    GsmBatch batch[2];               // streams that go on through the body, streams delivered as decoded: alive until the tick's last wait
+    std::vector<uint32_t> of[2];     // [pass]: record of the batch -> index into the stream table
+    size_t part = 0;                 // of gsm_tab per pass
+    uint64_t ws_samples = 0;
+};
+
+// bytes: the units' bytes on the host, or null when only the bound is asked for (nothing is named or read then)
+int gsm_tick_derive(const sk_gsm_tick_stream *gs, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes, size_t bytes_len,
+                    uint32_t n_states, GsmDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.assign(n_units, sk_pcm_unit{});
+    d.first.assign(n_streams, 0);
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    std::vector<uint8_t> named(bytes ? n_states : 0, 0);
+    uint64_t at = 0, cursor = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_gsm_tick_stream &g = gs[i];
+        if (!sk_gsm::variant_ok(g.variant) || g.channels != 1) return SK_ERR_INVALID_ARG;
+        if (bytes && (g.state >= n_states || named[g.state]++)) return SK_ERR_INVALID_ARG;
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = g.stream, t.n_units = g.n_units, t.channels = 1, t.out_bits = g.out_bits, t.out_channels = g.out_channels;
+        t.resample = g.resample, t.flush = g.flush, t.format = SK_FMT_S16LE;
+        d.tick.plain[i] = !g.resample && g.out_bits == 16 && g.out_channels == 1;
+        d.first[i] = (uint32_t)at;
+        if (at + g.n_units > n_units) return SK_ERR_INVALID_ARG;
+        for (uint32_t u = 0; u < g.n_units; ++u) {
+            const sk_pcm_unit &un = units[at + u];
+            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len % sk_gsm::packet_bytes(g.variant)) return SK_ERR_INVALID_ARG;
+            if (un.byte_offset > bytes_len || un.byte_len > bytes_len - un.byte_offset) return SK_ERR_INVALID_ARG;
+            const uint64_t samples = sk_gsm::samples_of(g.variant, un.byte_len);
+            if (samples > sk_gsm::kScratchSamples) return SK_ERR_INVALID_ARG;
+            if (bytes && !sk_gsm::frames_accepted(g.variant, bytes + un.byte_offset, un.byte_len, nullptr)) return SK_ERR_INVALID_ARG;
+            d.units[at + u] = sk_pcm_unit{cursor, (uint32_t)(samples * 2), 0};
+            cursor += g72x_up16((size_t)samples * 2);
+            d.ws_samples += samples;
+        }
+        at += g.n_units;
+    }
+    if (cursor > 0x7fffffffull || (bytes_len > 0x7fffffffull && bytes_len != (size_t)-1)) return SK_ERR_INVALID_ARG;
+    d.tick.decoded_len = (size_t)cursor;
+    d.part = GsmBatch::tables_bound(n_streams, n_units) + 64;
+    return at == n_units ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// one pass of the decode in front of the body: the units of the streams whose `plain` is as_is, each to where dst_of puts it
+int gsm_tick_decode(sk_engine *e, const sk_gsm_tick_stream *gs, const sk_pcm_unit *units, const sk_gsm_state *states, GsmDerived &d, bool as_is,
+                    const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+    const int p = as_is ? 1 : 0;
+    GsmBatch &b = d.batch[p];
+    for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
+        if ((d.tick.plain[i] != 0) != as_is || d.ts[i].n_units == 0) continue;
+        const sk_gsm_tick_stream &g = gs[i];
+        b.begin(g.variant, &states[g.state]);
+        d.of[p].push_back(i);
+        for (uint32_t u = 0; u < g.n_units; ++u) b.unit(g.variant, d_src + units[d.first[i] + u].byte_offset, dst_of(i, u), units[d.first[i] + u].byte_len);
+    }
+    if (b.streams.empty()) return SK_OK;
+    // both passes' tables have their own part of gsm_tab; the workspace is shared, the passes follow each other on the stream
+    SK_HIP(e->gsm_tab.reserve(2 * d.part), "alloc tick gsm tables");
+    SK_HIP(e->gsm_ws.reserve((size_t)d.ws_samples * 2 + 64), "alloc tick gsm workspace");
+    return gsm_launch(e, b, (uint8_t *)e->gsm_tab.p + (size_t)p * d.part, (int16_t *)e->gsm_ws.p);
+}
+
+int gsm_decoder_fail(sk_gsm_decoder *d, int rc, const std::string &text) {
+    d->error = text;
+    return rc;
+}
+
+// GsmDecoder::decode_i16: `written` samples into out (cap samples)
+int gsm_decoder_decode(sk_gsm_decoder *d, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written) {
+    if (!d || (len && !input) || !written || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    const size_t take = d->framer.ready(len);
+    const uint64_t samples = sk_gsm::samples_of(d->variant, take);
+    std::string text;
+    if (!sk_gsm::fits(samples, out_cap, &text)) return gsm_decoder_fail(d, SK_ERR_CAPACITY, text);  // before anything else, as the reference does
+    if (samples > 0x3fffffffull) return SK_ERR_INVALID_ARG;
+    sk_gsm::Framer after = d->framer;  // the framer moves on only when the decode succeeds
+    d->bytes.clear();
+    after.add(input, len, d->bytes);  // nothing completes a packet: the bytes wait, nothing is decoded
+    if (!sk_gsm::frames_accepted(d->variant, d->bytes.data(), take, &text)) return gsm_decoder_fail(d, SK_G72X_ERR_STREAM, text);
+    // a Decoder object is not the pipeline: its output is the caller's, so a call may exceed the pipeline's scratch -- in pieces of
+    // whole packets, the carry handed from piece to piece and kept only when all of them decoded
+    sk_gsm_stream s{};
+    s.variant = (uint32_t)d->variant, s.n_units = 1;
+    sk_gsm_state st = d->state;
+    const size_t piece = sk_gsm::kScratchSamples / sk_gsm::packet_samples(d->variant) * sk_gsm::packet_bytes(d->variant);
+    size_t done = 0, got = 0;
+    while (done < take) {
+        const size_t n = std::min(piece, take - done);
+        sk_g72x_unit u{};
+        u.size = (uint32_t)n;
+        size_t out_len = 0;
+        const int rc = gsm_decode_batch(d->eng, &s, 1, &u, 1, d->bytes.data() + done, n, false, (uint8_t *)(out + got), (out_cap - got) * 2, &out_len, &st, 1);
+        if (rc != SK_OK) return rc;
+        done += n, got += out_len / 2;
+    }
+    d->state = st, d->framer = after;
+    *written = got;
+    return SK_OK;
+}
+
+// decode_i32 / decode_f32: the s16 decode into the decoder's own buffer, then `widen` sample for sample
+template <typename T, typename F>
+int gsm_decoder_decode_as(sk_gsm_decoder *d, const uint8_t *input, size_t len, T *out, size_t out_cap, size_t *written, F widen) {
+    if (!d || !written || (out_cap && !out)) return SK_ERR_INVALID_ARG;
+    d->pcm.resize(out_cap);
+    const int rc = gsm_decoder_decode(d, input, len, d->pcm.data(), out_cap, written);
+    if (rc != SK_OK) return rc;
+    for (size_t i = 0; i < *written; ++i) out[i] = widen(d->pcm[i]);
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sk_gsm_state_init(sk_gsm_state *s) try {
+    sk::abi_enter();
+    if (s) sk_gsm::init_state(s);
+} catch (...) {
+    (void)sk::abi_caught("sk_gsm_state_init");
+}
+
+int sk_gsm_decode(sk_engine *e, int variant, const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap, size_t *out_len, sk_gsm_state *state, char *error,
+                  size_t error_cap) try {
+    sk::abi_enter();
+    return gsm_decode_one(e, variant, bytes, len, false, out, out_cap, out_len, state, error, error_cap);
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decode");
+}
+
+int sk_gsm_decode_dev(sk_engine *e, int variant, const uint8_t *d_bytes, size_t len, uint8_t *d_out, size_t out_cap, size_t *out_len, sk_gsm_state *state,
+                      char *error, size_t error_cap) try {
+    sk::abi_enter();
+    return gsm_decode_one(e, variant, d_bytes, len, true, d_out, out_cap, out_len, state, error, error_cap);
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decode_dev");
+}
+
+int sk_gsm_decode_batch(sk_engine *e, const sk_gsm_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *bytes,
+                        size_t bytes_len, uint8_t *out, size_t out_cap, size_t *out_len, sk_gsm_state *states, uint32_t n_states) try {
+    sk::abi_enter();
+    return gsm_decode_batch(e, streams, n_streams, units, n_units, bytes, bytes_len, false, out, out_cap, out_len, states, n_states);
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decode_batch");
+}
+
+int sk_gsm_decode_batch_dev(sk_engine *e, const sk_gsm_stream *streams, uint32_t n_streams, sk_g72x_unit *units, uint32_t n_units, const uint8_t *d_bytes,
+                            size_t bytes_len, uint8_t *d_out, size_t out_cap, size_t *out_len, sk_gsm_state *states, uint32_t n_states) try {
+    sk::abi_enter();
+    return gsm_decode_batch(e, streams, n_streams, units, n_units, d_bytes, bytes_len, true, d_out, out_cap, out_len, states, n_states);
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decode_batch_dev");
+}
+
+size_t sk_tick_gsm_out_bound_on(sk_engine *e, const sk_gsm_tick_stream *gs, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!gs && n_streams) || (!units && n_units)) return 0;
+    GsmDerived d;
+    if (gsm_tick_derive(gs, n_streams, units, n_units, nullptr, (size_t)-1, 0, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), n_units, max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_gsm_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_gsm(sk_engine *e, const sk_gsm_tick_stream *gs, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                    size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
+                    sk_gsm_state *states, uint32_t n_states) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && (!gs || !states)) || (n_units && (!units || !bytes))) return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    GsmDerived d;
+    static const uint8_t none = 0;  // a tick without units reads no bytes, but still names its records
+    int rc = gsm_tick_derive(gs, n_streams, units, n_units, bytes ? bytes : &none, bytes_len, n_states, d);
+    if (rc != SK_OK) return rc;
+    d.tick.decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+        return gsm_tick_decode(e, gs, units, states, d, as_is, dst_of, d_src);
+    };
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, &d.tick);
+    if (rc != SK_OK) return rc;  // the carries are the caller's records: untouched
+    for (int p = 0; p < 2; ++p)
+        for (size_t k = 0; k < d.of[p].size(); ++k) std::memcpy(&states[gs[d.of[p][k]].state], &d.batch[p].states[k * sk::kGsmStateWords], sizeof(sk_gsm_state));
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_gsm");
+}
+
+int sk_gsm_decoder_create(sk_engine *e, int variant, sk_gsm_decoder **out) try {
+    sk::abi_enter();
+    if (!e || !out || !sk_gsm::variant_ok(variant)) return SK_ERR_INVALID_ARG;
+    std::unique_ptr<sk_gsm_decoder> d(new sk_gsm_decoder());
+    d->eng = e, d->variant = variant;
+    d->framer = sk_gsm::Framer(variant);
+    sk_gsm::init_state(&d->state);
+    *out = d.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_create");
+}
+
+void sk_gsm_decoder_destroy(sk_gsm_decoder *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_gsm_decoder_destroy");
+}
+
+int sk_gsm_decoder_info(const sk_gsm_decoder *d, int *variant, uint32_t *sample_rate, uint32_t *channels) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (variant) *variant = d->variant;
+    if (sample_rate) *sample_rate = 8000;
+    if (channels) *channels = 1;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_info");
+}
+
+int sk_gsm_decoder_decode_i16(sk_gsm_decoder *d, const uint8_t *input, size_t len, int16_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return gsm_decoder_decode(d, input, len, out, out_cap, written);
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_decode_i16");
+}
+
+int sk_gsm_decoder_decode_i32(sk_gsm_decoder *d, const uint8_t *input, size_t len, int32_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return gsm_decoder_decode_as(d, input, len, out, out_cap, written, [](int16_t v) { return (int32_t)((uint32_t)(int32_t)v << 16); });
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_decode_i32");
+}
+
+int sk_gsm_decoder_decode_f32(sk_gsm_decoder *d, const uint8_t *input, size_t len, float *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    return gsm_decoder_decode_as(d, input, len, out, out_cap, written, [](int16_t v) { return (float)v / 32768.0f; });
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_decode_f32");
+}
+
+int sk_gsm_decoder_flush(sk_gsm_decoder *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    std::string text;
+    if (d->framer.flush(&text)) return SK_OK;
+    return gsm_decoder_fail(d, SK_G72X_ERR_STREAM, text);
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_flush");
+}
+
+int sk_gsm_decoder_reset(sk_gsm_decoder *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    sk_gsm::init_state(&d->state);
+    d->framer.pending.clear();
+    d->error.clear();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_gsm_decoder_reset");
+}
+
+const char *sk_gsm_decoder_last_error(const sk_gsm_decoder *d) try {
+    sk::abi_enter();
+    return d ? d->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_gsm_decoder_last_error");
     return "";
 }
 

@@ -131,6 +131,10 @@ struct PipelineGpuHooks {
     int (*tick_g72x)(sk_engine *, const sk_g72x_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t, sk_tick_output *,
                      uint32_t, uint32_t *, size_t *, sk_g726_state *, uint32_t, sk_g722_state *, uint32_t) = nullptr;
     size_t (*tick_g72x_out_bound)(sk_engine *, const sk_g72x_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
+    // sk_tick_run_gsm / sk_tick_gsm_out_bound_on: the GSM streams' units
+    int (*tick_gsm)(sk_engine *, const sk_gsm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t, sk_tick_output *,
+                    uint32_t, uint32_t *, size_t *, sk_gsm_state *, uint32_t) = nullptr;
+    size_t (*tick_gsm_out_bound)(sk_engine *, const sk_gsm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
     uint32_t (*wide_pcm_streams)(const sk_engine *) = nullptr;  // sk_engine_wide_pcm_streams
     int (*enable_wide_pcm)(sk_engine *, uint32_t) = nullptr;    // sk_engine_enable_wide_pcm
 };

@@ -19,6 +19,7 @@
 #include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
 #include "alac_stream.h"
 #include "g72x_stream.h"
+#include "gsm_stream.h"
 #include "flac_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
@@ -107,6 +108,12 @@ struct PStream {
     sk_g72x::G726Framer g726_framer;
     sk_g726_state g726_state{};
     sk_g722_state g722_state{};
+    // GSM 06.10 streams (sk_pipeline_spawn_gsm): the same shape -- the framer holds a partial packet back (worker thread), the carry
+    // goes into every tick and comes back from it (submission thread)
+    bool gsm = false;
+    uint8_t gsm_variant = 0;
+    sk_gsm::Framer gsm_framer;
+    sk_gsm_state gsm_state{};
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -114,8 +121,8 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -192,6 +199,8 @@ struct Batch {
     TickTable<sk_g72x_tick_stream, sk_pcm_unit> g72x_ts;  // telephony streams' units (sk_tick_run_g72x); row k's carry is record k of both arrays
     std::vector<sk_g726_state> g726_states;
     std::vector<sk_g722_state> g722_states;
+    TickTable<sk_gsm_tick_stream, sk_pcm_unit> gsm_ts;  // GSM streams' units (sk_tick_run_gsm); row k's carry is record k
+    std::vector<sk_gsm_state> gsm_states;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -219,6 +228,7 @@ struct Batch {
         flac_ts.clear();
         alac_ts.clear();
         g72x_ts.clear();
+        gsm_ts.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -697,7 +707,9 @@ int ensure_pcm(sk_lane *p) {
 bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     uint32_t rate, channels, bits;
     bool is_float, big_endian = false;
-    if (s.g72x) {  // the spawn's: create_audio_data_i16(d.sample_rate(), d.channels(), ...), always 16 bits
+    if (s.gsm) {  // GsmDecoder's: 8 kHz mono, create_audio_data_i16
+        rate = 8000, channels = 1, bits = 16, is_float = false;
+    } else if (s.g72x) {  // the spawn's: create_audio_data_i16(d.sample_rate(), d.channels(), ...), always 16 bits
         rate = s.g72x_rate, channels = s.g72x_channels, bits = 16, is_float = false;
     } else if (s.alac) {  // the cookie's
         rate = s.alac_cfg.sample_rate, channels = s.alac_cfg.channels, bits = s.alac_cfg.bit_depth, is_float = false;
@@ -741,6 +753,14 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         s.pcm_route = kPcmG72xTick;
         return true;
     }
+    if (s.gsm && (!hooks.tick_gsm || !hooks.tick_gsm_out_bound))
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: GSM decoding needs the device tick, which this build lacks");
+    if (s.gsm && target_rate == rate && target_bits == bits && target_channels == channels) {  // every frame has per-sample work: the tick's
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmGsmTick;
+        return true;
+    }
     if (s.alac && (!hooks.tick_alac || !hooks.tick_alac_out_bound))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: ALAC decoding needs the device tick, which this build lacks");
     if (s.alac && target_rate == rate && target_bits == bits && target_channels == channels) {  // every packet has per-sample work: the tick's
@@ -782,7 +802,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
+    s.pcm_route = s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
     return true;
 }
 
@@ -864,6 +884,58 @@ void parse_some_g72x(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
             break;
         }
         stage_unit(r, s, data, len, (uint32_t)(samples / s.channels), outputs);
+    }
+    r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
+}
+
+// A GSM stream's pass (sk_pipeline_spawn_gsm): the same decode_i16_with_drain shape (lib.rs:2358-2422) -- a send that completes at least
+// one packet is one decode and gives one AudioData, a send that completes none gives nothing.  What a send decodes now is one unit of
+// the GSM tick.  GsmDecoder::decode_i16 checks its room first (a send above the reference's scratch ends the stream with its text,
+// the pending bytes as they were), then gsm_decode every frame (a standard frame without the magic nibble ends the stream); the end of
+// the stream is GsmDecoder::flush (a partial packet left: its text).
+void parse_some_gsm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
+    uint32_t outputs = 0;
+    if (!s.pcm_route && !pcm_open(p, s, r)) return;
+    std::vector<uint8_t> whole;
+    while (!r.failed) {
+        if (s.saw_eof) {
+            std::string text;
+            if (!s.gsm_framer.flush(&text)) r.fail(SK_G72X_ERR_STREAM, "Decoding failed: " + text);
+            else r.eof = true;
+            break;
+        }
+        std::vector<uint8_t> chunk;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            if (s.in.empty()) break;
+            const size_t next = s.in.front().size();
+            if (next && (outputs >= room || r.pcm_units.size() >= per_pass || (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes))) {
+                r.more = true;
+                break;
+            }
+            chunk = std::move(s.in.front());
+            s.in.pop_front();
+        }
+        if (chunk.empty()) {
+            s.saw_eof = true;
+            continue;
+        }
+        s.queued_bytes.fetch_sub(chunk.size());
+        std::string text;
+        if (!sk_gsm::fits_scratch(sk_gsm::samples_of(s.gsm_variant, s.gsm_framer.ready(chunk.size())), &text)) {
+            r.fail(SK_G72X_ERR_STREAM, "Decoding failed: " + text);
+            break;
+        }
+        whole.clear();
+        const size_t len = s.gsm_framer.add(chunk.data(), chunk.size(), whole);
+        if (len == 0) continue;  // no packet completed: nothing is delivered for this send
+        if (!sk_gsm::frames_accepted(s.gsm_variant, whole.data(), len, &text)) {
+            r.fail(SK_G72X_ERR_STREAM, "Decoding failed: " + text);
+            break;
+        }
+        stage_unit(r, s, whole.data(), len, (uint32_t)sk_gsm::samples_of(s.gsm_variant, len), outputs);
     }
     r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
@@ -1129,6 +1201,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
     }
     if (s.codec == kCodecG72x) {
         parse_some_g72x(p, s, room, r);
+        return;
+    }
+    if (s.codec == kCodecGsm) {
+        parse_some_gsm(p, s, room, r);
         return;
     }
     if (s.codec == kCodecWav || s.codec == kCodecRawPcm || s.codec == kCodecAiff) {
@@ -1462,6 +1538,8 @@ void worker_body(sk_lane *p) {
                 } else if (s.pcm_route == kPcmG72xTick) {
                     if (sk_g72x_tick_stream *row = claim_tick_row(b, b->g72x_ts, s, r, r.pcm_units, be, pcm_at))
                         row->codec = s.g72x_codec, row->g726_rate = s.g726_rate, row->g726_packing = s.g726_packing;
+                } else if (s.pcm_route == kPcmGsmTick) {
+                    if (sk_gsm_tick_stream *row = claim_tick_row(b, b->gsm_ts, s, r, r.pcm_units, be, pcm_at)) row->variant = s.gsm_variant;
                 } else if (s.pcm_route == kPcmTick) {
                     if (sk_pcm_tick_stream *row = claim_tick_row(b, b->pcm_ts, s, r, r.pcm_units, be, pcm_at)) row->format = s.pcm_fmt;
                 }
@@ -1624,12 +1702,12 @@ void submit_body(sk_lane *p) {
         b->rc = SK_OK;
         b->n_out = 0;
         if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty() ||
-            !b->g72x_ts.rows.empty()) {
+            !b->g72x_ts.rows.empty() || !b->gsm_ts.rows.empty()) {
             // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, the ALAC tick's, then the PCM tick's: one buffer
             const size_t bound = (ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out)) +
                                  follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
                                  follow_on_bound(p, b->alac_ts, hooks.tick_alac_out_bound) +
-                                 follow_on_bound(p, b->g72x_ts, hooks.tick_g72x_out_bound) +
+                                 follow_on_bound(p, b->g72x_ts, hooks.tick_g72x_out_bound) + follow_on_bound(p, b->gsm_ts, hooks.tick_gsm_out_bound) +
                                  follow_on_bound(p, b->pcm_ts, hooks.tick_pcm_out_bound);
             if (bound > b->out_pinned_cap) {
                 // Pinned memory is slow to get (10 ms per 64 MB on an idle device, many times that beside a running lane): the
@@ -1649,7 +1727,7 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->pcm_ts.max_out;
+            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->gsm_ts.max_out + b->pcm_ts.max_out;
             if (b->recs.size() < n_recs) b->recs.resize(n_recs);
         }
         const bool with_md = b->n_mp3 && p->mp3_gpu;  // the MP3 streams' Huffman stage is the tick's as well
@@ -1727,6 +1805,18 @@ void submit_body(sk_lane *p) {
             if (s.g72x_codec == SK_G726) s.g726_state = b->g726_states[row];
             if (s.g72x_codec == SK_G722) s.g722_state = b->g722_states[row];
         }
+        follow_on_tick(b, b->gsm_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            const uint32_t rows = (uint32_t)b->gsm_ts.rows.size();  // row k names record k, as above
+            b->gsm_states.resize(rows);
+            for (uint32_t row = 0; row < rows; ++row) {
+                b->gsm_ts.rows[row].state = row;
+                b->gsm_states[row] = p->streams[b->entries[b->gsm_ts.entry[row]].handle]->gsm_state;
+            }
+            return hooks.tick_gsm(p->engine, b->gsm_ts.rows.data(), rows, b->gsm_ts.units.data(), (uint32_t)b->gsm_ts.units.size(), b->pcm_bytes, b->pcm_used, out,
+                                  out_cap, recs, recs_cap, n_out, out_used, b->gsm_states.data(), rows);
+        });
+        for (uint32_t row = 0; b->rc == SK_OK && row < b->gsm_ts.rows.size(); ++row)
+            p->streams[b->entries[b->gsm_ts.entry[row]].handle]->gsm_state = b->gsm_states[row];
         follow_on_tick(b, b->pcm_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
             return hooks.tick_pcm(p->engine, b->pcm_ts.rows.data(), (uint32_t)b->pcm_ts.rows.size(), b->pcm_ts.units.data(),
                                   (uint32_t)b->pcm_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used);
@@ -1735,7 +1825,7 @@ void submit_body(sk_lane *p) {
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
         p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_ts.units.size() +
-                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size());
+                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size() + (uint32_t)b->gsm_ts.units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -2234,6 +2324,7 @@ struct G72xSpawn {  // sk_pipeline_spawn_g711 / _g722 / _g726
     int codec;
     uint32_t sample_rate, channels, g726_rate;
     int g726_packing;
+    int gsm_variant = -1;  // sk_pipeline_spawn_gsm: 0 / 1, nothing else of this record is read then
 };
 
 int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
@@ -2290,6 +2381,10 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.g726_framer = sk_g72x::G726Framer();
     sk_g72x::init_state(&s.g726_state);
     sk_g72x::init_state(&s.g722_state);
+    s.gsm = false;
+    s.gsm_variant = 0;
+    s.gsm_framer = sk_gsm::Framer();
+    sk_gsm::init_state(&s.gsm_state);
     s.pcm_detected = false;
     s.pcm_route = 0, s.pcm_fmt = 0, s.pcm_flags = 0, s.pcm_bits = 0;
     s.pcm_fill = 0;
@@ -2310,7 +2405,13 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
         s.alac_cfg = *alac;
         s.pcm_detected = true;
     }
-    if (g72x) {  // spawn_g711 / spawn_g722 / spawn_g726*: the decoder is there from the start, nothing is detected or gathered
+    if (g72x && g72x->gsm_variant >= 0) {  // spawn_gsm: the same, with GsmDecoder
+        s.codec = kCodecGsm;
+        s.gsm = true;
+        s.gsm_variant = (uint8_t)g72x->gsm_variant;
+        s.gsm_framer = sk_gsm::Framer(g72x->gsm_variant);
+        s.pcm_detected = true;
+    } else if (g72x) {  // spawn_g711 / spawn_g722 / spawn_g726*: the decoder is there from the start, nothing is detected or gathered
         s.codec = kCodecG72x;
         s.g72x = true;
         s.g72x_codec = (uint8_t)g72x->codec, s.g72x_rate = g72x->sample_rate, s.g72x_channels = (uint8_t)g72x->channels;
@@ -2649,6 +2750,15 @@ int sk_pipeline_spawn_g726(sk_pipeline *p, uint32_t g726_rate, int g726_packing,
     return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, &g);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn_g726");
+}
+
+int sk_pipeline_spawn_gsm(sk_pipeline *p, int variant, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    if (!sk_gsm::variant_ok(variant)) return SK_ERR_INVALID_ARG;
+    const G72xSpawn g{0, 8000, 1, 0, 0, variant};
+    return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, &g);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_gsm");
 }
 
 int sk_pipeline_send(sk_pipeline *p, uint32_t handle, const uint8_t *data, size_t len) try {

@@ -660,4 +660,24 @@ hipError_t launch_g726(const G72xStream *streams, uint32_t n_streams, const G72x
 hipError_t launch_g722(const G72xStream *streams, uint32_t n_streams, const G72xUnit *units, const int32_t *states_in, int32_t *states_out, uint32_t *ws,
                        uint32_t max_bytes, hipStream_t s);
 
+// gsm_decode.hip -- GSM 06.10 full-rate frames to s16le: k_gsm_excite (one stream per wave) writes the short-term residual to the
+// workspace, k_gsm_synth (one stream per lane) filters it; the state is carried in the caller's records.
+constexpr uint32_t kGsmStateWords = 138;  // sk_gsm_state
+struct GsmUnit {
+    const uint8_t *src;  // 16-byte aligned; read in whole dwords up to the one that holds the last byte
+    uint8_t *dst;        // 16-byte aligned: 320 bytes a frame
+    uint32_t bytes;      // whole packets
+    uint32_t frames;     // of 160 samples
+};
+struct GsmStream {
+    uint32_t first_unit, n_units;  // into the unit table; a stream's units are decoded in order
+    uint32_t state;                // its record in states_in / states_out
+    uint32_t ws_offset;            // its first sample of the workspace, a multiple of 160 (one s16 per sample of the call)
+    uint32_t base_bit;             // of a unit's first frame: 4 (behind the magic nibble) or 0 (Microsoft)
+    uint32_t stride_bits;          // from one frame to the next: 264 or 260
+};
+// states_in and states_out are different arrays of kGsmStateWords words per record; a record belongs to one stream.  ws is 16-byte aligned.
+hipError_t launch_gsm(const GsmStream *streams, uint32_t n_streams, const GsmUnit *units, const int32_t *states_in, int32_t *states_out, int16_t *ws,
+                      hipStream_t s);
+
 }  // namespace sk

@@ -720,6 +720,84 @@ class Engine:
         return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
                 for r in recs[:n_out.value]]
 
+    def gsm_decode(self, data, state=None, variant=0):
+        """sk_gsm_decode: one GSM stream's whole packets (telephony.GSM_STANDARD / GSM_MICROSOFT) -> s16le bytes.  state: a
+        telephony.new_state(telephony.GSM) record carried from call to call and updated in place (None: a fresh stream)."""
+        import ctypes as C
+        from . import telephony
+        data = np.frombuffer(bytes(data), np.uint8)
+        st = state if state is not None else telephony.new_state(telephony.GSM)
+        out = np.zeros(max(telephony.gsm_decoded_samples(variant, data.size) * 2, 16), np.uint8)
+        n = C.c_size_t()
+        text = C.create_string_buffer(256)
+        rc = lib.sk_gsm_decode(self._h, int(variant), _ptr(data) if data.size else None, data.size, _ptr(out), out.size, C.byref(n), C.byref(st), text, 256)
+        if rc == telephony.ERR_STREAM:
+            raise telephony.TelephonyError(text.value.decode())
+        check(rc, "sk_gsm_decode", self._h)
+        return out[:n.value].tobytes()
+
+    @staticmethod
+    def _gsm_tables(streams, units, row_type, unit_type, offset_field, size_field):
+        """the stream rows, the state records and the unit table with every unit packed at a 16-byte aligned offset of one blob"""
+        from ._lib import GsmState
+        ts = (row_type * max(len(streams), 1))()
+        states = (GsmState * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            ts[i].variant, ts[i].n_units, ts[i].state = int(s.get("variant", 0)), int(s["n_units"]), i
+            states[i] = s["state"]
+        table = (unit_type * max(len(units), 1))()
+        total = 0
+        for k, u in enumerate(units):
+            setattr(table[k], offset_field, total)
+            setattr(table[k], size_field, len(u))
+            total += (len(u) + 15) & ~15
+        blob = np.zeros(max(total, 16), np.uint8)
+        at = 0
+        for u in units:
+            blob[at:at + len(u)] = np.frombuffer(bytes(u), np.uint8)
+            at += (len(u) + 15) & ~15
+        return ts, states, table, blob, total
+
+    def gsm_decode_batch(self, streams, units):
+        """sk_gsm_decode_batch.  streams: list of dicts {n_units, variant (0 when absent), state (a telephony.new_state(telephony.GSM)
+        record, updated in place)}; units: the pieces (bytes, whole packets) of all streams, stream by stream.  -> [s16le bytes per unit]."""
+        import ctypes as C
+        from . import telephony
+        from ._lib import GsmState, GsmStream, G72xUnit
+        ts, states, table, blob, total = self._gsm_tables(streams, units, GsmStream, G72xUnit, "offset", "size")
+        need = sum((len(u) * 10 + 15) & ~15 for u in units)  # 320 bytes out of 33, 640 out of 65
+        out = np.zeros(max(need, 16), np.uint8)
+        used = C.c_size_t()
+        rc = lib.sk_gsm_decode_batch(self._h, ts, len(streams), table, len(units), _ptr(blob), total, _ptr(out), out.size, C.byref(used), states, len(streams))
+        if rc == telephony.ERR_STREAM:
+            raise telephony.TelephonyError("GSM decoder rejected frame")
+        check(rc, "sk_gsm_decode_batch", self._h)
+        for i, s in enumerate(streams):
+            C.memmove(C.byref(s["state"]), C.byref(states[i]), C.sizeof(GsmState))
+        return [out[table[k].out_offset:table[k].out_offset + table[k].out_len].tobytes() for k in range(len(units))]
+
+    def tick_run_gsm(self, streams, units):
+        """One tick of GSM streams (sk_tick_run_gsm).  As tick_run_pcm, with `variant` in the place of `format` and "state": a
+        telephony.new_state(telephony.GSM) record, which is updated in place.  -> the same list of records."""
+        import ctypes as C
+        from ._lib import GsmState, GsmTickStream, PcmUnit, TickOutput
+        ts, states, table, blob, total = self._gsm_tables(streams, units, GsmTickStream, PcmUnit, "byte_offset", "byte_len")
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].channels = int(s.get("stream", 0)), 1
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_gsm_out_bound_on(self._h, ts, len(streams), table, len(units), C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_gsm(self._h, ts, len(streams), table, len(units), _ptr(blob), total, _ptr(out), out.size, recs, max_out.value,
+                                  C.byref(n_out), C.byref(used), states, len(streams)), "sk_tick_run_gsm", self._h)
+        for i, s in enumerate(streams):
+            C.memmove(C.byref(s["state"]), C.byref(states[i]), C.sizeof(GsmState))
+        return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                for r in recs[:n_out.value]]
+
     def tick_run_aiff(self, streams, units):
         """One tick of AIFF streams (sk_tick_run_aiff).  As tick_run_pcm, with `encoding` (AIFF_*) in the place of `format` and, for
         IMA4, "ima_state": [(predictor, step_index)] * 2, which is updated in the dict.  -> the same list of records."""

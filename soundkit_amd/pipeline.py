@@ -168,6 +168,20 @@ class BatchScheduler:
             raise SoundkitError(rc, "sk_pipeline_spawn_g726")
         return DecodePipelineHandle(self, handle.value)
 
+    def spawn_gsm(self, variant=0, options=None):
+        """a GSM 06.10 full-rate stream, 8 kHz mono (sk_pipeline_spawn_gsm): variant telephony.GSM_STANDARD (33-byte frames) /
+        GSM_MICROSOFT (65-byte pairs); a `send` that completes no packet gives nothing, a partial packet at the end or a frame without
+        the magic nibble is the stream's error"""
+        from . import telephony
+        telephony._check_gsm_variant(variant)
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_gsm(self._h, int(variant), C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_gsm")
+        return DecodePipelineHandle(self, handle.value)
+
     def wait_outputs(self, timeout_ms=100, cap=256):
         """Handles (as spawned: `handle.id`) that have outputs or have ended; blocks up to timeout_ms.  For callers that
         serve many streams from one thread."""
@@ -314,6 +328,10 @@ class DecodePipeline:
     @staticmethod
     def spawn_g726(rate=32000, packing=0, options=None):
         return default_scheduler().spawn_g726(rate, packing, options)
+
+    @staticmethod
+    def spawn_gsm(variant=0, options=None):
+        return default_scheduler().spawn_gsm(variant, options)
 
     @staticmethod
     def spawn_raw_pcm(format):
