@@ -533,6 +533,7 @@ void parse_some_mp3(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     if (s.resample) {
                         rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
                         if (rc != SK_OK) {
+                            s.resample = false;  // no resampler: the failed pass's row in the tick must not ask for one (the tick would refuse every stream in it)
                             r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
                             break;
                         }
@@ -658,6 +659,7 @@ void parse_some_mpa(sk_lane *p, PStream &s, uint32_t limit, Parsed &r) {
                     if (s.resample) {
                         rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
                         if (rc != SK_OK) {
+                            s.resample = false;  // no resampler: the failed pass's row in the tick must not ask for one (the tick would refuse every stream in it)
                             r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
                             break;
                         }
@@ -1255,6 +1257,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             if (s.resample) {
                 rc = sk_resampler_open(p->engine, s.engine_stream, s.rate, target);
                 if (rc != SK_OK) {  // StreamingResampler::new failing, lib.rs:3405-3417
+                    s.resample = false;  // no resampler: the failed pass's row in the tick must not ask for one (the tick would refuse every stream in it)
                     r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
                     break;
                 }

@@ -260,6 +260,173 @@ def random_access_unit(rng, sf_index, channels, dense=True):
     return w.bytes()
 
 
+# ---- the directed unit: every band of the table coded, the top one non-zero ------------------------------------------------------------
+
+def _directed_ics(rng, w, seq, grouping, max_sfb):
+    shape = int(rng.integers(2))
+    w.put(0, 1)
+    w.put(seq, 2)
+    w.put(shape, 1)
+    lens = [1]
+    if seq == EIGHT_SHORT:
+        w.put(max_sfb, 4)   # the field's 15 is the limit: Writer.put asserts it
+        w.put(grouping, 7)
+        for bit in range(7):
+            if (grouping >> (6 - bit)) & 1:
+                lens[-1] += 1
+            else:
+                lens.append(1)
+    else:
+        w.put(max_sfb, 6)
+        w.put(0, 1)  # predictor_data_present
+    return {"seq": seq, "shape": shape, "max_sfb": max_sfb, "groups": lens}
+
+
+def _directed_sections(rng, w, ics, bands, allow_intensity):
+    """per group: random books below the top band of the table, a spectral book (1..11) on it, book 0 on what lies beyond the table;
+    written as the run lengths of the row"""
+    width = 3 if ics["seq"] == EIGHT_SHORT else 5
+    esc = (1 << width) - 1
+    pool = [0] * 2 + list(range(1, 12)) * 3 + [13] * 3 + ([14, 15] * 2 if allow_intensity else [])
+    books = []
+    for _ in ics["groups"]:
+        row = []
+        while len(row) < bands - 1:
+            row += [int(rng.choice(pool))] * int(min(bands - 1 - len(row), 1 + rng.geometric(0.35)))
+        row.append(int(rng.integers(1, 12)))
+        row += [0] * (ics["max_sfb"] - bands)
+        at = 0
+        while at < len(row):
+            end = at
+            while end < len(row) and row[end] == row[at] and not (end == bands - 1 and end != at):
+                end += 1        # the top band starts a section of its own; it may run on into nothing (book 0 differs from 1..11)
+            w.put(row[at], 4)
+            rest = end - at
+            while rest >= esc:
+                w.put(esc, width)
+                rest -= esc
+            w.put(rest, width)
+            at = end
+        books.append(row)
+    return books
+
+
+def _directed_tns(rng, w, ics, bands):
+    """present; the first filter (of the first window, for eight short) is at least as long as the table has bands and has an order"""
+    w.put(1, 1)
+    short = ics["seq"] == EIGHT_SHORT
+    n_bits, len_bits, order_bits, max_order = (1, 4, 3, 7) if short else (2, 6, 5, 12)
+    for window in range(8 if short else 1):
+        n = int(rng.integers(1, 1 << n_bits)) if window == 0 else int(rng.integers(0, 1 << n_bits))
+        w.put(n, n_bits)
+        if not n:
+            continue
+        res = int(rng.integers(2))
+        w.put(res, 1)
+        for k in range(n):
+            first = window == 0 and k == 0
+            w.put(int(rng.integers(bands, 1 << len_bits)) if first else int(rng.integers(1 << len_bits)), len_bits)
+            order = int(rng.integers(1 if first else 0, max_order + 1))
+            w.put(order, order_bits)
+            if order:
+                w.put(int(rng.integers(2)), 1)
+                compress = int(rng.integers(2))
+                w.put(compress, 1)
+                bits = 3 + res - compress
+                for _ in range(order):
+                    w.put(int(rng.integers(1 << bits)), bits)
+
+
+def _nonzero_tuple(rng, w, book):
+    """one codeword of a spectral book whose values are not all zero (signs and escapes behind it); -> the values it covers"""
+    if book <= 4:
+        lo, hi, n = (-1, 2, 4) if book <= 2 else (0, 3, 4)
+    else:
+        lo, hi, n = {5: (-4, 5), 6: (-4, 5), 7: (0, 8), 8: (0, 8), 9: (0, 13), 10: (0, 13), 11: (0, 17)}[book] + (2,)
+    while True:
+        v = [int(x) for x in rng.integers(lo, hi, n)]
+        if any(v):
+            break
+    if book <= 2:
+        w.code(book, (v[0] + 1) * 27 + (v[1] + 1) * 9 + (v[2] + 1) * 3 + v[3] + 1)
+        return n
+    if book <= 4:
+        w.code(book, v[0] * 27 + v[1] * 9 + v[2] * 3 + v[3])
+    elif book <= 6:
+        w.code(book, (v[0] + 4) * 9 + v[1] + 4)
+        return n
+    else:
+        w.code(book, v[0] * hi + v[1])
+    for x in v:
+        if x:
+            w.put(int(rng.integers(2)), 1)
+    if book == 11:
+        for x in v:
+            if x == 16:
+                k = int(rng.choice(ESCAPE_SIZES))
+                for _ in range(k):
+                    w.put(1, 1)
+                w.put(0, 1)
+                w.put(int(rng.integers(1 << (k + 4))), k + 4)
+    return n
+
+
+def _directed_spectral(rng, w, ics, books, off, bands):
+    loud = float(rng.choice([0.15, 0.5, 0.9]))
+    short = ics["seq"] == EIGHT_SHORT
+    for g, glen in enumerate(ics["groups"]):
+        for sfb in range(bands):          # a band beyond the table carries book 0: nothing to write, no offset needed
+            book = books[g][sfb]
+            if 1 <= book <= 11:
+                for _ in range(glen if short else 1):
+                    done = _nonzero_tuple(rng, w, book) if sfb == bands - 1 else 0
+                    _band(rng, w, book, off[sfb + 1] - off[sfb] - done, loud)
+
+
+def _directed_body(rng, w, ics, allow_intensity, bands, gain, off):
+    """an individual_channel_stream behind its global_gain and ics_info"""
+    books = _directed_sections(rng, w, ics, bands, allow_intensity)
+    _scalefactors(rng, w, gain, books)
+    _pulse(rng, w, dict(ics, max_sfb=bands), books, off)   # pulses only inside the table
+    _directed_tns(rng, w, ics, bands)
+    w.put(0, 1)  # gain_control_data_present
+    _directed_spectral(rng, w, ics, books, off, bands)
+
+
+def directed_access_unit(rng, sf_index, channels, seq, grouping=0, over=0):
+    """One raw_data_block that reaches the top of the index's band table, which random_access_unit's uniform max_sfb rarely does:
+    max_sfb is the table's band count for `seq` plus `over`; in every group the last band inside the table carries a spectral book
+    with a non-zero value, a band beyond the table (over = 1) book 0; TNS is present and its first filter at least as long as the
+    table, so that the index's TNS band limit decides where it stops; a stereo unit is a channel pair with a common window and a
+    mid/side mask (ms_mask_present = 1) that sets the top band.  Draws from its own calls only: random_access_unit's are untouched."""
+    off = OF.short_offsets(sf_index) if seq == EIGHT_SHORT else OF.long_offsets(sf_index)
+    bands = len(off) - 1
+    w = Writer()
+    if channels == 1:
+        w.put(0, 3)
+        w.put(int(rng.integers(16)), 4)
+        gain = int(rng.integers(90, 180))
+        w.put(gain, 8)
+        ics = _directed_ics(rng, w, seq, grouping, bands + over)
+        _directed_body(rng, w, ics, False, bands, gain, off)
+    else:
+        w.put(1, 3)
+        w.put(int(rng.integers(16)), 4)
+        w.put(1, 1)                   # common_window
+        ics = _directed_ics(rng, w, seq, grouping, bands + over)
+        w.put(1, 2)                   # ms_mask_present = 1: one bit per group and band
+        for _ in ics["groups"]:
+            for sfb in range(ics["max_sfb"]):
+                w.put(1 if sfb == bands - 1 else 0 if sfb >= bands else int(rng.integers(2)), 1)
+        for right in (False, True):
+            gain = int(rng.integers(90, 180))
+            w.put(gain, 8)
+            _directed_body(rng, w, ics, right, bands, gain, off)
+    if rng.random() < 0.7:
+        w.put(7, 3)
+    return w.bytes()
+
+
 def asc_for(sf_index, channels):
     return bytes([(2 << 3) | (sf_index >> 1), ((sf_index & 1) << 7) | (channels << 3)])
 
