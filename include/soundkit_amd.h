@@ -1603,6 +1603,176 @@ int sk_gsm_decoder_flush(sk_gsm_decoder *);
 int sk_gsm_decoder_reset(sk_gsm_decoder *);
 const char *sk_gsm_decoder_last_error(const sk_gsm_decoder *);
 
+/* ---- Ogg pages and packets (host only, csrc/ogg_stream.h) ------------------------------------------------------------------- */
+/* OggPacketParser (soundkit/src/ogg.rs): bytes in any pieces in, whole packets out.  One logical stream; every page's CRC is checked;
+ * budgets: 4 MiB a call, 16 MiB a packet, 16 MiB + 64 KiB buffered.  A refusal is SK_VORBIS_ERR_STREAM with the reference's text in
+ * sk_ogg_parser_last_error (`Ogg CRC mismatch on page N`, `chained or multiplexed Ogg streams are unsupported`, `invalid Ogg capture
+ * pattern at byte N`, `Ogg input chunk exceeds the 4194304 byte streaming budget`, ...); the parser is of no use afterwards. */
+typedef struct sk_ogg_parser sk_ogg_parser;
+typedef struct sk_ogg_packet_info {
+    uint64_t granule_position; /* of the page, on the packet that ends it (has_granule) */
+    uint32_t size;
+    uint32_t serial;
+    uint8_t first_in_stream, last_in_page, last_in_stream, has_granule;
+    uint8_t reserved[4];
+} sk_ogg_packet_info;
+int sk_ogg_parser_create(sk_ogg_parser **out);
+void sk_ogg_parser_destroy(sk_ogg_parser *);
+int sk_ogg_parser_add(sk_ogg_parser *, const uint8_t *data, size_t len);
+int sk_ogg_parser_finish(sk_ogg_parser *);
+uint32_t sk_ogg_parser_pending(const sk_ogg_parser *); /* complete packets waiting */
+/* the oldest waiting packet: its record, and its bytes into `data` when data_cap holds them (then it is taken off the queue;
+ * otherwise SK_ERR_CAPACITY with info->size set and the packet stays).  SK_ERR_BAD_STREAM: none waiting. */
+int sk_ogg_parser_take(sk_ogg_parser *, sk_ogg_packet_info *info, uint8_t *data, size_t data_cap);
+const char *sk_ogg_parser_last_error(const sk_ogg_parser *);
+uint32_t sk_ogg_page_crc(const uint8_t *page, size_t len);
+
+/* ---- Vorbis I: headers and the stream's tables (host only, csrc/vorbis_stream.h) ---------------------------------------------- */
+enum sk_vorbis_status {
+    SK_VORBIS_NOT_AUDIO = -801,  /* per packet: the type bit says header */
+    SK_VORBIS_BAD_MODE = -802,   /* per packet: a mode number the setup does not have */
+    SK_VORBIS_SHORT = -803,      /* per packet: it ends inside its first bits (type, mode, window flags); also an empty packet */
+    SK_VORBIS_ERR_STREAM = -804  /* a header, an Ogg stream or a call was rejected with a text */
+};
+typedef struct sk_vorbis_ident {
+    uint32_t sample_rate;
+    uint32_t bitrate_maximum, bitrate_nominal, bitrate_minimum;
+    uint16_t blocksize_0, blocksize_1; /* 64 ... 8192, blocksize_0 <= blocksize_1 */
+    uint8_t channels;                  /* 1 ... 255 as read; the setup refuses more than 8 */
+    uint8_t reserved[3];
+} sk_vorbis_ident;
+/* Refusals are SK_VORBIS_ERR_STREAM with a text in `error` (NUL-terminated, cut to error_cap; may be NULL). */
+int sk_vorbis_parse_ident(const uint8_t *packet, size_t len, sk_vorbis_ident *out, char *error, size_t error_cap);
+int sk_vorbis_parse_comment(const uint8_t *packet, size_t len, char *error, size_t error_cap); /* walked and bounds-checked only */
+/* The setup header, parsed, validated and turned into the stream's device tables (Huffman lookup + tree, VQ values expanded to f32 as
+ * ((multiplicand * delta) + minimum) + last, floor, residue, mapping and mode records).  It is untrusted input: every book number,
+ * class and subclass book, class book dimension, coupling channel and floor X list is checked, and a code book whose lengths are neither
+ * a complete prefix code nor the one-entry case is refused.  SK_ERR_UNSUPPORTED with a text: floor type 0, more than 8 channels,
+ * tables above 4 MiB. */
+typedef struct sk_vorbis_setup sk_vorbis_setup;
+typedef struct sk_vorbis_setup_info {
+    uint32_t books, floors, residues, mappings, modes, blob_bytes;
+    uint16_t blocksize_0, blocksize_1;
+    uint8_t channels;
+    uint8_t reserved[3];
+} sk_vorbis_setup_info;
+int sk_vorbis_setup_create(const sk_vorbis_ident *, const uint8_t *packet, size_t len, sk_vorbis_setup **out, char *error, size_t error_cap);
+void sk_vorbis_setup_destroy(sk_vorbis_setup *);
+int sk_vorbis_setup_get_info(const sk_vorbis_setup *, sk_vorbis_setup_info *info);
+/* the first bits of an audio packet: SK_OK and the block size it will decode to, or the per-packet status */
+int sk_vorbis_packet_blocksize(const sk_vorbis_setup *, const uint8_t *packet, size_t len, uint32_t *blocksize);
+
+/* ---- Vorbis decode stage (GPU, csrc/vorbis_decode.hip) ------------------------------------------------------------------------- */
+/* Audio packets of one or many streams in one launch sequence.  packets[] lists stream 0's packets, then stream 1's, ...; packet k lies
+ * at bytes + packets[k].offset (a multiple of 16).  A stream enters with the block size of its previous accepted packet and that
+ * packet's windowed right half (prev_blocksize, 0 = none; overlap = [channels][prev_blocksize / 2] f32, room for blocksize_1 / 2 a
+ * channel) and leaves with both updated.  Per packet: status (SK_OK or SK_VORBIS_NOT_AUDIO / _BAD_MODE / _SHORT -- such a packet yields
+ * nothing and leaves the overlap as it was) and frames (prev / 4 + this / 4; 0 for a stream's first packet ever).  The output is the
+ * accepted packets' frames back to back, interleaved: s16 (x * 32768, saturated, truncated toward zero, as lewton's) or, as_f32 != 0,
+ * the f32 before narrowing.  out_cap and *out_len count bytes.  An out_cap too small: SK_ERR_CAPACITY with the need in *out_len, nothing
+ * decoded, the streams as they were.  A packet above 16 MiB, an offset that is no multiple of 16, a prev_blocksize that is neither of the
+ * setup's block sizes: SK_ERR_INVALID_ARG.  Not built: a device-resident form of these calls. */
+typedef struct sk_vorbis_stream {
+    const sk_vorbis_setup *setup;
+    float *overlap;
+    uint32_t n_packets;
+    uint32_t prev_blocksize;
+} sk_vorbis_stream;
+typedef struct sk_vorbis_packet {
+    uint32_t offset, size;
+} sk_vorbis_packet;
+int sk_vorbis_decode_packets(sk_engine *, sk_vorbis_stream *streams, uint32_t n_streams, const sk_vorbis_packet *packets, uint32_t n_packets,
+                             const uint8_t *bytes, size_t bytes_len, int as_f32, void *out, size_t out_cap, size_t *out_len,
+                             int32_t *status_per_packet, uint32_t *frames_per_packet);
+/* The entropy stage alone (k_vorbis_entropy), for tests that hold it to a model bit for bit: per packet the mode, the window flags,
+ * per channel the used flag, the final Y values and the posts' "used" flags, and into `residue` the packet's [channels][blocksize / 2]
+ * residue vectors as the VQ adds left them (before coupling and floor), packet after packet; a rejected packet has no place there.
+ * residue_cap and *residue_len count floats. */
+typedef struct sk_vorbis_packet_info {
+    int32_t status;
+    uint8_t mode, blockflag, prev_flag, next_flag;
+    uint32_t blocksize;
+    uint8_t used[8];
+    int16_t final_y[8][65];
+    uint8_t step2[8][65];
+} sk_vorbis_packet_info;
+int sk_vorbis_entropy_decode(sk_engine *, const sk_vorbis_stream *streams, uint32_t n_streams, const sk_vorbis_packet *packets, uint32_t n_packets,
+                             const uint8_t *bytes, size_t bytes_len, sk_vorbis_packet_info *info, float *residue, size_t residue_cap,
+                             size_t *residue_len);
+
+/* The tick of the Vorbis streams, sk_tick_run_alac's pattern with audio packets as units: packets[k] lies at bytes + packets[k].offset (a
+ * multiple of 16), stream after stream; the tick is budgeted in whole packets.  A stream's carry is the caller's, as in
+ * sk_vorbis_decode_packets (overlap, prev_blocksize: read on entry, written when the tick succeeded; on failure, or when the tick is
+ * refused -- an out_cap or outputs_cap below sk_tick_vorbis_out_bound_on's -- carries and resamplers are as they were).  The decode is
+ * sk_vorbis_decode_packets' to s16; a stream with nothing to change behind it (no rate change, out_bits = 16, out_channels = its
+ * channels) gets those bytes as its outputs, one per packet that yields frames (a stream's first packet ever and a rejected packet
+ * yield none; status_per_packet says which were rejected).  Every other stream then runs exactly what sk_tick_run_pcm runs on an
+ * interleaved s16le source of its channel count -- same kernels, records, bounds and limits; 3 ... 8 channels with a conversion need
+ * sk_engine_enable_wide_pcm.  The output does not depend on how a stream's packets are dealt out over ticks.  keep_frames cuts a
+ * packet's frames (the Ogg decoder's truncation of a stream's last packet to the final granule position); 0xffffffff keeps all. */
+typedef struct sk_vorbis_tick_packet {
+    uint32_t offset, size;
+    uint32_t keep_frames;
+    uint32_t reserved;
+} sk_vorbis_tick_packet;
+typedef struct sk_vorbis_tick_stream {
+    const sk_vorbis_setup *setup;
+    float *overlap;          /* [channels][blocksize_1 / 2] */
+    uint32_t stream;         /* engine stream (resample = 1 only) */
+    uint32_t n_units;        /* packets */
+    uint32_t prev_blocksize; /* 0: none yet */
+    uint8_t out_bits;        /* 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t channels;        /* 0, or the setup's */
+    uint8_t reserved[3];
+} sk_vorbis_tick_stream;
+size_t sk_tick_vorbis_out_bound_on(sk_engine *, const sk_vorbis_tick_stream *streams, uint32_t n_streams, const sk_vorbis_tick_packet *packets,
+                                   uint32_t n_packets, const uint8_t *bytes, size_t bytes_len, uint32_t *max_outputs);
+int sk_tick_run_vorbis(sk_engine *, sk_vorbis_tick_stream *streams, uint32_t n_streams, const sk_vorbis_tick_packet *packets, uint32_t n_packets,
+                       const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                       uint32_t *n_outputs, size_t *out_bytes_used, int32_t *status_per_packet);
+
+/* Vorbis in the scheduler.  sk_pipeline_spawn takes an Ogg Vorbis stream by its first bytes: `OggS`, and the first page's first packet
+ * begins `\x01vorbis` (any other Ogg stream goes the way it went before).  The Ogg walk and the three headers run on the entropy threads
+ * with the Ogg parser's and the header parsers' checks and texts, every audio packet is a unit of sk_tick_run_vorbis, and each packet
+ * that yields frames gives one AudioData (16 bits, or what the output options make of it), the stream's last one cut to the final granule
+ * position as VorbisDecoder cuts it.  A refusal ends the stream alone with `Decoding failed: ` and the text.
+ * sk_pipeline_spawn_vorbis_packets is the A_VORBIS case: the three header packets at the spawn (a refusal: the parser's status, its text
+ * in `error`), then demuxed audio packets, one per sk_pipeline_send; the empty send ends the stream. */
+int sk_pipeline_spawn_vorbis_packets(sk_pipeline *, const uint8_t *ident, size_t ident_len, const uint8_t *comment, size_t comment_len,
+                                     const uint8_t *setup, size_t setup_len, const sk_decode_options *opt, uint32_t *handle, char *error,
+                                     size_t error_cap);
+
+/* VorbisPacketDecoder (soundkit-vorbis/src/lib.rs:46-124): the three header packets, then raw audio packets (Matroska / WebM A_VORBIS),
+ * one per call.  *produced = 0 for a header (Ok(None)); 1 for an audio packet, with *written interleaved s16 samples in `out` (0 for the
+ * first audio packet; out_cap, in samples, must hold maximum_samples of _info).  A refused header is its parser's status with the text
+ * in _last_error and may be given again; a refused audio packet is its per-packet status, and the decoder goes on with the next. */
+typedef struct sk_vorbis_packet_decoder sk_vorbis_packet_decoder;
+int sk_vorbis_packet_decoder_create(sk_engine *, sk_vorbis_packet_decoder **out);
+void sk_vorbis_packet_decoder_destroy(sk_vorbis_packet_decoder *);
+/* SK_ERR_BAD_STREAM before the identification header */
+int sk_vorbis_packet_decoder_info(const sk_vorbis_packet_decoder *, uint32_t *sample_rate, uint8_t *channels, size_t *maximum_samples);
+int sk_vorbis_packet_decoder_decode_packet(sk_vorbis_packet_decoder *, const uint8_t *packet, size_t len, int16_t *out, size_t out_cap, size_t *written,
+                                           int *produced);
+const char *sk_vorbis_packet_decoder_last_error(const sk_vorbis_packet_decoder *);
+
+/* VorbisDecoder (soundkit-vorbis/src/lib.rs:137-296): Ogg bytes in any pieces through _add, then _finish; *written interleaved s16
+ * samples per call (0: Ok(None)), all audio packets a call completes in one launch sequence.  The reference's checks and texts:
+ * `Expected Vorbis identification header as first Ogg packet`, `Unexpected second Ogg logical bitstream`, the Ogg parser's; and its
+ * truncation of the stream's last packet to the final granule position, exactly as process_packet does it: cur_absgp becomes known at
+ * the first audio packet that ends a page and advances by each packet's samples in between.  An out_cap (in samples) too small is
+ * SK_ERR_CAPACITY with the need in *written: nothing is lost, the next call (which may add no bytes) delivers those samples first.  After
+ * any other error the decoder is of no further use (the reference's falls back to expecting an identification header). */
+typedef struct sk_vorbis_decoder sk_vorbis_decoder;
+int sk_vorbis_decoder_create(sk_engine *, sk_vorbis_decoder **out);
+void sk_vorbis_decoder_destroy(sk_vorbis_decoder *);
+int sk_vorbis_decoder_info(const sk_vorbis_decoder *, uint32_t *sample_rate, uint8_t *channels);
+int sk_vorbis_decoder_add(sk_vorbis_decoder *, const uint8_t *data, size_t len, int16_t *out, size_t out_cap, size_t *written);
+int sk_vorbis_decoder_finish(sk_vorbis_decoder *, int16_t *out, size_t out_cap, size_t *written);
+const char *sk_vorbis_decoder_last_error(const sk_vorbis_decoder *);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -506: "FlacInvalid", -507: "FlacStreamRejected",
              -601: "AlacInvalid", -602: "AlacStreamRejected", -603: "AlacUnsupportedElement",
              -701: "TelephonyStreamRejected",
+             -801: "VorbisNotAudio", -802: "VorbisBadMode", -803: "VorbisPacketShort", -804: "VorbisStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -273,6 +274,51 @@ class FlacTickStream(C.Structure):
     """sk_flac_tick_stream"""
     _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("channels", C.c_uint8), ("bits_per_sample", C.c_uint8), ("out_bits", C.c_uint8),
                 ("out_channels", C.c_uint8), ("resample", C.c_uint8), ("flush", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class OggPacketInfo(C.Structure):
+    """sk_ogg_packet_info"""
+    _fields_ = [("granule_position", C.c_uint64), ("size", C.c_uint32), ("serial", C.c_uint32)] + [
+        (n, C.c_uint8) for n in ("first_in_stream", "last_in_page", "last_in_stream", "has_granule")] + [("reserved", C.c_uint8 * 4)]
+
+
+class VorbisIdent(C.Structure):
+    """sk_vorbis_ident"""
+    _fields_ = [(n, C.c_uint32) for n in ("sample_rate", "bitrate_maximum", "bitrate_nominal", "bitrate_minimum")] + [
+        ("blocksize_0", C.c_uint16), ("blocksize_1", C.c_uint16), ("channels", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class VorbisSetupInfo(C.Structure):
+    """sk_vorbis_setup_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("books", "floors", "residues", "mappings", "modes", "blob_bytes")] + [
+        ("blocksize_0", C.c_uint16), ("blocksize_1", C.c_uint16), ("channels", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class VorbisStream(C.Structure):
+    """sk_vorbis_stream"""
+    _fields_ = [("setup", C.c_void_p), ("overlap", C.c_void_p), ("n_packets", C.c_uint32), ("prev_blocksize", C.c_uint32)]
+
+
+class VorbisTickStream(C.Structure):
+    """sk_vorbis_tick_stream"""
+    _fields_ = [("setup", C.c_void_p), ("overlap", C.c_void_p), ("stream", C.c_uint32), ("n_units", C.c_uint32), ("prev_blocksize", C.c_uint32)] + [
+        (n, C.c_uint8) for n in ("out_bits", "out_channels", "resample", "flush", "channels")] + [("reserved", C.c_uint8 * 3)]
+
+
+class VorbisTickPacket(C.Structure):
+    """sk_vorbis_tick_packet"""
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32), ("keep_frames", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class VorbisPacket(C.Structure):
+    """sk_vorbis_packet"""
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32)]
+
+
+class VorbisPacketInfo(C.Structure):
+    """sk_vorbis_packet_info"""
+    _fields_ = [("status", C.c_int32), ("mode", C.c_uint8), ("blockflag", C.c_uint8), ("prev_flag", C.c_uint8), ("next_flag", C.c_uint8),
+                ("blocksize", C.c_uint32), ("used", C.c_uint8 * 8), ("final_y", (C.c_int16 * 65) * 8), ("step2", (C.c_uint8 * 65) * 8)]
 
 
 class RawPcmFormatC(C.Structure):
@@ -589,6 +635,36 @@ _sig = {
     "sk_gsm_decoder_flush": (_i, [_vp]),
     "sk_gsm_decoder_reset": (_i, [_vp]),
     "sk_gsm_decoder_last_error": (C.c_char_p, [_vp]),
+    "sk_ogg_parser_create": (_i, [C.POINTER(_vp)]),
+    "sk_ogg_parser_destroy": (None, [_vp]),
+    "sk_ogg_parser_add": (_i, [_vp, _vp, _sz]),
+    "sk_ogg_parser_finish": (_i, [_vp]),
+    "sk_ogg_parser_pending": (_u32, [_vp]),
+    "sk_ogg_parser_take": (_i, [_vp, C.POINTER(OggPacketInfo), _vp, _sz]),
+    "sk_ogg_parser_last_error": (C.c_char_p, [_vp]),
+    "sk_ogg_page_crc": (_u32, [_vp, _sz]),
+    "sk_vorbis_parse_ident": (_i, [_vp, _sz, C.POINTER(VorbisIdent), _vp, _sz]),
+    "sk_vorbis_parse_comment": (_i, [_vp, _sz, _vp, _sz]),
+    "sk_vorbis_setup_create": (_i, [C.POINTER(VorbisIdent), _vp, _sz, C.POINTER(_vp), _vp, _sz]),
+    "sk_vorbis_setup_destroy": (None, [_vp]),
+    "sk_vorbis_setup_get_info": (_i, [_vp, C.POINTER(VorbisSetupInfo)]),
+    "sk_vorbis_packet_blocksize": (_i, [_vp, _vp, _sz, C.POINTER(_u32)]),
+    "sk_vorbis_decode_packets": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _i, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
+    "sk_vorbis_entropy_decode": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "sk_tick_vorbis_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, C.POINTER(_u32)]),
+    "sk_tick_run_vorbis": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz), _vp]),
+    "sk_pipeline_spawn_vorbis_packets": (_i, [_vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, C.POINTER(_u32), _vp, _sz]),
+    "sk_vorbis_packet_decoder_create": (_i, [_vp, C.POINTER(_vp)]),
+    "sk_vorbis_packet_decoder_destroy": (None, [_vp]),
+    "sk_vorbis_packet_decoder_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint8), C.POINTER(_sz)]),
+    "sk_vorbis_packet_decoder_decode_packet": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(_i)]),
+    "sk_vorbis_packet_decoder_last_error": (C.c_char_p, [_vp]),
+    "sk_vorbis_decoder_create": (_i, [_vp, C.POINTER(_vp)]),
+    "sk_vorbis_decoder_destroy": (None, [_vp]),
+    "sk_vorbis_decoder_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(C.c_uint8)]),
+    "sk_vorbis_decoder_add": (_i, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    "sk_vorbis_decoder_finish": (_i, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    "sk_vorbis_decoder_last_error": (C.c_char_p, [_vp]),
 }
 for _name in ("sk_pcm_interleave_i16", "sk_pcm_deinterleave_i16", "sk_pcm_deinterleave_s24", "sk_pcm_deinterleave_f32",
               "sk_pcm_interleave_f32"):

@@ -28,6 +28,8 @@
 
 #include "aac_entropy_tables.h"
 #include "alac_stream.h"
+#include "ogg_stream.h"
+#include "vorbis_stream.h"
 #include "g72x_stream.h"
 #include "gsm_stream.h"
 #include "flac_stream.h"
@@ -267,6 +269,9 @@ struct sk_engine {
     DevBuf tick_pcm_in;  // sk_tick_run_pcm: the units' bytes as they came off the wire
     DevBuf flac_in, flac_ws, flac_out;  // sk_flac_decode_frames: frames | tables | statuses, planar i32 workspace | subframe records, PCM
     DevBuf alac_in, alac_ws, alac_out;  // sk_alac_decode_packets: packets | tables | statuses, planar i32 workspace | channel records, PCM
+    DevBuf vorbis_in, vorbis_ws, vorbis_out, vorbis_tab;  // sk_vorbis_decode_packets: packets | blobs | tables | carried halves, residue | windowed PCM | classifications | records, PCM, the constants
+    sk::VorbisTables vorbis_tables{};
+    bool vorbis_tables_ready = false;
     DevBuf g72x_tab, g72x_ws;  // the telephony decode stage: stream / unit tables and state records, one word per G.722 byte
     DevBuf gsm_tab, gsm_ws;    // the GSM decode stage: stream / unit tables and state records, one s16 of short-term residual per sample
     DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
@@ -599,6 +604,10 @@ const char *sk_strerror(int status) try {
     case SK_ALAC_ERR_STREAM: return "ALAC stream rejected";
     case SK_ALAC_UNSUPPORTED: return "unsupported ALAC element";
     case SK_G72X_ERR_STREAM: return "telephony stream rejected";
+    case SK_VORBIS_NOT_AUDIO: return "not a Vorbis audio packet";
+    case SK_VORBIS_BAD_MODE: return "Vorbis packet names a mode the setup does not have";
+    case SK_VORBIS_SHORT: return "Vorbis packet ends inside its first bits";
+    case SK_VORBIS_ERR_STREAM: return "Ogg / Vorbis stream rejected";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -687,6 +696,10 @@ void sk_engine_destroy(sk_engine *e) try {
         e->alac_in.release();
         e->alac_ws.release();
         e->alac_out.release();
+        e->vorbis_in.release();
+        e->vorbis_ws.release();
+        e->vorbis_out.release();
+        e->vorbis_tab.release();
         e->g72x_tab.release();
         e->g72x_ws.release();
         e->gsm_tab.release();
@@ -7499,6 +7512,854 @@ const char *sk_gsm_decoder_last_error(const sk_gsm_decoder *d) try {
     return d ? d->error.c_str() : "";
 } catch (...) {
     (void)sk::abi_caught("sk_gsm_decoder_last_error");
+    return "";
+}
+
+}  // extern "C"
+
+// ---- Ogg and Vorbis (ogg_stream.h, vorbis_stream.h, vorbis_decode.hip) ------------------------------------------------------------
+
+struct sk_ogg_parser {
+    sk_ogg::Parser parser;
+    std::string error;
+    bool dead = false;
+};
+
+static_assert(sizeof(sk_vorbis_packet_info) == sizeof(sk::VorbisInfo) && offsetof(sk_vorbis_packet_info, final_y) == offsetof(sk::VorbisInfo, final_y) &&
+                  offsetof(sk_vorbis_packet_info, step2) == offsetof(sk::VorbisInfo, step2),
+              "the kernel writes the public record");
+
+namespace {
+
+// the engine's Vorbis constants, made on first use (engine lock held): the inverse-dB table -- the geometric series from 1.0649863e-07
+// to 1 in 255 steps -- and per block size 64 ... 8192 the window's rising half, the IMDCT's twiddles and the FFT's roots, all computed
+// in f64 and rounded to f32
+int vorbis_tables(sk_engine *e) {
+    if (e->vorbis_tables_ready) return SK_OK;
+    std::vector<float> h(256);
+    const double first = 1.0649863e-07;
+    for (int i = 0; i < 256; ++i) h[i] = (float)(first * std::pow(1.0 / first, i / 255.0));
+    size_t at_slope[8], at_tw[8], at_root[8];
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t n = 64u << k, half = n / 2, n4 = n / 4;
+        at_slope[k] = h.size();
+        for (uint32_t i = 0; i < half; ++i) {
+            const double s = std::sin((i + 0.5) / (2.0 * half) * M_PI);
+            h.push_back((float)std::sin(M_PI / 2 * (s * s)));
+        }
+        at_tw[k] = h.size();
+        for (uint32_t j = 0; j < n4; ++j) {
+            const double a = -M_PI * (8.0 * j + 1.0) / (8.0 * half);
+            h.push_back((float)std::cos(a)), h.push_back((float)std::sin(a));
+        }
+        at_root[k] = h.size();
+        for (uint32_t m = 0; m < n4 / 2; ++m) {
+            const double a = -2.0 * M_PI * m / n4;
+            h.push_back((float)std::cos(a)), h.push_back((float)std::sin(a));
+        }
+    }
+    SK_HIP(e->vorbis_tab.reserve(h.size() * 4), "alloc vorbis constants");
+    SK_HIP(hipMemcpyAsync(e->vorbis_tab.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D vorbis constants");
+    SK_HIP(hipStreamSynchronize(e->stream), "vorbis constants sync");
+    const float *d = (const float *)e->vorbis_tab.p;
+    e->vorbis_tables.inverse_db = d;
+    for (int k = 0; k < 8; ++k) {
+        e->vorbis_tables.slope[k] = d + at_slope[k];
+        e->vorbis_tables.twiddle[k] = (const float2 *)(d + at_tw[k]);
+        e->vorbis_tables.root[k] = (const float2 *)(d + at_root[k]);
+    }
+    e->vorbis_tables_ready = true;
+    return SK_OK;
+}
+
+enum VorbisWhat { kVorbisS16 = 0, kVorbisF32 = 1, kVorbisEntropy = 2 };
+
+// the tick's form of the decode: the samples stay on the device, packet k's at base + 2 * offsets[k] (s16); the caller holds the engine's
+// lock and its device
+struct VorbisDevDst {
+    uint8_t *base = nullptr;
+    std::vector<uint64_t> offsets;  // per packet of the call, in samples
+    std::vector<uint32_t> keep;     // per packet: at most so many of its frames (0xffffffff: all)
+};
+
+// sk_vorbis_decode_packets and sk_vorbis_entropy_decode.  The host reads every packet's first bits itself (sk_vorbis::packet_head), so the
+// place of every packet in the workspaces and in the output is known before anything is launched.  The host decides: a packet it refuses
+// gets no lane and keeps the host's status.  The device reads the bits of the accepted packets again as a guard; should it ever
+// disagree, the call is SK_ERR_INTERNAL.
+int vorbis_run(sk_engine *e, sk_vorbis_stream *streams, uint32_t n_streams, const sk_vorbis_packet *packets, uint32_t n_packets, const uint8_t *bytes,
+               size_t bytes_len, VorbisWhat what, void *out, size_t out_cap, size_t *out_len, int32_t *status, uint32_t *frames,
+               sk_vorbis_packet_info *info, const VorbisDevDst *dev = nullptr) {
+    if (!e || !out_len || (n_streams && !streams) || (n_packets && (!packets || !bytes || (!out && !dev)))) return SK_ERR_INVALID_ARG;
+    if (what == kVorbisEntropy ? (n_packets && !info) : (n_packets && (!status || !frames))) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (bytes_len > 0x7fffff00u) return SK_ERR_INVALID_ARG;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    std::vector<sk::VorbisPacket> table(n_packets);
+    std::vector<uint32_t> order, blobs;
+    std::vector<int32_t> head_status(n_packets, 0);
+    std::vector<std::pair<const sk_vorbis_setup *, uint32_t>> blob_of;
+    std::vector<sk::VorbisCarry> carries(n_streams);  // offset: the stream's part of the carry buffer, entering and leaving
+    uint64_t res_floats = 0, pcm_floats = 0, cls_bytes = 0, carry_floats = 0, out_samples = 0, at = 0;
+    uint32_t max_channels = 0;
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        sk_vorbis_stream &st = streams[s];
+        if (!st.setup || (uint64_t)at + st.n_packets > n_packets) return SK_ERR_INVALID_ARG;
+        const sk_vorbis::Setup &su = st.setup->setup;
+        if (st.prev_blocksize && st.prev_blocksize != su.bs[0] && st.prev_blocksize != su.bs[1]) return SK_ERR_INVALID_ARG;
+        if (what != kVorbisEntropy && !st.overlap) return SK_ERR_INVALID_ARG;
+        uint32_t blob = 0xffffffffu;
+        for (auto &b : blob_of)
+            if (b.first == st.setup) blob = b.second;
+        if (blob == 0xffffffffu) {
+            blob = (uint32_t)blobs.size();
+            blob_of.emplace_back(st.setup, blob);
+            blobs.insert(blobs.end(), su.blob.begin(), su.blob.end());
+            if (blobs.size() > (1u << 28)) return SK_ERR_CAPACITY;
+        }
+        const uint32_t ch = su.channels;
+        max_channels = std::max(max_channels, ch);
+        carries[s] = {0xffffffffu, (uint32_t)carry_floats};
+        carry_floats += (uint64_t)ch * (su.bs[1] / 2);
+        uint32_t prev_n = st.prev_blocksize, prev_pcm = carries[s].offset, prev_in_carry = 1;
+        for (uint32_t k = 0; k < st.n_packets; ++k, ++at) {
+            const sk_vorbis_packet &p = packets[at];
+            if ((p.offset & 15u) || p.size > sk_vorbis::kMaxPacketBytes || (uint64_t)p.offset + p.size > bytes_len) return SK_ERR_INVALID_ARG;
+            sk::VorbisPacket &t = table[at];
+            t = sk::VorbisPacket{};
+            t.byte_offset = p.offset, t.byte_len = p.size, t.blob = blob, t.channels = ch;
+            sk_vorbis::PacketHead h;
+            head_status[at] = sk_vorbis::packet_head(su, bytes + p.offset, p.size, &h);
+            if (head_status[at] != sk_vorbis::kOk) continue;
+            t.n = h.n;
+            t.res_offset = (uint32_t)res_floats, t.cls_offset = (uint32_t)cls_bytes, t.pcm_offset = (uint32_t)pcm_floats;
+            res_floats += (uint64_t)ch * (h.n / 2), cls_bytes += up16((uint64_t)ch * (h.n / 2)), pcm_floats += (uint64_t)ch * h.n;
+            t.prev_n = prev_n, t.prev_pcm = prev_pcm, t.prev_in_carry = prev_in_carry;
+            t.out_frames = prev_n ? prev_n / 4 + h.n / 4 : 0;
+            if (dev) t.out_frames = std::min(t.out_frames, dev->keep[at]);
+            t.out_offset = dev ? dev->offsets[at] : out_samples;
+            out_samples += (uint64_t)t.out_frames * ch;
+            prev_n = h.n, prev_pcm = t.pcm_offset + h.n / 2, prev_in_carry = 0;
+            carries[s].packet = (uint32_t)at;
+            order.push_back((uint32_t)at);
+            if (res_floats > 0x3fffffffu || pcm_floats > 0x3fffffffu || cls_bytes > 0x7fffffffu) return SK_ERR_CAPACITY;
+        }
+    }
+    if (at != n_packets) return SK_ERR_INVALID_ARG;
+    const size_t width = what == kVorbisS16 ? 2 : 4;
+    const uint64_t need = what == kVorbisEntropy ? res_floats * 4 : out_samples * width;
+    if (!dev && need > out_cap) {  // nothing decoded, nothing carried: the caller comes again with room
+        *out_len = (size_t)(what == kVorbisEntropy ? need / 4 : need);
+        return SK_ERR_CAPACITY;
+    }
+    if (n_packets == 0) return SK_OK;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return table[x].byte_len > table[y].byte_len; });
+
+    std::unique_lock<std::mutex> lock(e->mu, std::defer_lock);
+    std::unique_ptr<DeviceGuard> guard;
+    if (!dev) {
+        lock.lock();
+        guard.reset(new DeviceGuard(e));
+    }
+    if (const int rc = vorbis_tables(e)) return rc;
+    // vorbis_in: bytes (16 readable bytes behind them) | blobs | packet table | order | carried halves | carry records
+    const size_t at_blobs = up16(bytes_len + 16), at_table = at_blobs + up16(blobs.size() * 4), at_order = at_table + up16(table.size() * sizeof(sk::VorbisPacket)),
+                 at_carry = at_order + up16(order.size() * 4 + 4), at_crec = at_carry + up16((size_t)carry_floats * 4 + 4),
+                 in_len = at_crec + up16(carries.size() * sizeof(sk::VorbisCarry) + 4);
+    // vorbis_ws: residue vectors | windowed halves | classifications | records
+    const size_t at_pcm = up16((size_t)res_floats * 4 + 4), at_cls = at_pcm + up16((size_t)pcm_floats * 4 + 4), at_info = at_cls + up16((size_t)cls_bytes + 4),
+                 ws_len = at_info + (size_t)n_packets * sizeof(sk::VorbisInfo);
+    SK_HIP(e->vorbis_in.reserve(in_len), "alloc vorbis input");
+    SK_HIP(e->vorbis_ws.reserve(ws_len), "alloc vorbis workspace");
+    if (!dev) SK_HIP(e->vorbis_out.reserve(std::max<size_t>((size_t)need, 16)), "alloc vorbis output");
+    uint8_t *d_in = (uint8_t *)e->vorbis_in.p, *d_ws = (uint8_t *)e->vorbis_ws.p;
+    SK_HIP(hipMemsetAsync(d_in + (bytes_len & ~(size_t)3), 0, at_blobs - (bytes_len & ~(size_t)3), e->stream), "clear vorbis padding");
+    SK_HIP(hipMemcpyAsync(d_in, bytes, bytes_len, hipMemcpyHostToDevice, e->stream), "H2D vorbis packets");
+    SK_HIP(hipMemcpyAsync(d_in + at_blobs, blobs.data(), blobs.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D vorbis blobs");
+    SK_HIP(hipMemcpyAsync(d_in + at_table, table.data(), table.size() * sizeof(sk::VorbisPacket), hipMemcpyHostToDevice, e->stream), "H2D vorbis table");
+    if (!order.empty()) SK_HIP(hipMemcpyAsync(d_in + at_order, order.data(), order.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D vorbis order");
+    std::vector<float> h_carry;  // every stream's half in one copy each way: thousands of small copies cost more than the kernels
+    if (what != kVorbisEntropy) {
+        h_carry.assign((size_t)carry_floats, 0.0f);
+        for (uint32_t s = 0; s < n_streams; ++s)
+            if (streams[s].prev_blocksize)
+                std::memcpy(&h_carry[carries[s].offset], streams[s].overlap, (size_t)streams[s].setup->setup.channels * (streams[s].prev_blocksize / 2) * 4);
+        SK_HIP(hipMemcpyAsync(d_in + at_carry, h_carry.data(), h_carry.size() * 4, hipMemcpyHostToDevice, e->stream), "H2D vorbis overlap");
+        SK_HIP(hipMemcpyAsync(d_in + at_crec, carries.data(), carries.size() * sizeof(sk::VorbisCarry), hipMemcpyHostToDevice, e->stream), "H2D vorbis carries");
+    }
+    SK_HIP(hipMemsetAsync(d_ws, 0, at_pcm, e->stream), "clear vorbis residue");
+    SK_HIP(hipMemsetAsync(d_ws + at_info, 0, (size_t)n_packets * sizeof(sk::VorbisInfo), e->stream), "clear vorbis records");
+    const sk::VorbisPacket *d_table = (const sk::VorbisPacket *)(d_in + at_table);
+    const uint32_t *d_blobs = (const uint32_t *)(d_in + at_blobs);
+    sk::VorbisInfo *d_info = (sk::VorbisInfo *)(d_ws + at_info);
+    float *d_res = (float *)d_ws, *d_pcm = (float *)(d_ws + at_pcm);
+    SK_HIP(sk::launch_vorbis_entropy(d_table, (const uint32_t *)(d_in + at_order), (uint32_t)order.size(), d_blobs, d_in, d_res, d_ws + at_cls, d_info, e->stream),
+           "launch vorbis entropy");
+    if (what == kVorbisEntropy) {
+        std::vector<sk::VorbisInfo> h_info(n_packets);
+        SK_HIP(hipMemcpyAsync(h_info.data(), d_info, (size_t)n_packets * sizeof(sk::VorbisInfo), hipMemcpyDeviceToHost, e->stream), "D2H vorbis records");
+        if (res_floats) SK_HIP(hipMemcpyAsync(out, d_res, (size_t)res_floats * 4, hipMemcpyDeviceToHost, e->stream), "D2H vorbis residue");
+        SK_HIP(hipStreamSynchronize(e->stream), "vorbis sync");
+        for (uint32_t i = 0; i < n_packets; ++i) {
+            std::memcpy(&info[i], &h_info[i], sizeof(sk::VorbisInfo));
+            if (head_status[i] != 0) info[i].status = head_status[i];
+        }
+        *out_len = (size_t)res_floats;
+        return SK_OK;
+    }
+    SK_HIP(sk::launch_vorbis_spectrum(d_table, n_packets, d_blobs, d_info, d_res, e->vorbis_tables, e->stream), "launch vorbis spectrum");
+    SK_HIP(sk::launch_vorbis_imdct(d_table, n_packets, d_blobs, d_info, d_res, d_pcm, max_channels, e->vorbis_tables, e->stream), "launch vorbis imdct");
+    SK_HIP(sk::launch_vorbis_ola(d_table, n_packets, d_info, d_pcm, (const float *)(d_in + at_carry), dev ? (void *)dev->base : e->vorbis_out.p, what == kVorbisF32,
+                                 e->stream),
+           "launch vorbis ola");
+    SK_HIP(sk::launch_vorbis_carry(d_table, (const sk::VorbisCarry *)(d_in + at_crec), n_streams, d_pcm, (float *)(d_in + at_carry), e->stream),
+           "launch vorbis carry");
+    SK_HIP(hipMemcpyAsync(h_carry.data(), d_in + at_carry, h_carry.size() * 4, hipMemcpyDeviceToHost, e->stream), "D2H vorbis overlap");
+    std::vector<int32_t> d_status(n_packets);  // the records' status words alone: a record is 1 580 bytes
+    SK_HIP(hipMemcpy2DAsync(d_status.data(), 4, d_info, sizeof(sk::VorbisInfo), 4, n_packets, hipMemcpyDeviceToHost, e->stream), "D2H vorbis statuses");
+    if (need && !dev) SK_HIP(hipMemcpyAsync(out, e->vorbis_out.p, (size_t)need, hipMemcpyDeviceToHost, e->stream), "D2H vorbis PCM");
+    SK_HIP(hipStreamSynchronize(e->stream), "vorbis sync");
+    for (uint32_t i = 0; i < n_packets; ++i) {
+        status[i] = head_status[i] != 0 ? head_status[i] : d_status[i];
+        frames[i] = status[i] == 0 ? table[i].out_frames : 0;
+        if (head_status[i] == 0 && d_status[i] != 0) return SK_ERR_INTERNAL;  // the device read other first bits than the host
+    }
+    // the halves the streams leave with: the right half of each stream's last accepted packet
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        if (carries[s].packet == 0xffffffffu) continue;
+        const sk::VorbisPacket &t = table[carries[s].packet];
+        std::memcpy(streams[s].overlap, &h_carry[carries[s].offset], (size_t)t.channels * (t.n / 2) * 4);
+        streams[s].prev_blocksize = t.n;
+    }
+    *out_len = (size_t)need;
+    return SK_OK;
+}
+
+
+// sk_tick_run_vorbis / sk_tick_vorbis_out_bound_on: what stands in front of the PCM tick's body.  The host reads every packet's first
+// bits, so the frames each packet yields (prev / 4 + this / 4; none for a stream's first packet ever and for a refused one) are known:
+// the packets that yield frames are the body's units, interleaved s16le of the stream's channel count, 16-byte aligned one after the
+// other.  The decode works on copies of the streams' carries; they become the caller's only when the whole tick succeeded.
+struct VorbisDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;         // the decoded layout: one per packet that yields frames
+    std::vector<uint32_t> first_packet;     // per stream
+    std::vector<uint32_t> unit_of;          // per packet: its unit within its stream, or 0xffffffff
+    std::vector<uint32_t> packet_of;        // per unit of the call: its packet
+    std::vector<uint32_t> frames;           // per packet
+    std::vector<int32_t> status;            // per packet: the host's reading, then the decode's
+    std::vector<std::vector<float>> overlap;
+    std::vector<uint32_t> prev;
+    AiffTick tick;
+};
+
+int vorbis_tick_derive(const sk_vorbis_tick_stream *vs, uint32_t n_streams, const sk_vorbis_tick_packet *packets, uint32_t n_packets, const uint8_t *bytes,
+                       size_t bytes_len, VorbisDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.clear(), d.packet_of.clear();
+    d.first_packet.assign(n_streams, 0);
+    d.unit_of.assign(n_packets, 0xffffffffu);
+    d.frames.assign(n_packets, 0);
+    d.status.assign(n_packets, 0);
+    d.overlap.assign(n_streams, {});
+    d.prev.assign(n_streams, 0);
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    uint64_t at = 0, cursor = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_vorbis_tick_stream &v = vs[i];
+        if (!v.setup || !v.overlap || at + v.n_units > n_packets) return SK_ERR_INVALID_ARG;
+        const sk_vorbis::Setup &su = v.setup->setup;
+        if (v.prev_blocksize && v.prev_blocksize != su.bs[0] && v.prev_blocksize != su.bs[1]) return SK_ERR_INVALID_ARG;
+        const uint32_t ch = su.channels;
+        if (v.channels && v.channels != ch) return SK_ERR_INVALID_ARG;
+        d.first_packet[i] = (uint32_t)at;
+        d.prev[i] = v.prev_blocksize;
+        d.overlap[i].assign(v.overlap, v.overlap + (size_t)ch * (su.bs[1] / 2));
+        uint32_t prev = v.prev_blocksize, n_units = 0;
+        for (uint32_t u = 0; u < v.n_units; ++u, ++at) {
+            const sk_vorbis_tick_packet &p = packets[at];
+            if ((p.offset & 15u) || p.size > sk_vorbis::kMaxPacketBytes || (uint64_t)p.offset + p.size > bytes_len) return SK_ERR_INVALID_ARG;
+            sk_vorbis::PacketHead h;
+            d.status[at] = sk_vorbis::packet_head(su, bytes + p.offset, p.size, &h);
+            if (d.status[at] != sk_vorbis::kOk) continue;
+            d.frames[at] = std::min(prev ? prev / 4 + h.n / 4 : 0, p.keep_frames);
+            prev = h.n;
+            if (!d.frames[at]) continue;
+            const uint64_t decoded = (uint64_t)d.frames[at] * ch * 2;
+            d.unit_of[at] = n_units++;
+            d.packet_of.push_back((uint32_t)at);
+            d.units.push_back(sk_pcm_unit{cursor, (uint32_t)decoded, 0});
+            cursor += (decoded + 15) & ~15ull;
+        }
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = v.stream, t.n_units = n_units, t.channels = (uint8_t)ch, t.out_bits = v.out_bits, t.out_channels = v.out_channels;
+        t.resample = v.resample, t.flush = v.flush, t.format = SK_FMT_S16LE;
+        d.tick.plain[i] = !v.resample && v.out_bits == 16 && v.out_channels == ch;
+    }
+    if (cursor > 0x7fffffffull || bytes_len > 0x7fffff00ull) return SK_ERR_INVALID_ARG;
+    d.tick.decoded_len = (size_t)cursor;
+    return at == n_packets ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// one pass of the decode in front of the body: every packet of the streams whose `plain` is as_is (also of a stream that yields nothing
+// in this tick: its carry moves on), each packet's frames to where dst_of puts its unit
+int vorbis_tick_decode(sk_engine *e, const sk_vorbis_tick_stream *vs, const sk_vorbis_tick_packet *packets, const uint8_t *bytes, size_t bytes_len, VorbisDerived &d,
+                       bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of) {
+    std::vector<sk_vorbis_stream> sub;
+    std::vector<uint32_t> sub_of, index;
+    std::vector<sk_vorbis_packet> subp;
+    std::vector<uint8_t *> dst;
+    std::vector<uint32_t> keep;
+    uint8_t *base = nullptr;
+    for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
+        if ((d.tick.plain[i] != 0) != as_is || vs[i].n_units == 0) continue;
+        sub.push_back(sk_vorbis_stream{vs[i].setup, d.overlap[i].data(), vs[i].n_units, d.prev[i]});
+        sub_of.push_back(i);
+        for (uint32_t u = 0; u < vs[i].n_units; ++u) {
+            const uint32_t g = d.first_packet[i] + u;
+            uint8_t *to = d.unit_of[g] != 0xffffffffu ? dst_of(i, d.unit_of[g]) : nullptr;
+            if (to && (!base || to < base)) base = to;
+            index.push_back(g), subp.push_back(sk_vorbis_packet{packets[g].offset, packets[g].size}), dst.push_back(to), keep.push_back(packets[g].keep_frames);
+        }
+    }
+    if (sub.empty()) return SK_OK;
+    VorbisDevDst dev;
+    dev.base = base;
+    dev.offsets.assign(dst.size(), 0);
+    dev.keep = keep;
+    for (size_t k = 0; k < dst.size(); ++k)
+        if (dst[k]) dev.offsets[k] = (uint64_t)(dst[k] - base) / 2;
+    std::vector<int32_t> status(index.size(), 0);
+    std::vector<uint32_t> frames(index.size(), 0);
+    size_t len = 0;
+    const int rc = vorbis_run(e, sub.data(), (uint32_t)sub.size(), subp.data(), (uint32_t)subp.size(), bytes, bytes_len, kVorbisS16, nullptr, 0, &len,
+                              status.data(), frames.data(), nullptr, &dev);
+    if (rc != SK_OK) return rc;
+    for (size_t k = 0; k < index.size(); ++k) {
+        if (frames[k] != d.frames[index[k]]) return SK_ERR_INTERNAL;  // the plan and the decode read the same first bits
+        d.status[index[k]] = status[k];
+    }
+    for (size_t k = 0; k < sub.size(); ++k) d.prev[sub_of[k]] = sub[k].prev_blocksize;
+    return SK_OK;
+}
+
+void vorbis_text(char *error, size_t cap, const std::string &text) {
+    if (!error || cap == 0) return;
+    const size_t n = std::min(cap - 1, text.size());
+    std::memcpy(error, text.data(), n);
+    error[n] = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sk_ogg_parser_create(sk_ogg_parser **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_ogg_parser();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ogg_parser_create");
+}
+
+void sk_ogg_parser_destroy(sk_ogg_parser *p) try {
+    sk::abi_enter();
+    delete p;
+} catch (...) {
+    (void)sk::abi_caught("sk_ogg_parser_destroy");
+}
+
+int sk_ogg_parser_add(sk_ogg_parser *p, const uint8_t *data, size_t len) try {
+    sk::abi_enter();
+    if (!p || (len && !data)) return SK_ERR_INVALID_ARG;
+    if (p->dead) return SK_VORBIS_ERR_STREAM;
+    if (p->parser.add(data, len, &p->error)) return SK_OK;
+    p->dead = true;
+    return SK_VORBIS_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_ogg_parser_add");
+}
+
+int sk_ogg_parser_finish(sk_ogg_parser *p) try {
+    sk::abi_enter();
+    if (!p) return SK_ERR_INVALID_ARG;
+    if (p->dead) return SK_VORBIS_ERR_STREAM;
+    if (p->parser.finish(&p->error)) return SK_OK;
+    p->dead = true;
+    return SK_VORBIS_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_ogg_parser_finish");
+}
+
+uint32_t sk_ogg_parser_pending(const sk_ogg_parser *p) try {
+    sk::abi_enter();
+    return p ? (uint32_t)p->parser.pending.size() : 0;
+} catch (...) {
+    (void)sk::abi_caught("sk_ogg_parser_pending");
+    return 0;
+}
+
+int sk_ogg_parser_take(sk_ogg_parser *p, sk_ogg_packet_info *info, uint8_t *data, size_t data_cap) try {
+    sk::abi_enter();
+    if (!p || !info) return SK_ERR_INVALID_ARG;
+    if (p->parser.pending.empty()) return SK_ERR_BAD_STREAM;
+    const sk_ogg::Packet &k = p->parser.pending.front();
+    *info = sk_ogg_packet_info{};
+    info->granule_position = k.granule_position, info->size = (uint32_t)k.data.size(), info->serial = k.serial;
+    info->first_in_stream = k.first_in_stream, info->last_in_page = k.last_in_page, info->last_in_stream = k.last_in_stream, info->has_granule = k.has_granule;
+    if (k.data.size() > data_cap || (!data && !k.data.empty())) return SK_ERR_CAPACITY;
+    if (!k.data.empty()) std::memcpy(data, k.data.data(), k.data.size());
+    p->parser.pending.pop_front();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ogg_parser_take");
+}
+
+const char *sk_ogg_parser_last_error(const sk_ogg_parser *p) try {
+    sk::abi_enter();
+    return p ? p->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_ogg_parser_last_error");
+    return "";
+}
+
+uint32_t sk_ogg_page_crc(const uint8_t *page, size_t len) try {
+    sk::abi_enter();
+    return page ? sk_ogg::page_crc(page, len) : 0;
+} catch (...) {
+    (void)sk::abi_caught("sk_ogg_page_crc");
+    return 0;
+}
+
+int sk_vorbis_parse_ident(const uint8_t *packet, size_t len, sk_vorbis_ident *out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !packet) || !out) return SK_ERR_INVALID_ARG;
+    vorbis_text(error, error_cap, "");
+    sk_vorbis::Ident id;
+    std::string text;
+    if (const int rc = sk_vorbis::parse_ident(packet, len, &id, &text)) {
+        vorbis_text(error, error_cap, text);
+        return rc;
+    }
+    *out = sk_vorbis_ident{};
+    out->sample_rate = id.sample_rate, out->bitrate_maximum = id.bitrate_maximum, out->bitrate_nominal = id.bitrate_nominal;
+    out->bitrate_minimum = id.bitrate_minimum, out->blocksize_0 = id.blocksize_0, out->blocksize_1 = id.blocksize_1, out->channels = id.channels;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_parse_ident");
+}
+
+int sk_vorbis_parse_comment(const uint8_t *packet, size_t len, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if (len && !packet) return SK_ERR_INVALID_ARG;
+    vorbis_text(error, error_cap, "");
+    std::string text;
+    const int rc = sk_vorbis::parse_comment(packet, len, &text);
+    if (rc) vorbis_text(error, error_cap, text);
+    return rc;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_parse_comment");
+}
+
+int sk_vorbis_setup_create(const sk_vorbis_ident *ident, const uint8_t *packet, size_t len, sk_vorbis_setup **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if (!ident || (len && !packet) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    vorbis_text(error, error_cap, "");
+    const uint32_t b0 = ident->blocksize_0, b1 = ident->blocksize_1;
+    if (ident->channels == 0 || b0 < 64 || b1 > 8192 || b0 > b1 || (b0 & (b0 - 1)) || (b1 & (b1 - 1))) return SK_ERR_INVALID_ARG;
+    sk_vorbis::Ident id;
+    id.sample_rate = ident->sample_rate, id.blocksize_0 = ident->blocksize_0, id.blocksize_1 = ident->blocksize_1, id.channels = ident->channels;
+    std::unique_ptr<sk_vorbis_setup> s(new sk_vorbis_setup());
+    std::string text;
+    if (const int rc = sk_vorbis::parse_setup(packet, len, id, &s->setup, &text)) {
+        vorbis_text(error, error_cap, text);
+        return rc;
+    }
+    *out = s.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_setup_create");
+}
+
+void sk_vorbis_setup_destroy(sk_vorbis_setup *s) try {
+    sk::abi_enter();
+    delete s;
+} catch (...) {
+    (void)sk::abi_caught("sk_vorbis_setup_destroy");
+}
+
+int sk_vorbis_setup_get_info(const sk_vorbis_setup *s, sk_vorbis_setup_info *info) try {
+    sk::abi_enter();
+    if (!s || !info) return SK_ERR_INVALID_ARG;
+    *info = sk_vorbis_setup_info{};
+    const sk_vorbis::Setup &u = s->setup;
+    info->books = (uint32_t)u.books.size(), info->floors = (uint32_t)u.floors.size(), info->residues = (uint32_t)u.residues.size();
+    info->mappings = (uint32_t)u.mappings.size(), info->modes = (uint32_t)u.modes.size(), info->blob_bytes = (uint32_t)(u.blob.size() * 4);
+    info->blocksize_0 = (uint16_t)u.bs[0], info->blocksize_1 = (uint16_t)u.bs[1], info->channels = (uint8_t)u.channels;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_setup_get_info");
+}
+
+int sk_vorbis_packet_blocksize(const sk_vorbis_setup *s, const uint8_t *packet, size_t len, uint32_t *blocksize) try {
+    sk::abi_enter();
+    if (!s || (len && !packet) || !blocksize) return SK_ERR_INVALID_ARG;
+    sk_vorbis::PacketHead h;
+    const int rc = sk_vorbis::packet_head(s->setup, packet, len, &h);
+    *blocksize = rc ? 0 : h.n;
+    return rc;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_packet_blocksize");
+}
+
+int sk_vorbis_decode_packets(sk_engine *e, sk_vorbis_stream *streams, uint32_t n_streams, const sk_vorbis_packet *packets, uint32_t n_packets,
+                             const uint8_t *bytes, size_t bytes_len, int as_f32, void *out, size_t out_cap, size_t *out_len, int32_t *status_per_packet,
+                             uint32_t *frames_per_packet) try {
+    sk::abi_enter();
+    return vorbis_run(e, streams, n_streams, packets, n_packets, bytes, bytes_len, as_f32 ? kVorbisF32 : kVorbisS16, out, out_cap, out_len, status_per_packet,
+                      frames_per_packet, nullptr);
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_decode_packets");
+}
+
+size_t sk_tick_vorbis_out_bound_on(sk_engine *e, const sk_vorbis_tick_stream *vs, uint32_t n_streams, const sk_vorbis_tick_packet *packets, uint32_t n_packets,
+                                   const uint8_t *bytes, size_t bytes_len, uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!vs && n_streams) || (n_packets && (!packets || !bytes))) return 0;
+    VorbisDerived d;
+    if (vorbis_tick_derive(vs, n_streams, packets, n_packets, bytes, bytes_len, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), (uint32_t)d.units.size(), max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_vorbis_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_vorbis(sk_engine *e, sk_vorbis_tick_stream *vs, uint32_t n_streams, const sk_vorbis_tick_packet *packets, uint32_t n_packets, const uint8_t *bytes,
+                       size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
+                       int32_t *status_per_packet) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && !vs) || (n_packets && (!packets || !bytes || !status_per_packet))) return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    VorbisDerived d;
+    int rc = vorbis_tick_derive(vs, n_streams, packets, n_packets, bytes, bytes_len, d);
+    if (rc != SK_OK) return rc;
+    d.tick.decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *) {
+        return vorbis_tick_decode(e, vs, packets, bytes, bytes_len, d, as_is, dst_of);
+    };
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), (uint32_t)d.units.size(), bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes,
+                       &d.tick);
+    if (rc != SK_OK) return rc;  // the carries are the caller's: untouched
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        std::memcpy(vs[i].overlap, d.overlap[i].data(), d.overlap[i].size() * 4);
+        vs[i].prev_blocksize = d.prev[i];
+    }
+    for (uint32_t g = 0; g < n_packets; ++g) status_per_packet[g] = d.status[g];
+    // the records of a stream delivered as decoded say what its packets are: one per packet that yielded frames
+    std::vector<uint32_t> seen(n_streams, 0), first_unit(n_streams, 0);
+    for (uint32_t i = 1; i < n_streams; ++i) first_unit[i] = first_unit[i - 1] + d.ts[i - 1].n_units;
+    for (uint32_t k = 0; k < *n_outs; ++k) {
+        sk_tick_output &o = outs[k];
+        const uint32_t i = o.stream_index;
+        if (!d.tick.plain[i]) continue;
+        const uint32_t g = d.packet_of[first_unit[i] + seen[i]++];
+        o.frames = d.frames[g], o.channels = d.ts[i].channels, o.bits = 16, o.status = 0;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_vorbis");
+}
+
+int sk_vorbis_entropy_decode(sk_engine *e, const sk_vorbis_stream *streams, uint32_t n_streams, const sk_vorbis_packet *packets, uint32_t n_packets,
+                             const uint8_t *bytes, size_t bytes_len, sk_vorbis_packet_info *info, float *residue, size_t residue_cap, size_t *residue_len) try {
+    sk::abi_enter();
+    if (residue_cap > SIZE_MAX / 4) return SK_ERR_INVALID_ARG;
+    return vorbis_run(e, const_cast<sk_vorbis_stream *>(streams), n_streams, packets, n_packets, bytes, bytes_len, kVorbisEntropy, residue, residue_cap * 4,
+                      residue_len, nullptr, nullptr, info);
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_entropy_decode");
+}
+
+}  // extern "C"
+
+// ---- VorbisPacketDecoder and VorbisDecoder (soundkit-vorbis/src/lib.rs) over the calls above -----------------------------------------
+
+struct sk_vorbis_packet_decoder {
+    sk_engine *eng = nullptr;
+    int headers = 0;  // header packets taken: 0 ... 3
+    sk_vorbis::Ident ident;
+    std::unique_ptr<sk_vorbis_setup> setup;
+    std::vector<float> overlap;
+    uint32_t prev_blocksize = 0;
+    std::string error;
+
+    // the three headers in order; SK_OK or the parser's status with its text in error
+    int header(const uint8_t *p, size_t len) {
+        int rc = SK_OK;
+        if (headers == 0) {
+            rc = sk_vorbis::parse_ident(p, len, &ident, &error);
+        } else if (headers == 1) {
+            rc = sk_vorbis::parse_comment(p, len, &error);
+        } else {
+            std::unique_ptr<sk_vorbis_setup> s(new sk_vorbis_setup());
+            rc = sk_vorbis::parse_setup(p, len, ident, &s->setup, &error);
+            if (rc == SK_OK) {
+                setup = std::move(s);
+                overlap.assign((size_t)ident.channels * (ident.blocksize_1 / 2), 0.0f);
+            }
+        }
+        if (rc == SK_OK) ++headers;
+        return rc;
+    }
+};
+
+struct sk_vorbis_decoder {
+    sk_vorbis_packet_decoder dec;
+    sk_ogg::Parser parser;
+    uint32_t serial = 0;
+    bool have_absgp = false, dead = false;
+    uint64_t absgp = 0;
+    std::vector<int16_t> pending;  // samples a call could not hand over (SK_ERR_CAPACITY): the next call's first
+    std::string error;
+};
+
+namespace {
+
+// the audio packets of one call through sk_vorbis_decode_packets' body -> their samples, one vector per packet
+int vorbis_decode_some(sk_vorbis_packet_decoder &d, const std::vector<const std::vector<uint8_t> *> &packets, std::vector<std::vector<int16_t>> *out,
+                       std::vector<int32_t> *status) {
+    const uint32_t n = (uint32_t)packets.size();
+    std::vector<uint8_t> bytes;
+    std::vector<sk_vorbis_packet> table(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        bytes.resize((bytes.size() + 15) & ~(size_t)15);
+        table[i] = {(uint32_t)bytes.size(), (uint32_t)packets[i]->size()};
+        bytes.insert(bytes.end(), packets[i]->begin(), packets[i]->end());
+    }
+    if (bytes.empty()) bytes.resize(16);
+    const uint32_t ch = d.ident.channels;
+    std::vector<int16_t> pcm((size_t)n * (d.ident.blocksize_1 / 2) * ch + 8);
+    std::vector<uint32_t> frames(n);
+    status->assign(n, 0);
+    sk_vorbis_stream st{d.setup.get(), d.overlap.data(), n, d.prev_blocksize};
+    size_t used = 0;
+    const int rc = vorbis_run(d.eng, &st, 1, table.data(), n, bytes.data(), bytes.size(), kVorbisS16, pcm.data(), pcm.size() * 2, &used, status->data(),
+                              frames.data(), nullptr);
+    if (rc != SK_OK) return rc;
+    d.prev_blocksize = st.prev_blocksize;
+    out->clear();
+    size_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        out->emplace_back(pcm.begin() + (ptrdiff_t)at, pcm.begin() + (ptrdiff_t)(at + (size_t)frames[i] * ch));
+        at += (size_t)frames[i] * ch;
+    }
+    return SK_OK;
+}
+
+// VorbisDecoder::process_packet over the packets that became complete, the audio ones in one launch sequence
+int vorbis_decoder_process(sk_vorbis_decoder *d, std::vector<int16_t> *samples) {
+    auto fail = [&](int rc, const std::string &text) {
+        d->error = text, d->dead = true;
+        d->parser.pending.clear();
+        return rc;
+    };
+    std::vector<sk_ogg::Packet> audio;
+    while (!d->parser.pending.empty()) {
+        sk_ogg::Packet p = std::move(d->parser.pending.front());
+        d->parser.pending.pop_front();
+        if (d->dec.headers == 0) {
+            if (!p.first_in_stream) return fail(SK_VORBIS_ERR_STREAM, "Expected Vorbis identification header as first Ogg packet");
+            if (const int rc = d->dec.header(p.data.data(), p.data.size())) return fail(rc, d->dec.error);
+            d->serial = p.serial;
+            continue;
+        }
+        if (p.serial != d->serial) return fail(SK_VORBIS_ERR_STREAM, "Unexpected second Ogg logical bitstream");
+        if (d->dec.headers < 3) {
+            if (const int rc = d->dec.header(p.data.data(), p.data.size())) return fail(rc, d->dec.error);
+        } else {
+            audio.push_back(std::move(p));
+        }
+    }
+    if (audio.empty()) return SK_OK;
+    std::vector<const std::vector<uint8_t> *> ptrs;
+    for (auto &p : audio) ptrs.push_back(&p.data);
+    std::vector<std::vector<int16_t>> pcm;
+    std::vector<int32_t> status;
+    if (const int rc = vorbis_decode_some(d->dec, ptrs, &pcm, &status)) return fail(rc, sk_strerror(rc));
+    const uint32_t ch = d->dec.ident.channels;
+    for (size_t i = 0; i < audio.size(); ++i) {
+        if (status[i] != 0) return fail(status[i], std::string("Vorbis packet: ") + sk_strerror(status[i]));
+        size_t frames = pcm[i].size() / ch;
+        // the reference's truncation: only once cur_absgp is known, only on the stream's last packet
+        if (d->have_absgp && audio[i].last_in_stream && audio[i].has_granule) {
+            const uint64_t left = audio[i].granule_position > d->absgp ? audio[i].granule_position - d->absgp : 0;
+            if (left < frames) frames = (size_t)left;
+        }
+        if (audio[i].last_in_page) {
+            if (audio[i].has_granule) d->have_absgp = true, d->absgp = audio[i].granule_position;
+        } else if (d->have_absgp) {
+            d->absgp += frames;
+        }
+        samples->insert(samples->end(), pcm[i].begin(), pcm[i].begin() + (ptrdiff_t)(frames * ch));
+    }
+    return SK_OK;
+}
+
+// hands `samples` (behind what an earlier call left pending) to the caller, or keeps them for the next call
+int vorbis_decoder_deliver(sk_vorbis_decoder *d, std::vector<int16_t> &samples, int16_t *out, size_t out_cap, size_t *written) {
+    d->pending.insert(d->pending.end(), samples.begin(), samples.end());
+    *written = d->pending.size();
+    if (d->pending.size() > out_cap || (!out && !d->pending.empty())) {
+        d->error = "Output buffer too small for Vorbis decode: need " + std::to_string(d->pending.size()) + ", have " + std::to_string(out_cap);
+        return SK_ERR_CAPACITY;
+    }
+    if (!d->pending.empty()) std::memcpy(out, d->pending.data(), d->pending.size() * 2);
+    d->pending.clear();
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sk_vorbis_packet_decoder_create(sk_engine *e, sk_vorbis_packet_decoder **out) try {
+    sk::abi_enter();
+    if (!e || !out) return SK_ERR_INVALID_ARG;
+    *out = new sk_vorbis_packet_decoder();
+    (*out)->eng = e;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_packet_decoder_create");
+}
+
+void sk_vorbis_packet_decoder_destroy(sk_vorbis_packet_decoder *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_vorbis_packet_decoder_destroy");
+}
+
+int sk_vorbis_packet_decoder_info(const sk_vorbis_packet_decoder *d, uint32_t *sample_rate, uint8_t *channels, size_t *maximum_samples) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (d->headers == 0) return SK_ERR_BAD_STREAM;
+    if (sample_rate) *sample_rate = d->ident.sample_rate;
+    if (channels) *channels = d->ident.channels;
+    if (maximum_samples) *maximum_samples = (size_t)d->ident.channels * (d->ident.blocksize_1 / 2);
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_packet_decoder_info");
+}
+
+int sk_vorbis_packet_decoder_decode_packet(sk_vorbis_packet_decoder *d, const uint8_t *packet, size_t len, int16_t *out, size_t out_cap, size_t *written,
+                                           int *produced) try {
+    sk::abi_enter();
+    if (!d || (len && !packet) || !written || !produced) return SK_ERR_INVALID_ARG;
+    *written = 0, *produced = 0;
+    d->error.clear();
+    if (len > sk_ogg::kMaxPacketBytes) {
+        d->error = "Vorbis packet exceeds the " + std::to_string(sk_ogg::kMaxPacketBytes) + " byte budget";
+        return SK_VORBIS_ERR_STREAM;
+    }
+    if (d->headers < 3) return d->header(packet, len);
+    if (out_cap < (size_t)d->ident.channels * (d->ident.blocksize_1 / 2) || !out) {
+        d->error = "Output buffer too small for Vorbis decode";
+        return SK_ERR_CAPACITY;
+    }
+    const std::vector<uint8_t> one(packet, packet + len);
+    std::vector<std::vector<int16_t>> pcm;
+    std::vector<int32_t> status;
+    if (const int rc = vorbis_decode_some(*d, {&one}, &pcm, &status)) return rc;
+    if (status[0] != 0) {
+        d->error = std::string("Vorbis packet: ") + sk_strerror(status[0]);
+        return status[0];
+    }
+    if (!pcm[0].empty()) std::memcpy(out, pcm[0].data(), pcm[0].size() * 2);
+    *written = pcm[0].size(), *produced = 1;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_packet_decoder_decode_packet");
+}
+
+const char *sk_vorbis_packet_decoder_last_error(const sk_vorbis_packet_decoder *d) try {
+    sk::abi_enter();
+    return d ? d->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_vorbis_packet_decoder_last_error");
+    return "";
+}
+
+int sk_vorbis_decoder_create(sk_engine *e, sk_vorbis_decoder **out) try {
+    sk::abi_enter();
+    if (!e || !out) return SK_ERR_INVALID_ARG;
+    *out = new sk_vorbis_decoder();
+    (*out)->dec.eng = e;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_decoder_create");
+}
+
+void sk_vorbis_decoder_destroy(sk_vorbis_decoder *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_vorbis_decoder_destroy");
+}
+
+int sk_vorbis_decoder_info(const sk_vorbis_decoder *d, uint32_t *sample_rate, uint8_t *channels) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (d->dec.headers == 0) return SK_ERR_BAD_STREAM;
+    if (sample_rate) *sample_rate = d->dec.ident.sample_rate;
+    if (channels) *channels = d->dec.ident.channels;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_decoder_info");
+}
+
+int sk_vorbis_decoder_add(sk_vorbis_decoder *d, const uint8_t *data, size_t len, int16_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    if (!d || (len && !data) || !written) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    if (d->dead) return SK_VORBIS_ERR_STREAM;
+    if (!d->parser.add(data, len, &d->error)) {
+        d->dead = true;
+        return SK_VORBIS_ERR_STREAM;
+    }
+    std::vector<int16_t> samples;
+    if (const int rc = vorbis_decoder_process(d, &samples)) return rc;
+    return vorbis_decoder_deliver(d, samples, out, out_cap, written);
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_decoder_add");
+}
+
+int sk_vorbis_decoder_finish(sk_vorbis_decoder *d, int16_t *out, size_t out_cap, size_t *written) try {
+    sk::abi_enter();
+    if (!d || !written) return SK_ERR_INVALID_ARG;
+    *written = 0;
+    if (d->dead) return SK_VORBIS_ERR_STREAM;
+    std::vector<int16_t> samples;
+    if (d->pending.empty()) {  // a repeated finish after SK_ERR_CAPACITY only delivers
+        if (!d->parser.finish(&d->error)) {
+            d->dead = true;
+            return SK_VORBIS_ERR_STREAM;
+        }
+        if (const int rc = vorbis_decoder_process(d, &samples)) return rc;
+    }
+    return vorbis_decoder_deliver(d, samples, out, out_cap, written);
+} catch (...) {
+    return sk::abi_caught("sk_vorbis_decoder_finish");
+}
+
+const char *sk_vorbis_decoder_last_error(const sk_vorbis_decoder *d) try {
+    sk::abi_enter();
+    return d ? d->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_vorbis_decoder_last_error");
     return "";
 }
 

@@ -135,6 +135,11 @@ struct PipelineGpuHooks {
     int (*tick_gsm)(sk_engine *, const sk_gsm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t, sk_tick_output *,
                     uint32_t, uint32_t *, size_t *, sk_gsm_state *, uint32_t) = nullptr;
     size_t (*tick_gsm_out_bound)(sk_engine *, const sk_gsm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
+    // sk_tick_run_vorbis / sk_tick_vorbis_out_bound_on: the Vorbis streams' packets
+    int (*tick_vorbis)(sk_engine *, sk_vorbis_tick_stream *, uint32_t, const sk_vorbis_tick_packet *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
+                       sk_tick_output *, uint32_t, uint32_t *, size_t *, int32_t *) = nullptr;
+    size_t (*tick_vorbis_out_bound)(sk_engine *, const sk_vorbis_tick_stream *, uint32_t, const sk_vorbis_tick_packet *, uint32_t, const uint8_t *, size_t,
+                                    uint32_t *) = nullptr;
     uint32_t (*wide_pcm_streams)(const sk_engine *) = nullptr;  // sk_engine_wide_pcm_streams
     int (*enable_wide_pcm)(sk_engine *, uint32_t) = nullptr;    // sk_engine_enable_wide_pcm
 };

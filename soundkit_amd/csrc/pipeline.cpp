@@ -18,6 +18,8 @@
 #include "sk_abi.h"
 #include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
 #include "alac_stream.h"
+#include "ogg_stream.h"
+#include "vorbis_stream.h"
 #include "g72x_stream.h"
 #include "gsm_stream.h"
 #include "flac_stream.h"
@@ -114,6 +116,19 @@ struct PStream {
     uint8_t gsm_variant = 0;
     sk_gsm::Framer gsm_framer;
     sk_gsm_state gsm_state{};
+    // Vorbis streams: Ogg bytes the sniffing spawn took by their first page (vorbis_ogg: the page and packet parser runs on the worker
+    // thread) or demuxed packets (sk_pipeline_spawn_vorbis_packets: the three headers came with the spawn, every send is one audio
+    // packet).  Audio packets are the units of the Vorbis tick.  Worker thread: the headers, the block size of the last packet read
+    // (the frames a packet yields follow from it) and the Ogg decoder's granule bookkeeping.  Submission thread: the carry -- the block
+    // size of the last packet DECODED and its overlap half -- goes into every tick and comes back from it
+    bool vorbis = false, vorbis_ogg = false, ogg_finished = false, vorbis_have_absgp = false;
+    int vorbis_headers = 0;
+    std::unique_ptr<sk_ogg::Parser> ogg;
+    sk_vorbis::Ident vorbis_ident;
+    std::shared_ptr<sk_vorbis_setup> vorbis_setup;
+    std::vector<float> vorbis_overlap;
+    uint32_t vorbis_prev = 0, vorbis_parse_prev = 0, ogg_serial = 0;
+    uint64_t vorbis_absgp = 0;
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -121,8 +136,8 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10;
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -201,6 +216,8 @@ struct Batch {
     std::vector<sk_g722_state> g722_states;
     TickTable<sk_gsm_tick_stream, sk_pcm_unit> gsm_ts;  // GSM streams' units (sk_tick_run_gsm); row k's carry is record k
     std::vector<sk_gsm_state> gsm_states;
+    TickTable<sk_vorbis_tick_stream, sk_vorbis_tick_packet> vorbis_ts;  // Vorbis streams' packets (sk_tick_run_vorbis); the carry is the stream's own
+    std::vector<int32_t> vorbis_status;
     uint32_t writers = 0;  // claims whose memcpy is still running
     // the tick's results, handed from the submission thread to the delivery thread
     uint8_t *out_pinned = nullptr;
@@ -229,6 +246,7 @@ struct Batch {
         alac_ts.clear();
         g72x_ts.clear();
         gsm_ts.clear();
+        vorbis_ts.clear();
         ts.clear();
         entries.clear();
         row_of.clear();
@@ -383,6 +401,7 @@ struct Parsed {  // what one worker pass produced for one stream
     std::vector<sk_pcm_unit> pcm_units;
     std::vector<sk_flac_frame_info> flac_frames;  // a FLAC stream's pass: one per unit, offset into pcm_bytes
     std::vector<sk_alac_tick_packet> alac_packets;  // an ALAC stream's pass: one per unit, offset into pcm_bytes
+    std::vector<sk_vorbis_tick_packet> vorbis_packets;  // a Vorbis stream's pass: one per unit, offset into pcm_bytes
     std::vector<Output> pre;
     bool fail(int32_t st, const std::string &msg) {  // the pass ends its stream with this error; false, for a caller that returns it
         failed = true;
@@ -445,6 +464,14 @@ uint8_t sniff_codec(const uint8_t *d, size_t n) {
         if (n < 12) return 0;
         if (std::memcmp(d + 8, "AIFF", 4) == 0 || std::memcmp(d + 8, "AIFC", 4) == 0) return kCodecAiff;
     } else if (n > 0 && n < 4 && std::memcmp(d, "FORM", n) == 0) {
+        return 0;
+    }
+    // OggS, and the first page's first packet begins \x01vorbis -> Ogg Vorbis (AudioType::OggVorbis); a page header or a packet start
+    // not complete yet: wait.  Any other Ogg stream goes the way it always went
+    if (n >= 4 && std::memcmp(d, "OggS", 4) == 0) {
+        if (n < 27 || n < 27 + (size_t)d[26] + 7) return 0;
+        if (std::memcmp(d + 27 + d[26], "\x01vorbis", 7) == 0) return kCodecVorbis;
+    } else if (n > 0 && n < 4 && std::memcmp(d, "OggS", n) == 0) {
         return 0;
     }
     // fLaC -> native FLAC (AudioType::Flac); fewer than 4 bytes that match so far: wait
@@ -713,6 +740,8 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rate = 8000, channels = 1, bits = 16, is_float = false;
     } else if (s.g72x) {  // the spawn's: create_audio_data_i16(d.sample_rate(), d.channels(), ...), always 16 bits
         rate = s.g72x_rate, channels = s.g72x_channels, bits = 16, is_float = false;
+    } else if (s.vorbis) {  // the identification header's; VorbisDecoder hands out s16
+        rate = s.vorbis_ident.sample_rate, channels = s.vorbis_ident.channels, bits = 16, is_float = false;
     } else if (s.alac) {  // the cookie's
         rate = s.alac_cfg.sample_rate, channels = s.alac_cfg.channels, bits = s.alac_cfg.bit_depth, is_float = false;
     } else if (s.flac) {  // STREAMINFO's: the AudioData of a FLAC frame carries the stream's own depth (create_audio_data_i32_with_bits, lib.rs:3191-3236)
@@ -763,6 +792,14 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         s.pcm_route = kPcmGsmTick;
         return true;
     }
+    if (s.vorbis && (!hooks.tick_vorbis || !hooks.tick_vorbis_out_bound))
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: Vorbis decoding needs the device tick, which this build lacks");
+    if (s.vorbis && target_rate == rate && target_bits == bits && target_channels == channels) {  // every packet has per-sample work: the tick's
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmVorbisTick;
+        return true;
+    }
     if (s.alac && (!hooks.tick_alac || !hooks.tick_alac_out_bound))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: ALAC decoding needs the device tick, which this build lacks");
     if (s.alac && target_rate == rate && target_bits == bits && target_channels == channels) {  // every packet has per-sample work: the tick's
@@ -804,7 +841,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
+    s.pcm_route = s.vorbis ? kPcmVorbisTick : s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
     return true;
 }
 
@@ -986,6 +1023,132 @@ void parse_some_alac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         }
         const size_t at = stage_unit(r, s, chunk.data(), chunk.size(), frames, outputs);
         r.alac_packets.push_back(sk_alac_tick_packet{(uint32_t)at, (uint32_t)chunk.size(), frames, 0});
+    }
+    r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
+}
+
+// A Vorbis stream's pass.  From Ogg (the sniffing spawn): the chunks go through the page and packet parser, the first three packets are
+// the headers (VorbisDecoder::process_packet: the first must open the logical stream, every later one carry its serial), and the
+// stream joins the PCM family once the setup header is in.  From packets (sk_pipeline_spawn_vorbis_packets): the headers came with the
+// spawn and every chunk is one audio packet.  Either way whole audio packets are what the stream is budgeted in.  The host reads a
+// packet's first bits (vorbis_stream.h), so the frames it will yield are known here -- none for the stream's first packet -- and with
+// them the Ogg decoder's cut of the last packet to the final granule position.  A packet whose first bits are refused ends the stream
+// with its text, as read_audio_packet_generic's error does.
+void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
+    uint32_t outputs = 0;
+    auto header = [&](const uint8_t *d, size_t n) -> bool {
+        std::string text;
+        int rc;
+        if (s.vorbis_headers == 0) {
+            rc = sk_vorbis::parse_ident(d, n, &s.vorbis_ident, &text);
+        } else if (s.vorbis_headers == 1) {
+            rc = sk_vorbis::parse_comment(d, n, &text);
+        } else {
+            std::shared_ptr<sk_vorbis_setup> su = std::make_shared<sk_vorbis_setup>();
+            rc = sk_vorbis::parse_setup(d, n, s.vorbis_ident, &su->setup, &text);
+            if (rc == SK_OK) {
+                s.vorbis_setup = su;
+                s.vorbis_overlap.assign((size_t)s.vorbis_ident.channels * (s.vorbis_ident.blocksize_1 / 2), 0.0f);
+            }
+        }
+        if (rc != SK_OK) return r.fail(rc, "Decoding failed: " + text);
+        ++s.vorbis_headers;
+        return true;
+    };
+    auto audio = [&](const uint8_t *d, size_t n, const sk_ogg::Packet *op) -> bool {
+        if (!s.pcm_route && !pcm_open(p, s, r)) return false;
+        if (n > sk_vorbis::kMaxPacketBytes) return r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: Vorbis packet exceeds the " + std::to_string(sk_vorbis::kMaxPacketBytes) + " byte budget");
+        sk_vorbis::PacketHead h;
+        const int rc = sk_vorbis::packet_head(s.vorbis_setup->setup, d, n, &h);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: Vorbis packet rejected: ") + sk_strerror(rc));
+        uint32_t frames = s.vorbis_parse_prev ? s.vorbis_parse_prev / 4 + h.n / 4 : 0, keep = 0xffffffffu;
+        s.vorbis_parse_prev = h.n;
+        if (op) {  // process_packet's bookkeeping: cur_absgp is known from the first audio packet that ends a page
+            if (s.vorbis_have_absgp && op->last_in_stream && op->has_granule) {
+                const uint64_t left = op->granule_position > s.vorbis_absgp ? op->granule_position - s.vorbis_absgp : 0;
+                if (left < frames) frames = (uint32_t)left, keep = frames;
+            }
+            if (op->last_in_page) {
+                if (op->has_granule) s.vorbis_have_absgp = true, s.vorbis_absgp = op->granule_position;
+            } else if (s.vorbis_have_absgp) {
+                s.vorbis_absgp += frames;
+            }
+        }
+        const uint32_t before = outputs;
+        const size_t at = stage_unit(r, s, d, n, frames, outputs);
+        if (!frames) outputs = before;  // such a packet gives no AudioData
+        r.vorbis_packets.push_back(sk_vorbis_tick_packet{(uint32_t)at, (uint32_t)n, keep, 0});
+        return true;
+    };
+    auto full = [&](size_t next) {
+        return outputs >= room || r.pcm_units.size() >= per_pass || (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes);
+    };
+    if (s.vorbis_ogg && s.pending.size() > s.pending_pos) {  // the pending bytes of the detection go in first
+        std::string text;
+        const bool ok = s.ogg->add(s.pending.data() + s.pending_pos, s.pending.size() - s.pending_pos, &text);
+        s.pending.clear();
+        s.pending.shrink_to_fit();
+        s.pending_pos = 0;
+        if (!ok) r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: " + text);
+    }
+    while (!r.failed) {
+        if (s.vorbis_ogg && !s.ogg->pending.empty()) {
+            if (full(s.ogg->pending.front().data.size())) {
+                r.more = true;
+                break;
+            }
+            const sk_ogg::Packet pk = std::move(s.ogg->pending.front());
+            s.ogg->pending.pop_front();
+            if (s.vorbis_headers == 0) {
+                if (!pk.first_in_stream) {
+                    r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: Expected Vorbis identification header as first Ogg packet");
+                    break;
+                }
+                s.ogg_serial = pk.serial;
+                if (!header(pk.data.data(), pk.data.size())) break;
+                continue;
+            }
+            if (pk.serial != s.ogg_serial) {
+                r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: Unexpected second Ogg logical bitstream");
+                break;
+            }
+            if (s.vorbis_headers < 3 ? !header(pk.data.data(), pk.data.size()) : !audio(pk.data.data(), pk.data.size(), &pk)) break;
+            continue;
+        }
+        if (s.saw_eof) {
+            if (s.vorbis_ogg && !s.ogg_finished) {  // OggPacketParser::finish: a truncated page or packet, a missing EOS
+                s.ogg_finished = true;
+                std::string text;
+                if (!s.ogg->finish(&text)) r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: " + text);
+                continue;
+            }
+            r.eof = true;
+            break;
+        }
+        std::vector<uint8_t> chunk;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            if (s.in.empty()) break;
+            if (!s.in.front().empty() && full(s.vorbis_ogg ? 0 : s.in.front().size())) {
+                r.more = true;
+                break;
+            }
+            chunk = std::move(s.in.front());
+            s.in.pop_front();
+        }
+        if (chunk.empty()) {
+            s.saw_eof = true;
+            continue;
+        }
+        s.queued_bytes.fetch_sub(chunk.size());
+        if (s.vorbis_ogg) {
+            std::string text;
+            if (!s.ogg->add(chunk.data(), chunk.size(), &text)) r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: " + text);
+        } else if (!audio(chunk.data(), chunk.size(), nullptr)) {
+            break;
+        }
     }
     r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
@@ -1201,6 +1364,15 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         parse_some_alac(p, s, room, r);
         return;
     }
+    if (s.codec == kCodecVorbis) {
+        if (!s.vorbis) {  // taken by its first page: the Ogg walk starts here, with the bytes of the detection
+            s.vorbis = s.vorbis_ogg = true;
+            s.ogg.reset(new sk_ogg::Parser());
+            s.pcm_detected = true;
+        }
+        parse_some_vorbis(p, s, room, r);
+        return;
+    }
     if (s.codec == kCodecG72x) {
         parse_some_g72x(p, s, room, r);
         return;
@@ -1365,6 +1537,7 @@ void thread_debug_point(int where) {
 inline void shift_unit(sk_pcm_unit &u, size_t by) { u.byte_offset += by; }
 inline void shift_unit(sk_flac_frame_info &f, size_t by) { f.offset += (uint32_t)by; }
 inline void shift_unit(sk_alac_tick_packet &k, size_t by) { k.offset += (uint32_t)by; }
+inline void shift_unit(sk_vorbis_tick_packet &k, size_t by) { k.offset += (uint32_t)by; }
 
 // A PCM-family pass joins the table of its tick (batch_mu held): nothing when it neither brings units nor ends a resampler; else it
 // takes its place in the batch's staged bytes (pcm_at) and a row with what the three ticks' rows share, and its units follow with
@@ -1538,6 +1711,8 @@ void worker_body(sk_lane *p) {
                         const sk_alac_config &c = s.alac_cfg;
                         row->frame_length = c.frame_length, row->bit_depth = c.bit_depth, row->pb = c.pb, row->mb = c.mb, row->kb = c.kb;
                     }
+                } else if (s.pcm_route == kPcmVorbisTick) {
+                    (void)claim_tick_row(b, b->vorbis_ts, s, r, r.vorbis_packets, be, pcm_at);  // the carry joins the row on the submission thread
                 } else if (s.pcm_route == kPcmG72xTick) {
                     if (sk_g72x_tick_stream *row = claim_tick_row(b, b->g72x_ts, s, r, r.pcm_units, be, pcm_at))
                         row->codec = s.g72x_codec, row->g726_rate = s.g726_rate, row->g726_packing = s.g726_packing;
@@ -1705,12 +1880,21 @@ void submit_body(sk_lane *p) {
         b->rc = SK_OK;
         b->n_out = 0;
         if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty() ||
-            !b->g72x_ts.rows.empty() || !b->gsm_ts.rows.empty()) {
+            !b->g72x_ts.rows.empty() || !b->gsm_ts.rows.empty() || !b->vorbis_ts.rows.empty()) {
+            // the Vorbis streams' carry as the ticks before this one left it (this thread alone reads and writes it): the bound needs it too
+            for (uint32_t row = 0; row < b->vorbis_ts.rows.size(); ++row) {
+                PStream &s = *p->streams[b->entries[b->vorbis_ts.entry[row]].handle];
+                sk_vorbis_tick_stream &v = b->vorbis_ts.rows[row];
+                v.setup = s.vorbis_setup.get(), v.overlap = s.vorbis_overlap.data(), v.prev_blocksize = s.vorbis_prev;
+            }
             // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, the ALAC tick's, then the PCM tick's: one buffer
             const size_t bound = (ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out)) +
                                  follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
                                  follow_on_bound(p, b->alac_ts, hooks.tick_alac_out_bound) +
                                  follow_on_bound(p, b->g72x_ts, hooks.tick_g72x_out_bound) + follow_on_bound(p, b->gsm_ts, hooks.tick_gsm_out_bound) +
+                                 follow_on_bound(p, b->vorbis_ts,
+                                                 [&](sk_engine *e, const sk_vorbis_tick_stream *rows, uint32_t n, const sk_vorbis_tick_packet *units, uint32_t n_units,
+                                                     uint32_t *most) { return hooks.tick_vorbis_out_bound(e, rows, n, units, n_units, b->pcm_bytes, b->pcm_used, most); }) +
                                  follow_on_bound(p, b->pcm_ts, hooks.tick_pcm_out_bound);
             if (bound > b->out_pinned_cap) {
                 // Pinned memory is slow to get (10 ms per 64 MB on an idle device, many times that beside a running lane): the
@@ -1730,7 +1914,7 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->gsm_ts.max_out + b->pcm_ts.max_out;
+            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->gsm_ts.max_out + b->vorbis_ts.max_out + b->pcm_ts.max_out;
             if (b->recs.size() < n_recs) b->recs.resize(n_recs);
         }
         const bool with_md = b->n_mp3 && p->mp3_gpu;  // the MP3 streams' Huffman stage is the tick's as well
@@ -1820,6 +2004,14 @@ void submit_body(sk_lane *p) {
         });
         for (uint32_t row = 0; b->rc == SK_OK && row < b->gsm_ts.rows.size(); ++row)
             p->streams[b->entries[b->gsm_ts.entry[row]].handle]->gsm_state = b->gsm_states[row];
+        follow_on_tick(b, b->vorbis_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            b->vorbis_status.assign(b->vorbis_ts.units.size() + 1, 0);
+            return hooks.tick_vorbis(p->engine, b->vorbis_ts.rows.data(), (uint32_t)b->vorbis_ts.rows.size(), b->vorbis_ts.units.data(),
+                                     (uint32_t)b->vorbis_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used,
+                                     b->vorbis_status.data());
+        });
+        for (uint32_t row = 0; b->rc == SK_OK && row < b->vorbis_ts.rows.size(); ++row)  // the overlap half was written in place; the block size comes back
+            p->streams[b->entries[b->vorbis_ts.entry[row]].handle]->vorbis_prev = b->vorbis_ts.rows[row].prev_blocksize;
         follow_on_tick(b, b->pcm_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
             return hooks.tick_pcm(p->engine, b->pcm_ts.rows.data(), (uint32_t)b->pcm_ts.rows.size(), b->pcm_ts.units.data(),
                                   (uint32_t)b->pcm_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used);
@@ -1828,7 +2020,7 @@ void submit_body(sk_lane *p) {
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
         p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_ts.units.size() +
-                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size() + (uint32_t)b->gsm_ts.units.size());
+                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size() + (uint32_t)b->gsm_ts.units.size() + (uint32_t)b->vorbis_ts.units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -1853,6 +2045,7 @@ std::string device_error_text(sk_lane *p, const Batch *b, uint32_t entry, const 
         return status == SK_ERR_UNSUPPORTED ? "Decoding failed: ALAC packet rejected: a channel pair at 32 bits without extra bytes is not supported"
                : status == SK_ALAC_UNSUPPORTED ? "Decoding failed: ALAC packet rejected: a CCE or PCE element is not supported"
                                                : "Decoding failed: ALAC packet rejected: the elements break the syntax or miss the packet's end";
+    if (s.codec == kCodecVorbis) return std::string("Decoding failed: Vorbis packet rejected: ") + sk_strerror(status);
     if (s.codec == kCodecFlac)
         return status == SK_ERR_UNSUPPORTED ? "Decoding failed: FLAC frame rejected: 32-bit samples with a side channel are not supported"
                                             : "Decoding failed: FLAC frame rejected: the subframes break the syntax or miss the frame's end";
@@ -2323,6 +2516,10 @@ void lane_destroy(sk_lane *p) {
     delete p;
 }
 
+struct VorbisSpawn {  // sk_pipeline_spawn_vorbis_packets: the headers, parsed
+    sk_vorbis::Ident ident;
+    std::shared_ptr<sk_vorbis_setup> setup;
+};
 struct G72xSpawn {  // sk_pipeline_spawn_g711 / _g722 / _g726
     int codec;
     uint32_t sample_rate, channels, g726_rate;
@@ -2331,7 +2528,7 @@ struct G72xSpawn {  // sk_pipeline_spawn_g711 / _g722 / _g726
 };
 
 int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
-               const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr) {
+               const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr, const VorbisSpawn *vorbis = nullptr) {
     if (!p || !handle) return SK_ERR_INVALID_ARG;
     // RawPcmFormat::validate (raw_pcm.rs:117-125), and the sample formats there are
     if (raw && (raw->sample_rate == 0 || raw->channels == 0 || raw->format > SK_FMT_F32BE)) return SK_ERR_INVALID_ARG;
@@ -2388,6 +2585,14 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.gsm_variant = 0;
     s.gsm_framer = sk_gsm::Framer();
     sk_gsm::init_state(&s.gsm_state);
+    s.vorbis = s.vorbis_ogg = s.ogg_finished = s.vorbis_have_absgp = false;
+    s.vorbis_headers = 0;
+    s.ogg.reset();
+    s.vorbis_ident = sk_vorbis::Ident();
+    s.vorbis_setup.reset();
+    s.vorbis_overlap.clear();
+    s.vorbis_prev = s.vorbis_parse_prev = s.ogg_serial = 0;
+    s.vorbis_absgp = 0;
     s.pcm_detected = false;
     s.pcm_route = 0, s.pcm_fmt = 0, s.pcm_flags = 0, s.pcm_bits = 0;
     s.pcm_fill = 0;
@@ -2406,6 +2611,15 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
         s.codec = kCodecAlac;
         s.alac = true;
         s.alac_cfg = *alac;
+        s.pcm_detected = true;
+    }
+    if (vorbis) {  // sk_pipeline_spawn_vorbis_packets: the headers are the decoder, nothing is detected or gathered
+        s.codec = kCodecVorbis;
+        s.vorbis = true;
+        s.vorbis_headers = 3;
+        s.vorbis_ident = vorbis->ident;
+        s.vorbis_setup = vorbis->setup;
+        s.vorbis_overlap.assign((size_t)vorbis->ident.channels * (vorbis->ident.blocksize_1 / 2), 0.0f);
         s.pcm_detected = true;
     }
     if (g72x && g72x->gsm_variant >= 0) {  // spawn_gsm: the same, with GsmDecoder
@@ -2567,7 +2781,7 @@ inline sk_lane *lane_of(sk_pipeline *p, uint32_t handle, uint32_t *inner) {
 }
 
 int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
-                   const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr) {
+                   const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr, const VorbisSpawn *vorbis = nullptr) {
     if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
     const uint32_t n = (uint32_t)p->lanes.size();
     const uint32_t first = p->next_lane.fetch_add(1) % n;
@@ -2575,7 +2789,7 @@ int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pc
     for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
         const uint32_t li = (first + k) % n;
         uint32_t inner = 0;
-        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac, g72x);
+        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac, g72x, vorbis);
         if (rc == SK_OK) {
             *handle = inner * n + li;
             return SK_OK;
@@ -2715,6 +2929,30 @@ int sk_pipeline_spawn_alac_packets(sk_pipeline *p, const uint8_t *cookie, size_t
     return pipeline_spawn(p, opt, nullptr, handle, false, &cfg);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn_alac_packets");
+}
+
+int sk_pipeline_spawn_vorbis_packets(sk_pipeline *p, const uint8_t *ident, size_t ident_len, const uint8_t *comment, size_t comment_len, const uint8_t *setup,
+                                     size_t setup_len, const sk_decode_options *opt, uint32_t *handle, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((ident_len && !ident) || (comment_len && !comment) || (setup_len && !setup)) return SK_ERR_INVALID_ARG;
+    if (error && error_cap) error[0] = 0;
+    VorbisSpawn v;
+    v.setup = std::make_shared<sk_vorbis_setup>();
+    std::string text;
+    int rc = sk_vorbis::parse_ident(ident, ident_len, &v.ident, &text);
+    if (rc == SK_OK) rc = sk_vorbis::parse_comment(comment, comment_len, &text);
+    if (rc == SK_OK) rc = sk_vorbis::parse_setup(setup, setup_len, v.ident, &v.setup->setup, &text);
+    if (rc != SK_OK) {
+        if (error && error_cap) {
+            const size_t n = std::min(error_cap - 1, text.size());
+            std::memcpy(error, text.data(), n);
+            error[n] = 0;
+        }
+        return rc;
+    }
+    return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, nullptr, &v);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_vorbis_packets");
 }
 
 int sk_pipeline_spawn_g711(sk_pipeline *p, int law, uint32_t sample_rate, uint32_t channels, const sk_decode_options *opt, uint32_t *handle, char *error,

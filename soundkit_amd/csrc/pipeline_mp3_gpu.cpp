@@ -22,6 +22,8 @@ const bool g_hooked = [] {
     hooks.tick_g72x_out_bound = sk_tick_g72x_out_bound_on;
     hooks.tick_gsm = sk_tick_run_gsm;  // ... and the GSM streams'
     hooks.tick_gsm_out_bound = sk_tick_gsm_out_bound_on;
+    hooks.tick_vorbis = sk_tick_run_vorbis;  // ... and the Vorbis streams'
+    hooks.tick_vorbis_out_bound = sk_tick_vorbis_out_bound_on;
     hooks.mpa_find_layer = sk_mp12::find_layer;  // Layer I / II streams: their host front and their tick
     hooks.mpa_scan = sk_mpa_scan;
     hooks.mpa_parse_frame = sk_mpa_parse_frame;

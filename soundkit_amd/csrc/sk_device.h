@@ -680,4 +680,56 @@ struct GsmStream {
 hipError_t launch_gsm(const GsmStream *streams, uint32_t n_streams, const GsmUnit *units, const int32_t *states_in, int32_t *states_out, int16_t *ws,
                       hipStream_t s);
 
+// vorbis_decode.hip -- Vorbis I audio packets to PCM, f32 and integers, four launches over every packet of a call: k_vorbis_entropy
+// (one packet per lane: header bits, floor 1 values and their unwrapping, residue classification and VQ adds into a planar f32
+// workspace), k_vorbis_spectrum (one block per packet: inverse coupling, floor curve, product), k_vorbis_imdct (one block per
+// packet-channel: N/4-point complex FFT in LDS, window, both halves to a workspace) and k_vorbis_ola (one block per packet: right half
+// of the stream's previous packet + left half of this one, narrowed and interleaved).  The tables of a stream: vorbis_blob.h.
+struct VorbisPacket {
+    uint32_t byte_offset;  // in `bytes`, a multiple of 16
+    uint32_t byte_len;     // at most 16 MiB
+    uint32_t blob;         // word offset of its stream's blob in `blobs`
+    uint32_t n;            // the block size the host read from the packet's first bits; 0: refused by the host, no lane work
+    uint32_t res_offset;   // in floats: the packet's [channels][n / 2] residue vectors, zeroed by the caller
+    uint32_t cls_offset;   // in bytes: channels x n / 2 bytes of scratch for the residue classifications
+    uint32_t pcm_offset;   // in floats: the packet's [channels][n] windowed IMDCT output
+    uint32_t prev_n;       // block size of the stream's previous accepted packet; 0: none, the packet yields nothing
+    uint32_t prev_pcm;     // in floats: where that packet's right halves start -- in the windowed workspace (row stride prev_n), or,
+    uint32_t prev_in_carry;  // != 0, in the carry buffer (row stride prev_n / 2): the first accepted packet of a stream in the call
+    uint64_t out_offset;   // in samples (frames x channels) of the output
+    uint32_t out_frames;   // prev_n / 4 + n / 4, or 0
+    uint32_t channels;
+};
+struct VorbisInfo {        // sk_vorbis_packet_info
+    int32_t status;
+    uint8_t mode, blockflag, prev_flag, next_flag;
+    uint32_t n;
+    uint8_t used[8];
+    int16_t final_y[8][65];
+    uint8_t step2[8][65];
+};
+static_assert(sizeof(VorbisInfo) == 1580, "packed by hand");
+struct VorbisTables {      // the engine's constants, block size 2^e at index e - 6
+    const float *inverse_db;  // [256]
+    const float *slope[8];    // [n / 2]: the rising half of the window of length n
+    const float2 *twiddle[8]; // [n / 4]: exp(-i pi (8 j + 1) / (4 n)), before and behind the FFT
+    const float2 *root[8];    // [n / 8]: exp(-2 pi i m / (n / 4))
+};
+// by_length: the accepted packets' indices, longest first.  bytes: 16-byte aligned with 16 readable bytes behind the last packet (the reader
+// takes the word that holds a bit and the one behind it).
+hipError_t launch_vorbis_entropy(const VorbisPacket *packets, const uint32_t *by_length, uint32_t n_lanes, const uint32_t *blobs, const uint8_t *bytes,
+                                 float *res, uint8_t *cls, VorbisInfo *info, hipStream_t s);
+hipError_t launch_vorbis_spectrum(const VorbisPacket *packets, uint32_t n_packets, const uint32_t *blobs, const VorbisInfo *info, float *res,
+                                  const VorbisTables &t, hipStream_t s);
+hipError_t launch_vorbis_imdct(const VorbisPacket *packets, uint32_t n_packets, const uint32_t *blobs, const VorbisInfo *info, const float *res, float *pcm,
+                               uint32_t max_channels /* of the call's streams: the grid's y */, const VorbisTables &t, hipStream_t s);
+struct VorbisCarry {
+    uint32_t packet;  // the stream's last accepted packet of the call, or 0xffffffff: the stream leaves with what it entered with
+    uint32_t offset;  // in floats: the stream's [channels][n / 2] in the carry buffer
+};
+hipError_t launch_vorbis_carry(const VorbisPacket *packets, const VorbisCarry *carries, uint32_t n_streams, const float *pcm, float *carry, hipStream_t s);
+// out: interleaved s16 (x * 32768, saturated, truncated toward zero) or, as_f32, the f32 before that
+hipError_t launch_vorbis_ola(const VorbisPacket *packets, uint32_t n_packets, const VorbisInfo *info, const float *pcm, const float *carry, void *out,
+                             int as_f32, hipStream_t s);
+
 }  // namespace sk

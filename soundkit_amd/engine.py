@@ -548,6 +548,54 @@ class Engine:
         from . import flac
         return flac.decode_frames(frames, engine=self)
 
+    def vorbis_decode_packets(self, groups, as_f32=False):
+        """sk_vorbis_decode_packets: [(vorbis.StreamState, [audio packet bytes])], every stream's packets in one launch sequence; the
+        states are updated.  -> [per stream: [per packet: (status, samples as [frames][channels], s16 or -- as_f32 -- the f32 before
+        narrowing)]]"""
+        from . import vorbis
+        return vorbis.decode_packets(groups, as_f32=as_f32, engine=self)
+
+    def vorbis_entropy_decode(self, groups):
+        """sk_vorbis_entropy_decode: [(vorbis.Setup, [audio packet bytes])] -> per stream, per packet a dict of what the entropy stage
+        left: status, mode, window flags, per channel used / final_y / step2, and the residue vectors"""
+        from . import vorbis
+        return vorbis.entropy_decode(groups, engine=self)
+
+    def tick_run_vorbis(self, streams, packets, out_cap=None):
+        """One tick of Vorbis streams (sk_tick_run_vorbis).  streams: list of dicts {state (a vorbis.StreamState: the carry, updated when
+        the tick succeeded), out_bits, out_channels, n_units, and for a rate change: stream, resample, flush}; packets: [audio packet
+        bytes] of all streams, stream by stream.  out_cap: an output size other than the bound's (to have a tick refused).
+        -> (the same list of records as tick_run_pcm, [status per packet])."""
+        import ctypes as C
+        from . import vorbis
+        from ._lib import TickOutput, VorbisTickPacket, VorbisTickStream
+        ts = (VorbisTickStream * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            st = s["state"]
+            ts[i].setup, ts[i].overlap, ts[i].prev_blocksize = st.setup._h, st.overlap.ctypes.data, st.prev_blocksize
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+        n = len(packets)
+        table, blob = (VorbisTickPacket * max(n, 1))(), bytearray()
+        for k, p in enumerate(packets):
+            blob += bytes(-len(blob) % 16)
+            table[k].offset, table[k].size, table[k].keep_frames = len(blob), len(p), 0xffffffff
+            blob += p
+        src = np.frombuffer(bytes(blob) + bytes(16), np.uint8)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_vorbis_out_bound_on(self._h, ts, len(streams), table, n, _ptr(src), len(blob), C.byref(max_out))
+        out = np.zeros(max(cap if out_cap is None else out_cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        status = np.zeros(max(n, 1), np.int32)
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_vorbis(self._h, ts, len(streams), table, n, _ptr(src), len(blob), _ptr(out), out.size if out_cap is None else out_cap, recs,
+                                     max_out.value, C.byref(n_out), C.byref(used), _ptr(status)), "sk_tick_run_vorbis", self._h)
+        for i, s in enumerate(streams):
+            s["state"].prev_blocksize = int(ts[i].prev_blocksize)
+        return ([(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                 for r in recs[:n_out.value]], status[:n].tolist())
+
     def tick_run_flac(self, streams, frames):
         """One tick of FLAC streams (sk_tick_run_flac).  streams: list of dicts {channels, bits_per_sample, out_bits, out_channels, n_units,
         and for a rate change: stream, resample, flush}; frames: [(frame dict, frame bytes)] of all streams, stream by stream, each

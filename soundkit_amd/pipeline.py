@@ -130,6 +130,18 @@ class BatchScheduler:
             raise SoundkitError(rc, "sk_pipeline_spawn_alac_packets")
         return DecodePipelineHandle(self, handle.value)
 
+    def spawn_vorbis_packets(self, ident, comment, setup, options=None):
+        """a stream of demuxed Vorbis packets (sk_pipeline_spawn_vorbis_packets, the A_VORBIS case): the three header packets once, then
+        every `send` is exactly one audio packet; the empty send ends the stream and flushes the resampler"""
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        ident, comment, setup = bytes(ident), bytes(comment), bytes(setup)
+        handle, text = C.c_uint32(), C.create_string_buffer(256)
+        rc = lib.sk_pipeline_spawn_vorbis_packets(self._h, ident, len(ident), comment, len(comment), setup, len(setup), C.byref(o), C.byref(handle), text, 256)
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_vorbis_packets", text.value.decode())
+        return DecodePipelineHandle(self, handle.value)
+
     def spawn_g711(self, law, sample_rate, channels, options=None):
         """a headerless G.711 stream (sk_pipeline_spawn_g711): law = telephony.ULAW / ALAW; every non-empty `send` gives one AudioData"""
         from . import telephony
@@ -316,6 +328,10 @@ class DecodePipeline:
     @staticmethod
     def spawn_alac_packets(magic_cookie, options=None):
         return default_scheduler().spawn_alac_packets(magic_cookie, options)
+
+    @staticmethod
+    def spawn_vorbis_packets(ident, comment, setup, options=None):
+        return default_scheduler().spawn_vorbis_packets(ident, comment, setup, options)
 
     @staticmethod
     def spawn_g711(law, sample_rate, channels, options=None):
