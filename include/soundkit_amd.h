@@ -1241,8 +1241,8 @@ int sk_flac_decoder_decode_i16(sk_flac_decoder *, const uint8_t *input, size_t l
 const char *sk_flac_decoder_last_error(const sk_flac_decoder *);
 
 /* ---- Apple Lossless (ALAC): cookie, packet header, CAF packet index (host only, csrc/alac_stream.h) ----------------------- */
-/* ALAC arrives as packets that a container (CAF, MP4) has already cut, with the ALACSpecificConfig as its magic cookie.  Not built:
- * the MP4 side of the container (an MP4 demuxer hands its packets and cookie to the same calls). */
+/* ALAC arrives as packets that a container (CAF, MP4) has already cut, with the ALACSpecificConfig as its magic cookie.  The MP4 side
+ * of the container is sk_mp4_* below: its demuxer and index hand packets and cookie to the same calls. */
 enum sk_alac_status {
     SK_ALAC_INVALID = -601,     /* a packet breaks the syntax: a prediction type other than 0 / 15, a zero run past the element's end, a
                                    frame count of 0 or above the cookie's, elements whose counts differ, more or fewer channels than the
@@ -1290,6 +1290,67 @@ void sk_caf_alac_index_destroy(sk_caf_alac_index *);
 int sk_caf_alac_index_info(const sk_caf_alac_index *, sk_caf_alac_info *info);
 /* the packets' absolute offsets and sizes; cap < n_packets: SK_ERR_CAPACITY */
 int sk_caf_alac_index_packets(const sk_caf_alac_index *, uint64_t *offsets, uint32_t *sizes, uint32_t cap);
+
+/* ---- MP4 / M4A / fragmented MP4, audio only (host, csrc/mp4_stream.h) -------------------------------------------------------------
+ * The first audio track whose sample entry is `mp4a` (AAC) or `alac` is chosen; video tracks and unknown boxes are stepped over by
+ * size without being buffered.  Read: 32- and 64-bit box sizes, mvhd, tkhd, edts/elst (the first media edit), mdhd, hdlr, stsd with
+ * esds (descriptor tags 3, 4, 5, lengths of 1 to 4 bytes) or the `alac` child, stts, stsc, stsz (both forms), stco / co64; mvex/trex,
+ * moof/traf with tfhd (base-data-offset, default-base-is-moof, default duration and size), tfdt and trun under any flag combination,
+ * several traf per moof.  The layout is fragmented when moov holds mvex or its sample tables are empty.  Budgets: 4 MiB a call, 64 MiB
+ * of moov or moof payload (refused from the box header), 128 MiB a sample, 8 000 000 samples a track or fragment.
+ * A refusal is SK_MP4_ERR_STREAM with a text (sk_mp4_demuxer_last_error, or `error`: NUL-terminated, cut to error_cap; may be NULL).
+ * Not read: ctts, stss, edits behind the first media edit, `fLaC` and PCM sample entries, version-two sound descriptions, video. */
+enum sk_mp4_status { SK_MP4_ERR_STREAM = -901 };
+enum sk_mp4_codec { SK_MP4_CODEC_AAC = 1, SK_MP4_CODEC_ALAC = 2 };
+typedef struct sk_mp4_track_info {
+    uint32_t codec;        /* sk_mp4_codec; 0: no config yet (sk_mp4_demuxer_config before moov has arrived) */
+    uint32_t sample_rate;  /* AAC: the AudioSpecificConfig's where its two-byte form states one, else the sample entry's */
+    uint32_t channels;
+    uint32_t bits_per_sample; /* the sample entry's; 0 for AAC */
+    uint32_t track_id;
+    uint32_t timescale;    /* of the track: what packet times and the edit are counted in */
+    uint32_t sample_count; /* of the sample table; 0 in a fragmented file */
+    uint32_t fragmented;
+    uint32_t has_edit;     /* the first media edit of edts/elst, in the track's timescale (the duration rescaled from the movie's) */
+    uint32_t private_len;  /* bytes of codec-private data: the AudioSpecificConfig, or the `alac` child's payload (sk_alac_parse_cookie takes it) */
+    uint64_t edit_presentation_start, edit_media_start, edit_duration;
+} sk_mp4_track_info;
+
+/* The streaming demuxer: moov must come before mdat -- `MP4 mdat appears before moov; use the seekable MP4 packet API` otherwise, from
+ * the mdat header alone.  Events: one config (once moov has been parsed), then the track's samples in file order as their bytes arrive.
+ * A regular file's buffer is drained up to the next sample's offset; a fragmented file's samples follow their moof's trun tables.
+ * _finish: `truncated MP4 box header`, `truncated MP4 box NAME`, `truncated MP4 top-level box` for what the input ended in. */
+typedef struct sk_mp4_demuxer sk_mp4_demuxer;
+int sk_mp4_demuxer_create(sk_mp4_demuxer **out);
+void sk_mp4_demuxer_destroy(sk_mp4_demuxer *);
+int sk_mp4_demuxer_add(sk_mp4_demuxer *, const uint8_t *bytes, size_t len);
+int sk_mp4_demuxer_finish(sk_mp4_demuxer *);
+const char *sk_mp4_demuxer_last_error(const sk_mp4_demuxer *);
+/* the config event; codec_private may be NULL when private_cap is 0; private_cap < private_len: SK_ERR_CAPACITY (info is filled) */
+int sk_mp4_demuxer_config(const sk_mp4_demuxer *, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap);
+/* packets waiting, the first one's size and the bytes the demuxer holds that are no packet yet */
+int sk_mp4_demuxer_pending(const sk_mp4_demuxer *, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes);
+/* takes the first waiting packet: its raw bytes, decode time and duration in the track's timescale.  None waiting: SK_ERR_BAD_STREAM;
+ * cap too small: SK_ERR_CAPACITY, the packet stays */
+int sk_mp4_demuxer_take(sk_mp4_demuxer *, uint8_t *out, size_t cap, size_t *len, uint64_t *start_time, uint32_t *duration);
+/* sk_mp4_index_trim for a packet the demuxer gave (a fragmented file has no index): its times as sk_mp4_demuxer_take returned them */
+int sk_mp4_demuxer_trim(const sk_mp4_demuxer *, uint64_t start_time, uint32_t duration, uint32_t decoded_frames, uint32_t decoded_rate, uint32_t *first,
+                        uint32_t *count, char *error, size_t error_cap);
+
+/* Mp4MediaIndex::from_file for the chosen track: moov anywhere in the file; every sample's byte range is checked against the file.  A
+ * fragmented file gives its track and no samples (its packets come from the demuxer). */
+typedef struct sk_mp4_index sk_mp4_index;
+int sk_mp4_index_from_file(const uint8_t *file, size_t len, sk_mp4_index **out, char *error, size_t error_cap);
+void sk_mp4_index_destroy(sk_mp4_index *);
+int sk_mp4_index_info(const sk_mp4_index *, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap);
+/* per sample: absolute offset, size, duration and decode time; any array may be NULL; cap < sample_count: SK_ERR_CAPACITY */
+int sk_mp4_index_samples(const sk_mp4_index *, uint64_t *offsets, uint32_t *sizes, uint32_t *durations, uint64_t *start_times, uint32_t cap);
+/* resolve_pcm_packet_trim: the frames of sample `sample`'s decoded packet (decoded_frames at decoded_rate) that the edit keeps.  The
+ * start rounds up, the end down, both are clamped to decoded_frames; nothing kept: (decoded_frames, 0); no edit list: (0, decoded_frames) */
+int sk_mp4_index_trim(const sk_mp4_index *, uint32_t sample, uint32_t decoded_frames, uint32_t decoded_rate, uint32_t *first, uint32_t *count,
+                      char *error, size_t error_cap);
+/* create_adts_header: the seven bytes in front of a raw AAC sample (profile from the config's object type, no CRC) */
+int sk_mp4_adts_header(const uint8_t *asc, size_t asc_len, uint32_t sample_rate, uint32_t channels, size_t raw_len, uint8_t out[7]);
 
 /* ---- ALAC decode stage (GPU, csrc/alac_decode.hip) -------------------------------------------------------------------- */
 /* packets[i] lies at bytes + packets[i].offset, a multiple of 16.  Output: the packets one after the other in the order given, each

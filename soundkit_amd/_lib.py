@@ -25,6 +25,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -601: "AlacInvalid", -602: "AlacStreamRejected", -603: "AlacUnsupportedElement",
              -701: "TelephonyStreamRejected",
              -801: "VorbisNotAudio", -802: "VorbisBadMode", -803: "VorbisPacketShort", -804: "VorbisStreamRejected",
+             -901: "Mp4StreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -202,6 +203,13 @@ class CafAlacInfo(C.Structure):
     """sk_caf_alac_info"""
     _fields_ = [("config", AlacConfig), ("valid_frames", C.c_uint64), ("priming_frames", C.c_uint32), ("remainder_frames", C.c_uint32),
                 ("frames_per_packet", C.c_uint32), ("n_packets", C.c_uint32)]
+
+
+class Mp4TrackInfo(C.Structure):
+    """sk_mp4_track_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("codec", "sample_rate", "channels", "bits_per_sample", "track_id", "timescale", "sample_count",
+                                          "fragmented", "has_edit", "private_len")] + [
+        (n, C.c_uint64) for n in ("edit_presentation_start", "edit_media_start", "edit_duration")]
 
 
 class AlacTickStream(C.Structure):
@@ -586,6 +594,21 @@ _sig = {
     "sk_caf_alac_index_destroy": (None, [_vp]),
     "sk_caf_alac_index_info": (_i, [_vp, C.POINTER(CafAlacInfo)]),
     "sk_caf_alac_index_packets": (_i, [_vp, _vp, _vp, _u32]),
+    "sk_mp4_demuxer_create": (_i, [C.POINTER(_vp)]),
+    "sk_mp4_demuxer_destroy": (None, [_vp]),
+    "sk_mp4_demuxer_add": (_i, [_vp, _vp, _sz]),
+    "sk_mp4_demuxer_finish": (_i, [_vp]),
+    "sk_mp4_demuxer_last_error": (C.c_char_p, [_vp]),
+    "sk_mp4_demuxer_config": (_i, [_vp, C.POINTER(Mp4TrackInfo), _vp, _sz]),
+    "sk_mp4_demuxer_pending": (_i, [_vp, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
+    "sk_mp4_demuxer_take": (_i, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64), C.POINTER(_u32)]),
+    "sk_mp4_demuxer_trim": (_i, [_vp, C.c_uint64, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
+    "sk_mp4_index_from_file": (_i, [_vp, _sz, C.POINTER(_vp), _vp, _sz]),
+    "sk_mp4_index_destroy": (None, [_vp]),
+    "sk_mp4_index_info": (_i, [_vp, C.POINTER(Mp4TrackInfo), _vp, _sz]),
+    "sk_mp4_index_samples": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
+    "sk_mp4_index_trim": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
+    "sk_mp4_adts_header": (_i, [_vp, _sz, _u32, _u32, _sz, _vp]),
     "sk_alac_decode_packets": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_alac_decode_packets_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_tick_alac_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),

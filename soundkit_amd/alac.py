@@ -2,7 +2,7 @@
 (csrc/alac_decode.hip), soundkit-alac's AlacPacketDecoder and CafAlacPacketIndex (soundkit-alac/src/lib.rs:24-300) on top of them, and
 decode_caf: soundkit-decoder's decode_seekable_caf_audio (lib.rs:1029-1092) for an ALAC file.
 
-Channels leave in bitstream order.  Not built: ALAC in MP4 (an MP4 demuxer hands cookie and packets to the same calls)."""
+Channels leave in bitstream order.  ALAC in MP4: mp4.py (its demuxer hands cookie and packets to the same calls)."""
 import ctypes as C
 
 import numpy as np
@@ -189,9 +189,6 @@ def decode_caf(data, options=None, scheduler=None, engine=None):
     -> each trimmed by priming / valid frames -> the output options -> the resampler's flush.  -> (the index, [AudioData]).
     Without options that change anything the AudioData are the trimmed packets themselves; otherwise they are what the scheduler's raw
     PCM stream of the file's format makes of them (the same conversion stage every PCM-family input ends in)."""
-    from .audio_types import AudioData, Endianness, EncodingFlag
-    from .engine import FMT_S16LE, FMT_S24LE, FMT_S32LE
-    from .pipeline import DecodeError, DecodeOptions, RawPcmFormat, default_scheduler
     index = CafAlacPacketIndex.from_file(data)
     packets = index.packet_bytes(data)
     pcm, status, frames = decode_packets(index.config, packets, engine)
@@ -206,14 +203,23 @@ def decode_caf(data, options=None, scheduler=None, engine=None):
         at += n * width
     if not pieces:
         raise SoundkitError(ERR_STREAM, "decode_caf", "Decoding failed: CAF track emitted no audio frames")
+    return index, output_stage(pieces, index.sample_rate, index.channels, index.bit_depth, options, scheduler)
+
+
+def output_stage(pieces, sample_rate, channels, bit_depth, options=None, scheduler=None):
+    """[PCM bytes, signed little-endian] -> [AudioData] under the output options, the resampler flushed at the end (what decode_caf and
+    mp4.decode_file end in).  Without options that change anything the AudioData are the pieces themselves; otherwise they are what the
+    scheduler's raw PCM stream of that format makes of them (the same conversion stage every PCM-family input ends in)."""
+    from .audio_types import AudioData, Endianness, EncodingFlag
+    from .engine import FMT_S16LE, FMT_S24LE, FMT_S32LE
+    from .pipeline import DecodeError, DecodeOptions, RawPcmFormat, default_scheduler
     o = options or DecodeOptions()
-    same = ((o.output_sample_rate or index.sample_rate) == index.sample_rate and (o.output_channels or index.channels) == index.channels and
-            (o.output_bits_per_sample or index.bit_depth) == index.bit_depth)
+    same = ((o.output_sample_rate or sample_rate) == sample_rate and (o.output_channels or channels) == channels and
+            (o.output_bits_per_sample or bit_depth) == bit_depth)
     if same:
-        return index, [AudioData(index.bit_depth, index.channels, index.sample_rate, p, EncodingFlag.PCMSigned, Endianness.LittleEndian)
-                       for p in pieces]
-    fmt = {16: FMT_S16LE, 24: FMT_S24LE, 32: FMT_S32LE}[index.bit_depth]
-    h = (scheduler or default_scheduler()).spawn_raw_pcm(RawPcmFormat(index.sample_rate, index.channels, fmt), o)
+        return [AudioData(bit_depth, channels, sample_rate, p, EncodingFlag.PCMSigned, Endianness.LittleEndian) for p in pieces]
+    fmt = {16: FMT_S16LE, 24: FMT_S24LE, 32: FMT_S32LE}[bit_depth]
+    h = (scheduler or default_scheduler()).spawn_raw_pcm(RawPcmFormat(sample_rate, channels, fmt), o)
     out = []
 
     def take():
@@ -238,4 +244,4 @@ def decode_caf(data, options=None, scheduler=None, engine=None):
             pass
     finally:
         h.cancel()
-    return index, out
+    return out

@@ -23,6 +23,7 @@
 #include "g72x_stream.h"
 #include "gsm_stream.h"
 #include "flac_stream.h"
+#include "mp4_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
 #include <hip/hip_runtime.h>
@@ -129,6 +130,12 @@ struct PStream {
     std::vector<float> vorbis_overlap;
     uint32_t vorbis_prev = 0, vorbis_parse_prev = 0, ogg_serial = 0;
     uint64_t vorbis_absgp = 0;
+    // MP4 / M4A streams (the sniffing spawn took them by their `ftyp`): the demuxer runs on the worker thread; every AAC sample leaves it
+    // wrapped in an ADTS header and is appended to `pending`, where the ADTS pass finds it as it finds an ADTS stream's frame.  mp4_error:
+    // what ends the stream once the frames in front of it have gone; mp4_done: nothing more is pulled
+    std::unique_ptr<sk_mp4::Demuxer> mp4;
+    bool mp4_checked = false, mp4_done = false;
+    std::string mp4_error;
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -136,11 +143,12 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10;
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11;
 constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
+constexpr size_t kMaxMp4QueuedBytes = 4u * 1024 * 1024;  // MAX_AAC_BUFFERED_BYTES (soundkit-aac/src/lib.rs:22): AacDecoderMp4's queue of ADTS frames
 constexpr size_t kMinDetectionBytes = 8192, kMaxDetectionBytes = 65536;  // MIN_ / MAX_DETECTION_BYTES, lib.rs:75-76
 
 struct BatchEntry {  // bookkeeping beside one sk_tick_stream
@@ -437,6 +445,70 @@ int pull_input(PStream &s) {
     return 1;
 }
 
+// An MP4 stream's demuxer output joins `pending` as ADTS frames.  The config event comes first: a track that is not AAC, or an
+// AudioSpecificConfig the AAC-LC config check refuses (sk_aac_decoder_create: explicit SBR or PS, another object type, 960-sample frames, a
+// program config element, more than two channels), ends the stream before any audio.  AacDecoderMp4's queue budget holds.
+void mp4_drain(PStream &s) {
+    sk_mp4::Demuxer &m = *s.mp4;
+    if (m.have_track && !s.mp4_checked && s.mp4_error.empty()) {
+        s.mp4_checked = true;
+        if (m.track.codec != sk_mp4::kCodecAac) {
+            s.mp4_error = "MP4/M4A audio track is not AAC";
+        } else {
+            static const uint8_t none[1] = {0};
+            const std::vector<uint8_t> &asc = m.track.codec_private;
+            sk_aac_decoder *probe = nullptr;
+            const int rc = sk_aac_decoder_create(asc.empty() ? none : asc.data(), asc.size(), &probe);
+            if (rc != SK_OK) s.mp4_error = std::string("AAC-LC decoder init: ") + sk_strerror(rc);
+            sk_aac_decoder_destroy(probe);
+        }
+    }
+    while (!m.packets.empty()) {
+        if (s.mp4_error.empty()) {
+            const std::vector<uint8_t> &raw = m.packets.front().data;
+            if (raw.size() + 7 > 8191) {
+                s.mp4_error = "MP4 AAC sample of " + std::to_string(raw.size()) + " bytes exceeds an ADTS frame";
+            } else if (s.pending.size() - s.pending_pos + raw.size() + 7 > kMaxMp4QueuedBytes) {
+                s.mp4_error = "MP4 AAC packet queue exceeds the " + std::to_string(kMaxMp4QueuedBytes) + " byte streaming budget";
+            } else {
+                uint8_t head[7];
+                sk_mp4::adts_header(m.track.codec_private.data(), m.track.codec_private.size(), m.track.sample_rate, m.track.channels, raw.size(), head);
+                s.pending.insert(s.pending.end(), head, head + 7);
+                s.pending.insert(s.pending.end(), raw.begin(), raw.end());
+            }
+        }
+        m.packets.pop_front();
+    }
+    if (m.failed && s.mp4_error.empty()) s.mp4_error = m.error;
+    if (!s.mp4_error.empty()) s.mp4_done = true;
+}
+
+// pull_input for an MP4 stream: the chunk goes through the demuxer; the end-of-stream marker finishes it
+int pull_mp4(PStream &s) {
+    if (s.mp4_done) return 0;
+    std::vector<uint8_t> chunk;
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (s.in.empty()) return 0;
+        chunk = std::move(s.in.front());
+        s.in.pop_front();
+    }
+    if (s.pending_pos > 0 && s.pending_pos >= s.pending.size() / 2) {  // compact
+        s.pending.erase(s.pending.begin(), s.pending.begin() + (ptrdiff_t)s.pending_pos);
+        s.pending_pos = 0;
+    }
+    if (chunk.empty()) {
+        s.saw_eof = true;
+        s.mp4_done = true;
+        (void)s.mp4->finish();
+    } else {
+        s.queued_bytes.fetch_sub(chunk.size());
+        (void)s.mp4->add(chunk.data(), chunk.size());
+    }
+    mp4_drain(s);
+    return chunk.empty() ? -1 : 1;
+}
+
 // The tables an MP3 stream needs: the code book for the host's Huffman stage, band tables and synthesis window on the engine;
 // the batches get their granule arrays.  Once per lane, at the first MP3 stream.
 int ensure_mp3(sk_lane *p);
@@ -452,6 +524,9 @@ namespace {
 // What the stream's first bytes are (detect_audio at lib.rs:3042 looks at magic numbers; on this path two formats exist):
 // an ID3v2 tag or an MPEG audio sync with a layer field -> MP3; an ADTS sync (layer bits 00) -> AAC.  0 = not enough bytes yet.
 uint8_t sniff_codec(const uint8_t *d, size_t n) {
+    // ....ftyp -> MP4 / M4A (AudioType::M4A, looks_like_mp4: 12 bytes); fewer bytes that may still become that: wait
+    if (n >= 8 && std::memcmp(d + 4, "ftyp", 4) == 0) return n < 12 ? 0 : kCodecMp4;
+    if (n > 4 && n < 8 && std::memcmp(d + 4, "ftyp", n - 4) == 0) return 0;
     // RIFF....WAVE / RF64....WAVE -> WAV (AudioType::Wav, lib.rs:3090-3093); fewer than 12 bytes that may still become that: wait
     if (n >= 4 && (std::memcmp(d, "RIFF", 4) == 0 || std::memcmp(d, "RF64", 4) == 0)) {
         if (n < 12) return 0;
@@ -1385,6 +1460,18 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         parse_some_pcm(p, s, room, r);
         return;
     }
+    if (s.codec == kCodecMp4 && !s.mp4) {  // taken by its ftyp: the box walk starts here, with the bytes of the detection
+        s.mp4.reset(new sk_mp4::Demuxer());
+        const std::vector<uint8_t> head(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
+        s.pending.clear();
+        s.pending_pos = 0;
+        for (size_t at = 0; at < head.size(); at += 1u << 20) (void)s.mp4->add(head.data() + at, std::min<size_t>(1u << 20, head.size() - at));
+        if (s.saw_eof) {
+            s.mp4_done = true;
+            (void)s.mp4->finish();
+        }
+        mp4_drain(s);
+    }
     while (r.n_frames < limit && !r.failed) {
         // make sure a whole frame is in `pending`
         size_t avail = s.pending.size() - s.pending_pos;
@@ -1402,6 +1489,14 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             break;
         }
         if (!have) {
+            if (s.mp4 && !s.mp4_done) {  // an MP4 stream: more frames come out of the demuxer
+                if (pull_mp4(s) == 0) break;
+                continue;
+            }
+            if (s.mp4 && !s.mp4_error.empty()) {  // every complete unit has gone: what the demuxer or the config check refused
+                r.fail(SK_MP4_ERR_STREAM, "Decoding failed: " + s.mp4_error);
+                break;
+            }
             if (s.saw_eof) {  // whatever is left is not a frame: flush_decoder has nothing more to give
                 r.eof = true;
                 break;
@@ -2573,6 +2668,9 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.flac_plain = false;
     s.alac = s.alac_plain = false;
     s.alac_cfg = sk_alac_config{};
+    s.mp4.reset();
+    s.mp4_checked = s.mp4_done = false;
+    s.mp4_error.clear();
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
@@ -3286,6 +3384,213 @@ const char *sk_aiff_reader_last_error(const sk_aiff_reader *r) try {
 } catch (...) {
     (void)sk::abi_caught("sk_aiff_reader_last_error");
     return "";
+}
+
+}  // extern "C"
+
+// ---- MP4 / M4A (mp4_stream.h) -----------------------------------------------------------------------------------------------------
+
+struct sk_mp4_demuxer {
+    sk_mp4::Demuxer demuxer;
+};
+
+struct sk_mp4_index {
+    sk_mp4::Track track;
+};
+
+namespace {
+
+void mp4_text(char *error, size_t cap, const std::string &text) {
+    if (!error || cap == 0) return;
+    const size_t n = std::min(cap - 1, text.size());
+    std::memcpy(error, text.data(), n);
+    error[n] = 0;
+}
+
+int mp4_track_info(const sk_mp4::Track &t, bool have, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap) {
+    std::memset(info, 0, sizeof *info);
+    if (!have) return SK_OK;
+    info->codec = t.codec, info->sample_rate = t.sample_rate, info->channels = t.channels, info->bits_per_sample = t.bits;
+    info->track_id = t.id, info->timescale = t.timescale, info->sample_count = (uint32_t)t.samples.size();
+    info->fragmented = t.fragmented ? 1 : 0, info->has_edit = t.has_edit ? 1 : 0;
+    info->private_len = (uint32_t)t.codec_private.size();
+    info->edit_presentation_start = t.edit_presentation_start, info->edit_media_start = t.edit_media_start, info->edit_duration = t.edit_duration;
+    if (private_cap < t.codec_private.size()) return SK_ERR_CAPACITY;
+    if (!t.codec_private.empty()) std::memcpy(codec_private, t.codec_private.data(), t.codec_private.size());
+    return SK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sk_mp4_demuxer_create(sk_mp4_demuxer **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_mp4_demuxer();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_create");
+}
+
+void sk_mp4_demuxer_destroy(sk_mp4_demuxer *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_mp4_demuxer_destroy");
+}
+
+int sk_mp4_demuxer_add(sk_mp4_demuxer *d, const uint8_t *bytes, size_t len) try {
+    sk::abi_enter();
+    if (!d || (len && !bytes)) return SK_ERR_INVALID_ARG;
+    return d->demuxer.add(bytes, len) ? SK_OK : SK_MP4_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_add");
+}
+
+int sk_mp4_demuxer_finish(sk_mp4_demuxer *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    return d->demuxer.finish() ? SK_OK : SK_MP4_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_finish");
+}
+
+const char *sk_mp4_demuxer_last_error(const sk_mp4_demuxer *d) try {
+    sk::abi_enter();
+    return d ? d->demuxer.error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_mp4_demuxer_last_error");
+    return "";
+}
+
+int sk_mp4_demuxer_config(const sk_mp4_demuxer *d, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap) try {
+    sk::abi_enter();
+    if (!d || !info || (private_cap && !codec_private)) return SK_ERR_INVALID_ARG;
+    return mp4_track_info(d->demuxer.track, d->demuxer.have_track, info, codec_private, private_cap);
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_config");
+}
+
+int sk_mp4_demuxer_pending(const sk_mp4_demuxer *d, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (n_packets) *n_packets = (uint32_t)d->demuxer.packets.size();
+    if (front_bytes) *front_bytes = d->demuxer.packets.empty() ? 0 : d->demuxer.packets.front().data.size();
+    if (buffered_bytes) *buffered_bytes = d->demuxer.buffered();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_pending");
+}
+
+int sk_mp4_demuxer_take(sk_mp4_demuxer *d, uint8_t *out, size_t cap, size_t *len, uint64_t *start_time, uint32_t *duration) try {
+    sk::abi_enter();
+    if (!d || !len || (cap && !out)) return SK_ERR_INVALID_ARG;
+    if (d->demuxer.packets.empty()) return SK_ERR_BAD_STREAM;
+    const sk_mp4::Packet &p = d->demuxer.packets.front();
+    *len = p.data.size();
+    if (cap < p.data.size()) return SK_ERR_CAPACITY;
+    if (!p.data.empty()) std::memcpy(out, p.data.data(), p.data.size());
+    if (start_time) *start_time = p.start;
+    if (duration) *duration = p.duration;
+    d->demuxer.packets.pop_front();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_take");
+}
+
+int sk_mp4_demuxer_trim(const sk_mp4_demuxer *d, uint64_t start_time, uint32_t duration, uint32_t decoded_frames, uint32_t decoded_rate, uint32_t *first,
+                        uint32_t *count, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if (!d || !first || !count) return SK_ERR_INVALID_ARG;
+    mp4_text(error, error_cap, "");
+    std::string text = "MP4 demuxer has no track yet";
+    sk_mp4::Sample s;
+    s.start = start_time, s.duration = duration;
+    if (!d->demuxer.have_track || !sk_mp4::trim(d->demuxer.track, s, decoded_frames, decoded_rate, first, count, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_MP4_ERR_STREAM;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_trim");
+}
+
+int sk_mp4_index_from_file(const uint8_t *file, size_t len, sk_mp4_index **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !file) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    mp4_text(error, error_cap, "");
+    std::unique_ptr<sk_mp4_index> ix(new sk_mp4_index());
+    std::string text;
+    static const uint8_t none[1] = {0};
+    if (!sk_mp4::index_from_file(len ? file : none, len, &ix->track, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_MP4_ERR_STREAM;
+    }
+    *out = ix.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_index_from_file");
+}
+
+void sk_mp4_index_destroy(sk_mp4_index *ix) try {
+    sk::abi_enter();
+    delete ix;
+} catch (...) {
+    (void)sk::abi_caught("sk_mp4_index_destroy");
+}
+
+int sk_mp4_index_info(const sk_mp4_index *ix, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap) try {
+    sk::abi_enter();
+    if (!ix || !info || (private_cap && !codec_private)) return SK_ERR_INVALID_ARG;
+    return mp4_track_info(ix->track, true, info, codec_private, private_cap);
+} catch (...) {
+    return sk::abi_caught("sk_mp4_index_info");
+}
+
+int sk_mp4_index_samples(const sk_mp4_index *ix, uint64_t *offsets, uint32_t *sizes, uint32_t *durations, uint64_t *start_times, uint32_t cap) try {
+    sk::abi_enter();
+    if (!ix) return SK_ERR_INVALID_ARG;
+    const std::vector<sk_mp4::Sample> &s = ix->track.samples;
+    if (cap < s.size()) return SK_ERR_CAPACITY;
+    for (size_t i = 0; i < s.size(); ++i) {
+        if (offsets) offsets[i] = s[i].offset;
+        if (sizes) sizes[i] = s[i].size;
+        if (durations) durations[i] = s[i].duration;
+        if (start_times) start_times[i] = s[i].start;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_index_samples");
+}
+
+int sk_mp4_index_trim(const sk_mp4_index *ix, uint32_t sample, uint32_t decoded_frames, uint32_t decoded_rate, uint32_t *first, uint32_t *count,
+                      char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if (!ix || !first || !count) return SK_ERR_INVALID_ARG;
+    mp4_text(error, error_cap, "");
+    std::string text;
+    if (sample >= ix->track.samples.size()) {
+        mp4_text(error, error_cap, "MP4 sample index " + std::to_string(sample) + " is out of range");
+        return SK_MP4_ERR_STREAM;
+    }
+    if (!sk_mp4::trim(ix->track, ix->track.samples[sample], decoded_frames, decoded_rate, first, count, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_MP4_ERR_STREAM;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_index_trim");
+}
+
+int sk_mp4_adts_header(const uint8_t *asc, size_t asc_len, uint32_t sample_rate, uint32_t channels, size_t raw_len, uint8_t out[7]) try {
+    sk::abi_enter();
+    if ((asc_len && !asc) || !out) return SK_ERR_INVALID_ARG;
+    sk_mp4::adts_header(asc, asc_len, sample_rate, channels, raw_len, out);
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_adts_header");
 }
 
 int sk_debug_throw_in_thread(int n, int where) {

@@ -9,6 +9,8 @@ streams; a stream with nothing to change is passed through as it is, any width a
 `spawn_raw_pcm[_with_options](RawPcmFormat)`, and AIFF / AIFF-C (`FORM....AIFF|AIFC`, or `spawn_aiff[_with_options]`: the walker of
 soundkit-aiff, its per-sample decode -- byte order, widening, f64, G.711, IMA4 -- and the same output stage in the batched tick).
 AudioData from WAV / raw PCM / AIFF streams carries the real `audio_format` and `endianness`.
+MP4 / M4A (`....ftyp`) with an AAC-LC track, regular (`moov` in front of `mdat`) or fragmented: demuxed on the entropy thread
+(csrc/mp4_stream.h), then exactly an ADTS stream; whole files in any box order, and ALAC tracks, go through `mp4.decode_file`.
 The reference's other formats stay with their CPU decoders (out of scope)."""
 import ctypes as C
 from dataclasses import dataclass
