@@ -1352,6 +1352,63 @@ int sk_mp4_index_trim(const sk_mp4_index *, uint32_t sample, uint32_t decoded_fr
 /* create_adts_header: the seven bytes in front of a raw AAC sample (profile from the config's object type, no CRC) */
 int sk_mp4_adts_header(const uint8_t *asc, size_t asc_len, uint32_t sample_rate, uint32_t channels, size_t raw_len, uint8_t out[7]);
 
+/* ---- WebM / Matroska, audio only (host, csrc/webm_stream.h) -------------------------------------------------------------------------
+ * The streaming EBML walk of soundkit-webm's WebmAudioDemuxer with its checks, texts and budgets: the EBML header (read version, id and
+ * size widths, DocType `webm` / `matroska`), a Segment of known or unknown size, Info / TimecodeScale, Tracks / TrackEntry (TrackNumber,
+ * TrackType, CodecID, CodecPrivate, DefaultDuration, CodecDelay, SeekPreRoll, TrackTimestampScale, ContentEncodings -- header stripping
+ * alone -- and Audio's SamplingFrequency and Channels), then Clusters of known or unknown size with Timecode, SimpleBlock, Block and
+ * BlockGroup (BlockDuration, ReferenceBlock, DiscardPadding), all four lacings.  Everything else is stepped over by its size.  Reported:
+ * the audio tracks whose CodecID is A_VORBIS, A_AAC, A_FLAC, A_ALAC or A_OPUS (of a repeated TrackNumber the first entry), once the first
+ * Cluster header has arrived; blocks of other tracks are dropped.  Budgets: 4 MiB a call, 16 MiB a metadata element, 64 MiB a block
+ * element (both from the element's header), 64 MiB + 64 KiB buffered.  A refusal is SK_WEBM_ERR_STREAM with a text
+ * (sk_webm_demuxer_last_error, or `error`: NUL-terminated, cut to error_cap; may be NULL); the demuxer stays refused.
+ * Not read: Cues / seeking, chained segments, EBML CRC-32, any other ContentCompression, encryption, the old A_AAC/MPEG4/... ids, video. */
+enum sk_webm_status { SK_WEBM_ERR_STREAM = -1001 };
+enum sk_webm_codec { SK_WEBM_CODEC_VORBIS = 1, SK_WEBM_CODEC_AAC = 2, SK_WEBM_CODEC_FLAC = 3, SK_WEBM_CODEC_ALAC = 4, SK_WEBM_CODEC_OPUS = 5 };
+typedef struct sk_webm_track_info {
+    uint64_t track_number;
+    uint64_t codec_delay_ns, seek_pre_roll_ns;
+    uint64_t default_duration_ns; /* 0: none */
+    uint64_t timecode_scale_ns;   /* the Segment's: Info / TimecodeScale, 1 000 000 without one */
+    double track_timestamp_scale;
+    uint32_t codec;               /* sk_webm_codec */
+    uint32_t sample_rate;         /* Audio / SamplingFrequency rounded; 48 000 without one */
+    uint32_t channels;            /* 2 without one */
+    uint32_t private_len;         /* bytes of CodecPrivate */
+    uint32_t prefix_len;          /* bytes header stripping took off every frame (the demuxer has put them back) */
+    uint32_t reserved;
+} sk_webm_track_info;
+typedef struct sk_webm_demuxer sk_webm_demuxer;
+int sk_webm_demuxer_create(sk_webm_demuxer **out);
+void sk_webm_demuxer_destroy(sk_webm_demuxer *);
+int sk_webm_demuxer_add(sk_webm_demuxer *, const uint8_t *bytes, size_t len);
+/* `truncated WebM element: N buffered bytes remain`, then `WebM source has no supported audio track` */
+int sk_webm_demuxer_finish(sk_webm_demuxer *);
+const char *sk_webm_demuxer_last_error(const sk_webm_demuxer *);
+/* the config events: 0 tracks before the first Cluster header */
+uint32_t sk_webm_demuxer_n_tracks(const sk_webm_demuxer *);
+/* track `index` of them; either byte array may be NULL with a cap of 0; a cap below its length: SK_ERR_CAPACITY (info is filled) */
+int sk_webm_demuxer_config(const sk_webm_demuxer *, uint32_t index, sk_webm_track_info *info, uint8_t *codec_private, size_t private_cap,
+                           uint8_t *prefix, size_t prefix_cap);
+/* packets waiting, the first one's size and the bytes the demuxer holds that are no packet yet */
+int sk_webm_demuxer_pending(const sk_webm_demuxer *, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes);
+typedef struct sk_webm_packet_info {
+    uint64_t track_number;
+    int64_t timestamp_ns;       /* (cluster + relative timecode) x TimecodeScale x TrackTimestampScale, rounded, minus CodecDelay; laced frames advance by their durations */
+    uint64_t duration_ns;       /* BlockDuration / frames of the block, else DefaultDuration, else (Opus) the packet's own */
+    int64_t discard_padding_ns; /* on the block's last frame: negative trims the decoded front, positive the back */
+    uint32_t codec;             /* sk_webm_codec */
+    uint8_t has_duration, has_discard_padding;
+    uint8_t reserved[2];
+} sk_webm_packet_info;
+/* takes the first waiting packet.  None waiting: SK_ERR_BAD_STREAM; cap too small: SK_ERR_CAPACITY, the packet stays */
+int sk_webm_demuxer_take(sk_webm_demuxer *, uint8_t *out, size_t cap, size_t *len, sk_webm_packet_info *info);
+/* parse_vorbis_codec_private: an A_VORBIS CodecPrivate -> its three headers as offsets into it and sizes */
+int sk_webm_vorbis_headers(const uint8_t *codec_private, size_t len, size_t offsets[3], size_t sizes[3], char *error, size_t error_cap);
+/* discard_padding_frames: ceil(|padding_ns| x sample_rate / 1e9) capped at decoded_frames, off the front (negative) or the back */
+int sk_webm_discard_frames(int64_t padding_ns, uint32_t sample_rate, uint32_t decoded_frames, uint32_t *front, uint32_t *back, char *error,
+                           size_t error_cap);
+
 /* ---- ALAC decode stage (GPU, csrc/alac_decode.hip) -------------------------------------------------------------------- */
 /* packets[i] lies at bytes + packets[i].offset, a multiple of 16.  Output: the packets one after the other in the order given, each
  * frames x channels samples interleaved in bitstream channel order, little-endian in bit_depth / 8 bytes.  frames_per_packet[i] is what
@@ -1770,11 +1827,13 @@ int sk_vorbis_entropy_decode(sk_engine *, const sk_vorbis_stream *streams, uint3
  * yield none; status_per_packet says which were rejected).  Every other stream then runs exactly what sk_tick_run_pcm runs on an
  * interleaved s16le source of its channel count -- same kernels, records, bounds and limits; 3 ... 8 channels with a conversion need
  * sk_engine_enable_wide_pcm.  The output does not depend on how a stream's packets are dealt out over ticks.  keep_frames cuts a
- * packet's frames (the Ogg decoder's truncation of a stream's last packet to the final granule position); 0xffffffff keeps all. */
+ * packet's frames (the Ogg decoder's truncation of a stream's last packet to the final granule position); 0xffffffff keeps all.
+ * skip_frames drops that many of the packet's frames at its front (Matroska's negative DiscardPadding) before keep_frames applies to
+ * what is left; a packet of which nothing is left yields no output, and its overlap half is carried on as ever. */
 typedef struct sk_vorbis_tick_packet {
     uint32_t offset, size;
     uint32_t keep_frames;
-    uint32_t reserved;
+    uint32_t skip_frames;
 } sk_vorbis_tick_packet;
 typedef struct sk_vorbis_tick_stream {
     const sk_vorbis_setup *setup;

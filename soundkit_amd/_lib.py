@@ -26,6 +26,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -701: "TelephonyStreamRejected",
              -801: "VorbisNotAudio", -802: "VorbisBadMode", -803: "VorbisPacketShort", -804: "VorbisStreamRejected",
              -901: "Mp4StreamRejected",
+             -1001: "WebmStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -212,6 +213,18 @@ class Mp4TrackInfo(C.Structure):
         (n, C.c_uint64) for n in ("edit_presentation_start", "edit_media_start", "edit_duration")]
 
 
+class WebmTrackInfo(C.Structure):
+    """sk_webm_track_info"""
+    _fields_ = [(n, C.c_uint64) for n in ("track_number", "codec_delay_ns", "seek_pre_roll_ns", "default_duration_ns", "timecode_scale_ns")] + [
+        ("track_timestamp_scale", C.c_double)] + [(n, C.c_uint32) for n in ("codec", "sample_rate", "channels", "private_len", "prefix_len", "reserved")]
+
+
+class WebmPacketInfo(C.Structure):
+    """sk_webm_packet_info"""
+    _fields_ = [("track_number", C.c_uint64), ("timestamp_ns", C.c_int64), ("duration_ns", C.c_uint64), ("discard_padding_ns", C.c_int64),
+                ("codec", C.c_uint32), ("has_duration", C.c_uint8), ("has_discard_padding", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
 class AlacTickStream(C.Structure):
     """sk_alac_tick_stream"""
     _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("frame_length", C.c_uint32)] + [
@@ -315,7 +328,7 @@ class VorbisTickStream(C.Structure):
 
 class VorbisTickPacket(C.Structure):
     """sk_vorbis_tick_packet"""
-    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32), ("keep_frames", C.c_uint32), ("reserved", C.c_uint32)]
+    _fields_ = [("offset", C.c_uint32), ("size", C.c_uint32), ("keep_frames", C.c_uint32), ("skip_frames", C.c_uint32)]
 
 
 class VorbisPacket(C.Structure):
@@ -609,6 +622,17 @@ _sig = {
     "sk_mp4_index_samples": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
     "sk_mp4_index_trim": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
     "sk_mp4_adts_header": (_i, [_vp, _sz, _u32, _u32, _sz, _vp]),
+    "sk_webm_demuxer_create": (_i, [C.POINTER(_vp)]),
+    "sk_webm_demuxer_destroy": (None, [_vp]),
+    "sk_webm_demuxer_add": (_i, [_vp, _vp, _sz]),
+    "sk_webm_demuxer_finish": (_i, [_vp]),
+    "sk_webm_demuxer_last_error": (C.c_char_p, [_vp]),
+    "sk_webm_demuxer_n_tracks": (_u32, [_vp]),
+    "sk_webm_demuxer_config": (_i, [_vp, _u32, C.POINTER(WebmTrackInfo), _vp, _sz, _vp, _sz]),
+    "sk_webm_demuxer_pending": (_i, [_vp, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
+    "sk_webm_demuxer_take": (_i, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(WebmPacketInfo)]),
+    "sk_webm_vorbis_headers": (_i, [_vp, _sz, C.POINTER(_sz * 3), C.POINTER(_sz * 3), _vp, _sz]),
+    "sk_webm_discard_frames": (_i, [C.c_int64, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
     "sk_alac_decode_packets": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_alac_decode_packets_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_tick_alac_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),

@@ -609,6 +609,7 @@ const char *sk_strerror(int status) try {
     case SK_VORBIS_SHORT: return "Vorbis packet ends inside its first bits";
     case SK_VORBIS_ERR_STREAM: return "Ogg / Vorbis stream rejected";
     case SK_MP4_ERR_STREAM: return "MP4 stream rejected";
+    case SK_WEBM_ERR_STREAM: return "WebM stream rejected";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -7580,8 +7581,12 @@ enum VorbisWhat { kVorbisS16 = 0, kVorbisF32 = 1, kVorbisEntropy = 2 };
 struct VorbisDevDst {
     uint8_t *base = nullptr;
     std::vector<uint64_t> offsets;  // per packet of the call, in samples
-    std::vector<uint32_t> keep;     // per packet: at most so many of its frames (0xffffffff: all)
+    std::vector<uint32_t> keep;     // per packet: at most so many of its frames (0xffffffff: all) ...
+    std::vector<uint32_t> skip;     // ... of those behind the first skip[k]
 };
+
+// the frames a packet of `full` frames gives once `skip` have gone off its front and at most `keep` of the rest stay
+inline uint32_t vorbis_kept(uint32_t full, uint32_t skip, uint32_t keep) { return std::min(full - std::min(full, skip), keep); }
 
 // sk_vorbis_decode_packets and sk_vorbis_entropy_decode.  The host reads every packet's first bits itself (sk_vorbis::packet_head), so the
 // place of every packet in the workspaces and in the output is known before anything is launched.  The host decides: a packet it refuses
@@ -7636,7 +7641,10 @@ int vorbis_run(sk_engine *e, sk_vorbis_stream *streams, uint32_t n_streams, cons
             res_floats += (uint64_t)ch * (h.n / 2), cls_bytes += up16((uint64_t)ch * (h.n / 2)), pcm_floats += (uint64_t)ch * h.n;
             t.prev_n = prev_n, t.prev_pcm = prev_pcm, t.prev_in_carry = prev_in_carry;
             t.out_frames = prev_n ? prev_n / 4 + h.n / 4 : 0;
-            if (dev) t.out_frames = std::min(t.out_frames, dev->keep[at]);
+            if (dev) {
+                t.out_skip = std::min(t.out_frames, dev->skip[at]);
+                t.out_frames = vorbis_kept(t.out_frames, dev->skip[at], dev->keep[at]);
+            }
             t.out_offset = dev ? dev->offsets[at] : out_samples;
             out_samples += (uint64_t)t.out_frames * ch;
             prev_n = h.n, prev_pcm = t.pcm_offset + h.n / 2, prev_in_carry = 0;
@@ -7783,7 +7791,7 @@ int vorbis_tick_derive(const sk_vorbis_tick_stream *vs, uint32_t n_streams, cons
             sk_vorbis::PacketHead h;
             d.status[at] = sk_vorbis::packet_head(su, bytes + p.offset, p.size, &h);
             if (d.status[at] != sk_vorbis::kOk) continue;
-            d.frames[at] = std::min(prev ? prev / 4 + h.n / 4 : 0, p.keep_frames);
+            d.frames[at] = vorbis_kept(prev ? prev / 4 + h.n / 4 : 0, p.skip_frames, p.keep_frames);
             prev = h.n;
             if (!d.frames[at]) continue;
             const uint64_t decoded = (uint64_t)d.frames[at] * ch * 2;
@@ -7810,7 +7818,7 @@ int vorbis_tick_decode(sk_engine *e, const sk_vorbis_tick_stream *vs, const sk_v
     std::vector<uint32_t> sub_of, index;
     std::vector<sk_vorbis_packet> subp;
     std::vector<uint8_t *> dst;
-    std::vector<uint32_t> keep;
+    std::vector<uint32_t> keep, skip;
     uint8_t *base = nullptr;
     for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
         if ((d.tick.plain[i] != 0) != as_is || vs[i].n_units == 0) continue;
@@ -7820,7 +7828,7 @@ int vorbis_tick_decode(sk_engine *e, const sk_vorbis_tick_stream *vs, const sk_v
             const uint32_t g = d.first_packet[i] + u;
             uint8_t *to = d.unit_of[g] != 0xffffffffu ? dst_of(i, d.unit_of[g]) : nullptr;
             if (to && (!base || to < base)) base = to;
-            index.push_back(g), subp.push_back(sk_vorbis_packet{packets[g].offset, packets[g].size}), dst.push_back(to), keep.push_back(packets[g].keep_frames);
+            index.push_back(g), subp.push_back(sk_vorbis_packet{packets[g].offset, packets[g].size}), dst.push_back(to), keep.push_back(packets[g].keep_frames), skip.push_back(packets[g].skip_frames);
         }
     }
     if (sub.empty()) return SK_OK;
@@ -7828,6 +7836,7 @@ int vorbis_tick_decode(sk_engine *e, const sk_vorbis_tick_stream *vs, const sk_v
     dev.base = base;
     dev.offsets.assign(dst.size(), 0);
     dev.keep = keep;
+    dev.skip = skip;
     for (size_t k = 0; k < dst.size(); ++k)
         if (dst[k]) dev.offsets[k] = (uint64_t)(dst[k] - base) / 2;
     std::vector<int32_t> status(index.size(), 0);

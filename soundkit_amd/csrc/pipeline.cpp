@@ -24,6 +24,7 @@
 #include "gsm_stream.h"
 #include "flac_stream.h"
 #include "mp4_stream.h"
+#include "webm_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
 #include <hip/hip_runtime.h>
@@ -136,6 +137,14 @@ struct PStream {
     std::unique_ptr<sk_mp4::Demuxer> mp4;
     bool mp4_checked = false, mp4_done = false;
     std::string mp4_error;
+    // WebM / Matroska streams (taken by their EBML magic): the demuxer runs on the worker thread.  At the first Cluster its single audio
+    // track decides where the frames go (webm_open), and the stream is from then on a Vorbis stream whose packets come from the demuxer,
+    // an ADTS stream (every frame wrapped in seven bytes, as an MP4 sample is) or a native FLAC stream (the CodecPrivate, then the
+    // frames).  webm_error: what ends the stream once the units in front of it have gone; webm_done: nothing more is pulled
+    std::unique_ptr<sk_webm::Demuxer> webm;
+    bool webm_routed = false, webm_done = false, webm_flac_head = false;
+    uint32_t webm_rate = 0, webm_channels = 0;  // A_AAC: the AudioSpecificConfig's, for the ADTS headers
+    std::string webm_error;
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -143,12 +152,13 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11;
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11, kCodecWebm = 12;
 constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
 constexpr size_t kMaxMp4QueuedBytes = 4u * 1024 * 1024;  // MAX_AAC_BUFFERED_BYTES (soundkit-aac/src/lib.rs:22): AacDecoderMp4's queue of ADTS frames
+constexpr size_t kMaxWebmQueuedBytes = 16u * 1024 * 1024;  // what a WebM stream's demuxer may hold as packets between two passes (half a tick's staging buffer)
 constexpr size_t kMinDetectionBytes = 8192, kMaxDetectionBytes = 65536;  // MIN_ / MAX_DETECTION_BYTES, lib.rs:75-76
 
 struct BatchEntry {  // bookkeeping beside one sk_tick_stream
@@ -509,6 +519,82 @@ int pull_mp4(PStream &s) {
     return chunk.empty() ? -1 : 1;
 }
 
+// A WebM stream's demuxer takes a chunk, or (end) the end of the input.  A refusal is kept for when the units in front of it have gone;
+// so is a queue of packets beyond the budget (frames far smaller than their header-stripping prefix can make one out of a 4 MiB chunk).
+void webm_feed(PStream &s, const uint8_t *data, size_t len, bool end) {
+    sk_webm::Demuxer &w = *s.webm;
+    if (end) {
+        s.webm_done = true;
+        (void)w.finish();
+    } else {
+        (void)w.add(data, len);
+    }
+    if (w.failed && s.webm_error.empty()) s.webm_error = w.error;
+    if (s.webm_error.empty() && w.queued_bytes() > kMaxWebmQueuedBytes)
+        s.webm_error = "WebM packet queue exceeds the " + std::to_string(kMaxWebmQueuedBytes) + " byte streaming budget";
+    if (!s.webm_error.empty()) s.webm_done = true;
+}
+
+// pull_input for a WebM stream: the chunk goes through the demuxer; the end-of-stream marker finishes it
+int webm_pull(PStream &s) {
+    if (s.webm_done) return 0;
+    std::vector<uint8_t> chunk;
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (s.in.empty()) return 0;
+        chunk = std::move(s.in.front());
+        s.in.pop_front();
+    }
+    if (chunk.empty()) {
+        s.saw_eof = true;
+        webm_feed(s, nullptr, 0, true);
+        return -1;
+    }
+    s.queued_bytes.fetch_sub(chunk.size());
+    webm_feed(s, chunk.data(), chunk.size(), false);
+    return 1;
+}
+
+// An A_AAC track's frames join `pending` as ADTS frames, as an MP4 track's samples do (mp4_drain), under the same queue budget
+void webm_drain_aac(PStream &s) {
+    sk_webm::Demuxer &w = *s.webm;
+    if (s.pending_pos > 0 && s.pending_pos >= s.pending.size() / 2) {  // compact
+        s.pending.erase(s.pending.begin(), s.pending.begin() + (ptrdiff_t)s.pending_pos);
+        s.pending_pos = 0;
+    }
+    const std::vector<uint8_t> &asc = w.audio.front().codec_private;
+    while (!w.packets.empty()) {
+        if (s.webm_error.empty()) {
+            const std::vector<uint8_t> &raw = w.packets.front().data;
+            if (raw.size() + 7 > 8191) {
+                s.webm_error = "WebM AAC frame of " + std::to_string(raw.size()) + " bytes exceeds an ADTS frame";
+            } else if (s.pending.size() - s.pending_pos + raw.size() + 7 > kMaxMp4QueuedBytes) {
+                s.webm_error = "WebM AAC packet queue exceeds the " + std::to_string(kMaxMp4QueuedBytes) + " byte streaming budget";
+            } else {
+                uint8_t head[7];
+                sk_mp4::adts_header(asc.data(), asc.size(), s.webm_rate, s.webm_channels, raw.size(), head);
+                s.pending.insert(s.pending.end(), head, head + 7);
+                s.pending.insert(s.pending.end(), raw.begin(), raw.end());
+            }
+        }
+        w.pop_packet();
+    }
+    if (!s.webm_error.empty()) s.webm_done = true;
+}
+
+// An A_FLAC track's bytes as a native FLAC stream: the CodecPrivate (`fLaC` and the metadata blocks) once, then the frames
+void webm_flac_bytes(PStream &s, std::vector<uint8_t> &out) {
+    sk_webm::Demuxer &w = *s.webm;
+    if (s.webm_flac_head) {
+        s.webm_flac_head = false;
+        out = w.audio.front().codec_private;
+    }
+    while (!w.packets.empty()) {
+        out.insert(out.end(), w.packets.front().data.begin(), w.packets.front().data.end());
+        w.pop_packet();
+    }
+}
+
 // The tables an MP3 stream needs: the code book for the host's Huffman stage, band tables and synthesis window on the engine;
 // the batches get their granule arrays.  Once per lane, at the first MP3 stream.
 int ensure_mp3(sk_lane *p);
@@ -524,6 +610,10 @@ namespace {
 // What the stream's first bytes are (detect_audio at lib.rs:3042 looks at magic numbers; on this path two formats exist):
 // an ID3v2 tag or an MPEG audio sync with a layer field -> MP3; an ADTS sync (layer bits 00) -> AAC.  0 = not enough bytes yet.
 uint8_t sniff_codec(const uint8_t *d, size_t n) {
+    // 1A 45 DF A3 -> WebM / Matroska (AudioType::Webm); fewer bytes that match so far: wait.  Before the MPEG sync scan, which would
+    // find a sync somewhere inside the file
+    static const uint8_t ebml[4] = {0x1A, 0x45, 0xDF, 0xA3};
+    if (n > 0 && std::memcmp(d, ebml, std::min<size_t>(n, 4)) == 0) return n < 4 ? 0 : kCodecWebm;
     // ....ftyp -> MP4 / M4A (AudioType::M4A, looks_like_mp4: 12 bytes); fewer bytes that may still become that: wait
     if (n >= 8 && std::memcmp(d + 4, "ftyp", 4) == 0) return n < 12 ? 0 : kCodecMp4;
     if (n > 4 && n < 8 && std::memcmp(d + 4, "ftyp", n - 4) == 0) return 0;
@@ -1108,12 +1198,10 @@ void parse_some_alac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
 // spawn and every chunk is one audio packet.  Either way whole audio packets are what the stream is budgeted in.  The host reads a
 // packet's first bits (vorbis_stream.h), so the frames it will yield are known here -- none for the stream's first packet -- and with
 // them the Ogg decoder's cut of the last packet to the final granule position.  A packet whose first bits are refused ends the stream
-// with its text, as read_audio_packet_generic's error does.
-void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
-    r.pcm = true;
-    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
-    uint32_t outputs = 0;
-    auto header = [&](const uint8_t *d, size_t n) -> bool {
+// with its text, as read_audio_packet_generic's error does.  From WebM (webm_open has read the headers out of the CodecPrivate): the
+// chunks go through the demuxer and every frame it hands out is one audio packet; a frame's DiscardPadding becomes the tick's
+// skip_frames / keep_frames through the reference's conversion, at the identification header's rate.
+bool vorbis_header(PStream &s, Parsed &r, const uint8_t *d, size_t n) {
         std::string text;
         int rc;
         if (s.vorbis_headers == 0) {
@@ -1131,15 +1219,27 @@ void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: " + text);
         ++s.vorbis_headers;
         return true;
-    };
-    auto audio = [&](const uint8_t *d, size_t n, const sk_ogg::Packet *op) -> bool {
+}
+
+void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
+    r.pcm = true;
+    const uint32_t per_pass = std::min<uint32_t>(std::max<uint32_t>(p->cfg.max_stream_frames_per_tick, 1), 65536);
+    uint32_t outputs = 0;
+    auto header = [&](const uint8_t *d, size_t n) -> bool { return vorbis_header(s, r, d, n); };
+    auto audio = [&](const uint8_t *d, size_t n, const sk_ogg::Packet *op, const sk_webm::Packet *wp = nullptr) -> bool {
         if (!s.pcm_route && !pcm_open(p, s, r)) return false;
         if (n > sk_vorbis::kMaxPacketBytes) return r.fail(SK_VORBIS_ERR_STREAM, "Decoding failed: Vorbis packet exceeds the " + std::to_string(sk_vorbis::kMaxPacketBytes) + " byte budget");
         sk_vorbis::PacketHead h;
         const int rc = sk_vorbis::packet_head(s.vorbis_setup->setup, d, n, &h);
         if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: Vorbis packet rejected: ") + sk_strerror(rc));
-        uint32_t frames = s.vorbis_parse_prev ? s.vorbis_parse_prev / 4 + h.n / 4 : 0, keep = 0xffffffffu;
+        uint32_t frames = s.vorbis_parse_prev ? s.vorbis_parse_prev / 4 + h.n / 4 : 0, keep = 0xffffffffu, skip = 0;
         s.vorbis_parse_prev = h.n;
+        if (wp && wp->has_discard) {  // decode_vorbis: [front, max(frames - back, front)) of the packet's frames stays
+            uint32_t front, back;
+            std::string text;
+            if (!sk_webm::discard_frames(wp->discard_ns, s.vorbis_ident.sample_rate, frames, &front, &back, &text)) return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + text);
+            skip = front, frames -= front + back, keep = frames;
+        }
         if (op) {  // process_packet's bookkeeping: cur_absgp is known from the first audio packet that ends a page
             if (s.vorbis_have_absgp && op->last_in_stream && op->has_granule) {
                 const uint64_t left = op->granule_position > s.vorbis_absgp ? op->granule_position - s.vorbis_absgp : 0;
@@ -1154,7 +1254,7 @@ void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         const uint32_t before = outputs;
         const size_t at = stage_unit(r, s, d, n, frames, outputs);
         if (!frames) outputs = before;  // such a packet gives no AudioData
-        r.vorbis_packets.push_back(sk_vorbis_tick_packet{(uint32_t)at, (uint32_t)n, keep, 0});
+        r.vorbis_packets.push_back(sk_vorbis_tick_packet{(uint32_t)at, (uint32_t)n, keep, skip});
         return true;
     };
     auto full = [&](size_t next) {
@@ -1190,6 +1290,35 @@ void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
                 break;
             }
             if (s.vorbis_headers < 3 ? !header(pk.data.data(), pk.data.size()) : !audio(pk.data.data(), pk.data.size(), &pk)) break;
+            continue;
+        }
+        if (s.webm) {
+            if (!s.webm->packets.empty()) {
+                if (full(s.webm->packets.front().data.size())) {
+                    r.more = true;
+                    break;
+                }
+                const sk_webm::Packet pk = s.webm->take_packet();
+                if (!audio(pk.data.data(), pk.data.size(), nullptr, &pk)) break;
+                continue;
+            }
+            if (!s.webm_error.empty()) {  // every complete packet has gone: what the demuxer refused
+                r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + s.webm_error);
+                break;
+            }
+            if (s.webm_done) {
+                r.eof = true;
+                break;
+            }
+            {
+                std::lock_guard<std::mutex> lk(s.mu);
+                if (s.in.empty()) break;
+                if (!s.in.front().empty() && full(0)) {
+                    r.more = true;
+                    break;
+                }
+            }
+            if (webm_pull(s) == 0) break;
             continue;
         }
         if (s.saw_eof) {
@@ -1228,6 +1357,58 @@ void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
 
+// A WebM stream up to its first Cluster: the demuxer starts with the bytes of the detection, and the first audio track it reports
+// decides what the stream is from here on (WebmDecoder::configure: the first configuration is taken or refused, a second one is
+// refused).  A_VORBIS: the three headers out of the CodecPrivate go through the steps an Ogg stream's go through.  A_AAC: the
+// CodecPrivate is an AudioSpecificConfig and meets the AAC-LC config check, as an MP4 track's does.  A_FLAC: the CodecPrivate is `fLaC`
+// and the metadata blocks.  Anything else is what the reference says in a build without that codec.  false: more input is needed, or
+// the stream has failed (r says how).
+bool webm_open(PStream &s, Parsed &r) {
+    if (!s.webm) {
+        s.webm.reset(new sk_webm::Demuxer());
+        const std::vector<uint8_t> head(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
+        s.pending.clear();
+        s.pending_pos = 0;
+        for (size_t at = 0; at < head.size() && !s.webm_done; at += 1u << 20) webm_feed(s, head.data() + at, std::min<size_t>(1u << 20, head.size() - at), false);
+        if (s.saw_eof && !s.webm_done) webm_feed(s, nullptr, 0, true);
+    }
+    sk_webm::Demuxer &w = *s.webm;
+    while (!w.configured || w.audio.empty()) {
+        if (!s.webm_error.empty()) return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + s.webm_error);
+        if (webm_pull(s) == 0) return false;
+    }
+    const sk_webm::Track &t = w.audio.front();
+    const std::vector<uint8_t> &priv = t.codec_private;
+    std::string text;
+    if (t.codec == sk_webm::kCodecVorbis) {
+        size_t offsets[3], sizes[3];
+        if (!sk_webm::vorbis_headers(priv.data(), priv.size(), offsets, sizes, &text)) return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + text);
+        s.vorbis = s.pcm_detected = true;
+        for (int k = 0; k < 3; ++k)
+            if (!vorbis_header(s, r, priv.data() + offsets[k], sizes[k])) return false;
+        s.codec = kCodecVorbis;
+    } else if (t.codec == sk_webm::kCodecAac) {
+        if (!sk_mp4::asc_rate_channels(priv.data(), priv.size(), &s.webm_rate, &s.webm_channels))
+            return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: WebM A_AAC CodecPrivate holds no AudioSpecificConfig with a rate of the table");
+        sk_aac_decoder *probe = nullptr;
+        const int rc = sk_aac_decoder_create(priv.data(), priv.size(), &probe);
+        sk_aac_decoder_destroy(probe);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: AAC-LC decoder init: ") + sk_strerror(rc));
+        s.codec = kCodecAac;
+    } else if (t.codec == sk_webm::kCodecFlac) {
+        if (priv.size() < 42 || std::memcmp(priv.data(), "fLaC", 4) != 0)
+            return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: WebM A_FLAC CodecPrivate holds no fLaC marker and STREAMINFO block");
+        s.webm_flac_head = true;
+        s.codec = kCodecFlac;
+    } else {
+        return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: unsupported or disabled WebM codec: " + t.codec_id);
+    }
+    if (w.audio.size() > 1) return r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: WebM decoder received more than one audio configuration");
+    s.webm_routed = true;
+    if (s.codec == kCodecAac) webm_drain_aac(s);
+    return true;
+}
+
 // A FLAC stream's pass: the reader cuts whole frames out of the chunks (marker and metadata first), and whole frames are what the
 // stream is budgeted in -- `room` AudioData (one per frame, or one per completed 4096-frame chunk through the resampler) and the units
 // of one stream in a tick.  Frames the reader holds beyond that come with the next pass (r.more).  A stream the reader rejects ends
@@ -1264,8 +1445,14 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     auto fits = [&](size_t next) {
         return r.pcm_bytes.size() + s.flac->buffered_bytes() + next + 16 * (size_t)per_pass + 4096 <= kPcmTickBytes;
     };
-    // the pending bytes of the detection (parse_some gathered them) go in first
-    if (s.pending.size() > s.pending_pos) {
+    // an A_FLAC track of a WebM stream: the chunks go through the demuxer, and what it hands out -- the CodecPrivate, then the frames --
+    // is the native stream the reader takes.  A feed gets at most the demuxer's queue budget
+    std::vector<uint8_t> demuxed;
+    if (s.webm) {
+        if (s.more && !feed(nullptr, 0, s.saw_eof && s.flac->finalised())) return;  // frames left over by the pass before
+        if (!r.more) webm_flac_bytes(s, demuxed);  // (else they stay with the demuxer for the next pass)
+        if (!demuxed.empty() && !feed(demuxed.data(), demuxed.size(), false)) return;
+    } else if (s.pending.size() > s.pending_pos) {  // the pending bytes of the detection (parse_some gathered them) go in first
         std::vector<uint8_t> first(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
         s.pending.clear();
         s.pending.shrink_to_fit();
@@ -1288,12 +1475,22 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         {
             std::lock_guard<std::mutex> lk(s.mu);
             if (s.in.empty()) break;
-            if (!s.in.front().empty() && !r.pcm_units.empty() && !fits(s.in.front().size())) {
+            if (!s.in.front().empty() && !r.pcm_units.empty() && !fits(s.webm ? kMaxWebmQueuedBytes : s.in.front().size())) {
                 r.more = true;
                 break;
             }
             chunk = std::move(s.in.front());
             s.in.pop_front();
+        }
+        if (s.webm) {  // the frames in front of a refusal are fed; the last of them waits in the reader for its end and goes with the stream
+            if (chunk.empty()) s.saw_eof = true;
+            else s.queued_bytes.fetch_sub(chunk.size());
+            webm_feed(s, chunk.data(), chunk.size(), chunk.empty());
+            demuxed.clear();
+            webm_flac_bytes(s, demuxed);
+            if (!demuxed.empty() && !feed(demuxed.data(), demuxed.size(), false)) break;
+            if (!s.webm_error.empty()) r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + s.webm_error);
+            continue;
         }
         if (chunk.empty()) {
             s.saw_eof = true;
@@ -1407,6 +1604,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         }
         if (pull_input(s) == 0) return;  // needs more input
     }
+    if (s.codec == kCodecWebm && !webm_open(s, r)) return;  // taken by its EBML magic: from its first Cluster on it is one of the streams below
     if (s.codec == kCodecMp3) {
         // MPEG audio of which layer: that of the stream's first confirmed frame (two consistent headers one frame length apart)
         const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
@@ -1492,6 +1690,15 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
             if (s.mp4 && !s.mp4_done) {  // an MP4 stream: more frames come out of the demuxer
                 if (pull_mp4(s) == 0) break;
                 continue;
+            }
+            if (s.webm && !s.webm_done) {  // a WebM stream's A_AAC track: more frames come out of the demuxer
+                if (webm_pull(s) == 0) break;
+                webm_drain_aac(s);
+                continue;
+            }
+            if (s.webm && !s.webm_error.empty()) {
+                r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + s.webm_error);
+                break;
             }
             if (s.mp4 && !s.mp4_error.empty()) {  // every complete unit has gone: what the demuxer or the config check refused
                 r.fail(SK_MP4_ERR_STREAM, "Decoding failed: " + s.mp4_error);
@@ -2671,6 +2878,10 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.mp4.reset();
     s.mp4_checked = s.mp4_done = false;
     s.mp4_error.clear();
+    s.webm.reset();
+    s.webm_routed = s.webm_done = s.webm_flac_head = false;
+    s.webm_rate = s.webm_channels = 0;
+    s.webm_error.clear();
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
@@ -3591,6 +3802,143 @@ int sk_mp4_adts_header(const uint8_t *asc, size_t asc_len, uint32_t sample_rate,
     return SK_OK;
 } catch (...) {
     return sk::abi_caught("sk_mp4_adts_header");
+}
+
+}  // extern "C"
+
+// ---- WebM / Matroska (webm_stream.h) ------------------------------------------------------------------------------------------------
+
+struct sk_webm_demuxer {
+    sk_webm::Demuxer demuxer;
+};
+
+extern "C" {
+
+int sk_webm_demuxer_create(sk_webm_demuxer **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_webm_demuxer();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_webm_demuxer_create");
+}
+
+void sk_webm_demuxer_destroy(sk_webm_demuxer *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_webm_demuxer_destroy");
+}
+
+int sk_webm_demuxer_add(sk_webm_demuxer *d, const uint8_t *bytes, size_t len) try {
+    sk::abi_enter();
+    if (!d || (len && !bytes)) return SK_ERR_INVALID_ARG;
+    return d->demuxer.add(bytes, len) ? SK_OK : SK_WEBM_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_webm_demuxer_add");
+}
+
+int sk_webm_demuxer_finish(sk_webm_demuxer *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    return d->demuxer.finish() ? SK_OK : SK_WEBM_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_webm_demuxer_finish");
+}
+
+const char *sk_webm_demuxer_last_error(const sk_webm_demuxer *d) try {
+    sk::abi_enter();
+    return d ? d->demuxer.error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_webm_demuxer_last_error");
+    return "";
+}
+
+uint32_t sk_webm_demuxer_n_tracks(const sk_webm_demuxer *d) try {
+    sk::abi_enter();
+    return d && d->demuxer.configured ? (uint32_t)d->demuxer.audio.size() : 0;
+} catch (...) {
+    (void)sk::abi_caught("sk_webm_demuxer_n_tracks");
+    return 0;
+}
+
+int sk_webm_demuxer_config(const sk_webm_demuxer *d, uint32_t index, sk_webm_track_info *info, uint8_t *codec_private, size_t private_cap, uint8_t *prefix,
+                           size_t prefix_cap) try {
+    sk::abi_enter();
+    if (!d || !info || (private_cap && !codec_private) || (prefix_cap && !prefix)) return SK_ERR_INVALID_ARG;
+    if (!d->demuxer.configured || index >= d->demuxer.audio.size()) return SK_ERR_INVALID_ARG;
+    const sk_webm::Track &t = d->demuxer.audio[index];
+    std::memset(info, 0, sizeof *info);
+    info->track_number = t.number, info->codec_delay_ns = t.codec_delay_ns, info->seek_pre_roll_ns = t.seek_pre_roll_ns;
+    info->default_duration_ns = t.has_default_duration ? t.default_duration_ns : 0, info->timecode_scale_ns = d->demuxer.timecode_scale_ns;
+    info->track_timestamp_scale = t.timestamp_scale, info->codec = t.codec;
+    info->sample_rate = t.has_rate ? t.sample_rate : 48000, info->channels = t.has_channels ? t.channels : 2;
+    info->private_len = (uint32_t)t.codec_private.size(), info->prefix_len = (uint32_t)t.prefix.size();
+    if (private_cap < t.codec_private.size() || prefix_cap < t.prefix.size()) return SK_ERR_CAPACITY;
+    if (!t.codec_private.empty()) std::memcpy(codec_private, t.codec_private.data(), t.codec_private.size());
+    if (!t.prefix.empty()) std::memcpy(prefix, t.prefix.data(), t.prefix.size());
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_webm_demuxer_config");
+}
+
+int sk_webm_demuxer_pending(const sk_webm_demuxer *d, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (n_packets) *n_packets = (uint32_t)d->demuxer.packets.size();
+    if (front_bytes) *front_bytes = d->demuxer.packets.empty() ? 0 : d->demuxer.packets.front().data.size();
+    if (buffered_bytes) *buffered_bytes = d->demuxer.buffered();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_webm_demuxer_pending");
+}
+
+int sk_webm_demuxer_take(sk_webm_demuxer *d, uint8_t *out, size_t cap, size_t *len, sk_webm_packet_info *info) try {
+    sk::abi_enter();
+    if (!d || !len || (cap && !out)) return SK_ERR_INVALID_ARG;
+    if (d->demuxer.packets.empty()) return SK_ERR_BAD_STREAM;
+    const sk_webm::Packet &p = d->demuxer.packets.front();
+    *len = p.data.size();
+    if (cap < p.data.size()) return SK_ERR_CAPACITY;
+    if (!p.data.empty()) std::memcpy(out, p.data.data(), p.data.size());
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->track_number = p.track, info->timestamp_ns = p.timestamp_ns, info->duration_ns = p.duration_ns, info->discard_padding_ns = p.discard_ns;
+        info->codec = p.codec, info->has_duration = p.has_duration, info->has_discard_padding = p.has_discard;
+    }
+    d->demuxer.pop_packet();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_webm_demuxer_take");
+}
+
+int sk_webm_vorbis_headers(const uint8_t *codec_private, size_t len, size_t offsets[3], size_t sizes[3], char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !codec_private) || !offsets || !sizes) return SK_ERR_INVALID_ARG;
+    mp4_text(error, error_cap, "");
+    std::string text;
+    if (!sk_webm::vorbis_headers(codec_private, len, offsets, sizes, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_WEBM_ERR_STREAM;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_webm_vorbis_headers");
+}
+
+int sk_webm_discard_frames(int64_t padding_ns, uint32_t sample_rate, uint32_t decoded_frames, uint32_t *front, uint32_t *back, char *error,
+                           size_t error_cap) try {
+    sk::abi_enter();
+    if (!front || !back) return SK_ERR_INVALID_ARG;
+    mp4_text(error, error_cap, "");
+    std::string text;
+    if (!sk_webm::discard_frames(padding_ns, sample_rate, decoded_frames, front, back, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_WEBM_ERR_STREAM;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_webm_discard_frames");
 }
 
 int sk_debug_throw_in_thread(int n, int where) {

@@ -697,8 +697,9 @@ struct VorbisPacket {
     uint32_t prev_pcm;     // in floats: where that packet's right halves start -- in the windowed workspace (row stride prev_n), or,
     uint32_t prev_in_carry;  // != 0, in the carry buffer (row stride prev_n / 2): the first accepted packet of a stream in the call
     uint64_t out_offset;   // in samples (frames x channels) of the output
-    uint32_t out_frames;   // prev_n / 4 + n / 4, or 0
+    uint32_t out_frames;   // prev_n / 4 + n / 4, or 0; the tick: what its skip_frames and keep_frames leave of them
     uint32_t channels;
+    uint32_t out_skip;     // the first frame that is written: out_skip + out_frames <= prev_n / 4 + n / 4
 };
 struct VorbisInfo {        // sk_vorbis_packet_info
     int32_t status;

@@ -406,7 +406,7 @@ __global__ void __launch_bounds__(256) k_vorbis_ola(const VorbisPacket *packets,
     const uint32_t rstride = pk.prev_in_carry ? pn >> 1 : pn;
     const float *left = pcm_base + pk.pcm_offset;
     for (uint32_t q = threadIdx.x; q < frames * ch; q += 256u) {
-        const uint32_t i = q / ch, c = q - i * ch;
+        const uint32_t f = q / ch, c = q - f * ch, i = f + pk.out_skip;
         const float *R = right + c * rstride, *L = left + c * n;
         float v;
         if (pn == n) {

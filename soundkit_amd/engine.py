@@ -561,10 +561,11 @@ class Engine:
         from . import vorbis
         return vorbis.entropy_decode(groups, engine=self)
 
-    def tick_run_vorbis(self, streams, packets, out_cap=None):
+    def tick_run_vorbis(self, streams, packets, out_cap=None, skip_frames=None, keep_frames=None):
         """One tick of Vorbis streams (sk_tick_run_vorbis).  streams: list of dicts {state (a vorbis.StreamState: the carry, updated when
         the tick succeeded), out_bits, out_channels, n_units, and for a rate change: stream, resample, flush}; packets: [audio packet
         bytes] of all streams, stream by stream.  out_cap: an output size other than the bound's (to have a tick refused).
+        skip_frames / keep_frames: per packet, the frames dropped at its front and how many of the rest stay at most (None: 0 / all).
         -> (the same list of records as tick_run_pcm, [status per packet])."""
         import ctypes as C
         from . import vorbis
@@ -580,7 +581,9 @@ class Engine:
         table, blob = (VorbisTickPacket * max(n, 1))(), bytearray()
         for k, p in enumerate(packets):
             blob += bytes(-len(blob) % 16)
-            table[k].offset, table[k].size, table[k].keep_frames = len(blob), len(p), 0xffffffff
+            table[k].offset, table[k].size = len(blob), len(p)
+            table[k].keep_frames = 0xffffffff if keep_frames is None else int(keep_frames[k])
+            table[k].skip_frames = 0 if skip_frames is None else int(skip_frames[k])
             blob += p
         src = np.frombuffer(bytes(blob) + bytes(16), np.uint8)
         max_out = C.c_uint32()

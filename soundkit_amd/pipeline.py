@@ -11,6 +11,8 @@ soundkit-aiff, its per-sample decode -- byte order, widening, f64, G.711, IMA4 -
 AudioData from WAV / raw PCM / AIFF streams carries the real `audio_format` and `endianness`.
 MP4 / M4A (`....ftyp`) with an AAC-LC track, regular (`moov` in front of `mdat`) or fragmented: demuxed on the entropy thread
 (csrc/mp4_stream.h), then exactly an ADTS stream; whole files in any box order, and ALAC tracks, go through `mp4.decode_file`.
+WebM / Matroska (`1A 45 DF A3`) with one A_VORBIS, A_AAC or A_FLAC track: demuxed on the entropy thread (csrc/webm_stream.h), then
+exactly a Vorbis-packet, ADTS or native FLAC stream; anything else in it: `unsupported or disabled WebM codec: ID`.
 The reference's other formats stay with their CPU decoders (out of scope)."""
 import ctypes as C
 from dataclasses import dataclass
