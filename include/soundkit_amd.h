@@ -1409,7 +1409,63 @@ int sk_webm_vorbis_headers(const uint8_t *codec_private, size_t len, size_t offs
 int sk_webm_discard_frames(int64_t padding_ns, uint32_t sample_rate, uint32_t decoded_frames, uint32_t *front, uint32_t *back, char *error,
                            size_t error_cap);
 
-/* ---- ALAC decode stage (GPU, csrc/alac_decode.hip) -------------------------------------------------------------------- */
+/* ---- MPEG transport stream, audio only (host, csrc/ts_stream.h) ---------------------------------------------------------------------
+ * The incremental walk of soundkit-audio-demux's MpegTsAudioDemuxer with its checks, texts and budgets: packets at stride 188, at 192
+ * behind a 4-byte prefix (.m2ts) or at 204 (five syncs decide; a lost sync is searched byte by byte), the continuity counter per PID,
+ * PAT (the lowest non-zero program) and PMT sections with CRC-32/MPEG-2, the first stream of the PMT whose type is known (0x0F ADTS
+ * AAC, 0x11 LATM AAC, 0x03 / 0x04 MPEG audio, 0x80 Blu-ray LPCM, 0x81 / 0x87 AC-3, 0x82 DTS, 0x06 with an AC-3 descriptor or an HDMV
+ * program), its PES packets with PTS / DTS unwrapped from 33 bits.  Handed out: one packet per ADTS frame, per MPEG audio frame, per
+ * LOAS frame, per Blu-ray LPCM PES (without its 4-byte header), per AC-3 or DTS PES.  The output does not depend on how the bytes are
+ * cut into calls.  Budgets: 4 MiB a call, 1 MiB a PES.  A refusal is SK_TS_ERR_STREAM with a text (sk_ts_demuxer_last_error); the
+ * packets complete in front of it stay takeable and the demuxer stays refused.  A Blu-ray LPCM PES payload begins with four bytes:
+ * 0-1 the big-endian size of what follows, byte 2 the channel assignment (high nibble) and the rate code (low nibble: 1 = 48 000,
+ * 4 = 96 000, 5 = 192 000), byte 3's top two bits the depth code (1 = 16, 2 = 20, 3 = 24).  Built: stereo (channel assignment 3) at 16 or
+ * 24 bits; mono, 20 bits, the multichannel assignments and a size field that disagrees with its payload are refused with texts of
+ * this project's own.  Not read: PCR, video, data PIDs, any program but the one chosen. */
+enum sk_ts_status { SK_TS_ERR_STREAM = -1101 };
+enum sk_ts_codec { SK_TS_CODEC_AAC = 1, SK_TS_CODEC_PCM = 2, SK_TS_CODEC_AC3 = 3, SK_TS_CODEC_DTS = 4, SK_TS_CODEC_MP3 = 5, SK_TS_CODEC_MP1 = 6,
+                   SK_TS_CODEC_MP2 = 7, SK_TS_CODEC_MPEG_AUDIO = 8 };
+enum sk_ts_packet_format { SK_TS_FORMAT_RAW = 0, SK_TS_FORMAT_ADTS = 1, SK_TS_FORMAT_LATM = 2 };
+typedef struct sk_ts_track_info {
+    uint32_t codec;          /* sk_ts_codec: MPEG audio is named by its first frame's layer */
+    uint32_t packet_format;  /* sk_ts_packet_format */
+    uint32_t stream_type;    /* the PMT's */
+    uint32_t pid, program_number;
+    uint32_t packet_stride, packet_prefix; /* 188 / 0, 192 / 4, 204 / 0 */
+    uint32_t sample_rate, channels;        /* of the first frame; 0 where has_rate / has_channels is 0 (LATM, AC-3, DTS) */
+    uint32_t bits_per_sample, bytes_per_frame, frames_per_packet; /* Blu-ray LPCM alone (big-endian, signed, interleaved), else 0 */
+    uint8_t has_rate, has_channels;
+    uint8_t lpcm_header[4];  /* Blu-ray LPCM: the first PES's four header bytes */
+    uint8_t reserved[2];
+} sk_ts_track_info;
+typedef struct sk_ts_packet_info {
+    uint64_t pts, dts;       /* 90 kHz units, unwrapped; a frame behind the first of its PES is its durations later */
+    uint32_t duration;       /* 90 kHz units */
+    uint8_t has_pts, has_dts, has_duration;
+    uint8_t continuity_counter; /* of the packet that started the PES */
+    uint8_t discontinuity;      /* on the first frame of a PES that met the flag or a gap */
+    uint8_t reserved[3];
+} sk_ts_packet_info;
+typedef struct sk_ts_demuxer sk_ts_demuxer;
+int sk_ts_demuxer_create(sk_ts_demuxer **out);
+void sk_ts_demuxer_destroy(sk_ts_demuxer *);
+int sk_ts_demuxer_add(sk_ts_demuxer *, const uint8_t *bytes, size_t len);
+/* the last PES is handed out */
+int sk_ts_demuxer_finish(sk_ts_demuxer *);
+const char *sk_ts_demuxer_last_error(const sk_ts_demuxer *);
+/* the config event: it comes with the track's first packet.  SK_ERR_BAD_STREAM before that */
+int sk_ts_demuxer_config(const sk_ts_demuxer *, sk_ts_track_info *info);
+/* packets waiting, the first one's size and the bytes the demuxer holds that are no packet yet */
+int sk_ts_demuxer_pending(const sk_ts_demuxer *, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes);
+/* takes the first waiting packet.  None waiting: SK_ERR_BAD_STREAM; cap too small: SK_ERR_CAPACITY, the packet stays */
+int sk_ts_demuxer_take(sk_ts_demuxer *, uint8_t *out, size_t cap, size_t *len, sk_ts_packet_info *info);
+/* looks_like_mpeg_ts of the decoder: three syncs at stride 188, or at stride 192 behind four bytes.  1 / 0 */
+int sk_ts_sniff(const uint8_t *bytes, size_t len);
+/* a stream known to be a transport stream, for a join in mid-segment where the first bytes are no sync (the demuxer finds it);
+ * sk_pipeline_spawn takes a transport stream by sk_ts_sniff itself */
+int sk_pipeline_spawn_mpeg_ts(sk_pipeline *, const sk_decode_options *opt /* NULL = defaults */, uint32_t *handle);
+
+/* ---- ALAC decode stage (GPU, csrc/alac_decode.hip)-------------------------------------------------------------------- */
 /* packets[i] lies at bytes + packets[i].offset, a multiple of 16.  Output: the packets one after the other in the order given, each
  * frames x channels samples interleaved in bitstream channel order, little-endian in bit_depth / 8 bytes.  frames_per_packet[i] is what
  * sk_alac_packet_frames reads (0 where it refuses: such a packet has no place in `out`); status_per_packet[i]: SK_OK, SK_ALAC_INVALID,

@@ -27,6 +27,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -801: "VorbisNotAudio", -802: "VorbisBadMode", -803: "VorbisPacketShort", -804: "VorbisStreamRejected",
              -901: "Mp4StreamRejected",
              -1001: "WebmStreamRejected",
+             -1101: "TsStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -223,6 +224,19 @@ class WebmPacketInfo(C.Structure):
     """sk_webm_packet_info"""
     _fields_ = [("track_number", C.c_uint64), ("timestamp_ns", C.c_int64), ("duration_ns", C.c_uint64), ("discard_padding_ns", C.c_int64),
                 ("codec", C.c_uint32), ("has_duration", C.c_uint8), ("has_discard_padding", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+class TsTrackInfo(C.Structure):
+    """sk_ts_track_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("codec", "packet_format", "stream_type", "pid", "program_number", "packet_stride", "packet_prefix", "sample_rate",
+                                          "channels", "bits_per_sample", "bytes_per_frame", "frames_per_packet")] + [
+        ("has_rate", C.c_uint8), ("has_channels", C.c_uint8), ("lpcm_header", C.c_uint8 * 4), ("reserved", C.c_uint8 * 2)]
+
+
+class TsPacketInfo(C.Structure):
+    """sk_ts_packet_info"""
+    _fields_ = [("pts", C.c_uint64), ("dts", C.c_uint64), ("duration", C.c_uint32), ("has_pts", C.c_uint8), ("has_dts", C.c_uint8), ("has_duration", C.c_uint8),
+                ("continuity_counter", C.c_uint8), ("discontinuity", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
 class AlacTickStream(C.Structure):
@@ -633,6 +647,16 @@ _sig = {
     "sk_webm_demuxer_take": (_i, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(WebmPacketInfo)]),
     "sk_webm_vorbis_headers": (_i, [_vp, _sz, C.POINTER(_sz * 3), C.POINTER(_sz * 3), _vp, _sz]),
     "sk_webm_discard_frames": (_i, [C.c_int64, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
+    "sk_ts_demuxer_create": (_i, [C.POINTER(_vp)]),
+    "sk_ts_demuxer_destroy": (None, [_vp]),
+    "sk_ts_demuxer_add": (_i, [_vp, _vp, _sz]),
+    "sk_ts_demuxer_finish": (_i, [_vp]),
+    "sk_ts_demuxer_last_error": (C.c_char_p, [_vp]),
+    "sk_ts_demuxer_config": (_i, [_vp, C.POINTER(TsTrackInfo)]),
+    "sk_ts_demuxer_pending": (_i, [_vp, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
+    "sk_ts_demuxer_take": (_i, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(TsPacketInfo)]),
+    "sk_ts_sniff": (_i, [_vp, _sz]),
+    "sk_pipeline_spawn_mpeg_ts": (_i, [_vp, _vp, C.POINTER(_u32)]),
     "sk_alac_decode_packets": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_alac_decode_packets_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_tick_alac_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),

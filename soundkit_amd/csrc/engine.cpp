@@ -610,6 +610,7 @@ const char *sk_strerror(int status) try {
     case SK_VORBIS_ERR_STREAM: return "Ogg / Vorbis stream rejected";
     case SK_MP4_ERR_STREAM: return "MP4 stream rejected";
     case SK_WEBM_ERR_STREAM: return "WebM stream rejected";
+    case SK_TS_ERR_STREAM: return "MPEG-TS stream rejected";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";

@@ -25,6 +25,7 @@
 #include "flac_stream.h"
 #include "mp4_stream.h"
 #include "webm_stream.h"
+#include "ts_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
 #include <hip/hip_runtime.h>
@@ -145,6 +146,14 @@ struct PStream {
     bool webm_routed = false, webm_done = false, webm_flac_head = false;
     uint32_t webm_rate = 0, webm_channels = 0;  // A_AAC: the AudioSpecificConfig's, for the ADTS headers
     std::string webm_error;
+    // MPEG transport streams (taken by sk_ts::sniff, or sk_pipeline_spawn_mpeg_ts): the demuxer runs on the worker thread.  The config
+    // that comes with the track's first packet decides where the packets go (ts_open): ADTS frames and MPEG audio frames are appended to
+    // `pending`, where the ADTS pass and the MPEG audio passes find them as they find an elementary stream's (pull_input goes through
+    // the demuxer); a Blu-ray LPCM stream is a raw PCM stream whose pieces are the PES payloads.  ts_error: what ends the stream once the
+    // units in front of it have gone; ts_done: nothing more is pulled
+    std::unique_ptr<sk_ts::Demuxer> ts;
+    bool ts_routed = false, ts_done = false;
+    std::string ts_error;
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -152,7 +161,7 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11, kCodecWebm = 12;
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11, kCodecWebm = 12, kCodecTs = 13;
 constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
@@ -429,8 +438,58 @@ struct Parsed {  // what one worker pass produced for one stream
     }
 };
 
+// What a routed transport stream's demuxer has handed out joins `pending`: ADTS frames and MPEG audio frames one after the other are the
+// elementary stream.  (A Blu-ray LPCM track's packets wait in the demuxer as the pieces of the PCM pass.)
+void ts_drain(PStream &s) {
+    if (!s.ts_routed || s.codec == kCodecRawPcm) return;
+    if (s.pending_pos > 0 && s.pending_pos >= s.pending.size() / 2) {  // compact
+        s.pending.erase(s.pending.begin(), s.pending.begin() + (ptrdiff_t)s.pending_pos);
+        s.pending_pos = 0;
+    }
+    while (!s.ts->packets.empty()) {
+        const sk_ts::Packet pk = s.ts->take_packet();
+        s.pending.insert(s.pending.end(), pk.data.begin(), pk.data.end());
+    }
+}
+
+// A transport stream's demuxer takes a chunk, or (end) the end of the input.  A refusal is kept for when the units in front of it have
+// gone, and ends the input: the passes see the end of their elementary stream.
+void ts_feed(PStream &s, const uint8_t *data, size_t len, bool end) {
+    sk_ts::Demuxer &t = *s.ts;
+    if (end) {
+        s.ts_done = true;
+        (void)t.finish();
+    } else {
+        (void)t.add(data, len);
+    }
+    if (t.failed && s.ts_error.empty()) s.ts_error = t.error;
+    ts_drain(s);
+    if (!s.ts_error.empty()) s.ts_done = s.saw_eof = true;
+}
+
+// pull_input for a transport stream
+int ts_pull(PStream &s) {
+    if (s.ts_done) return 0;
+    std::vector<uint8_t> chunk;
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (s.in.empty()) return 0;
+        chunk = std::move(s.in.front());
+        s.in.pop_front();
+    }
+    if (chunk.empty()) {
+        s.saw_eof = true;
+        ts_feed(s, nullptr, 0, true);
+        return -1;
+    }
+    s.queued_bytes.fetch_sub(chunk.size());
+    ts_feed(s, chunk.data(), chunk.size(), false);
+    return 1;
+}
+
 // 1 = a chunk was appended to s.pending, 0 = nothing queued right now, -1 = the end-of-stream marker was taken (s.saw_eof set)
 int pull_input(PStream &s) {
+    if (s.ts) return ts_pull(s);  // (1: a chunk went through the demuxer, whatever it handed out)
     std::vector<uint8_t> chunk;
     bool got = false;
     {
@@ -609,7 +668,8 @@ namespace {
 
 // What the stream's first bytes are (detect_audio at lib.rs:3042 looks at magic numbers; on this path two formats exist):
 // an ID3v2 tag or an MPEG audio sync with a layer field -> MP3; an ADTS sync (layer bits 00) -> AAC.  0 = not enough bytes yet.
-uint8_t sniff_codec(const uint8_t *d, size_t n) {
+// eof: the stream has ended, so the one rule that waits for bytes which may never decide anything (the transport stream's) does not.
+uint8_t sniff_codec(const uint8_t *d, size_t n, bool eof) {
     // 1A 45 DF A3 -> WebM / Matroska (AudioType::Webm); fewer bytes that match so far: wait.  Before the MPEG sync scan, which would
     // find a sync somewhere inside the file
     static const uint8_t ebml[4] = {0x1A, 0x45, 0xDF, 0xA3};
@@ -642,6 +702,11 @@ uint8_t sniff_codec(const uint8_t *d, size_t n) {
     // fLaC -> native FLAC (AudioType::Flac); fewer than 4 bytes that match so far: wait
     if (n >= 4 && std::memcmp(d, "fLaC", 4) == 0) return kCodecFlac;
     if (n > 0 && n < 4 && std::memcmp(d, "fLaC", n) == 0) return 0;
+    // an MPEG transport stream (looks_like_mpeg_ts: three syncs at stride 188, or at 192 behind four bytes), before the MPEG sync scan,
+    // which would stop at the first FF Fx inside some PES payload.  A 47 where the first sync would be: wait for the 389 bytes that
+    // settle it, unless the stream has ended; a stream that is none goes on to the rules below as it always did
+    if (sk_ts::sniff(d, n)) return kCodecTs;
+    if (!eof && n < 389 && n > 0 && (d[0] == 0x47 || (n > 4 && d[4] == 0x47))) return 0;
     if (n >= 3 && d[0] == 'I' && d[1] == 'D' && d[2] == '3') return kCodecMp3;
     for (size_t i = 0; i + 1 < n; ++i)
         if (d[i] == 0xff && (d[i + 1] & 0xe0) == 0xe0) return ((d[i + 1] >> 1) & 3) == 0 ? kCodecAac : kCodecMp3;
@@ -1357,6 +1422,44 @@ void parse_some_vorbis(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     r.pcm_bytes.resize((r.pcm_bytes.size() + 15) & ~(size_t)15);
 }
 
+// A transport stream up to its track's first packet: the demuxer starts with the bytes of the detection, and the config that comes with
+// the first packet decides what the stream is from here on (consume_mpeg_ts_events, soundkit-decoder/src/lib.rs:946: the first
+// configuration is taken or refused).  ADTS AAC: an ADTS stream.  MPEG audio: an MPEG audio stream of the first frame's layer -- all three
+// layers, where the reference's decode side takes Layer II alone.  Blu-ray LPCM: a raw PCM stream of big-endian samples at the header's
+// rate.  LATM, AC-3, DTS: the reference's refusal.  false: more input is needed, or the stream has failed (r says how).
+bool ts_open(PStream &s, Parsed &r) {
+    if (!s.ts) {
+        s.ts.reset(new sk_ts::Demuxer());
+        const std::vector<uint8_t> head(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
+        s.pending.clear();
+        s.pending_pos = 0;
+        for (size_t at = 0; at < head.size() && !s.ts_done; at += 1u << 20) ts_feed(s, head.data() + at, std::min<size_t>(1u << 20, head.size() - at), false);
+        if (s.saw_eof && !s.ts_done) ts_feed(s, nullptr, 0, true);
+    }
+    sk_ts::Demuxer &t = *s.ts;
+    while (!t.configured) {
+        if (!s.ts_error.empty()) return r.fail(SK_TS_ERR_STREAM, "Invalid input format: " + s.ts_error);
+        if (s.ts_done) return r.fail(SK_TS_ERR_STREAM, "Invalid input format: MPEG-TS has no supported audio track");
+        if (ts_pull(s) == 0) return false;
+    }
+    const sk_ts::Config &c = t.config;
+    if (c.codec == sk_ts::kCodecAac && c.format == sk_ts::kFormatAdts) {
+        s.codec = kCodecAac;
+    } else if (c.codec == sk_ts::kCodecMp3 || c.codec == sk_ts::kCodecMp2 || c.codec == sk_ts::kCodecMp1) {
+        s.codec = kCodecMp3;
+        if (sk_mp3_internal::pipeline_gpu_hooks().mpa_find_layer) s.mpa_layer = c.codec == sk_ts::kCodecMp3 ? 3 : (c.codec == sk_ts::kCodecMp2 ? 2 : 1);
+    } else if (c.codec == sk_ts::kCodecPcm && c.lpcm) {
+        s.codec = kCodecRawPcm;
+        s.raw_format = sk_raw_pcm_format{c.sample_rate, c.channels, (uint8_t)(c.bits == 16 ? SK_FMT_S16BE : SK_FMT_S24BE), 0};
+        s.raw.reset(new sk_pcm::RawPcmStream(c.bytes_per_frame));
+    } else {
+        return r.fail(SK_TS_ERR_STREAM, std::string("Invalid input format: unsupported MPEG-TS audio codec ") + sk_ts::codec_name(c.codec));
+    }
+    s.ts_routed = true;
+    ts_drain(s);  // the packets that came with the config go where the route says
+    return true;
+}
+
 // A WebM stream up to its first Cluster: the demuxer starts with the bytes of the detection, and the first audio track it reports
 // decides what the stream is from here on (WebmDecoder::configure: the first configuration is taken or refused, a second one is
 // refused).  A_VORBIS: the three headers out of the CodecPrivate go through the steps an Ogg stream's go through.  A_AAC: the
@@ -1558,7 +1661,25 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         s.pending_pos = 0;
         if (!ok) return;
     }
+    // the pass's limits: the output queue's room, the units of one stream in a tick, the bytes one tick takes
+    auto full = [&](size_t next) {
+        return outputs >= room || r.pcm_units.size() + r.pre.size() >= p->cfg.max_stream_frames_per_tick ||
+               (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes);
+    };
     while (!r.failed) {
+        if (s.ts && (!s.ts->packets.empty() || !s.saw_eof)) {  // Blu-ray LPCM out of a transport stream: every PES payload is one piece
+            if (s.ts->packets.empty()) {
+                if (ts_pull(s) == 0) break;
+                continue;
+            }
+            if (full(s.ts->packets.front().data.size())) {
+                r.more = true;
+                break;
+            }
+            const sk_ts::Packet pk = s.ts->take_packet();
+            if (!process(pk.data.data(), pk.data.size())) break;
+            continue;
+        }
         if (s.saw_eof) {  // flush_decoder (lib.rs:3139-3169): the framer's partial frame is an error, the resampler is flushed by the tick
             std::string err;
             if (s.raw && !s.raw->flush(err)) r.fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
@@ -1570,10 +1691,8 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         {
             std::lock_guard<std::mutex> lk(s.mu);
             if (s.in.empty()) break;
-            // the pass's limits: the output queue's room, the units of one stream in a tick, the bytes one tick takes
             const size_t next = s.in.front().size();
-            if (next && (outputs >= room || r.pcm_units.size() + r.pre.size() >= p->cfg.max_stream_frames_per_tick ||
-                         (!r.pcm_units.empty() && r.pcm_bytes.size() + next + 4096 > kPcmTickBytes))) {
+            if (next && full(next)) {
                 r.more = true;
                 break;
             }
@@ -1596,7 +1715,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
     const bool gpu_entropy = p->cfg.gpu_entropy == 1;
     const bool quant = p->cfg.gpu_entropy == 2;  // host Huffman decode, the rest of the front-end on the device (sk_tick_run_q)
     while (s.codec == 0) {  // the worker's detect_and_init_decoder: the stream's first bytes choose the decoder
-        s.codec = sniff_codec(s.pending.data() + s.pending_pos, s.pending.size() - s.pending_pos);
+        s.codec = sniff_codec(s.pending.data() + s.pending_pos, s.pending.size() - s.pending_pos, s.saw_eof);
         if (s.codec) break;
         if (s.saw_eof) {
             s.codec = kCodecAac;  // too short to tell: the ADTS path ends it
@@ -1605,6 +1724,7 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         if (pull_input(s) == 0) return;  // needs more input
     }
     if (s.codec == kCodecWebm && !webm_open(s, r)) return;  // taken by its EBML magic: from its first Cluster on it is one of the streams below
+    if (s.codec == kCodecTs && !ts_open(s, r)) return;      // a transport stream: from its track's first packet on it is one of the streams below
     if (s.codec == kCodecMp3) {
         // MPEG audio of which layer: that of the stream's first confirmed frame (two consistent headers one frame length apart)
         const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
@@ -1905,6 +2025,11 @@ void worker_body(sk_lane *p) {
         try {
             thread_debug_point(0);
             parse_some(p, s, limit, coeffs.data(), descs.data(), au_stage, au_items.data(), room, r);
+            // a transport stream the demuxer refused: its pass has come to the end of the units in front of the refusal
+            if (s.ts && r.eof && !r.failed && !s.ts_error.empty()) {
+                r.eof = false;
+                r.fail(SK_TS_ERR_STREAM, "Invalid input format: " + s.ts_error);
+            }
         } catch (...) {
             // whatever was thrown while this stream's input was parsed is this stream's error and nobody else's
             // (soundkit-decoder/src/lib.rs:3131-3134); the frames of this pass are dropped with it
@@ -2830,7 +2955,7 @@ struct G72xSpawn {  // sk_pipeline_spawn_g711 / _g722 / _g726
 };
 
 int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
-               const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr, const VorbisSpawn *vorbis = nullptr) {
+               const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr, const VorbisSpawn *vorbis = nullptr, bool ts = false) {
     if (!p || !handle) return SK_ERR_INVALID_ARG;
     // RawPcmFormat::validate (raw_pcm.rs:117-125), and the sample formats there are
     if (raw && (raw->sample_rate == 0 || raw->channels == 0 || raw->format > SK_FMT_F32BE)) return SK_ERR_INVALID_ARG;
@@ -2882,6 +3007,9 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.webm_routed = s.webm_done = s.webm_flac_head = false;
     s.webm_rate = s.webm_channels = 0;
     s.webm_error.clear();
+    s.ts.reset();
+    s.ts_routed = s.ts_done = false;
+    s.ts_error.clear();
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
@@ -2945,6 +3073,7 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
         s.g726_framer = sk_g72x::G726Framer(sk_g72x::g726_bits(g72x->g726_rate));
         s.pcm_detected = true;
     }
+    if (ts) s.codec = kCodecTs;  // sk_pipeline_spawn_mpeg_ts: nothing is detected, the demuxer finds the first sync itself
     *handle = h;
     return SK_OK;
 }
@@ -3090,7 +3219,7 @@ inline sk_lane *lane_of(sk_pipeline *p, uint32_t handle, uint32_t *inner) {
 }
 
 int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pcm_format *raw, uint32_t *handle, bool aiff = false,
-                   const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr, const VorbisSpawn *vorbis = nullptr) {
+                   const sk_alac_config *alac = nullptr, const G72xSpawn *g72x = nullptr, const VorbisSpawn *vorbis = nullptr, bool ts = false) {
     if (!p || !handle || p->lanes.empty()) return SK_ERR_INVALID_ARG;
     const uint32_t n = (uint32_t)p->lanes.size();
     const uint32_t first = p->next_lane.fetch_add(1) % n;
@@ -3098,7 +3227,7 @@ int pipeline_spawn(sk_pipeline *p, const sk_decode_options *opt, const sk_raw_pc
     for (uint32_t k = 0; k < n; ++k) {  // round robin; a full lane passes the stream on
         const uint32_t li = (first + k) % n;
         uint32_t inner = 0;
-        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac, g72x, vorbis);
+        rc = lane_spawn(p->lanes[li], opt, raw, &inner, aiff, alac, g72x, vorbis, ts);
         if (rc == SK_OK) {
             *handle = inner * n + li;
             return SK_OK;
@@ -3220,6 +3349,13 @@ int sk_pipeline_spawn_raw_pcm(sk_pipeline *p, const sk_raw_pcm_format *format, c
     return pipeline_spawn(p, opt, format, handle);
 } catch (...) {
     return sk::abi_caught("sk_pipeline_spawn_raw_pcm");
+}
+
+int sk_pipeline_spawn_mpeg_ts(sk_pipeline *p, const sk_decode_options *opt, uint32_t *handle) try {
+    sk::abi_enter();
+    return pipeline_spawn(p, opt, nullptr, handle, false, nullptr, nullptr, nullptr, true);
+} catch (...) {
+    return sk::abi_caught("sk_pipeline_spawn_mpeg_ts");
 }
 
 int sk_pipeline_spawn_aiff(sk_pipeline *p, const sk_decode_options *opt, uint32_t *handle) try {
@@ -3939,6 +4075,112 @@ int sk_webm_discard_frames(int64_t padding_ns, uint32_t sample_rate, uint32_t de
     return SK_OK;
 } catch (...) {
     return sk::abi_caught("sk_webm_discard_frames");
+}
+
+}  // extern "C"
+
+// ---- MPEG transport stream (ts_stream.h) --------------------------------------------------------------------------------------------
+
+struct sk_ts_demuxer {
+    sk_ts::Demuxer demuxer;
+};
+
+extern "C" {
+
+int sk_ts_demuxer_create(sk_ts_demuxer **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_ts_demuxer();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ts_demuxer_create");
+}
+
+void sk_ts_demuxer_destroy(sk_ts_demuxer *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_ts_demuxer_destroy");
+}
+
+int sk_ts_demuxer_add(sk_ts_demuxer *d, const uint8_t *bytes, size_t len) try {
+    sk::abi_enter();
+    if (!d || (len && !bytes)) return SK_ERR_INVALID_ARG;
+    return d->demuxer.add(bytes, len) ? SK_OK : SK_TS_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_ts_demuxer_add");
+}
+
+int sk_ts_demuxer_finish(sk_ts_demuxer *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    return d->demuxer.finish() ? SK_OK : SK_TS_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_ts_demuxer_finish");
+}
+
+const char *sk_ts_demuxer_last_error(const sk_ts_demuxer *d) try {
+    sk::abi_enter();
+    return d ? d->demuxer.error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_ts_demuxer_last_error");
+    return "";
+}
+
+int sk_ts_demuxer_config(const sk_ts_demuxer *d, sk_ts_track_info *info) try {
+    sk::abi_enter();
+    if (!d || !info) return SK_ERR_INVALID_ARG;
+    if (!d->demuxer.configured) return SK_ERR_BAD_STREAM;
+    const sk_ts::Config &c = d->demuxer.config;
+    std::memset(info, 0, sizeof *info);
+    info->codec = c.codec, info->packet_format = c.format, info->stream_type = c.stream_type, info->pid = c.pid, info->program_number = c.program;
+    info->packet_stride = c.stride, info->packet_prefix = c.prefix;
+    info->has_rate = c.has_rate, info->has_channels = c.has_channels;
+    info->sample_rate = c.has_rate ? c.sample_rate : 0, info->channels = c.has_channels ? c.channels : 0;
+    info->bits_per_sample = c.bits, info->bytes_per_frame = c.bytes_per_frame, info->frames_per_packet = c.frames_per_packet;
+    std::memcpy(info->lpcm_header, c.lpcm_header, 4);
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ts_demuxer_config");
+}
+
+int sk_ts_demuxer_pending(const sk_ts_demuxer *d, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    if (n_packets) *n_packets = (uint32_t)d->demuxer.packets.size();
+    if (front_bytes) *front_bytes = d->demuxer.packets.empty() ? 0 : d->demuxer.packets.front().data.size();
+    if (buffered_bytes) *buffered_bytes = d->demuxer.buffered();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ts_demuxer_pending");
+}
+
+int sk_ts_demuxer_take(sk_ts_demuxer *d, uint8_t *out, size_t cap, size_t *len, sk_ts_packet_info *info) try {
+    sk::abi_enter();
+    if (!d || !len || (cap && !out)) return SK_ERR_INVALID_ARG;
+    if (d->demuxer.packets.empty()) return SK_ERR_BAD_STREAM;
+    const sk_ts::Packet &p = d->demuxer.packets.front();
+    *len = p.data.size();
+    if (cap < p.data.size()) return SK_ERR_CAPACITY;
+    if (!p.data.empty()) std::memcpy(out, p.data.data(), p.data.size());
+    if (info) {
+        std::memset(info, 0, sizeof *info);
+        info->pts = p.has_pts ? p.pts : 0, info->dts = p.has_dts ? p.dts : 0, info->duration = p.has_duration ? p.duration : 0;
+        info->has_pts = p.has_pts, info->has_dts = p.has_dts, info->has_duration = p.has_duration;
+        info->continuity_counter = p.continuity, info->discontinuity = p.discontinuity;
+    }
+    (void)d->demuxer.take_packet();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ts_demuxer_take");
+}
+
+int sk_ts_sniff(const uint8_t *bytes, size_t len) try {
+    sk::abi_enter();
+    return bytes && sk_ts::sniff(bytes, len) ? 1 : 0;
+} catch (...) {
+    (void)sk::abi_caught("sk_ts_sniff");
+    return 0;
 }
 
 int sk_debug_throw_in_thread(int n, int where) {

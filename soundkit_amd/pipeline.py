@@ -13,6 +13,9 @@ MP4 / M4A (`....ftyp`) with an AAC-LC track, regular (`moov` in front of `mdat`)
 (csrc/mp4_stream.h), then exactly an ADTS stream; whole files in any box order, and ALAC tracks, go through `mp4.decode_file`.
 WebM / Matroska (`1A 45 DF A3`) with one A_VORBIS, A_AAC or A_FLAC track: demuxed on the entropy thread (csrc/webm_stream.h), then
 exactly a Vorbis-packet, ADTS or native FLAC stream; anything else in it: `unsupported or disabled WebM codec: ID`.
+MPEG transport stream (`.ts`, `.m2ts`: three syncs at stride 188 or 192, or `spawn_mpeg_ts` for a join in mid-segment) with an ADTS AAC,
+MPEG Layer I / II / III or stereo Blu-ray LPCM track: demuxed on the entropy thread (csrc/ts_stream.h), then exactly an ADTS, MPEG audio
+or big-endian raw PCM stream; LATM, AC-3, DTS: `unsupported MPEG-TS audio codec NAME`.
 The reference's other formats stay with their CPU decoders (out of scope)."""
 import ctypes as C
 from dataclasses import dataclass
@@ -110,6 +113,17 @@ class BatchScheduler:
         rc = lib.sk_pipeline_spawn_raw_pcm(self._h, C.byref(f), C.byref(o), C.byref(handle))
         if rc != 0:
             raise SoundkitError(rc, "sk_pipeline_spawn_raw_pcm")
+        return DecodePipelineHandle(self, handle.value)
+
+    def spawn_mpeg_ts(self, options=None):
+        """a stream known to be an MPEG transport stream (sk_pipeline_spawn_mpeg_ts): nothing is detected, the demuxer finds the first
+        sync itself -- for a join in mid-segment; `spawn` takes a stream that begins at a packet by itself"""
+        options = options or DecodeOptions()
+        o = DecodeOptionsC(options.output_sample_rate or 0, options.output_bits_per_sample or 0, options.output_channels or 0, 0)
+        handle = C.c_uint32()
+        rc = lib.sk_pipeline_spawn_mpeg_ts(self._h, C.byref(o), C.byref(handle))
+        if rc != 0:
+            raise SoundkitError(rc, "sk_pipeline_spawn_mpeg_ts")
         return DecodePipelineHandle(self, handle.value)
 
     def spawn_aiff(self, options=None):
@@ -320,6 +334,10 @@ class DecodePipeline:
     @staticmethod
     def spawn_with_options(options):
         return default_scheduler().spawn(options)
+
+    @staticmethod
+    def spawn_mpeg_ts(options=None):
+        return default_scheduler().spawn_mpeg_ts(options)
 
     @staticmethod
     def spawn_aiff():
