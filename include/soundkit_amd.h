@@ -1112,6 +1112,92 @@ int sk_tick_run_aiff(sk_engine *, sk_aiff_tick_stream *streams, uint32_t n_strea
                      const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
                      uint32_t *n_outputs, size_t *out_bytes_used);
 
+/* ---- Compressed WAV: the coded walker (host only) and the ADPCM decode stage (GPU) ----------------------------------- */
+/* A decision beyond the reference, whose WavStreamProcessor (sk_wav_reader above, unchanged) takes format tags 1, 3 and 0xFFFE only.
+ * sk_wav_coded_reader is the same RIFF / RF64 walk with the same budgets and texts that additionally takes
+ *   6 / 7   A-law / mu-law (8 bits per sample; otherwise `WAV G.711 requires 8 bits per sample, found N`): pieces are whole frames of
+ *           `channels` bytes, which sk_aiff_decode expands with SK_AIFF_ALAW / SK_AIFF_ULAW;
+ *   0x11    IMA / DVI ADPCM: nBlockAlign a multiple of 4 x channels, (nBlockAlign - 4 x channels) x 2 / channels + 1 frames a block;
+ *   2       Microsoft ADPCM: nBlockAlign >= 7 x channels, (nBlockAlign - 7 x channels) x 2 / channels + 2 frames a block, wNumCoef
+ *           (1 ... 32) coefficient pairs read from the fmt extension -- the file's table, never an assumed one.
+ * Both ADPCM tags: 4 bits per sample, 1 or 2 channels, at most 65 536 frames a block, a wSamplesPerBlock (cbSize >= 2) that agrees
+ * with the block size; pieces are whole blocks, and a data chunk that ends inside one is `WAV data chunk is not block-aligned`.  A
+ * `fact` chunk in front of `data` is kept: where its dwSampleLength is neither zero nor more than the blocks hold, it is the ADPCM
+ * stream's total_frames, so the padding samples of the last block can be cut.  Tags 1 / 3 / 0xFFFE behave as in sk_wav_reader.
+ * Not built: ADPCM with more than two channels (`WAV ADPCM with N channels is not built: mono and stereo are`); the coded tags inside
+ * WAVE_FORMAT_EXTENSIBLE, GSM 6.10 (0x31), G.726 / G.722 tags, MPEG tags 0x50 / 0x55 -- each ends as `unsupported WAV format tag N`. */
+enum sk_wav_tag { SK_WAV_TAG_PCM = 1, SK_WAV_TAG_MS_ADPCM = 2, SK_WAV_TAG_FLOAT = 3, SK_WAV_TAG_ALAW = 6, SK_WAV_TAG_ULAW = 7, SK_WAV_TAG_IMA_ADPCM = 0x11 };
+typedef struct sk_wav_coded_info { /* zeros until the fmt chunk has been read */
+    uint32_t tag;              /* enum sk_wav_tag (for WAVE_FORMAT_EXTENSIBLE: of the sub-format) */
+    uint32_t sample_rate;
+    uint32_t channels;
+    uint32_t bits;             /* wBitsPerSample: 4 for the ADPCM tags, 8 for G.711 */
+    uint32_t is_float;
+    uint32_t block_align;      /* bytes of a piece's unit: an ADPCM block, else a frame */
+    uint32_t frames_per_block; /* 1 unless ADPCM */
+    uint32_t n_coef;           /* Microsoft ADPCM only */
+    int16_t coef[32][2];       /* {iCoef1, iCoef2} */
+    uint32_t fact_frames;      /* dwSampleLength as read, 0 without a fact chunk */
+    uint32_t reserved;
+    uint64_t total_frames;     /* of the data chunk as declared, cut by fact for ADPCM; 0 while unknown */
+} sk_wav_coded_info;
+typedef struct sk_wav_coded_reader sk_wav_coded_reader;
+int sk_wav_coded_reader_create(sk_wav_coded_reader **out);
+void sk_wav_coded_reader_destroy(sk_wav_coded_reader *);
+/* sk_wav_reader_add's signature and piece contract */
+int sk_wav_coded_reader_add(sk_wav_coded_reader *, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece);
+int sk_wav_coded_reader_info(const sk_wav_coded_reader *, sk_wav_coded_info *info);
+const char *sk_wav_coded_reader_last_error(const sk_wav_coded_reader *);
+
+/* Whole blocks of tag SK_WAV_TAG_IMA_ADPCM or SK_WAV_TAG_MS_ADPCM on the GPU (csrc/wav_adpcm.hip: one block-channel per lane; neither
+ * form carries state from block to block): len = n x block_align bytes in, n x frames_per_block x channels interleaved little-endian
+ * s16 out (*out_len), and one status per block: SK_OK, or SK_WAV_BAD_BLOCK for a block its header rules out -- an IMA step index
+ * above 88, an MS bPredictor >= n_coef -- whose output is zeros; the other blocks are not touched by it.
+ *   IMA: per channel {predictor s16le = first sample, step index, reserved}, then groups of 4 bytes per channel, low nibble first.
+ *   MS:  bPredictor, iDelta, iSamp1, iSamp2 (each for every channel); output iSamp2, iSamp1, then the nibbles, high first (stereo:
+ *        high = left); pred = (samp1 x c1 + samp2 x c2) / 256 DIVIDED, truncating toward zero, as Microsoft's text and FFmpeg do and
+ *        libsndfile's shift does not; delta = AdaptationTable[n] x delta / 256 kept within 16 ... INT_MAX / 768.
+ * coef / n_coef: the fmt chunk's pairs (ignored for IMA).  SK_ERR_INVALID_ARG: another tag, a block size the walker would refuse, len
+ * no whole number of blocks, out_cap too small.  The _dev form takes 16-byte aligned device pointers (status: 4-byte aligned, on the
+ * device too) and is queued on the engine's stream; it waits only for its job record's upload. */
+enum sk_wav_status { SK_WAV_BAD_BLOCK = -1201 };
+int sk_wav_adpcm_decode(sk_engine *, int tag, uint32_t channels, uint32_t block_align, const int16_t *coef /*[n_coef][2]*/, uint32_t n_coef,
+                        const uint8_t *bytes, size_t len, uint8_t *out, size_t out_cap, size_t *out_len, int32_t *status_per_block);
+int sk_wav_adpcm_decode_dev(sk_engine *, int tag, uint32_t channels, uint32_t block_align, const int16_t *coef /*[n_coef][2], host*/, uint32_t n_coef,
+                            const uint8_t *d_bytes, size_t len, uint8_t *d_out, size_t out_cap, size_t *out_len, int32_t *d_status_per_block);
+
+/* The tick of the WAV ADPCM streams, sk_tick_run_aiff's twin: every unit (= whole blocks, the piece of one sk_wav_coded_reader_add,
+ * packed at a 16-byte aligned offset) is first decoded to s16 on the device.  A stream with nothing further to change (no rate change,
+ * out_bits = 16, out_channels = channels) gets those bytes as its outputs, one per unit.  Every other stream then runs exactly what
+ * sk_tick_run_pcm runs on an SK_FMT_S16LE source -- same kernels, records, bounds and limits.  The fields are sk_pcm_tick_stream's, plus
+ * the stream's description and frames_left, the `fact` cap: a unit's decoded frames are cut to it before anything downstream sees
+ * them; the call decrements it on success and leaves it alone on failure; SK_WAV_NO_FRAME_CAP: no cap.  A stream whose cap is used
+ * up brings no more units (SK_ERR_INVALID_ARG).  Neither block form carries state, so the output does not depend on how a stream's
+ * blocks are split into units or dealt out over ticks.  status_per_unit[k]: 0, or 1 + the index of the unit's first block that its
+ * header rules out; such a block decodes to zeros, its unit's record -- behind a conversion every record of its stream in this
+ * tick -- has status SK_WAV_BAD_BLOCK, and the caller ends that stream; the other streams are not touched by it. */
+#define SK_WAV_NO_FRAME_CAP 0xFFFFFFFFFFFFFFFFull
+typedef struct sk_wav_adpcm_tick_stream {
+    uint32_t stream;           /* engine stream (resample = 1 only) */
+    uint32_t n_units;
+    uint16_t tag;              /* SK_WAV_TAG_IMA_ADPCM / SK_WAV_TAG_MS_ADPCM */
+    uint8_t channels;          /* 1 or 2 */
+    uint8_t out_bits;          /* 16 / 24 / 32 */
+    uint8_t out_channels;
+    uint8_t resample;
+    uint8_t flush;
+    uint8_t n_coef;            /* Microsoft ADPCM: 1 ... 32 */
+    uint32_t block_align;
+    uint32_t frames_per_block; /* 0, or what block_align gives */
+    uint64_t frames_left;      /* in: decoded frames the stream may still give; out: less what this tick gave */
+    int16_t coef[32][2];
+} sk_wav_adpcm_tick_stream;
+size_t sk_tick_wav_adpcm_out_bound_on(sk_engine *, const sk_wav_adpcm_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units,
+                                      uint32_t n_units, uint32_t *max_outputs);
+int sk_tick_run_wav_adpcm(sk_engine *, sk_wav_adpcm_tick_stream *streams, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                          const uint8_t *bytes, size_t bytes_len, uint8_t *out_bytes, size_t out_cap, sk_tick_output *outputs, uint32_t outputs_cap,
+                          uint32_t *n_outputs, size_t *out_bytes_used, int32_t *status_per_unit);
+
 /* ---- FLAC (RFC 9639): header parser, framer, stream reader (host only) ----------------------------------------------- */
 /* Native FLAC streams (`fLaC`).  Not built: Ogg FLAC, FLAC in MP4, decode_f32, 32-bit frames with a side channel (33-bit samples:
  * SK_ERR_UNSUPPORTED as that frame's status), MD5 / total-sample verification at the end of a stream. */

@@ -28,6 +28,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -901: "Mp4StreamRejected",
              -1001: "WebmStreamRejected",
              -1101: "TsStreamRejected",
+             -1201: "WavBadBlock",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -174,6 +175,19 @@ class AiffInfo(C.Structure):
     """sk_aiff_info"""
     _fields_ = [("sample_rate", C.c_uint32), ("buffered_bytes", C.c_uint32), ("channels", C.c_uint8), ("encoding", C.c_uint8),
                 ("bits", C.c_uint8), ("is_float", C.c_uint8)]
+
+
+class WavCodedInfo(C.Structure):
+    """sk_wav_coded_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("tag", "sample_rate", "channels", "bits", "is_float", "block_align", "frames_per_block", "n_coef")] + [
+        ("coef", (C.c_int16 * 2) * 32), ("fact_frames", C.c_uint32), ("reserved", C.c_uint32), ("total_frames", C.c_uint64)]
+
+
+class WavAdpcmTickStream(C.Structure):
+    """sk_wav_adpcm_tick_stream"""
+    _fields_ = [("stream", C.c_uint32), ("n_units", C.c_uint32), ("tag", C.c_uint16), ("channels", C.c_uint8), ("out_bits", C.c_uint8),
+                ("out_channels", C.c_uint8), ("resample", C.c_uint8), ("flush", C.c_uint8), ("n_coef", C.c_uint8), ("block_align", C.c_uint32),
+                ("frames_per_block", C.c_uint32), ("frames_left", C.c_uint64), ("coef", (C.c_int16 * 2) * 32)]
 
 
 class FlacStreamInfo(C.Structure):
@@ -593,6 +607,15 @@ _sig = {
     "sk_aiff_reader_last_error": (C.c_char_p, [_vp]),
     "sk_aiff_decode": (_i, [_vp, _i, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
     "sk_aiff_decode_dev": (_i, [_vp, _i, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_wav_coded_reader_create": (_i, [C.POINTER(_vp)]),
+    "sk_wav_coded_reader_destroy": (None, [_vp]),
+    "sk_wav_coded_reader_add": (_i, [_vp, _vp, _sz, C.POINTER(C.c_uint64), C.POINTER(_sz), C.POINTER(_vp)]),
+    "sk_wav_coded_reader_info": (_i, [_vp, C.POINTER(WavCodedInfo)]),
+    "sk_wav_coded_reader_last_error": (C.c_char_p, [_vp]),
+    "sk_wav_adpcm_decode": (_i, [_vp, _i, _u32, _u32, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_wav_adpcm_decode_dev": (_i, [_vp, _i, _u32, _u32, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    "sk_tick_wav_adpcm_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
+    "sk_tick_run_wav_adpcm": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz), _vp]),
     "sk_tick_aiff_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),
     "sk_tick_run_aiff": (_i, [_vp, _vp, _u32, _vp, _u32, _vp, _sz, _vp, _sz, _vp, _u32, C.POINTER(_u32), C.POINTER(_sz)]),
     "sk_flac_parse_header": (_i, [_vp, _sz, _vp, _vp]),

@@ -272,6 +272,7 @@ struct sk_engine {
     DevBuf vorbis_in, vorbis_ws, vorbis_out, vorbis_tab;  // sk_vorbis_decode_packets: packets | blobs | tables | carried halves, residue | windowed PCM | classifications | records, PCM, the constants
     sk::VorbisTables vorbis_tables{};
     bool vorbis_tables_ready = false;
+    DevBuf wav_tab;            // the WAV ADPCM decode stage: job table and per-block status
     DevBuf g72x_tab, g72x_ws;  // the telephony decode stage: stream / unit tables and state records, one word per G.722 byte
     DevBuf gsm_tab, gsm_ws;    // the GSM decode stage: stream / unit tables and state records, one s16 of short-term residual per sample
     DevBuf tick_aiff;    // sk_tick_run_aiff: the units decoded to the contract's PCM, what the PCM tick's body then reads
@@ -611,6 +612,7 @@ const char *sk_strerror(int status) try {
     case SK_MP4_ERR_STREAM: return "MP4 stream rejected";
     case SK_WEBM_ERR_STREAM: return "WebM stream rejected";
     case SK_TS_ERR_STREAM: return "MPEG-TS stream rejected";
+    case SK_WAV_BAD_BLOCK: return "WAV ADPCM block header is invalid";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
     case SK_AAC_ERR_INVALID_BITSTREAM: return "invalid AAC bitstream";
@@ -704,6 +706,7 @@ void sk_engine_destroy(sk_engine *e) try {
         e->vorbis_out.release();
         e->vorbis_tab.release();
         e->g72x_tab.release();
+        e->wav_tab.release();
         e->g72x_ws.release();
         e->gsm_tab.release();
         e->gsm_ws.release();
@@ -5491,6 +5494,234 @@ int sk_aiff_decode_dev(sk_engine *e, int encoding, uint32_t channels, const uint
     return aiff_decode_one(e, encoding, channels, d_bytes, true, len, d_out, out_cap, out_len, state);
 } catch (...) {
     return sk::abi_caught("sk_aiff_decode_dev");
+}
+
+// n_blocks x frames x channels s16 must stay a 31-bit byte count (keep_frames and the lane index are 32-bit)
+static bool need_overflows(uint64_t n_blocks, uint32_t frames, uint32_t channels) { return n_blocks * frames * channels * 2 > 0x7fffffffull; }
+
+// whole blocks of one WAV ADPCM stream, one call: a table of one job in front of k_wav_ima / k_wav_ms (wav_adpcm.hip)
+static int wav_adpcm_decode_one(sk_engine *e, int tag, uint32_t channels, uint32_t block_align, const int16_t *coef, uint32_t n_coef, const uint8_t *bytes,
+                                bool on_device, size_t len, uint8_t *out, size_t out_cap, size_t *out_len, int32_t *status) {
+    static_assert(SK_WAV_BAD_BLOCK == sk::kWavAdpcmBadBlock, "the kernels' status is the header's");
+    if (!e || !out_len) return SK_ERR_INVALID_ARG;
+    *out_len = 0;
+    if (tag != SK_WAV_TAG_IMA_ADPCM && tag != SK_WAV_TAG_MS_ADPCM) return SK_ERR_INVALID_ARG;
+    const uint32_t frames = sk_pcm::wav_adpcm_block_frames((uint32_t)tag, channels, block_align);
+    if (frames == 0 || frames > sk_pcm::kMaxWavAdpcmBlockFrames) return SK_ERR_INVALID_ARG;
+    if (tag == SK_WAV_TAG_MS_ADPCM && (!coef || n_coef < 1 || n_coef > sk_pcm::kMaxWavAdpcmCoefs)) return SK_ERR_INVALID_ARG;
+    if (len % block_align || need_overflows(len / block_align, frames, channels) || (len && (!bytes || !out || !status))) return SK_ERR_INVALID_ARG;
+    const size_t n_blocks = len / block_align, need = n_blocks * frames * channels * 2;
+    if (need > out_cap) return SK_ERR_INVALID_ARG;
+    if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15 || ((uintptr_t)status & 3))) return SK_ERR_INVALID_ARG;
+    if (n_blocks == 0) return SK_OK;
+    std::lock_guard<std::mutex> lock(e->mu);
+    DeviceGuard guard(e);
+    sk::WavAdpcmJob job{};
+    job.src = bytes, job.dst = out, job.status = status;
+    const size_t status_at = (need + 15) & ~(size_t)15;
+    SK_HIP(e->wav_tab.reserve(sizeof job), "alloc wav adpcm job");
+    if (!on_device) {
+        SK_HIP(e->in_buf.reserve(len), "alloc staging");
+        SK_HIP(e->out_buf.reserve(status_at + n_blocks * sizeof(int32_t)), "alloc staging");
+        SK_HIP(hipMemcpyAsync(e->in_buf.p, bytes, len, hipMemcpyHostToDevice, e->stream), "H2D wav adpcm");
+        job.src = (const uint8_t *)e->in_buf.p, job.dst = (uint8_t *)e->out_buf.p, job.status = (int32_t *)((uint8_t *)e->out_buf.p + status_at);
+    }
+    job.n_blocks = (uint32_t)n_blocks, job.block_align = block_align, job.frames_per_block = frames;
+    job.keep_frames = (uint32_t)(n_blocks * frames);
+    job.tag = (uint16_t)tag, job.channels = (uint8_t)channels;
+    if (tag == SK_WAV_TAG_MS_ADPCM) {
+        job.n_coef = (uint8_t)n_coef;
+        std::memcpy(job.coef, coef, (size_t)n_coef * 2 * sizeof(int16_t));
+    }
+    SK_HIP(hipMemcpyAsync(e->wav_tab.p, &job, sizeof job, hipMemcpyHostToDevice, e->stream), "H2D wav adpcm job");
+    SK_HIP(hipStreamSynchronize(e->stream), "wav adpcm job sync");  // job leaves scope with this call
+    SK_HIP(sk::launch_wav_adpcm((const sk::WavAdpcmJob *)e->wav_tab.p, 1, tag == SK_WAV_TAG_IMA_ADPCM, (uint32_t)(n_blocks * channels), e->stream),
+           "launch wav adpcm");
+    if (!on_device) {
+        SK_HIP(hipMemcpyAsync(out, job.dst, need, hipMemcpyDeviceToHost, e->stream), "D2H wav adpcm");
+        SK_HIP(hipMemcpyAsync(status, job.status, n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H wav adpcm status");
+        SK_HIP(hipStreamSynchronize(e->stream), "wav adpcm sync");
+    }
+    *out_len = need;
+    return SK_OK;
+}
+
+int sk_wav_adpcm_decode(sk_engine *e, int tag, uint32_t channels, uint32_t block_align, const int16_t *coef, uint32_t n_coef, const uint8_t *bytes, size_t len,
+                        uint8_t *out, size_t out_cap, size_t *out_len, int32_t *status_per_block) try {
+    sk::abi_enter();
+    return wav_adpcm_decode_one(e, tag, channels, block_align, coef, n_coef, bytes, false, len, out, out_cap, out_len, status_per_block);
+} catch (...) {
+    return sk::abi_caught("sk_wav_adpcm_decode");
+}
+
+int sk_wav_adpcm_decode_dev(sk_engine *e, int tag, uint32_t channels, uint32_t block_align, const int16_t *coef, uint32_t n_coef, const uint8_t *d_bytes,
+                            size_t len, uint8_t *d_out, size_t out_cap, size_t *out_len, int32_t *d_status_per_block) try {
+    sk::abi_enter();
+    return wav_adpcm_decode_one(e, tag, channels, block_align, coef, n_coef, d_bytes, true, len, d_out, out_cap, out_len, d_status_per_block);
+} catch (...) {
+    return sk::abi_caught("sk_wav_adpcm_decode_dev");
+}
+
+// sk_tick_run_wav_adpcm / sk_tick_wav_adpcm_out_bound_on: checks the table and derives what the PCM tick's body works on, as
+// aiff_tick_derive does -- per stream an s16le source, per unit where its decoded frames lie (16-byte aligned, unit after unit; a unit
+// that the `fact` cap cuts is that much shorter) -- and the decode that stands in front of the body: one launch per tag and pass.
+struct WavAdpcmDerived {
+    std::vector<sk_pcm_tick_stream> ts;
+    std::vector<sk_pcm_unit> units;     // the decoded layout
+    std::vector<uint32_t> first;        // per stream: its first unit
+    std::vector<uint32_t> frames;       // per unit: frames kept
+    std::vector<uint32_t> block0;       // per unit: its first block's place in the status array
+    std::vector<uint64_t> left_after;   // per stream: frames_left behind this tick
+    std::vector<sk::WavAdpcmJob> jobs;  // as uploaded, pass after pass
+    std::vector<int32_t> status;        // per block, read back behind the tick's last wait
+    uint32_t n_blocks = 0;
+    AiffTick tick;
+};
+
+static int wav_adpcm_tick_derive(const sk_wav_adpcm_tick_stream *ws, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, size_t bytes_len,
+                                 WavAdpcmDerived &d) {
+    d.ts.assign(n_streams, sk_pcm_tick_stream{});
+    d.units.assign(n_units, sk_pcm_unit{});
+    d.first.assign(n_streams, 0);
+    d.frames.assign(n_units, 0);
+    d.block0.assign(n_units, 0);
+    d.left_after.assign(n_streams, 0);
+    d.tick.plain.assign(n_streams, 0);
+    d.tick.states.assign((size_t)n_streams * 2, 0);
+    uint64_t at = 0, cursor = 0, blocks = 0;
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        const sk_wav_adpcm_tick_stream &w = ws[i];
+        if (w.tag != SK_WAV_TAG_IMA_ADPCM && w.tag != SK_WAV_TAG_MS_ADPCM) return SK_ERR_INVALID_ARG;
+        const uint32_t per = sk_pcm::wav_adpcm_block_frames(w.tag, w.channels, w.block_align);
+        if (per == 0 || per > sk_pcm::kMaxWavAdpcmBlockFrames || (w.frames_per_block && w.frames_per_block != per)) return SK_ERR_INVALID_ARG;
+        if (w.tag == SK_WAV_TAG_MS_ADPCM && (w.n_coef < 1 || w.n_coef > sk_pcm::kMaxWavAdpcmCoefs)) return SK_ERR_INVALID_ARG;
+        sk_pcm_tick_stream &t = d.ts[i];
+        t.stream = w.stream, t.n_units = w.n_units, t.channels = w.channels, t.out_bits = w.out_bits, t.out_channels = w.out_channels;
+        t.resample = w.resample, t.flush = w.flush, t.format = SK_FMT_S16LE;
+        d.tick.plain[i] = !w.resample && w.out_bits == 16 && w.out_channels == w.channels;
+        d.first[i] = (uint32_t)at;
+        if (at + w.n_units > n_units) return SK_ERR_INVALID_ARG;
+        uint64_t left = w.frames_left;
+        for (uint32_t u = 0; u < w.n_units; ++u) {
+            const sk_pcm_unit &un = units[at + u];
+            if (un.byte_offset % 16 || un.byte_len == 0 || un.byte_len % w.block_align) return SK_ERR_INVALID_ARG;
+            if (un.byte_offset > bytes_len || un.byte_len > bytes_len - un.byte_offset) return SK_ERR_INVALID_ARG;
+            const uint64_t n_blocks = un.byte_len / w.block_align;
+            if (need_overflows(n_blocks, per, w.channels)) return SK_ERR_INVALID_ARG;
+            const uint64_t keep = std::min<uint64_t>(n_blocks * per, left);
+            if (keep == 0) return SK_ERR_INVALID_ARG;  // a stream whose cap is used up has no more units
+            if (left != UINT64_MAX) left -= keep;
+            d.frames[at + u] = (uint32_t)keep, d.block0[at + u] = (uint32_t)blocks;
+            d.units[at + u] = sk_pcm_unit{cursor, (uint32_t)(keep * w.channels * 2), 0};
+            cursor += (keep * w.channels * 2 + 15) & ~15ull;
+            blocks += n_blocks;
+        }
+        d.left_after[i] = left;
+        at += w.n_units;
+    }
+    if (cursor > 0x7fffffffull || blocks > 0x3fffffffull) return SK_ERR_INVALID_ARG;
+    d.tick.decoded_len = (size_t)cursor;
+    d.n_blocks = (uint32_t)blocks;
+    return at == n_units ? SK_OK : SK_ERR_INVALID_ARG;
+}
+
+// one pass of the decode in front of the body: the units of the streams whose `plain` is as_is, each to where dst_of puts it.
+// wav_tab holds every unit's job (pass after pass) and behind them every block's status.
+static int wav_adpcm_tick_decode(sk_engine *e, const sk_wav_adpcm_tick_stream *ws, const sk_pcm_unit *units, WavAdpcmDerived &d, bool as_is,
+                                 const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+    const size_t n_units = d.units.size(), status_at = (n_units * sizeof(sk::WavAdpcmJob) + 15) & ~(size_t)15;
+    if (d.jobs.capacity() < n_units) {  // the first pass: both passes' room at once, so that nothing moves under a queued launch
+        d.jobs.reserve(n_units);
+        d.status.assign(d.n_blocks, 0);
+        SK_HIP(e->wav_tab.reserve(status_at + (size_t)d.n_blocks * sizeof(int32_t) + 64), "alloc tick wav adpcm tables");
+    }
+    int32_t *d_status = (int32_t *)((uint8_t *)e->wav_tab.p + status_at);
+    for (int ima = 0; ima < 2; ++ima) {
+        const size_t begin = d.jobs.size();
+        uint32_t max_lanes = 0;
+        for (uint32_t i = 0; i < (uint32_t)d.ts.size(); ++i) {
+            const sk_wav_adpcm_tick_stream &w = ws[i];
+            if ((d.tick.plain[i] != 0) != as_is || (w.tag == SK_WAV_TAG_IMA_ADPCM) != (ima != 0)) continue;
+            for (uint32_t u = 0; u < w.n_units; ++u) {
+                const uint32_t g = d.first[i] + u;
+                sk::WavAdpcmJob job{};
+                job.src = d_src + units[g].byte_offset, job.dst = dst_of(i, u), job.status = d_status + d.block0[g];
+                job.n_blocks = units[g].byte_len / w.block_align, job.block_align = w.block_align;
+                job.frames_per_block = sk_pcm::wav_adpcm_block_frames(w.tag, w.channels, w.block_align);
+                job.keep_frames = d.frames[g], job.tag = w.tag, job.channels = w.channels;
+                if (!ima) {
+                    job.n_coef = w.n_coef;
+                    std::memcpy(job.coef, w.coef, (size_t)w.n_coef * 2 * sizeof(int16_t));
+                }
+                max_lanes = std::max(max_lanes, job.n_blocks * w.channels);
+                d.jobs.push_back(job);
+            }
+        }
+        const size_t n = d.jobs.size() - begin;
+        if (n == 0) continue;
+        sk::WavAdpcmJob *d_jobs = (sk::WavAdpcmJob *)e->wav_tab.p + begin;
+        SK_HIP(hipMemcpyAsync(d_jobs, d.jobs.data() + begin, n * sizeof(sk::WavAdpcmJob), hipMemcpyHostToDevice, e->stream), "H2D tick wav adpcm jobs");
+        SK_HIP(sk::launch_wav_adpcm(d_jobs, (uint32_t)n, ima != 0, max_lanes, e->stream), "tick wav adpcm decode");
+    }
+    // every block's status so far, read behind the tick's last wait (the second pass brings the whole array again, complete then)
+    if (d.n_blocks) SK_HIP(hipMemcpyAsync(d.status.data(), d_status, (size_t)d.n_blocks * sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), "D2H tick wav adpcm status");
+    return SK_OK;
+}
+
+size_t sk_tick_wav_adpcm_out_bound_on(sk_engine *e, const sk_wav_adpcm_tick_stream *ws, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units,
+                                      uint32_t *max_outputs) try {
+    sk::abi_enter();
+    if (max_outputs) *max_outputs = 0;
+    if (!e || (!ws && n_streams) || (!units && n_units)) return 0;
+    WavAdpcmDerived d;
+    if (wav_adpcm_tick_derive(ws, n_streams, units, n_units, (size_t)-1, d) != SK_OK) return 0;
+    std::lock_guard<std::mutex> lk(e->mu);
+    return tick_pcm_out_bound(e, d.ts.data(), n_streams, d.units.data(), n_units, max_outputs, d.tick.plain.data());
+} catch (...) {
+    (void)sk::abi_caught("sk_tick_wav_adpcm_out_bound_on");
+    return 0;
+}
+
+int sk_tick_run_wav_adpcm(sk_engine *e, sk_wav_adpcm_tick_stream *ws, uint32_t n_streams, const sk_pcm_unit *units, uint32_t n_units, const uint8_t *bytes,
+                          size_t bytes_len, uint8_t *out, size_t out_cap, sk_tick_output *outs, uint32_t outs_cap, uint32_t *n_outs, size_t *out_bytes,
+                          int32_t *status_per_unit) try {
+    sk::abi_enter();
+    if (!e || !n_outs || (n_streams && !ws) || (n_units && (!units || !bytes || !status_per_unit))) return SK_ERR_INVALID_ARG;
+    *n_outs = 0;
+    if (out_bytes) *out_bytes = 0;
+    WavAdpcmDerived d;
+    int rc = wav_adpcm_tick_derive(ws, n_streams, units, n_units, bytes_len, d);
+    if (rc != SK_OK) return rc;
+    d.tick.decode = [&](bool as_is, const std::function<uint8_t *(uint32_t, uint32_t)> &dst_of, const uint8_t *d_src) {
+        return wav_adpcm_tick_decode(e, ws, units, d, as_is, dst_of, d_src);
+    };
+    rc = tick_pcm_impl(e, d.ts.data(), n_streams, d.units.data(), n_units, bytes, bytes_len, out, out_cap, outs, outs_cap, n_outs, out_bytes, &d.tick);
+    if (rc != SK_OK) return rc;  // frames_left is the caller's record: untouched
+    for (uint32_t i = 0; i < n_streams; ++i) {
+        ws[i].frames_left = d.left_after[i];
+        for (uint32_t u = 0; u < ws[i].n_units; ++u) {  // a unit's status: 0, or 1 + the index of its first block that its header rules out
+            const uint32_t g = d.first[i] + u, n = units[g].byte_len / ws[i].block_align;
+            status_per_unit[g] = 0;
+            for (uint32_t b = 0; b < n && status_per_unit[g] == 0; ++b)
+                if (d.status[d.block0[g] + b] != 0) status_per_unit[g] = (int32_t)(b + 1);
+        }
+    }
+    // the records of a stream delivered as decoded correspond to its units; a unit with a bad block marks its record, or -- behind a
+    // conversion, where records and units do not correspond -- every record of its stream in this tick
+    std::vector<uint32_t> seen(n_streams, 0);
+    for (uint32_t k = 0; k < *n_outs; ++k) {
+        sk_tick_output &o = outs[k];
+        const uint32_t i = o.stream_index;
+        if (d.tick.plain[i]) {
+            if (status_per_unit[d.first[i] + seen[i]++] != 0) o.status = SK_WAV_BAD_BLOCK;
+        } else {
+            for (uint32_t u = 0; u < ws[i].n_units && o.status == 0; ++u)
+                if (status_per_unit[d.first[i] + u] != 0) o.status = SK_WAV_BAD_BLOCK;
+        }
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_tick_run_wav_adpcm");
 }
 
 int sk_aac_entropy_decode(sk_engine *e, const uint32_t *streams, const uint32_t *units_per_stream, uint32_t n_streams,

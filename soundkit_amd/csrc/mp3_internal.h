@@ -140,6 +140,10 @@ struct PipelineGpuHooks {
                        sk_tick_output *, uint32_t, uint32_t *, size_t *, int32_t *) = nullptr;
     size_t (*tick_vorbis_out_bound)(sk_engine *, const sk_vorbis_tick_stream *, uint32_t, const sk_vorbis_tick_packet *, uint32_t, const uint8_t *, size_t,
                                     uint32_t *) = nullptr;
+    // sk_tick_run_wav_adpcm / sk_tick_wav_adpcm_out_bound_on: the WAV ADPCM streams' blocks
+    int (*tick_wav_adpcm)(sk_engine *, sk_wav_adpcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, const uint8_t *, size_t, uint8_t *, size_t,
+                          sk_tick_output *, uint32_t, uint32_t *, size_t *, int32_t *) = nullptr;
+    size_t (*tick_wav_adpcm_out_bound)(sk_engine *, const sk_wav_adpcm_tick_stream *, uint32_t, const sk_pcm_unit *, uint32_t, uint32_t *) = nullptr;
     uint32_t (*wide_pcm_streams)(const sk_engine *) = nullptr;  // sk_engine_wide_pcm_streams
     int (*enable_wide_pcm)(sk_engine *, uint32_t) = nullptr;    // sk_engine_enable_wide_pcm
 };

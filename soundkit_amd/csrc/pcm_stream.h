@@ -1,6 +1,7 @@
 // pcm_stream.h -- the two stream processors in front of the PCM tick: host code, no GPU.
 //
-//   WavStream     = WavStreamProcessor::add with install_fmt / install_ds64 (soundkit/src/wav.rs:95-324)
+//   WavStream     = WavStreamProcessor::add with install_fmt / install_ds64 (soundkit/src/wav.rs:95-324); WavStream(true), the coded
+//                   mode, is this project's own: the same walk, and four more format tags (see the class)
 //   RawPcmStream  = RawPcmStreamProcessor::add / flush (soundkit/src/raw_pcm.rs:150-190)
 //   AiffStream    = AiffDecoder::add without its per-sample work (soundkit-aiff/src/lib.rs:93-475); see the class
 //
@@ -33,8 +34,29 @@ struct Piece {
     uint64_t stream_offset = 0;     // where the piece starts, counted over every byte ever passed to add()
 };
 
+// The coded mode (WavStream(true); sk_wav_coded_reader_*): a decision beyond the reference, whose WavStreamProcessor is the default
+// mode bit for bit.  The chunk walk, the budgets and every text of the default mode stay; the fmt installer additionally takes
+//   6 / 7   A-law / mu-law: 8 bits per sample, a frame is `channels` bytes, pieces are whole frames
+//   0x11    IMA / DVI ADPCM, 2 Microsoft ADPCM: 4 bits per sample, 1 or 2 channels, pieces are whole blocks of nBlockAlign bytes
+// and a `fact` chunk in front of `data` is kept (the metadata budget bounds it): its dwSampleLength caps total_frames() of the two
+// ADPCM tags, so the padding samples of a last block can be cut; absent, zero or larger than what the blocks hold it is ignored.
+// Not taken: the coded tags inside WAVE_FORMAT_EXTENSIBLE, ADPCM with more than two channels, every other tag.
+constexpr uint32_t kWavTagPcm = 1, kWavTagMsAdpcm = 2, kWavTagFloat = 3, kWavTagAlaw = 6, kWavTagUlaw = 7, kWavTagImaAdpcm = 0x11;
+constexpr uint32_t kMaxWavAdpcmBlockFrames = 65536;
+constexpr uint32_t kMaxWavAdpcmCoefs = 32;
+
+// frames of one ADPCM block; 0 where the block size is no block of the tag (the walker's rules, shared with the decode stage)
+inline uint32_t wav_adpcm_block_frames(uint32_t tag, uint32_t channels, uint32_t block_align) {
+    if (channels < 1 || channels > 2) return 0;
+    if (tag == kWavTagImaAdpcm) return block_align < 4 * channels || block_align % (4 * channels) ? 0 : (block_align - 4 * channels) * 2 / channels + 1;
+    if (tag == kWavTagMsAdpcm) return block_align < 7 * channels ? 0 : (block_align - 7 * channels) * 2 / channels + 2;
+    return 0;
+}
+
 class WavStream {
 public:
+    explicit WavStream(bool coded = false) : coded_(coded) {}
+
     // false = error (text in `err`); the processor is finished then, as the reference's is (state left at Finished)
     bool add(const uint8_t *chunk, size_t len, Piece &piece, std::string &err) {
         piece = Piece{};
@@ -124,6 +146,8 @@ public:
                 }
                 if (std::memcmp(kind_, "fmt ", 4) == 0) {
                     if (!install_fmt(err)) return false;
+                } else if (std::memcmp(kind_, "fact", 4) == 0) {
+                    if (coded_ && payload_.size() >= 4) fact_frames_ = le32(payload_.data());
                 } else if (std::memcmp(kind_, "ds64", 4) == 0) {
                     if (!install_ds64(err)) return false;
                 }
@@ -131,7 +155,7 @@ public:
                 break;
             }
             case ReadingData: {
-                const size_t frame = (size_t)(bits_ / 8) * channels_;
+                const size_t frame = (size_t)frame_bytes();
                 if (frame == 0) {
                     err = "WAV fmt has zero bytes per frame";
                     return false;
@@ -140,7 +164,7 @@ public:
                 const size_t n = available / frame * frame;
                 if (n == 0) {
                     if ((uint64_t)avail >= remaining_ && remaining_ > 0) {
-                        err = "WAV data chunk is not frame-aligned";
+                        err = is_adpcm() ? "WAV data chunk is not block-aligned" : "WAV data chunk is not frame-aligned";
                         return false;
                     }
                     state_ = ReadingData;
@@ -167,16 +191,30 @@ public:
     bool is_float() const { return float_; }
     // total_frames (wav.rs:86-93): 0 = not known (no data chunk header yet, or an empty one)
     uint64_t total_frames() const {
-        const uint64_t frame = (uint64_t)(bits_ / 8) * channels_;
-        return frame == 0 || data_chunk_size_ == 0 ? 0 : data_chunk_size_ / frame;
+        const uint64_t frame = frame_bytes();
+        if (frame == 0 || data_chunk_size_ == 0) return 0;
+        if (!is_adpcm()) return data_chunk_size_ / frame;
+        const uint64_t held = data_chunk_size_ / frame * frames_per_block_;  // the fact chunk's count where it cuts, else what the blocks hold
+        return fact_frames_ != 0 && fact_frames_ <= held ? fact_frames_ : held;
     }
+    // the coded mode's description (the default mode: tag 1 or 3, the rest zero)
+    uint32_t tag() const { return tag_; }
+    uint32_t block_align() const { return is_adpcm() ? block_align_ : (uint32_t)frame_bytes(); }
+    uint32_t frames_per_block() const { return is_adpcm() ? frames_per_block_ : (frame_bytes() ? 1 : 0); }
+    uint32_t n_coef() const { return n_coef_; }
+    const int16_t (*coef() const)[2] { return coef_; }
+    uint32_t fact_frames() const { return fact_frames_; }
+    bool is_adpcm() const { return tag_ == kWavTagMsAdpcm || tag_ == kWavTagImaAdpcm; }
 
 private:
     enum State { Initial, ChunkHeader, ChunkPayload, ReadingData, Finished };
     static uint32_t le16(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
     static uint32_t le32(const uint8_t *p) { return le16(p) | (le16(p + 2) << 16); }
     static uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
-    bool is_meta() const { return std::memcmp(kind_, "fmt ", 4) == 0 || std::memcmp(kind_, "ds64", 4) == 0; }
+    bool is_meta() const {
+        return std::memcmp(kind_, "fmt ", 4) == 0 || std::memcmp(kind_, "ds64", 4) == 0 || (coded_ && std::memcmp(kind_, "fact", 4) == 0);
+    }
+    uint64_t frame_bytes() const { return is_adpcm() ? block_align_ : (uint64_t)(bits_ / 8) * channels_; }
 
     bool install_fmt(std::string &err) {
         const std::vector<uint8_t> &p = payload_;
@@ -185,6 +223,7 @@ private:
             return false;
         }
         uint32_t format = le16(p.data());
+        const bool coded_tag = coded_ && (format == kWavTagMsAdpcm || format == kWavTagAlaw || format == kWavTagUlaw || format == kWavTagImaAdpcm);
         if (format == 0xfffe) {
             if (p.size() < 40) {
                 err = "WAVE_FORMAT_EXTENSIBLE fmt chunk is truncated";
@@ -199,6 +238,8 @@ private:
             float_ = false;
         } else if (format == 3) {
             float_ = true;
+        } else if (coded_tag) {
+            float_ = false;
         } else {
             err = "unsupported WAV format tag " + std::to_string(format);
             return false;
@@ -207,10 +248,76 @@ private:
             err = "WAV fmt contains invalid audio geometry";
             return false;
         }
+        tag_ = format, block_align_ = frames_per_block_ = n_coef_ = 0;
+        if (coded_tag) return install_coded(err);
         if (bits_ % 8 != 0) {
             err = "WAV sample width must be byte-aligned";
             return false;
         }
+        return true;
+    }
+
+    // the four tags of the coded mode (an error finishes the walker, as every other does)
+    bool install_coded(std::string &err) {
+        const std::vector<uint8_t> &p = payload_;
+        const uint32_t bits = bits_, channels = channels_;
+        if (tag_ == kWavTagAlaw || tag_ == kWavTagUlaw) {
+            if (bits != 8) {
+                err = "WAV G.711 requires 8 bits per sample, found " + std::to_string(bits);
+                return false;
+            }
+            return true;
+        }
+        const bool ima = tag_ == kWavTagImaAdpcm;
+        if (bits != 4) {
+            err = "WAV ADPCM requires 4 bits per sample, found " + std::to_string(bits);
+            return false;
+        }
+        if (channels > 2) {
+            err = "WAV ADPCM with " + std::to_string(channels) + " channels is not built: mono and stereo are";
+            return false;
+        }
+        const uint32_t align = le16(p.data() + 12);
+        const uint32_t frames = wav_adpcm_block_frames(tag_, channels, align);
+        if (frames == 0) {
+            err = std::string(ima ? "WAV IMA ADPCM" : "WAV MS ADPCM") + " block size " + std::to_string(align) + " is invalid for " + std::to_string(channels) + " channels";
+            return false;
+        }
+        if (frames > kMaxWavAdpcmBlockFrames) {
+            err = "WAV ADPCM block of " + std::to_string(frames) + " samples exceeds the " + std::to_string(kMaxWavAdpcmBlockFrames) + " sample budget";
+            return false;
+        }
+        const uint32_t cb = p.size() >= 18 ? le16(p.data() + 16) : 0;
+        if (!ima && (p.size() < 22 || cb < 4)) {  // wSamplesPerBlock and wNumCoef are not optional here
+            err = "WAV MS ADPCM fmt chunk is truncated";
+            return false;
+        }
+        if (cb >= 2) {
+            if (p.size() < 20) {
+                err = "WAV IMA ADPCM fmt chunk is truncated";
+                return false;
+            }
+            const uint32_t declared = le16(p.data() + 18);
+            if (declared != frames) {
+                err = "WAV ADPCM fmt declares " + std::to_string(declared) + " samples per block, the block holds " + std::to_string(frames);
+                return false;
+            }
+        }
+        if (!ima) {
+            const uint32_t n = le16(p.data() + 20);
+            if (n < 1 || n > kMaxWavAdpcmCoefs) {
+                err = "WAV MS ADPCM fmt declares " + std::to_string(n) + " coefficient sets: 1 to " + std::to_string(kMaxWavAdpcmCoefs) + " are read";
+                return false;
+            }
+            if (p.size() < 22 + (size_t)4 * n || cb < 4 + 4 * n) {
+                err = "WAV MS ADPCM fmt chunk is truncated";
+                return false;
+            }
+            for (uint32_t i = 0; i < n; ++i)
+                for (int k = 0; k < 2; ++k) coef_[i][k] = (int16_t)le16(p.data() + 22 + 4 * i + 2 * k);
+            n_coef_ = n;
+        }
+        block_align_ = align, frames_per_block_ = frames;
         return true;
     }
 
@@ -245,6 +352,10 @@ private:
     uint32_t bits_ = 0, channels_ = 0, rate_ = 0;
     bool float_ = false, rf64_ = false, have_ds64_ = false;
     uint64_t rf64_data_size_ = 0, data_chunk_size_ = 0;
+    // the coded mode
+    const bool coded_;
+    uint32_t tag_ = 0, block_align_ = 0, frames_per_block_ = 0, n_coef_ = 0, fact_frames_ = 0;
+    int16_t coef_[kMaxWavAdpcmCoefs][2] = {};
 };
 
 class RawPcmStream {

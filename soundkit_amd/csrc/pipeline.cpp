@@ -89,6 +89,11 @@ struct PStream {
     // WAV / raw PCM streams (FormatDecoder::Wav / RawPcm, lib.rs:2292-2297): the stream processor, and what its first piece decided
     std::unique_ptr<sk_pcm::WavStream> wav;
     std::unique_ptr<sk_pcm::RawPcmStream> raw;
+    // a WAV stream of a coded tag (the walker's coded mode, beyond the reference): A-law / mu-law pieces are units of the AIFF tick
+    // (aiff_enc says which), ADPCM blocks units of the ADPCM tick.  The fact cap is counted twice: by the worker that cuts the pieces
+    // to it, and by the submission thread, whose count goes into the stream's row when its tick runs and comes back from it.
+    bool wav_g711 = false, wav_adpcm = false;
+    uint64_t wav_parse_left = 0, wav_tick_left = 0;
     // AIFF / AIFF-C streams (FormatDecoder::Aiff): the container walker; its pieces are source-encoded, the AIFF tick decodes them.
     // The IMA4 carry belongs to the submission thread: it goes into the stream's row when its tick runs and comes back from it.
     std::unique_ptr<sk_pcm::AiffStream> aiff;
@@ -162,7 +167,7 @@ struct PStream {
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
 constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11, kCodecWebm = 12, kCodecTs = 13;
-constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
+constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8, kPcmWavAdpcmTick = 9;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
 constexpr size_t kPcmTickBytes = 32u * 1024 * 1024;
@@ -234,6 +239,8 @@ struct Batch {
     size_t pcm_cap = 0, pcm_used = 0;
     TickTable<sk_pcm_tick_stream, sk_pcm_unit> pcm_ts;
     TickTable<sk_aiff_tick_stream, sk_pcm_unit> aiff_ts;
+    TickTable<sk_wav_adpcm_tick_stream, sk_pcm_unit> wav_ts;  // WAV ADPCM streams' blocks (sk_tick_run_wav_adpcm)
+    std::vector<int32_t> wav_status;
     TickTable<sk_flac_tick_stream, sk_flac_frame_info> flac_ts;
     std::vector<int32_t> flac_status;
     TickTable<sk_alac_tick_stream, sk_alac_tick_packet> alac_ts;  // ALAC streams' packets (sk_tick_run_alac)
@@ -269,6 +276,7 @@ struct Batch {
         pcm_used = 0;
         pcm_ts.clear();
         aiff_ts.clear();
+        wav_ts.clear();
         flac_ts.clear();
         alac_ts.clear();
         g72x_ts.clear();
@@ -981,6 +989,12 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         s.aiff_enc = (uint8_t)s.aiff->encoding();
     } else if (s.wav) {
         rate = s.wav->sample_rate(), channels = s.wav->channels(), bits = s.wav->bits(), is_float = s.wav->is_float();
+        const uint32_t tag = s.wav->tag();
+        s.wav_g711 = tag == SK_WAV_TAG_ALAW || tag == SK_WAV_TAG_ULAW;
+        s.wav_adpcm = s.wav->is_adpcm();
+        if (s.wav_g711 || s.wav_adpcm) bits = 16;  // what the decode emits, as for AIFF-C
+        if (s.wav_g711) s.aiff_enc = tag == SK_WAV_TAG_ALAW ? SK_AIFF_ALAW : SK_AIFF_ULAW;
+        if (s.wav_adpcm) s.wav_parse_left = s.wav_tick_left = s.wav->total_frames();
     } else {
         const int f = s.raw_format.format;
         rate = s.raw_format.sample_rate, channels = s.raw_format.channels;
@@ -1030,6 +1044,14 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         s.pcm_route = kPcmVorbisTick;
         return true;
     }
+    if (s.wav_adpcm && (!hooks.tick_wav_adpcm || !hooks.tick_wav_adpcm_out_bound))
+        return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: WAV ADPCM decoding needs the device tick, which this build lacks");
+    if (s.wav_adpcm && target_rate == rate && target_bits == bits && target_channels == channels) {  // every block has per-sample work: the tick's
+        const int rc = ensure_pcm(p);
+        if (rc != SK_OK) return r.fail(rc, std::string("Decoding failed: PCM staging buffers: ") + sk_strerror(rc));
+        s.pcm_route = kPcmWavAdpcmTick;
+        return true;
+    }
     if (s.alac && (!hooks.tick_alac || !hooks.tick_alac_out_bound))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: ALAC decoding needs the device tick, which this build lacks");
     if (s.alac && target_rate == rate && target_bits == bits && target_channels == channels) {  // every packet has per-sample work: the tick's
@@ -1041,7 +1063,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     }
     if (target_rate == rate && target_bits == bits && target_channels == channels) {
         // sowt / 23ni are the contract's bytes already; every other encoding has per-sample work, which is the tick's
-        if (!s.aiff || s.aiff_enc == SK_AIFF_S16LE || s.aiff_enc == SK_AIFF_S32LE) {
+        if ((!s.aiff && !s.wav_g711) || (s.aiff && (s.aiff_enc == SK_AIFF_S16LE || s.aiff_enc == SK_AIFF_S32LE))) {
             s.pcm_route = kPcmFast;
             return true;
         }
@@ -1059,7 +1081,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     // 3 ... 8 channels: the tick takes them on an engine whose pool of wide streams was reserved (sk_engine_enable_wide_pcm)
     if (channels > SK_MAX_CHANNELS && (channels > SK_MAX_PCM_CHANNELS || !hooks.wide_pcm_streams || hooks.wide_pcm_streams(p->engine) == 0))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
-    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound || (s.aiff && (!hooks.tick_aiff || !hooks.tick_aiff_out_bound)))
+    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound || ((s.aiff || s.wav_g711) && (!hooks.tick_aiff || !hooks.tick_aiff_out_bound)))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
     s.pcm_fmt = (uint8_t)((bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : (is_float ? SK_FMT_F32LE : SK_FMT_S32LE))) + (big_endian ? 1 : 0));
     int rc = ensure_pcm(p);
@@ -1071,7 +1093,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.vorbis ? kPcmVorbisTick : s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff ? kPcmAiffTick : kPcmTick));
+    s.pcm_route = s.vorbis ? kPcmVorbisTick : s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff || s.wav_g711 ? kPcmAiffTick : (s.wav_adpcm ? kPcmWavAdpcmTick : kPcmTick)));
     return true;
 }
 
@@ -1613,6 +1635,31 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
 void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     r.pcm = true;
     uint32_t outputs = 0;
+    // A piece of whole ADPCM blocks: cut to the blocks the fact cap still needs, and to the blocks in front of the first one its header
+    // rules out -- those are staged as a unit, then the stream ends with the block's text.
+    auto process_wav_adpcm = [&](const sk_pcm::Piece &piece) -> bool {
+        const uint32_t align = s.wav->block_align(), per = s.wav->frames_per_block(), tag = s.wav->tag();
+        size_t blocks = piece.len / align;
+        blocks = (size_t)std::min<uint64_t>(blocks, (s.wav_parse_left + per - 1) / per);  // what lies behind the cap is padding
+        std::string bad;
+        for (size_t k = 0; k < blocks && bad.empty(); ++k) {
+            const uint8_t *blk = piece.data + k * align;
+            for (uint32_t c = 0; c < s.channels && bad.empty(); ++c) {
+                if (tag == SK_WAV_TAG_IMA_ADPCM && blk[4 * c + 2] > 88)
+                    bad = "WAV IMA ADPCM block step index " + std::to_string(blk[4 * c + 2]) + " exceeds 88";
+                if (tag == SK_WAV_TAG_MS_ADPCM && blk[c] >= s.wav->n_coef())
+                    bad = "WAV MS ADPCM block predictor " + std::to_string(blk[c]) + " exceeds the " + std::to_string(s.wav->n_coef()) + " coefficient sets";
+            }
+            if (!bad.empty()) blocks = k;
+        }
+        if (blocks) {
+            const uint32_t frames = (uint32_t)std::min<uint64_t>((uint64_t)blocks * per, s.wav_parse_left);
+            s.wav_parse_left -= frames;
+            stage_unit(r, s, piece.data, blocks * align, frames, outputs);
+        }
+        if (!bad.empty()) r.fail(SK_PCM_ERR_STREAM, "Decoding failed: " + bad);
+        return bad.empty();
+    };
     auto process = [&](const uint8_t *data, size_t len) -> bool {
         sk_pcm::Piece piece;
         std::string err;
@@ -1623,9 +1670,10 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         }
         if (piece.len == 0) return true;
         if (!s.pcm_route && !pcm_open(p, s, r)) return false;
-        // (an AIFF piece is source-encoded: its frames follow from its sample groups)
+        if (s.wav_adpcm) return process_wav_adpcm(piece);
+        // (an AIFF piece is source-encoded: its frames follow from its sample groups; so is a G.711 WAV's, a byte a sample)
         const uint32_t frame_bytes = (uint32_t)s.pcm_bits / 8 * s.channels;
-        const uint32_t frames = s.aiff ? (uint32_t)(piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) * (s.aiff_enc == SK_AIFF_IMA4 ? 64 : 1) /
+        const uint32_t frames = s.wav_g711 ? (uint32_t)(piece.len / s.channels) : s.aiff ? (uint32_t)(piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) * (s.aiff_enc == SK_AIFF_IMA4 ? 64 : 1) /
                                                     (s.aiff_enc == SK_AIFF_IMA4 ? 1 : s.channels))
                                        : (uint32_t)(piece.len / frame_bytes);
         // the decoder emits every complete SAMPLE of an add: a piece may end inside a frame.  Delivered as it is that is what the
@@ -1650,7 +1698,7 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         while (s.pending.size() - s.pending_pos < kMinDetectionBytes && !s.saw_eof)
             if (pull_input(s) == 0) return;  // needs more input
         if (s.codec == kCodecAiff) s.aiff.reset(new sk_pcm::AiffStream());
-        else s.wav.reset(new sk_pcm::WavStream());
+        else s.wav.reset(new sk_pcm::WavStream(true));  // the coded mode: tags 1 and 3 walk as before
         s.pcm_detected = true;
         const uint8_t *d = s.pending.data() + s.pending_pos;
         const size_t n = s.pending.size() - s.pending_pos, first = std::min(n, kMaxDetectionBytes);
@@ -2126,6 +2174,11 @@ void worker_body(sk_lane *p) {
                 t.flush = 0;
                 if (s.pcm_route == kPcmAiffTick) {
                     if (sk_aiff_tick_stream *row = claim_tick_row(b, b->aiff_ts, s, r, r.pcm_units, be, pcm_at)) row->encoding = s.aiff_enc;
+                } else if (s.pcm_route == kPcmWavAdpcmTick) {
+                    if (sk_wav_adpcm_tick_stream *row = claim_tick_row(b, b->wav_ts, s, r, r.pcm_units, be, pcm_at)) {
+                        row->tag = (uint16_t)s.wav->tag(), row->block_align = s.wav->block_align(), row->n_coef = (uint8_t)s.wav->n_coef();
+                        std::memcpy(row->coef, s.wav->coef(), sizeof row->coef);  // (the cap joins the row on the submission thread)
+                    }
                 } else if (s.pcm_route == kPcmFlacTick) {
                     if (sk_flac_tick_stream *row = claim_tick_row(b, b->flac_ts, s, r, r.flac_frames, be, pcm_at)) {
                         const uint8_t depth = s.flac->info().bits_per_sample;
@@ -2306,7 +2359,7 @@ void submit_body(sk_lane *p) {
         size_t used = 0;
         b->rc = SK_OK;
         b->n_out = 0;
-        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty() ||
+        if (!ts.empty() || !b->pcm_ts.rows.empty() || !b->aiff_ts.rows.empty() || !b->wav_ts.rows.empty() || !b->flac_ts.rows.empty() || !b->alac_ts.rows.empty() ||
             !b->g72x_ts.rows.empty() || !b->gsm_ts.rows.empty() || !b->vorbis_ts.rows.empty()) {
             // the Vorbis streams' carry as the ticks before this one left it (this thread alone reads and writes it): the bound needs it too
             for (uint32_t row = 0; row < b->vorbis_ts.rows.size(); ++row) {
@@ -2314,9 +2367,13 @@ void submit_body(sk_lane *p) {
                 sk_vorbis_tick_stream &v = b->vorbis_ts.rows[row];
                 v.setup = s.vorbis_setup.get(), v.overlap = s.vorbis_overlap.data(), v.prev_blocksize = s.vorbis_prev;
             }
+            // the WAV ADPCM streams' fact cap likewise: a unit it cuts is that much shorter
+            for (uint32_t row = 0; row < b->wav_ts.rows.size(); ++row)
+                b->wav_ts.rows[row].frames_left = p->streams[b->entries[b->wav_ts.entry[row]].handle]->wav_tick_left;
             // the main tick's outputs, the AIFF tick's behind those, then the FLAC tick's, the ALAC tick's, then the PCM tick's: one buffer
             const size_t bound = (ts.empty() ? 0 : sk_tick_out_bound_on(p->engine, ts.data(), (uint32_t)ts.size(), &max_out)) +
-                                 follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
+                                 follow_on_bound(p, b->aiff_ts, hooks.tick_aiff_out_bound) + follow_on_bound(p, b->wav_ts, hooks.tick_wav_adpcm_out_bound) +
+                                 follow_on_bound(p, b->flac_ts, hooks.tick_flac_out_bound) +
                                  follow_on_bound(p, b->alac_ts, hooks.tick_alac_out_bound) +
                                  follow_on_bound(p, b->g72x_ts, hooks.tick_g72x_out_bound) + follow_on_bound(p, b->gsm_ts, hooks.tick_gsm_out_bound) +
                                  follow_on_bound(p, b->vorbis_ts,
@@ -2341,7 +2398,7 @@ void submit_body(sk_lane *p) {
                 static const bool trace = std::getenv("SK_TICK_TRACE") != nullptr;
                 if (trace) std::fprintf(stderr, "sk_pipeline: output buffer of batch %d regrown to %zu bytes in %.2f ms\n", index, b->out_pinned_cap, ns_since(t_alloc) * 1e-6);
             }
-            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->gsm_ts.max_out + b->vorbis_ts.max_out + b->pcm_ts.max_out;
+            const size_t n_recs = (size_t)max_out + b->aiff_ts.max_out + b->wav_ts.max_out + b->flac_ts.max_out + b->alac_ts.max_out + b->g72x_ts.max_out + b->gsm_ts.max_out + b->vorbis_ts.max_out + b->pcm_ts.max_out;
             if (b->recs.size() < n_recs) b->recs.resize(n_recs);
         }
         const bool with_md = b->n_mp3 && p->mp3_gpu;  // the MP3 streams' Huffman stage is the tick's as well
@@ -2389,6 +2446,14 @@ void submit_body(sk_lane *p) {
             PStream &s = *p->streams[b->entries[b->aiff_ts.entry[row]].handle];
             s.aiff_ima[0] = b->aiff_ts.rows[row].ima_state[0], s.aiff_ima[1] = b->aiff_ts.rows[row].ima_state[1];
         }
+        follow_on_tick(b, b->wav_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
+            b->wav_status.assign(b->wav_ts.units.size() + 1, 0);  // (the worker has looked at every block header: no unit holds a bad one)
+            return hooks.tick_wav_adpcm(p->engine, b->wav_ts.rows.data(), (uint32_t)b->wav_ts.rows.size(), b->wav_ts.units.data(),
+                                        (uint32_t)b->wav_ts.units.size(), b->pcm_bytes, b->pcm_used, out, out_cap, recs, recs_cap, n_out, out_used,
+                                        b->wav_status.data());
+        });
+        for (uint32_t row = 0; b->rc == SK_OK && row < b->wav_ts.rows.size(); ++row)  // the cap as this tick leaves it
+            p->streams[b->entries[b->wav_ts.entry[row]].handle]->wav_tick_left = b->wav_ts.rows[row].frames_left;
         follow_on_tick(b, b->flac_ts, used, [&](uint8_t *out, size_t out_cap, sk_tick_output *recs, uint32_t recs_cap, uint32_t *n_out, size_t *out_used) {
             b->flac_status.assign(b->flac_ts.units.size() + 1, 0);
             return hooks.tick_flac(p->engine, b->flac_ts.rows.data(), (uint32_t)b->flac_ts.rows.size(), b->flac_ts.units.data(),
@@ -2447,7 +2512,7 @@ void submit_body(sk_lane *p) {
         p->tick_ns.fetch_add(ns_since(t0));
         p->n_ticks.fetch_add(1);
         p->n_frames.fetch_add(n_frames + (uint32_t)b->n_mp3 + (uint32_t)b->mpa_recs.size() + (uint32_t)b->pcm_ts.units.size() +
-                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size() + (uint32_t)b->gsm_ts.units.size() + (uint32_t)b->vorbis_ts.units.size());
+                              (uint32_t)b->aiff_ts.units.size() + (uint32_t)b->wav_ts.units.size() + (uint32_t)b->flac_ts.units.size() + (uint32_t)b->alac_ts.units.size() + (uint32_t)b->g72x_ts.units.size() + (uint32_t)b->gsm_ts.units.size() + (uint32_t)b->vorbis_ts.units.size());
         b->rec_begin.assign(b->row_of.size() + 1, b->n_out);
         {
             uint32_t k = 0;
@@ -2996,6 +3061,8 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.raw.reset();
     s.aiff.reset();
     s.aiff_enc = 0;
+    s.wav_g711 = s.wav_adpcm = false;
+    s.wav_parse_left = s.wav_tick_left = 0;
     s.flac.reset();
     s.flac_plain = false;
     s.alac = s.alac_plain = false;
@@ -3187,6 +3254,10 @@ int lane_get_stats(sk_lane *p, sk_pipeline_stats *out) {
 
 struct sk_wav_reader {
     sk_pcm::WavStream stream;
+    std::string error;
+};
+struct sk_wav_coded_reader {
+    sk_pcm::WavStream stream{true};
     std::string error;
 };
 struct sk_aiff_reader {
@@ -3630,6 +3701,62 @@ const char *sk_wav_reader_last_error(const sk_wav_reader *r) try {
     return r ? r->error.c_str() : "";
 } catch (...) {
     (void)sk::abi_caught("sk_wav_reader_last_error");
+    return "";
+}
+
+// the walker in its coded mode (A-law, mu-law, IMA and Microsoft ADPCM besides PCM and float): this project's own
+int sk_wav_coded_reader_create(sk_wav_coded_reader **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_wav_coded_reader();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_wav_coded_reader_create");
+}
+
+void sk_wav_coded_reader_destroy(sk_wav_coded_reader *r) try {
+    sk::abi_enter();
+    delete r;
+} catch (...) {
+    (void)sk::abi_caught("sk_wav_coded_reader_destroy");
+}
+
+int sk_wav_coded_reader_add(sk_wav_coded_reader *r, const uint8_t *bytes, size_t len, uint64_t *piece_offset, size_t *piece_len, const uint8_t **piece) try {
+    sk::abi_enter();
+    if (!r || (len && !bytes) || !piece_offset || !piece_len) return SK_ERR_INVALID_ARG;
+    sk_pcm::Piece got;
+    *piece_offset = 0, *piece_len = 0;
+    if (piece) *piece = nullptr;
+    if (!r->stream.add(bytes, len, got, r->error)) return SK_PCM_ERR_STREAM;
+    *piece_offset = got.stream_offset, *piece_len = got.len;
+    if (piece) *piece = got.data;
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_wav_coded_reader_add");
+}
+
+int sk_wav_coded_reader_info(const sk_wav_coded_reader *r, sk_wav_coded_info *info) try {
+    sk::abi_enter();
+    if (!r || !info) return SK_ERR_INVALID_ARG;
+    std::memset(info, 0, sizeof *info);
+    const sk_pcm::WavStream &s = r->stream;
+    if (s.tag() == 0 || s.bits() == 0) return SK_OK;
+    info->tag = s.tag(), info->sample_rate = s.sample_rate(), info->channels = s.channels(), info->bits = s.bits();
+    info->is_float = s.is_float() ? 1 : 0;
+    info->block_align = s.block_align(), info->frames_per_block = s.frames_per_block(), info->n_coef = s.n_coef();
+    std::memcpy(info->coef, s.coef(), sizeof info->coef);
+    info->fact_frames = s.fact_frames();
+    info->total_frames = s.total_frames();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_wav_coded_reader_info");
+}
+
+const char *sk_wav_coded_reader_last_error(const sk_wav_coded_reader *r) try {
+    sk::abi_enter();
+    return r ? r->error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_wav_coded_reader_last_error");
     return "";
 }
 

@@ -14,6 +14,8 @@ const bool g_hooked = [] {
     hooks.tick_pcm_out_bound = sk_tick_pcm_out_bound_on;
     hooks.tick_aiff = sk_tick_run_aiff;  // ... and the AIFF streams'
     hooks.tick_aiff_out_bound = sk_tick_aiff_out_bound_on;
+    hooks.tick_wav_adpcm = sk_tick_run_wav_adpcm;  // ... and the WAV ADPCM streams'
+    hooks.tick_wav_adpcm_out_bound = sk_tick_wav_adpcm_out_bound_on;
     hooks.tick_flac = sk_tick_run_flac;  // ... and the FLAC streams'
     hooks.tick_flac_out_bound = sk_tick_flac_out_bound_on;
     hooks.tick_alac = sk_tick_run_alac;  // ... and the ALAC streams'

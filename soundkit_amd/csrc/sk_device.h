@@ -572,6 +572,25 @@ struct AiffImaStream {
 // states_out[2 * stream + channel] = (uint16_t)predictor | step_index << 16: what the stream leaves with
 hipError_t launch_aiff_ima4(const AiffImaStream *streams, uint32_t n_streams, const AiffImaUnit *units, uint32_t *states_out, hipStream_t s);
 
+// wav_adpcm.hip -- the blocks of WAV's two ADPCM tags (0x11 IMA / DVI, 2 Microsoft) to interleaved s16: one (block, channel) per
+// lane, no state from block to block.  A job is a run of whole blocks of one stream (a unit of a tick); a block that its header rules
+// out (an IMA step index above 88, an MS predictor at or past n_coef) gets status kWavAdpcmBadBlock and zeros.  Only the job's first
+// keep_frames frames are written (the `fact` cut of a stream's last block).  grid = (slices of 256 lanes, jobs).
+constexpr int32_t kWavAdpcmBadBlock = -1201;  // SK_WAV_BAD_BLOCK
+struct WavAdpcmJob {
+    const uint8_t *src;  // n_blocks x block_align bytes; 4-byte aligned for IMA
+    uint8_t *dst;        // n_blocks x frames_per_block x channels s16
+    int32_t *status;     // [n_blocks]
+    uint32_t n_blocks, block_align, frames_per_block;
+    uint32_t keep_frames;  // <= n_blocks x frames_per_block
+    uint16_t tag;        // 0x11 or 2
+    uint8_t channels;    // 1 or 2
+    uint8_t n_coef;      // MS: 1 ... 32
+    int16_t coef[32][2];
+};
+// the jobs of one launch are all IMA or all MS (`ima`); max_lanes = the largest n_blocks x channels among them
+hipError_t launch_wav_adpcm(const WavAdpcmJob *jobs, uint32_t n_jobs, bool ima, uint32_t max_lanes, hipStream_t s);
+
 // flac_decode.hip -- FLAC frames (RFC 9639 9.2-9.3) to interleaved PCM, integer only, three launches over every frame of a call:
 // k_flac_residual (one frame per lane: subframe headers, warm-up samples and Rice residuals into a planar i32 workspace, one record
 // per subframe), k_flac_restore (one subframe per lane: the FIXED / LPC recurrence in place, 64-bit accumulate) and k_flac_output

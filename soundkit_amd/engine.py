@@ -22,6 +22,23 @@ FMT_S16LE, FMT_S16BE, FMT_S24LE, FMT_S24BE, FMT_S32LE, FMT_S32BE, FMT_F32LE, FMT
 AIFF_GROUP_BYTES = {AIFF_U8: 1, AIFF_S8: 1, AIFF_S16BE: 2, AIFF_S16LE: 2, AIFF_S24BE: 3, AIFF_S32BE: 4, AIFF_S32LE: 4, AIFF_F32BE: 4,
                     AIFF_F64BE: 8, AIFF_ULAW: 1, AIFF_ALAW: 1}  # IMA4: 34 bytes per channel
 
+# enum sk_wav_tag: the format tags the coded WAV walker takes; WAV_BAD_BLOCK = SK_WAV_BAD_BLOCK, a block's status
+WAV_TAG_PCM, WAV_TAG_MS_ADPCM, WAV_TAG_FLOAT, WAV_TAG_ALAW, WAV_TAG_ULAW, WAV_TAG_IMA_ADPCM = 1, 2, 3, 6, 7, 0x11
+WAV_BAD_BLOCK = -1201
+WAV_NO_FRAME_CAP = 0xFFFFFFFFFFFFFFFF
+
+
+def wav_adpcm_block_frames(tag, channels, block_align):
+    """Frames of one ADPCM block of nBlockAlign bytes; 0 where the size is no block of the tag."""
+    if channels not in (1, 2):
+        return 0
+    if tag == WAV_TAG_IMA_ADPCM:
+        return 0 if block_align < 4 * channels or block_align % (4 * channels) else (block_align - 4 * channels) * 2 // channels + 1
+    if tag == WAV_TAG_MS_ADPCM:
+        return 0 if block_align < 7 * channels else (block_align - 7 * channels) * 2 // channels + 2
+    return 0
+
+
 PCM_OPS = [
     "I16LE_TO_F32", "I16_TO_I16LE", "I16LE_TO_I16", "S24LE_TO_I32", "S24LE_TO_I16", "S24BE_TO_I16",
     "S32LE_TO_I32", "S32BE_TO_I32", "S32LE_TO_S24", "S32BE_TO_S24", "S32LE_TO_F32", "S32BE_TO_F32",
@@ -542,6 +559,23 @@ class Engine:
             return got, [(st[c].predictor, st[c].step_index) for c in range(2)]
         return got
 
+    def wav_adpcm_decode(self, tag, channels, block_align, data, coef=None):
+        """sk_wav_adpcm_decode: whole blocks of a WAV stream of tag WAV_TAG_IMA_ADPCM / WAV_TAG_MS_ADPCM -> (interleaved little-endian
+        s16 as bytes, frames_per_block x channels samples a block; [status per block]: 0, or WAV_BAD_BLOCK for a block its header
+        rules out, whose samples are zeros).  coef: the fmt chunk's [(iCoef1, iCoef2)] (Microsoft ADPCM only)."""
+        data = np.frombuffer(bytes(data), np.uint8)
+        block_align, channels = int(block_align), int(channels)
+        table = np.asarray(coef if coef is not None else [], np.int16).reshape(-1, 2)
+        n_blocks = data.size // block_align if block_align > 0 else 0
+        per_block = 2 * channels * wav_adpcm_block_frames(int(tag), channels, block_align)  # 0: the library refuses that geometry
+        out = np.zeros(max(n_blocks * per_block, 16), np.uint8)
+        status = np.zeros(max(n_blocks, 1), np.int32)
+        n = C.c_size_t()
+        check(lib.sk_wav_adpcm_decode(self._h, int(tag), channels, block_align, _ptr(table) if table.size else None, table.shape[0],
+                                      _ptr(data) if data.size else None, data.size, _ptr(out), n_blocks * per_block, C.byref(n), _ptr(status)),
+              "sk_wav_adpcm_decode", self._h)
+        return out[:n.value].tobytes(), status[:n_blocks].tolist()
+
     def flac_decode(self, frames):
         """sk_flac_decode_frames: [(frame dict, frame bytes)] as flac.FlacReader.add / flac.scan cut them -> (the contract's interleaved
         little-endian PCM as bytes, [status per frame])"""
@@ -883,6 +917,57 @@ class Engine:
                 s["ima_state"] = [(ts[i].ima_state[c].predictor, ts[i].ima_state[c].step_index) for c in range(2)]
         return [(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
                 for r in recs[:n_out.value]]
+
+    def _wav_adpcm_tick_tables(self, streams, units):
+        from ._lib import PcmUnit, WavAdpcmTickStream
+        ts = (WavAdpcmTickStream * max(len(streams), 1))()
+        for i, s in enumerate(streams):
+            ts[i].stream, ts[i].n_units = int(s.get("stream", 0)), int(s["n_units"])
+            ts[i].tag, ts[i].channels, ts[i].block_align = int(s["tag"]), int(s["channels"]), int(s["block_align"])
+            ts[i].out_bits, ts[i].out_channels = int(s["out_bits"]), int(s["out_channels"])
+            ts[i].resample, ts[i].flush = int(bool(s.get("resample", 0))), int(bool(s.get("flush", 0)))
+            ts[i].frames_left = WAV_NO_FRAME_CAP if s.get("frames_left") is None else int(s["frames_left"])
+            coef = s.get("coef") or []
+            ts[i].n_coef = len(coef)
+            for k, (a, b) in enumerate(coef):
+                ts[i].coef[k][0], ts[i].coef[k][1] = int(a), int(b)
+        table = (PcmUnit * max(len(units), 1))()
+        total = 0
+        for k, u in enumerate(units):
+            table[k].byte_offset, table[k].byte_len = total, len(u)
+            total += (len(u) + 15) & ~15
+        blob = np.zeros(max(total, 16), np.uint8)
+        for k, u in enumerate(units):
+            blob[table[k].byte_offset:table[k].byte_offset + len(u)] = np.frombuffer(bytes(u), np.uint8)
+        return ts, table, blob, total
+
+    def tick_wav_adpcm_out_bound(self, streams, units):
+        """sk_tick_wav_adpcm_out_bound_on for the tables tick_run_wav_adpcm would build -> (bytes, records)"""
+        ts, table, _, _ = self._wav_adpcm_tick_tables(streams, units)
+        max_out = C.c_uint32()
+        return lib.sk_tick_wav_adpcm_out_bound_on(self._h, ts, len(streams), table, len(units), C.byref(max_out)), max_out.value
+
+    def tick_run_wav_adpcm(self, streams, units, out_cap=None):
+        """One tick of WAV ADPCM streams (sk_tick_run_wav_adpcm).  As tick_run_pcm, with the stream's description in the place of
+        `format`: tag (WAV_TAG_IMA_ADPCM / WAV_TAG_MS_ADPCM), block_align, coef ([(iCoef1, iCoef2)], Microsoft ADPCM), and frames_left,
+        the fact chunk's cap (None: no cap), which is updated in the dict when the tick succeeded.  units: whole blocks.  out_cap: an
+        output size other than the bound's (to have a tick refused).  -> (the same list of records, [status per unit: 0, or 1 + the
+        index of the unit's first bad block])."""
+        from ._lib import TickOutput
+        ts, table, blob, total = self._wav_adpcm_tick_tables(streams, units)
+        n = len(units)
+        max_out = C.c_uint32()
+        cap = lib.sk_tick_wav_adpcm_out_bound_on(self._h, ts, len(streams), table, n, C.byref(max_out))
+        out = np.zeros(max(cap, 16), np.uint8)
+        recs = (TickOutput * max(max_out.value, 1))()
+        status = np.zeros(max(n, 1), np.int32)
+        n_out, used = C.c_uint32(), C.c_size_t()
+        check(lib.sk_tick_run_wav_adpcm(self._h, ts, len(streams), table, n, _ptr(blob), total, _ptr(out), out.size if out_cap is None else out_cap, recs,
+                                        max_out.value, C.byref(n_out), C.byref(used), _ptr(status)), "sk_tick_run_wav_adpcm", self._h)
+        for i, s in enumerate(streams):
+            s["frames_left"] = None if ts[i].frames_left == WAV_NO_FRAME_CAP else int(ts[i].frames_left)
+        return ([(r.stream_index, r.status, r.frames, r.channels, r.bits, out[r.byte_offset:r.byte_offset + r.bytes].tobytes(), bool(r.reserved & 1))
+                 for r in recs[:n_out.value]], status[:n].tolist())
 
     def tick_run_mpa(self, streams, frames=None):
         """One tick of MPEG Layer I / II streams alone (sk_tick_run_mixed_mpa with no AAC unit and no Layer III granule).  streams:
