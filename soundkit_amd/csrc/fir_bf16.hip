@@ -79,8 +79,16 @@ __host__ __device__ constexpr int products_of(int s, bool in16, bool f16) { retu
 #endif
 // half-chunks of input in flight per wave (2, 3, 4 or 6: a divisor of the 12 steps of the unrolled body).  In round 1 three made
 // no difference (profiles/r01_ab_fir.md); with this round's shorter steps the loads of two half-chunks no longer land in time:
-// 2 -> 3 is 4 % of the launch (0.381-0.386 -> 0.364-0.370 ms on one box), 4 the same, 6 spills (profiles/r03_ab_fir.md).
+// 2 -> 3 is 4 % of the launch (0.381-0.386 -> 0.364-0.370 ms on one box), 4 the same, 6 spills (profiles/r03_ab_fir.md).  Four
+// again with the registers 32-bit addressing freed (164 VGPRs, no spill): 0.3276 against 0.3266 ms, no gain (profiles/fir_interior.md).
 constexpr int kAhead = SK_BF_AHEAD;
+#ifndef SK_FIR_READ_EARLY
+#define SK_FIR_READ_EARLY 1
+#endif
+// how many of a step's two B windows an interior body reads from LDS in front of the step's ring writes (0, 1 or 2).  One -- the
+// window of the step's own second half -- is 2 % of the launch (0.328 -> 0.321 ms, below in each of seven alternations) and costs
+// no register inside the body; the second adds eight live registers and measured between the two (profiles/fir_interior.md).
+constexpr int kReadEarly = SK_FIR_READ_EARLY;
 
 __host__ __device__ constexpr int ring_index(int rho) { return ((rho % kRing) + kRing) % kRing; }
 
@@ -119,22 +127,44 @@ __device__ __forceinline__ void split_pair16(uint32_t u, uint32_t &p1, uint32_t 
 // (the f16 planes of s16 samples: dev_split_pair16_f16, sk_device.h -- shared with the fused decode-tail kernel)
 __device__ __forceinline__ void split_pair16_f16(uint32_t u, uint32_t &p1, uint32_t &p2) { dev_split_pair16_f16(u, p1, p2); }
 
-template <bool IN16>
+// A32 (s16 rows only): 32-bit addressing.  The sixteen rows of a wave's group are read through one buffer descriptor whose base is
+// the group's first row (a scalar), each lane keeps a 32-bit byte offset per load instead of a 64-bit pointer, and the wave-uniform
+// time offset rides in the instruction's scalar-offset operand: no 64-bit vector add per load, eight registers fewer.  The host
+// takes this form only where every offset of a group stays below 2^31 (launch_fir_48k_16k).
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+constexpr int kRsrcFlags = 0x00027000;  // raw buffer (stride 0, range-checked in bytes), 32-bit data format
+
+template <bool IN16, bool A32 = false>
 struct Stage {
     // ALIGNED: load ld (0..3) of a chunk holds samples 4 (lane & 15) .. + 3 of row 4 ld + (lane >> 4)
     // otherwise: its word e holds sample `lane` of row 4 ld + e
     // a half-chunk = loads 2 half, 2 half + 1 (eight rows); it sits in slot pair v[2 slot], v[2 slot + 1]
     using Elem = std::conditional_t<IN16, int16_t, float>;
     using Vec = std::conditional_t<IN16, u32x2, f32x4>;  // four samples of a row
-    const Elem *base[4];
+    std::conditional_t<A32, uint32_t, const Elem *> base[4];  // A32: byte offset of the lane's four samples from the group's first row
+    rsrc_t rs;  // A32: the group's rows
     uint32_t ok_mask;
     Vec v[2 * kAhead];  // kAhead half-chunks (two loads each) in flight
 };
 
-template <bool ALIGNED, bool PACKED, bool IN16>
-__device__ __forceinline__ void stage_init(const FirArgs &a, int lane, uint32_t row0, Stage<IN16> &st) {
+template <bool ALIGNED, bool PACKED, bool IN16, bool A32>
+__device__ __forceinline__ void stage_init(const FirArgs &a, int lane, uint32_t row0, Stage<IN16, A32> &st) {
     st.ok_mask = 0;
-    if (ALIGNED) {
+    if constexpr (A32) {
+        static_assert(IN16 && ALIGNED && PACKED, "32-bit addressing is built for the frame-packed s16 rows");
+        const size_t g0 = row_base_offset<PACKED>(a, row0);
+        // the group's extent in bytes: its last row, the last sample.  Rows past the end alias the group's first row.
+        const uint32_t last = (a.rows - row0 < 16u ? a.rows - row0 : 16u) - 1u;
+        const size_t extent = row_base_offset<PACKED>(a, row0 + last) - g0 + time_offset<PACKED>(a, a.in_frames - 1u) + 1u;
+        st.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int16_t *>(a.in16 + g0), 0, (int)(uint32_t)(2 * extent), kRsrcFlags);
+#pragma unroll
+        for (int ld = 0; ld < 4; ++ld) {
+            const uint32_t r = row0 + 4 * ld + (lane >> 4);
+            const bool ok = r < a.rows;
+            st.base[ld] = (uint32_t)(2 * (row_base_offset<PACKED>(a, ok ? r : row0) - g0)) + 8u * (lane & 15);
+            if (ok) st.ok_mask |= 1u << ld;
+        }
+    } else if (ALIGNED) {
 #pragma unroll
         for (int ld = 0; ld < 4; ++ld) {
             const uint32_t r = row0 + 4 * ld + (lane >> 4);
@@ -148,15 +178,15 @@ __device__ __forceinline__ void stage_init(const FirArgs &a, int lane, uint32_t 
 }
 
 // issue the global loads of loads [ld0, ld1) of the chunk that starts at stream sample n (wave-uniform)
-template <bool ALIGNED, bool PACKED, bool INTERIOR = false, bool IN16 = false>
-__device__ __forceinline__ void stage_issue(const FirArgs &a, int lane, uint32_t row0, int64_t n, Stage<IN16> &st, int half, int slot) {
-    using Vec = typename Stage<IN16>::Vec;
-    using Elem = typename Stage<IN16>::Elem;
+template <bool ALIGNED, bool PACKED, bool INTERIOR = false, bool IN16 = false, bool A32 = false>
+__device__ __forceinline__ void stage_issue(const FirArgs &a, int lane, uint32_t row0, int64_t n, Stage<IN16, A32> &st, int half, int slot) {
+    using Vec = typename Stage<IN16, A32>::Vec;
+    using Elem = typename Stage<IN16, A32>::Elem;
     if (ALIGNED) {
         const int64_t c0 = n - a.in_origin;  // the chunk's first sample in the row
         // the usual chunk lies inside the row (and inside one 1024-sample block of the frame-packed layout): one scalar
-        // offset for the wave and one 64-bit add per load.  The loads sit between matrix instructions, where every
-        // vector instruction beyond two per MFMA costs its full issue time.
+        // offset for the wave and one 64-bit add per load (A32: none, the offset is the load's scalar operand).  The loads sit
+        // between matrix instructions, where every vector instruction beyond two per MFMA costs its full issue time.
         const bool inside = c0 >= 0 && c0 + 64 <= (int64_t)a.in_frames;
         const bool one_block = !PACKED || (((uint32_t)c0 & 1023u) + 64u <= 1024u);
         if (INTERIOR || __builtin_expect(inside && one_block, 1)) {  // INTERIOR: the caller has checked the whole body
@@ -164,7 +194,8 @@ __device__ __forceinline__ void stage_issue(const FirArgs &a, int lane, uint32_t
 #pragma unroll
             for (int e2 = 0; e2 < 2; ++e2) {
                 const int ld = 2 * half + e2, sl = 2 * slot + e2;
-                st.v[sl] = *reinterpret_cast<const Vec *>(st.base[ld] + off);
+                if constexpr (A32) st.v[sl] = __builtin_amdgcn_raw_buffer_load_b64(st.rs, st.base[ld], (int)(uint32_t)(2 * off), 0);
+                else st.v[sl] = *reinterpret_cast<const Vec *>(st.base[ld] + off);
             }
         } else {
             asm volatile("; chunk at an edge of the row" ::: "memory");  // a real branch: not if-converted into the loads above
@@ -175,8 +206,16 @@ __device__ __forceinline__ void stage_issue(const FirArgs &a, int lane, uint32_t
 #pragma unroll
             for (int e2 = 0; e2 < 2; ++e2) {
                 const int ld = 2 * half + e2, sl = 2 * slot + e2;
-                const Elem *src = ((sel >> ld) & 1u) ? st.base[ld] + off : reinterpret_cast<const Elem *>(a.zeros) + 4 * lane;
-                st.v[sl] = *reinterpret_cast<const Vec *>(src);
+                if constexpr (A32) {
+                    // a lane outside the row reads the start of its row instead and drops what it read (no 64-bit address here
+                    // either: pointers formed for this path would stay alive across the interior loop)
+                    const bool use = ((sel >> ld) & 1u) != 0;
+                    const Vec got = __builtin_amdgcn_raw_buffer_load_b64(st.rs, st.base[ld] + (use ? (uint32_t)(2 * off) : 0u), 0, 0);
+                    st.v[sl] = use ? got : (Vec){0u, 0u};
+                } else {
+                    const Elem *src = ((sel >> ld) & 1u) ? st.base[ld] + off : reinterpret_cast<const Elem *>(a.zeros) + 4 * lane;
+                    st.v[sl] = *reinterpret_cast<const Vec *>(src);
+                }
             }
         }
     } else if constexpr (!IN16) {  // s16 rows are only taken aligned (launch_fir_48k_16k checks)
@@ -198,8 +237,8 @@ __device__ __forceinline__ void stage_issue(const FirArgs &a, int lane, uint32_t
 }
 
 // split loads [ld0, ld1) and write them to the ring at sample position `ring_at` (of the chunk's first sample)
-template <bool ALIGNED, bool IN16, bool F16 = false>
-__device__ __forceinline__ void stage_commit(unsigned char *lds, int lane, int ring_at, const Stage<IN16> &st, int half, int slot) {
+template <bool ALIGNED, bool IN16, bool F16 = false, bool A32 = false>
+__device__ __forceinline__ void stage_commit(unsigned char *lds, int lane, int ring_at, const Stage<IN16, A32> &st, int half, int slot) {
 #pragma unroll
     for (int e2 = 0; e2 < 2; ++e2) {
         const int ld = 2 * half + e2, sl = 2 * slot + e2;
@@ -248,7 +287,7 @@ __device__ __forceinline__ f32x4 mfma_bf16(const u32x4 &av, const u32x4 &bv, con
 __device__ __forceinline__ f32x4 mfma_f16(const u32x4 &av, const u32x4 &bv, const f32x4 &c) { return dev_mfma_f16(av, bv, c); }
 
 // OUT16: 0 = f32 rows out.  F16 (with IN16): f16 planes and the f16 matrix instruction instead of bf16.
-template <bool ALIGNED, bool PACKED, int OUT16, bool IN16 = false, bool F16 = false>
+template <bool ALIGNED, bool PACKED, int OUT16, bool IN16 = false, bool F16 = false, bool A32 = false>
 // the f16 form holds two planes of tap fragments (80 registers instead of 120): three waves per SIMD fit (168 VGPRs, a dozen
 // words spilled), measured 4 % faster than two with the grid cut into 3072 waves
 #ifndef SK_FIR_F16_WAVES
@@ -258,6 +297,7 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
                                                             uint32_t n_segs, int out_vec) {
     static_assert(!IN16 || ALIGNED, "s16 rows are read four samples at a time");
     static_assert(!F16 || IN16, "the f16 planes exist for s16 rows");
+    static_assert(!A32 || F16, "32-bit addressing is built for the f16 form on s16 rows");
     constexpr int kPlanes = IN16 ? 2 : 3;
     __shared__ __attribute__((aligned(16))) unsigned char lds[16 * row_bytes(kPlanes)];
 
@@ -281,8 +321,8 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
             for (int k = 0; k < kTapPlanes; ++k) af[s][k] = src[(s * kTapPlanes + k) * 64 + lane];
     }
 
-    Stage<IN16> st;
-    stage_init<ALIGNED, PACKED, IN16>(a, lane, row0, st);
+    Stage<IN16, A32> st;
+    stage_init<ALIGNED, PACKED, IN16, A32>(a, lane, row0, st);
 
     // body-relative time rho = n - 96 P0 (P0 = first period of an unrolled body of four): the ring index of rho is
     // static because 4 periods = 384 samples = 2 ring revolutions
@@ -290,13 +330,13 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
     // the ring starts with rho in [-128, 0) in place and the half-chunks that the first kAhead steps commit in flight
 #pragma unroll
     for (int c = -2; c < 0; ++c) {
-        stage_issue<ALIGNED, PACKED, false, IN16>(a, lane, row0, n_begin + 64 * c, st, 0, 0);
-        stage_issue<ALIGNED, PACKED, false, IN16>(a, lane, row0, n_begin + 64 * c, st, 1, 1);
-        stage_commit<ALIGNED, IN16, F16>(lds, lane, ring_index(64 * c), st, 0, 0);
-        stage_commit<ALIGNED, IN16, F16>(lds, lane, ring_index(64 * c), st, 1, 1);
+        stage_issue<ALIGNED, PACKED, false, IN16, A32>(a, lane, row0, n_begin + 64 * c, st, 0, 0);
+        stage_issue<ALIGNED, PACKED, false, IN16, A32>(a, lane, row0, n_begin + 64 * c, st, 1, 1);
+        stage_commit<ALIGNED, IN16, F16, A32>(lds, lane, ring_index(64 * c), st, 0, 0);
+        stage_commit<ALIGNED, IN16, F16, A32>(lds, lane, ring_index(64 * c), st, 1, 1);
     }
 #pragma unroll
-    for (int i = 0; i < kAhead; ++i) stage_issue<ALIGNED, PACKED, false, IN16>(a, lane, row0, n_begin + 64 * (i >> 1), st, i & 1, i % kAhead);
+    for (int i = 0; i < kAhead; ++i) stage_issue<ALIGNED, PACKED, false, IN16, A32>(a, lane, row0, n_begin + 64 * (i >> 1), st, i & 1, i % kAhead);
 
     const uint32_t out_row = row0 + j;
     float *out_ptr = OUT16 ? nullptr
@@ -319,11 +359,35 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
     float *out_lane = to_s16 ? nullptr : out_ptr + 4 * q;
     // s16: the lane of a stream's first channel writes the interleaved frames of all its channels
     int16_t *out16_ptr = to_s16 ? a.out16 + (size_t)((row_exists ? out_row : 0) / (OUT16 ? OUT16 : 1)) * a.out16_stride * OUT16 : nullptr;
+    // interior stores of interleaved stereo: which half of a row pair's four frames the lane writes, and its byte selectors
+    const bool odd_lane = (j & 1) != 0;
+    const uint32_t sel_first = odd_lane ? 0x01000504u : 0x05040100u;   // low halves:  L | R << 16 of the first frame
+    const uint32_t sel_second = odd_lane ? 0x03020706u : 0x07060302u;  // high halves: the second frame
+    // A32: the group's output rows behind one descriptor, the lane's place in them as a 32-bit byte offset; the tile's
+    // wave-uniform offset is the store's scalar operand.  Rows the group does not have lie beyond the descriptor's range.
+    rsrc_t out_rs;
+    uint32_t row_voff = 0, out_voff = 0;  // of the lane's row, and of the four outputs the lane writes per tile in it
+    if constexpr (A32) {
+        const uint32_t n_rows = a.rows - row0 < 16u ? a.rows - row0 : 16u;
+        if constexpr (to_s16) {
+            constexpr uint32_t kCh = OUT16 ? OUT16 : 1;
+            const uint32_t stream_bytes = (uint32_t)a.out16_stride * kCh * 2u;
+            out_rs = __builtin_amdgcn_make_buffer_rsrc(a.out16 + (size_t)(row0 / kCh) * a.out16_stride * kCh, 0,
+                                                       (int)((n_rows / kCh) * stream_bytes), kRsrcFlags);
+            row_voff = (j / kCh) * stream_bytes;
+            out_voff = row_voff + (kCh == 2 ? 16u * q + 8u * (j & 1) : 8u * q);
+        } else {
+            const uint32_t row_out_bytes = (uint32_t)a.out_stride * 4u;
+            out_rs = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)row0 * a.out_stride, 0, (int)(n_rows * row_out_bytes), kRsrcFlags);
+            row_voff = j * row_out_bytes;
+            out_voff = row_voff + 16u * q;
+        }
+    }
     auto store_tile = [&](auto itag, const f32x4 &vraw, int32_t pair, int parity) __attribute__((always_inline)) {
         // the samples went in as integers (and the f16 taps times 2^16): powers of two, they commute with every rounding
         const f32x4 v = F16 ? vraw * (1.0f / 2147483648.0f) : (IN16 ? vraw * (1.0f / 32768.0f) : vraw);
         // INTERIOR: every tile of the body lies inside the segment and the output range, all 16 rows exist, stores are
-        // vector stores -- no branch, so a whole body is one scheduling region
+        // vector stores by every lane -- no branch inside a body (the per-step sched_barrier still cuts it into twelve regions)
         constexpr bool INTERIOR = decltype(itag)::value;
         if (!INTERIOR && (pair < p_begin || pair >= p_end)) return;  // wave-uniform
         const int32_t rel_tile = 32 * pair + 16 * parity - (int32_t)a.out_first;  // wave-uniform
@@ -331,13 +395,20 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
         const bool row_ok = INTERIOR || row_exists;
         const int32_t rel = rel_tile + 4 * q;
         if (!to_s16) {
-            if (INTERIOR || __builtin_expect(whole, 1)) {
-                if (row_ok) *reinterpret_cast<f32x4 *>(out_lane + rel_tile) = v;
+            if constexpr (INTERIOR && A32) {
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rs, out_voff, 4 * rel_tile, 0);
+            } else if (INTERIOR || __builtin_expect(whole, 1)) {
+                if constexpr (A32) {
+                    if (row_ok) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rs, out_voff, 4 * rel_tile, 0);
+                } else if (row_ok) *reinterpret_cast<f32x4 *>(out_lane + rel_tile) = v;
             } else {
                 asm volatile("; tile at an edge of the output, or unaligned rows" ::: "memory");
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (row_ok && rel + r >= 0 && rel + r < (int32_t)a.out_count) out_ptr[rel + r] = v[r];
+                    if (row_ok && rel + r >= 0 && rel + r < (int32_t)a.out_count) {
+                        if constexpr (A32) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v[r]), out_rs, row_voff + 4u * (uint32_t)(rel + r), 0, 0);
+                        else out_ptr[rel + r] = v[r];
+                    }
             }
             return;
         }
@@ -352,7 +423,17 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
             mine01 = dev_pack2_s16(v[0], v[1]);
             mine23 = dev_pack2_s16(v[2], v[3]);
         }
-        if (OUT16 == 2) {
+        if constexpr (INTERIOR && OUT16 == 2) {
+            // Every lane stores: of the four interleaved frames of a row pair the left channel's lane (j even) writes frames
+            // rel, rel + 1 and the right channel's lane frames rel + 2, rel + 3, eight bytes each.  A lane sends the packed pair
+            // it does not write to its neighbour (lane ^ 1, DPP quad_perm [1,0,3,2]), keeps the other, and two byte permutes
+            // with a per-lane selector put L in the low half and R in the high half.  No lane is masked off, so no branch.
+            const uint32_t keep = odd_lane ? mine23 : mine01, send = odd_lane ? mine01 : mine23;
+            const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send, 0xB1, 0xF, 0xF, true);
+            const u32x2 w = {__builtin_amdgcn_perm(recv, keep, sel_first), __builtin_amdgcn_perm(recv, keep, sel_second)};
+            if constexpr (A32) __builtin_amdgcn_raw_buffer_store_b64(w, out_rs, out_voff, 4 * rel_tile, 0);
+            else *reinterpret_cast<u32x2 *>(reinterpret_cast<uint32_t *>(out16_ptr) + rel + 2 * (int)odd_lane) = w;
+        } else if (OUT16 == 2) {
             // the neighbouring row's lane (lane ^ 1) holds the other channel: two packed dwords cross by DPP quad_perm [1,0,3,2]
             const uint32_t other01 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine01, 0xB1, 0xF, 0xF, true);
             const uint32_t other23 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine23, 0xB1, 0xF, 0xF, true);
@@ -362,25 +443,34 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
             w[2] = (mine23 & 0xffffu) | (other23 << 16);
             w[3] = (mine23 >> 16) | (other23 & 0xffff0000u);
             if ((j & 1) == 0 && row_ok) {
-                uint32_t *dst = reinterpret_cast<uint32_t *>(out16_ptr) + rel;
-                if (INTERIOR || __builtin_expect(whole, 1)) {
-                    *reinterpret_cast<u32x4 *>(dst) = (u32x4){w[0], w[1], w[2], w[3]};
+                uint32_t *dst = A32 ? nullptr : reinterpret_cast<uint32_t *>(out16_ptr) + rel;
+                if (__builtin_expect(whole, 1)) {
+                    if constexpr (A32) __builtin_amdgcn_raw_buffer_store_b128((u32x4){w[0], w[1], w[2], w[3]}, out_rs, row_voff + 16u * q, 4 * rel_tile, 0);
+                    else *reinterpret_cast<u32x4 *>(dst) = (u32x4){w[0], w[1], w[2], w[3]};
                 } else {
                     asm volatile("; tile at an edge of the output, or unaligned rows" ::: "memory");
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (rel + r >= 0 && rel + r < (int32_t)a.out_count) dst[r] = w[r];
+                        if (rel + r >= 0 && rel + r < (int32_t)a.out_count) {
+                            if constexpr (A32) __builtin_amdgcn_raw_buffer_store_b32(w[r], out_rs, row_voff + 4u * (uint32_t)(rel + r), 0, 0);
+                            else dst[r] = w[r];
+                        }
                 }
             }
         } else if (row_ok) {
-            int16_t *dst = out16_ptr + rel;
+            int16_t *dst = A32 ? nullptr : out16_ptr + rel;
             if (INTERIOR || __builtin_expect(whole, 1)) {
-                *reinterpret_cast<u32x2 *>(dst) = (u32x2){mine01, mine23};
+                if constexpr (A32) __builtin_amdgcn_raw_buffer_store_b64((u32x2){mine01, mine23}, out_rs, out_voff, 2 * rel_tile, 0);
+                else *reinterpret_cast<u32x2 *>(dst) = (u32x2){mine01, mine23};
             } else {
                 asm volatile("; tile at an edge of the output, or unaligned rows" ::: "memory");
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (rel + r >= 0 && rel + r < (int32_t)a.out_count) dst[r] = (int16_t)((r < 2 ? mine01 : mine23) >> (16 * (r & 1)));
+                    if (rel + r >= 0 && rel + r < (int32_t)a.out_count) {
+                        const int16_t one = (int16_t)((r < 2 ? mine01 : mine23) >> (16 * (r & 1)));
+                        if constexpr (A32) __builtin_amdgcn_raw_buffer_store_b16(one, out_rs, row_voff + 2u * (uint32_t)(rel + r), 0, 0);
+                        else dst[r] = one;
+                    }
             }
         }
     };
@@ -401,14 +491,21 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
 #pragma unroll
         for (int wi = 0; wi < 3; ++wi) {
             const int step = 3 * K + wi;  // 0..11 within the body, t = 32 step
+            BFrag bpar1, bstep;  // the windows of this step's second half and of the next step's first
             // staging: chunk c = step / 2 covers rho in [64 c, 64 c + 64); its first eight rows are split and written in
             // the even step, the other eight in the odd step.  Loads run kAhead steps ahead of that.
             {
                 // the scheduler works on one step at a time: across a whole branch-free body it hoists loads and LDS reads
                 // far enough to spill
                 __builtin_amdgcn_sched_barrier(0);
-                stage_commit<ALIGNED, IN16, F16>(lds, lane, ring_index(64 * (step >> 1)), st, step & 1, step % kAhead);
-                stage_issue<ALIGNED, PACKED, INTERIOR, IN16>(a, lane, row0, n_body + 64 * ((step + kAhead) >> 1), st,
+                // The step's two windows were committed by earlier steps (they end at t - 48; this step writes from 64 (step / 2)
+                // on, half a ring away), but the compiler cannot tell an LDS read from the ring's writes apart: read behind
+                // stage_commit, a window waits for the whole split in front of it, and the matrix instructions that use it bunch
+                // up behind that.  Read first, both are in flight while the split runs.
+                if (INTERIOR && kReadEarly >= 1) bpar1 = read_b(32 * step - 80);
+                if (INTERIOR && kReadEarly >= 2) bstep = read_b(32 * step + 32 - 128);
+                stage_commit<ALIGNED, IN16, F16, A32>(lds, lane, ring_index(64 * (step >> 1)), st, step & 1, step % kAhead);
+                stage_issue<ALIGNED, PACKED, INTERIOR, IN16, A32>(a, lane, row0, n_body + 64 * ((step + kAhead) >> 1), st,
                                                              (step + kAhead) & 1, step % kAhead);
             }
 #pragma unroll
@@ -416,7 +513,7 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
                 const int t = 32 * step;
                 // next half-step's window
                 const int rho_next = par == 0 ? t - 80 : t + 32 - 128;
-                const BFrag bnext = read_b(rho_next);
+                const BFrag bnext = INTERIOR && kReadEarly > par ? (par == 0 ? bpar1 : bstep) : read_b(rho_next);
                 // products in an order that never puts two MFMAs on one accumulator back to back
 #pragma unroll
                 for (int prod = 0; prod < 6; ++prod) {
@@ -447,6 +544,7 @@ __global__ __launch_bounds__(64, F16 ? SK_FIR_F16_WAVES : 2) void k_fir_48k_16k_
 #pragma unroll
                 for (int d = 0; d < 4; ++d)
                     if (3 * d + wi < kWindows) mfmas += 2 * products_of(3 * d + wi, IN16, F16);
+                if (kReadEarly) __builtin_amdgcn_sched_group_barrier(0x100, kPlanes * kReadEarly, 0);  // the early LDS reads
 #pragma unroll
                 for (int g = 0; g < mfmas; ++g) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
@@ -499,6 +597,20 @@ static bool fir_bf16_supported(const FirArgs &a) {
     return a.afrag16 != nullptr && end_pair <= 0x7ffffff0ll / 96 && a.out_count <= 0x7fffff00u;
 }
 
+// 32-bit addressing (the A32 instantiations: frame-packed s16 rows, f16 planes): every byte offset a wave forms from the first row
+// of its group of sixteen -- row, time, lane -- and from the group's first output row stays below 2^31, bounded here from above.
+// Row maps and output columns send rows anywhere: those calls, and SK_FIR_ADDR64=1 (read once), keep the 64-bit pointers.
+static bool fir_addr32_fits(const FirArgs &a) {
+    static const bool forced64 = [] { const char *v = std::getenv("SK_FIR_ADDR64"); return v && v[0] == '1'; }();
+    if (forced64 || a.row_map || a.out_off || a.in_block != 1024 || a.in_ch < 1 || a.in_ch > 2) return false;
+    constexpr uint64_t kLimit = 1ull << 31;
+    if (a.in_group_stride >= kLimit || a.in_block_stride >= kLimit || a.out16_stride >= kLimit || a.out_stride >= kLimit) return false;
+    const uint64_t in_bytes = 2 * ((uint64_t)(16 / a.in_ch) * a.in_group_stride + 2048 + ((uint64_t)a.in_frames / 1024 + 1) * a.in_block_stride + 1024);
+    const uint64_t out_bytes = a.out16 ? 2 * (16 * (uint64_t)a.out16_stride + 2 * (uint64_t)a.out_count + 64)
+                                       : 4 * (16 * (uint64_t)a.out_stride + (uint64_t)a.out_count + 64);
+    return in_bytes < kLimit && out_bytes < kLimit;
+}
+
 hipError_t launch_fir_48k_16k(const FirArgs &a, hipStream_t s) {
     if (a.rows == 0 || a.out_count == 0) return hipSuccess;
     if (!fir_bf16_supported(a)) return hipErrorInvalidValue;
@@ -536,10 +648,14 @@ hipError_t launch_fir_48k_16k(const FirArgs &a, hipStream_t s) {
         if (!packed || !aligned) return hipErrorInvalidValue;
         // f16 planes (24 MFMAs per tile) unless SK_FIR_S16_BF16=1 asks for the bf16 form (36) of the same filter
         const bool use_f16 = f16_rows;
-#define SK_FIR_LAUNCH16(O16, F)                                                                                                    \
-    hipLaunchKernelGGL((k_fir_48k_16k_bf16<true, true, O16, true, F>), grid, block, 0, s, a, (int32_t)first_pair, (int32_t)end_pair, \
+#define SK_FIR_LAUNCH16(O16, F, ...)                                                                                               \
+    hipLaunchKernelGGL((k_fir_48k_16k_bf16<true, true, O16, true, F, ##__VA_ARGS__>), grid, block, 0, s, a, (int32_t)first_pair, (int32_t)end_pair, \
                        (int32_t)pps, n_segs, out_vec)
-        if (use_f16 && a.afrag_f16) {
+        if (use_f16 && a.afrag_f16 && fir_addr32_fits(a)) {
+            if (!a.out16) SK_FIR_LAUNCH16(0, true, true);
+            else if (a.out16_ch == 2) SK_FIR_LAUNCH16(2, true, true);
+            else SK_FIR_LAUNCH16(1, true, true);
+        } else if (use_f16 && a.afrag_f16) {
             if (!a.out16) SK_FIR_LAUNCH16(0, true);
             else if (a.out16_ch == 2) SK_FIR_LAUNCH16(2, true);
             else SK_FIR_LAUNCH16(1, true);

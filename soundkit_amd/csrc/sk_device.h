@@ -187,14 +187,26 @@ __device__ __forceinline__ uint32_t dev_pack2_s16_scaled(float lo, float hi) {
 typedef uint32_t sk_u32x4 __attribute__((ext_vector_type(4)));
 typedef float sk_f32x4 __attribute__((ext_vector_type(4)));
 // two s16 samples in one dword (the earlier one low) -> their two f16 planes: p1 = the sample rounded TOWARD ZERO to f16 (eleven
-// significand bits; no overflow at 32767), p2 = the rest (same sign, below 32: exact).  Three and a half vector instructions per sample.
+// significand bits; no overflow at 32767), p2 = the rest (same sign, below 32: exact).
+#ifndef SK_SPLIT_MIX
+#define SK_SPLIT_MIX 1  // 0: the subtraction in f32 and a second conversion (the form every result was first checked with)
+#endif
 __device__ __forceinline__ void dev_split_pair16_f16(uint32_t u, uint32_t &p1, uint32_t &p2) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2 f = {(float)(short)(u & 0xffffu), (float)((int)u >> 16)};
     const auto a = __builtin_amdgcn_cvt_pkrtz(f.x, f.y);
-    const f32x2 r = f - (f32x2){(float)a[0], (float)a[1]};  // exact; one packed subtraction
     p1 = __builtin_bit_cast(uint32_t, a);
+#if SK_SPLIT_MIX
+    // the rest as one mixed-precision fused multiply-add per sample: f32(p1's f16 half) * -1 + f, written as the f16 half of p2.
+    // The difference is an integer below 32 -- exact in f16 under any rounding mode, +0 where it vanishes -- so the planes are the
+    // bits of the form below at 2.5 instead of 4 instructions per sample.  Plain C does not get there ((_Float16)fmaf((float)a0,
+    // -1.0f, f) compiles to the convert and subtract below), hence the two instructions by name.
+    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(p2) : "v"(p1), "v"(f.x));
+    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(p2) : "v"(p1), "v"(f.y));
+#else
+    const f32x2 r = f - (f32x2){(float)a[0], (float)a[1]};  // exact; one packed subtraction
     p2 = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(r.x, r.y));
+#endif
 }
 __device__ __forceinline__ sk_f32x4 dev_mfma_f16(const sk_u32x4 &av, const sk_u32x4 &bv, const sk_f32x4 &c) {
 #if SK_MFMA_K16  // experiment (-DSK_MFMA_K16=1): the K = 16 form older parts have, twice -- a lane's eight k values as two groups of four,
