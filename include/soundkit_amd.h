@@ -1049,7 +1049,9 @@ const char *sk_raw_pcm_framer_last_error(const sk_raw_pcm_framer *);
  * sk_aiff_decode or sk_tick_run_aiff turn into the little-endian PCM of the output contract.  *piece_offset counts sound bytes. */
 enum sk_aiff_encoding {
     SK_AIFF_U8 = 0, SK_AIFF_S8, SK_AIFF_S16BE, SK_AIFF_S16LE, SK_AIFF_S24BE, SK_AIFF_S32BE, SK_AIFF_S32LE, SK_AIFF_F32BE, SK_AIFF_F64BE,
-    SK_AIFF_ULAW, SK_AIFF_ALAW, SK_AIFF_IMA4
+    SK_AIFF_ULAW, SK_AIFF_ALAW, SK_AIFF_IMA4,
+    SK_AIFF_F64LE = 13 /* 64-bit float, little-endian: no AIFF-C file holds it; container PCM does (QuickTime `fl64` with enda = 1, CAF
+                          lpcm).  12 stays unassigned: it has always been refused as unknown, and still is */
 };
 typedef struct sk_aiff_info { /* zeros (but buffered_bytes) until COMM has been read */
     uint32_t sample_rate;
@@ -1377,17 +1379,69 @@ int sk_caf_alac_index_info(const sk_caf_alac_index *, sk_caf_alac_info *info);
 /* the packets' absolute offsets and sizes; cap < n_packets: SK_ERR_CAPACITY */
 int sk_caf_alac_index_packets(const sk_caf_alac_index *, uint64_t *offsets, uint32_t *sizes, uint32_t cap);
 
+/* ---- CAF, `lpcm` and `alac` (host, csrc/caf_stream.h) -----------------------------------------------------------------------------------
+ * CafAudioIndex (soundkit-audio-demux/src/caf.rs) with its checks and texts: the chunk walk of a whole file (`caff`, version 1, flags 0;
+ * desc, kuki, pakt, chan and data at most once; -1 as the size of the data chunk alone; budgets of 32 bytes, 1 MiB, 64 MiB and 1 MiB on
+ * desc, kuki, pakt and chan), the description, the packet table, and the packets of the data chunk.  sk_caf_alac_index_* above stays
+ * as it was.  A refusal is SK_CAF_ERR_STREAM with a text in `error` (NUL-terminated, cut to error_cap; may be NULL).
+ * `lpcm`: flag bit 0 is float, bit 1 little-endian; `CAF LPCM bits per channel is zero`, `CAF float PCM must use 32-bit or 64-bit
+ * samples`, `CAF LPCM requires a constant packet size`, `CAF LPCM packet geometry is not frame-aligned`, `CAF LPCM bytes per frame cannot
+ * hold its channels`; any other format but `alac`: `unsupported CAF audio format NAME`.  Two things are this library's own: a frame padded
+ * beyond channels x ceil(bits / 8) bytes is refused (`CAF LPCM frames padded beyond their channels are unsupported`; the reference marks
+ * it unpacked and then reads it as packed), and an `lpcm` file's packets -- one frame each in common files -- are handed out as runs of
+ * whole packets of at most 4096 frames and 1 MiB, so the packet budget of 8 000 000 counts runs.  An `alac` file's packets are the file's. */
+enum sk_caf_status { SK_CAF_ERR_STREAM = -1301 };
+enum sk_caf_codec { SK_CAF_CODEC_ALAC = 1, SK_CAF_CODEC_PCM = 2 };
+typedef struct sk_caf_info {
+    uint32_t codec;             /* sk_caf_codec */
+    char format_id[4];          /* the description's mFormatID (no NUL) */
+    uint32_t sample_rate, channels;
+    uint32_t bits_per_sample;   /* 0: the description states none (alac may) */
+    uint32_t format_flags;
+    uint32_t big_endian, is_float, bytes_per_frame; /* lpcm; zeros for alac */
+    uint32_t frames_per_packet; /* the description's: of a packet of the file, not of a run */
+    uint32_t priming_frames, remainder_frames;
+    uint32_t n_packets;         /* alac: the file's packets; lpcm: runs */
+    uint32_t cookie_len;        /* bytes of the kuki chunk */
+    uint64_t valid_frames;
+} sk_caf_info;
+typedef struct sk_caf_index sk_caf_index;
+int sk_caf_index_from_file(const uint8_t *file, size_t len, sk_caf_index **out, char *error, size_t error_cap);
+/* CafAudioIndex::from_metadata: the chunks' payloads as a caller with a seekable source read them; pakt NULL: the file holds none;
+ * data_offset points at the data chunk's four-byte edit count */
+int sk_caf_index_create(const uint8_t *desc, size_t desc_len, const uint8_t *cookie, size_t cookie_len, const uint8_t *pakt, size_t pakt_len,
+                        uint64_t data_offset, uint64_t data_size, sk_caf_index **out, char *error, size_t error_cap);
+void sk_caf_index_destroy(sk_caf_index *);
+/* cookie may be NULL when cookie_cap is 0; cookie_cap < cookie_len: SK_ERR_CAPACITY (info is filled) */
+int sk_caf_index_info(const sk_caf_index *, sk_caf_info *info, uint8_t *cookie, size_t cookie_cap);
+/* per packet (or run): absolute offset, size, frames and the first frame's place on the file's timeline (what pcm_packet_trim counts
+ * from); any array may be NULL; cap < n_packets: SK_ERR_CAPACITY */
+int sk_caf_index_packets(const sk_caf_index *, uint64_t *offsets, uint32_t *sizes, uint32_t *frames, uint64_t *start_frames, uint32_t cap);
+
 /* ---- MP4 / M4A / fragmented MP4, audio only (host, csrc/mp4_stream.h) -------------------------------------------------------------
- * The first audio track whose sample entry is `mp4a` (AAC) or `alac` is chosen; video tracks and unknown boxes are stepped over by
- * size without being buffered.  Read: 32- and 64-bit box sizes, mvhd, tkhd, edts/elst (the first media edit), mdhd, hdlr, stsd with
+ * The first audio track whose sample entry is `mp4a` (AAC), `alac`, `fLaC` or a PCM entry (`sowt twos in24 in32 fl32 fl64 lpcm`) is
+ * chosen; video tracks and unknown boxes are stepped over by size without being buffered.  Read: 32- and 64-bit box sizes, mvhd, tkhd, edts/elst (the first media edit), mdhd, hdlr, stsd with
  * esds (descriptor tags 3, 4, 5, lengths of 1 to 4 bytes) or the `alac` child, stts, stsc, stsz (both forms), stco / co64; mvex/trex,
  * moof/traf with tfhd (base-data-offset, default-base-is-moof, default duration and size), tfdt and trun under any flag combination,
  * several traf per moof.  The layout is fragmented when moov holds mvex or its sample tables are empty.  Budgets: 4 MiB a call, 64 MiB
  * of moov or moof payload (refused from the box header), 128 MiB a sample, 8 000 000 samples a track or fragment.
  * A refusal is SK_MP4_ERR_STREAM with a text (sk_mp4_demuxer_last_error, or `error`: NUL-terminated, cut to error_cap; may be NULL).
- * Not read: ctts, stss, edits behind the first media edit, `fLaC` and PCM sample entries, version-two sound descriptions, video. */
+ * Sound descriptions of version 0, 1 and 2 are read (`unsupported QuickTime audio sample-entry version N` otherwise); `enda` and `dfLa`
+ * are looked for in the entry and inside `wave` / `sinf` / `schi`.  `sowt` is little-endian and `twos` big-endian at the declared width;
+ * `in24 in32 fl32 fl64` are 24, 32, 32 and 64 bits, big-endian unless `enda` is 1 (`invalid QuickTime enda flag N` for any value but 0
+ * and 1); `lpcm` needs version two (`QuickTime lpcm requires a version-two sample entry`) and takes its flags: bit 0 float, bit 1
+ * big-endian; `non-interleaved QuickTime LPCM is unsupported` (bit 5), and for an integer entry `unsigned QuickTime LPCM is unsupported`
+ * (bit 2 clear), `unpacked QuickTime LPCM is unsupported` (bit 3 clear), `aligned-high QuickTime LPCM is unsupported` (bit 4).
+ * A PCM track's samples are single frames; what the index and the demuxer hand out are the same runs of frames: of a constant stsz with
+ * one stts entry, per chunk at most 4096 frames and 1 MiB a run (no record per frame is made); otherwise neighbours merge while they
+ * are contiguous in bytes and in time, up to the same two limits.  A `fLaC` track's codec-private data is `fLaC` followed by the
+ * metadata blocks: from data that already begins so, a bare 34-byte STREAMINFO, or a `dfLa` payload (`MP4 dfLa decoder configuration
+ * is truncated`, `MP4 dfLa has no leading FLAC STREAMINFO block`, `MP4 dfLa has an invalid FLAC STREAMINFO block`: refused where the
+ * entry is read, so the index and the demuxer's config event fail alike and such a file gives no sample table).
+ * Not read: ctts, stss, edits behind the first media edit, the `ulaw` / `alaw` / `ima4` / `raw ` entries, `chan`, video; `fLaC` and PCM
+ * tracks of a fragmented file are described but not decoded by anything above this layer. */
 enum sk_mp4_status { SK_MP4_ERR_STREAM = -901 };
-enum sk_mp4_codec { SK_MP4_CODEC_AAC = 1, SK_MP4_CODEC_ALAC = 2 };
+enum sk_mp4_codec { SK_MP4_CODEC_AAC = 1, SK_MP4_CODEC_ALAC = 2, SK_MP4_CODEC_FLAC = 3, SK_MP4_CODEC_PCM = 4 };
 typedef struct sk_mp4_track_info {
     uint32_t codec;        /* sk_mp4_codec; 0: no config yet (sk_mp4_demuxer_config before moov has arrived) */
     uint32_t sample_rate;  /* AAC: the AudioSpecificConfig's where its two-byte form states one, else the sample entry's */
@@ -1398,9 +1452,19 @@ typedef struct sk_mp4_track_info {
     uint32_t sample_count; /* of the sample table; 0 in a fragmented file */
     uint32_t fragmented;
     uint32_t has_edit;     /* the first media edit of edts/elst, in the track's timescale (the duration rescaled from the movie's) */
-    uint32_t private_len;  /* bytes of codec-private data: the AudioSpecificConfig, or the `alac` child's payload (sk_alac_parse_cookie takes it) */
+    uint32_t private_len;  /* bytes of codec-private data: the AudioSpecificConfig, the `alac` child's payload (sk_alac_parse_cookie takes
+                              it), or for FLAC `fLaC` + the metadata blocks (what the FLAC decoder is fed before the packets); 0 for PCM */
     uint64_t edit_presentation_start, edit_media_start, edit_duration;
 } sk_mp4_track_info;
+/* what a SK_MP4_CODEC_PCM track's bytes are: signed integers or IEEE floats, packed, interleaved.  All zero for any other codec. */
+typedef struct sk_mp4_pcm_info {
+    char codec_id[4];           /* the sample entry's name: `sowt`, `twos`, `in24`, `in32`, `fl32`, `fl64`, `lpcm` (no NUL) */
+    uint32_t big_endian;        /* 1: big-endian, 0: little-endian */
+    uint32_t is_float;
+    uint32_t bits_per_sample;   /* = sk_mp4_track_info.bits_per_sample; 0: the entry states none */
+    uint32_t bytes_per_frame;   /* the entry's (version one and two), else channels x ceil(bits / 8); 0: unknown */
+    uint32_t frames_per_packet; /* the entry's: 1 for version zero; 0: not stated */
+} sk_mp4_pcm_info;
 
 /* The streaming demuxer: moov must come before mdat -- `MP4 mdat appears before moov; use the seekable MP4 packet API` otherwise, from
  * the mdat header alone.  Events: one config (once moov has been parsed), then the track's samples in file order as their bytes arrive.
@@ -1414,6 +1478,8 @@ int sk_mp4_demuxer_finish(sk_mp4_demuxer *);
 const char *sk_mp4_demuxer_last_error(const sk_mp4_demuxer *);
 /* the config event; codec_private may be NULL when private_cap is 0; private_cap < private_len: SK_ERR_CAPACITY (info is filled) */
 int sk_mp4_demuxer_config(const sk_mp4_demuxer *, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap);
+/* the PCM description of the config event (zeros before moov has arrived and for a track that is not PCM) */
+int sk_mp4_demuxer_pcm_info(const sk_mp4_demuxer *, sk_mp4_pcm_info *info);
 /* packets waiting, the first one's size and the bytes the demuxer holds that are no packet yet */
 int sk_mp4_demuxer_pending(const sk_mp4_demuxer *, uint32_t *n_packets, size_t *front_bytes, size_t *buffered_bytes);
 /* takes the first waiting packet: its raw bytes, decode time and duration in the track's timescale.  None waiting: SK_ERR_BAD_STREAM;
@@ -1429,12 +1495,15 @@ typedef struct sk_mp4_index sk_mp4_index;
 int sk_mp4_index_from_file(const uint8_t *file, size_t len, sk_mp4_index **out, char *error, size_t error_cap);
 void sk_mp4_index_destroy(sk_mp4_index *);
 int sk_mp4_index_info(const sk_mp4_index *, sk_mp4_track_info *info, uint8_t *codec_private, size_t private_cap);
+int sk_mp4_index_pcm_info(const sk_mp4_index *, sk_mp4_pcm_info *info);
 /* per sample: absolute offset, size, duration and decode time; any array may be NULL; cap < sample_count: SK_ERR_CAPACITY */
 int sk_mp4_index_samples(const sk_mp4_index *, uint64_t *offsets, uint32_t *sizes, uint32_t *durations, uint64_t *start_times, uint32_t cap);
 /* resolve_pcm_packet_trim: the frames of sample `sample`'s decoded packet (decoded_frames at decoded_rate) that the edit keeps.  The
  * start rounds up, the end down, both are clamped to decoded_frames; nothing kept: (decoded_frames, 0); no edit list: (0, decoded_frames) */
 int sk_mp4_index_trim(const sk_mp4_index *, uint32_t sample, uint32_t decoded_frames, uint32_t decoded_rate, uint32_t *first, uint32_t *count,
                       char *error, size_t error_cap);
+/* normalize_mp4_flac_decoder_configuration on its own: *out_len is what the result needs; out_cap smaller: SK_ERR_CAPACITY */
+int sk_mp4_flac_config(const uint8_t *data, size_t len, uint8_t *out, size_t out_cap, size_t *out_len, char *error, size_t error_cap);
 /* create_adts_header: the seven bytes in front of a raw AAC sample (profile from the config's object type, no CRC) */
 int sk_mp4_adts_header(const uint8_t *asc, size_t asc_len, uint32_t sample_rate, uint32_t channels, size_t raw_len, uint8_t out[7]);
 

@@ -11,3 +11,9 @@ from .engine import (EIGHT_SHORT, KBD, LONG_START, LONG_STOP, ONLY_LONG, SINE, E
                      default_engine, descs_from_arrays, make_descs)
 
 __version__ = "0.1.0"
+
+
+def decode_audio_file(data, options=None, scheduler=None, engine=None):
+    """a complete audio or video file -> media_file.DecodedAudioFile (soundkit-decoder's decode_audio_file, lib.rs:171-255)"""
+    from .media_file import decode_audio_file as run
+    return run(data, options, scheduler, engine)

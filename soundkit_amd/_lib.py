@@ -29,6 +29,7 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -1001: "WebmStreamRejected",
              -1101: "TsStreamRejected",
              -1201: "WavBadBlock",
+             -1301: "CafStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -226,6 +227,18 @@ class Mp4TrackInfo(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("codec", "sample_rate", "channels", "bits_per_sample", "track_id", "timescale", "sample_count",
                                           "fragmented", "has_edit", "private_len")] + [
         (n, C.c_uint64) for n in ("edit_presentation_start", "edit_media_start", "edit_duration")]
+
+
+class Mp4PcmInfo(C.Structure):
+    """sk_mp4_pcm_info"""
+    _fields_ = [("codec_id", C.c_char * 4)] + [(n, C.c_uint32) for n in ("big_endian", "is_float", "bits_per_sample", "bytes_per_frame", "frames_per_packet")]
+
+
+class CafInfo(C.Structure):
+    """sk_caf_info"""
+    _fields_ = [("codec", C.c_uint32), ("format_id", C.c_char * 4)] + [(n, C.c_uint32) for n in (
+        "sample_rate", "channels", "bits_per_sample", "format_flags", "big_endian", "is_float", "bytes_per_frame", "frames_per_packet",
+        "priming_frames", "remainder_frames", "n_packets", "cookie_len")] + [("valid_frames", C.c_uint64)]
 
 
 class WebmTrackInfo(C.Structure):
@@ -644,20 +657,28 @@ _sig = {
     "sk_caf_alac_index_destroy": (None, [_vp]),
     "sk_caf_alac_index_info": (_i, [_vp, C.POINTER(CafAlacInfo)]),
     "sk_caf_alac_index_packets": (_i, [_vp, _vp, _vp, _u32]),
+    "sk_caf_index_from_file": (_i, [_vp, _sz, C.POINTER(_vp), _vp, _sz]),
+    "sk_caf_index_create": (_i, [_vp, _sz, _vp, _sz, _vp, _sz, C.c_uint64, C.c_uint64, C.POINTER(_vp), _vp, _sz]),
+    "sk_caf_index_destroy": (None, [_vp]),
+    "sk_caf_index_info": (_i, [_vp, C.POINTER(CafInfo), _vp, _sz]),
+    "sk_caf_index_packets": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
     "sk_mp4_demuxer_create": (_i, [C.POINTER(_vp)]),
     "sk_mp4_demuxer_destroy": (None, [_vp]),
     "sk_mp4_demuxer_add": (_i, [_vp, _vp, _sz]),
     "sk_mp4_demuxer_finish": (_i, [_vp]),
     "sk_mp4_demuxer_last_error": (C.c_char_p, [_vp]),
     "sk_mp4_demuxer_config": (_i, [_vp, C.POINTER(Mp4TrackInfo), _vp, _sz]),
+    "sk_mp4_demuxer_pcm_info": (_i, [_vp, C.POINTER(Mp4PcmInfo)]),
     "sk_mp4_demuxer_pending": (_i, [_vp, C.POINTER(_u32), C.POINTER(_sz), C.POINTER(_sz)]),
     "sk_mp4_demuxer_take": (_i, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64), C.POINTER(_u32)]),
     "sk_mp4_demuxer_trim": (_i, [_vp, C.c_uint64, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
     "sk_mp4_index_from_file": (_i, [_vp, _sz, C.POINTER(_vp), _vp, _sz]),
     "sk_mp4_index_destroy": (None, [_vp]),
     "sk_mp4_index_info": (_i, [_vp, C.POINTER(Mp4TrackInfo), _vp, _sz]),
+    "sk_mp4_index_pcm_info": (_i, [_vp, C.POINTER(Mp4PcmInfo)]),
     "sk_mp4_index_samples": (_i, [_vp, _vp, _vp, _vp, _vp, _u32]),
     "sk_mp4_index_trim": (_i, [_vp, _u32, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32), _vp, _sz]),
+    "sk_mp4_flac_config": (_i, [_vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _sz]),
     "sk_mp4_adts_header": (_i, [_vp, _sz, _u32, _u32, _sz, _vp]),
     "sk_webm_demuxer_create": (_i, [C.POINTER(_vp)]),
     "sk_webm_demuxer_destroy": (None, [_vp]),

@@ -206,19 +206,24 @@ def decode_caf(data, options=None, scheduler=None, engine=None):
     return index, output_stage(pieces, index.sample_rate, index.channels, index.bit_depth, options, scheduler)
 
 
-def output_stage(pieces, sample_rate, channels, bit_depth, options=None, scheduler=None):
-    """[PCM bytes, signed little-endian] -> [AudioData] under the output options, the resampler flushed at the end (what decode_caf and
-    mp4.decode_file end in).  Without options that change anything the AudioData are the pieces themselves; otherwise they are what the
-    scheduler's raw PCM stream of that format makes of them (the same conversion stage every PCM-family input ends in)."""
+def output_stage(pieces, sample_rate, channels, bit_depth, options=None, scheduler=None, is_float=False, big_endian=False):
+    """[PCM bytes: signed little-endian, or as is_float / big_endian say] -> [AudioData] under the output options, the resampler flushed
+    at the end (what decode_caf, mp4.decode_file and caf.decode_file end in).  Without options that change anything the AudioData are the
+    pieces themselves, in the byte order they came in; otherwise they are what the scheduler's raw PCM stream of that format makes of
+    them (the same conversion stage every PCM-family input ends in)."""
     from .audio_types import AudioData, Endianness, EncodingFlag
-    from .engine import FMT_S16LE, FMT_S24LE, FMT_S32LE
+    from .engine import FMT_F32BE, FMT_F32LE, FMT_S16BE, FMT_S16LE, FMT_S24BE, FMT_S24LE, FMT_S32BE, FMT_S32LE
     from .pipeline import DecodeError, DecodeOptions, RawPcmFormat, default_scheduler
     o = options or DecodeOptions()
     same = ((o.output_sample_rate or sample_rate) == sample_rate and (o.output_channels or channels) == channels and
             (o.output_bits_per_sample or bit_depth) == bit_depth)
     if same:
-        return [AudioData(bit_depth, channels, sample_rate, p, EncodingFlag.PCMSigned, Endianness.LittleEndian) for p in pieces]
-    fmt = {16: FMT_S16LE, 24: FMT_S24LE, 32: FMT_S32LE}[bit_depth]
+        return [AudioData(bit_depth, channels, sample_rate, p, EncodingFlag.PCMFloat if is_float else EncodingFlag.PCMSigned,
+                          Endianness.BigEndian if big_endian else Endianness.LittleEndian) for p in pieces]
+    if is_float:
+        fmt = {32: FMT_F32BE if big_endian else FMT_F32LE}[bit_depth]
+    else:
+        fmt = {16: (FMT_S16LE, FMT_S16BE), 24: (FMT_S24LE, FMT_S24BE), 32: (FMT_S32LE, FMT_S32BE)}[bit_depth][1 if big_endian else 0]
     h = (scheduler or default_scheduler()).spawn_raw_pcm(RawPcmFormat(sample_rate, channels, fmt), o)
     out = []
 

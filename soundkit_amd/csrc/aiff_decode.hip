@@ -3,7 +3,7 @@
 // every stream of a tick.  Source-encoded sample groups in, little-endian PCM of the output contract (lib.rs:41-54) out:
 //
 //   k_aiff_elem   every encoding but IMA4: u8 / s8 widened to s16, 2- / 3- / 4-byte big-endian samples reversed (f32be as an integer
-//                 swap: NaN payloads and subnormals survive), the little-endian forms copied, f64be rounded to f32 in integer
+//                 swap: NaN payloads and subnormals survive), the little-endian forms copied, f64be and f64le rounded to f32 in integer
 //                 arithmetic (nearest even, subnormal results kept, overflow to infinity), mu-law and A-law expanded to s16.
 //                 pcm_tick.hip's conventions: a job table, grid = (slices of kPcmSliceSamples samples, jobs), units at 16-byte
 //                 aligned offsets so a lane moves its 16 samples with 16-byte loads and stores; a unit's last incomplete 16 go
@@ -26,13 +26,13 @@ namespace sk {
 namespace {
 
 enum : uint32_t {  // enum sk_aiff_encoding
-    kU8, kS8, kS16BE, kS16LE, kS24BE, kS32BE, kS32LE, kF32BE, kF64BE, kUlaw, kAlaw, kIma4
+    kU8, kS8, kS16BE, kS16LE, kS24BE, kS32BE, kS32LE, kF32BE, kF64BE, kUlaw, kAlaw, kIma4, kUnassigned12, kF64LE  // kF64LE = 13: appended, the range tests below rest on the order
 };
 
 __device__ __forceinline__ int enc_in_bytes(uint32_t enc) {
-    return enc <= kS8 || enc == kUlaw || enc == kAlaw ? 1 : (enc <= kS16LE ? 2 : (enc == kS24BE ? 3 : (enc == kF64BE ? 8 : 4)));
+    return enc <= kS8 || enc == kUlaw || enc == kAlaw ? 1 : (enc <= kS16LE ? 2 : (enc == kS24BE ? 3 : (enc == kF64BE || enc == kF64LE ? 8 : 4)));
 }
-__device__ __forceinline__ int enc_out_bytes(uint32_t enc) { return enc == kS24BE ? 3 : (enc >= kS32BE && enc <= kF64BE ? 4 : 2); }
+__device__ __forceinline__ int enc_out_bytes(uint32_t enc) { return enc == kS24BE ? 3 : ((enc >= kS32BE && enc <= kF64BE) || enc == kF64LE ? 4 : 2); }
 
 // ITU-T G.711 expansion to 16-bit linear
 __device__ __forceinline__ uint32_t ulaw_to_s16(uint32_t code) {
@@ -126,6 +126,17 @@ __global__ __launch_bounds__(256) void k_aiff_elem(const AiffElemJob *jobs, uint
         }
         return;
     }
+    if (s0 + 16 <= total && enc == kF64LE) {  // f64le: as f64be below, the dwords as they lie (the low one first)
+        const uint4 *p = reinterpret_cast<const uint4 *>(job.src + (size_t)s0 * 8);
+        uint4 *d = reinterpret_cast<uint4 *>(job.dst + (size_t)s0 * 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint4 q0 = p[2 * k], q1 = p[2 * k + 1];
+            d[k] = make_uint4(f64_bits_to_f32_bits(q0.y, q0.x), f64_bits_to_f32_bits(q0.w, q0.z), f64_bits_to_f32_bits(q1.y, q1.x),
+                              f64_bits_to_f32_bits(q1.w, q1.z));
+        }
+        return;
+    }
     if (s0 + 16 <= total && ib == 8) {  // f64be: eight 16-byte loads, four 16-byte stores
         const uint4 *p = reinterpret_cast<const uint4 *>(job.src + (size_t)s0 * 8);
         uint4 *d = reinterpret_cast<uint4 *>(job.dst + (size_t)s0 * 4);
@@ -162,7 +173,11 @@ __global__ __launch_bounds__(256) void k_aiff_elem(const AiffElemJob *jobs, uint
     for (uint32_t s = s0; s < total; ++s) {
         const uint8_t *p = job.src + (size_t)s * ib;
         uint32_t v;
-        if (ib == 8) {
+        if (enc == kF64LE) {
+            const uint32_t lo = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+            const uint32_t hi = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
+            v = f64_bits_to_f32_bits(hi, lo);
+        } else if (ib == 8) {
             const uint32_t hi = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
             const uint32_t lo = ((uint32_t)p[4] << 24) | ((uint32_t)p[5] << 16) | ((uint32_t)p[6] << 8) | p[7];
             v = f64_bits_to_f32_bits(hi, lo);

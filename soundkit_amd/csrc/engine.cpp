@@ -610,6 +610,7 @@ const char *sk_strerror(int status) try {
     case SK_VORBIS_SHORT: return "Vorbis packet ends inside its first bits";
     case SK_VORBIS_ERR_STREAM: return "Ogg / Vorbis stream rejected";
     case SK_MP4_ERR_STREAM: return "MP4 stream rejected";
+    case SK_CAF_ERR_STREAM: return "CAF stream rejected";
     case SK_WEBM_ERR_STREAM: return "WebM stream rejected";
     case SK_TS_ERR_STREAM: return "MPEG-TS stream rejected";
     case SK_WAV_BAD_BLOCK: return "WAV ADPCM block header is invalid";
@@ -5103,7 +5104,7 @@ int aiff_tick_derive(const sk_aiff_tick_stream *as, uint32_t n_streams, const sk
     uint64_t at = 0, cursor = 0;
     for (uint32_t i = 0; i < n_streams; ++i) {
         const sk_aiff_tick_stream &a = as[i];
-        if (a.encoding >= sk_pcm::kAiffEncodings || a.channels == 0 || a.channels > sk_pcm::kMaxAiffChannels) return SK_ERR_INVALID_ARG;
+        if (!sk_pcm::aiff_encoding_known(a.encoding) || a.channels == 0 || a.channels > sk_pcm::kMaxAiffChannels) return SK_ERR_INVALID_ARG;
         if (a.encoding == SK_AIFF_IMA4 && (a.channels > 2 || a.ima_state[0].step_index > 88 || a.ima_state[1].step_index > 88)) return SK_ERR_INVALID_ARG;
         const uint32_t bits = sk_pcm::aiff_contract_bits(a.encoding);
         sk_pcm_tick_stream &t = d.ts[i];
@@ -5433,7 +5434,7 @@ int sk_tick_run_aiff(sk_engine *e, sk_aiff_tick_stream *as, uint32_t n_streams, 
 // one stream's bytes, one call: a table of one job in front of the same kernels
 static int aiff_decode_one(sk_engine *e, int encoding, uint32_t channels, const uint8_t *bytes, bool on_device, size_t len, uint8_t *out, size_t out_cap,
                            size_t *out_len, sk_aiff_ima_state *state) {
-    if (!e || !out_len || encoding < 0 || encoding >= sk_pcm::kAiffEncodings || channels == 0 || channels > sk_pcm::kMaxAiffChannels) return SK_ERR_INVALID_ARG;
+    if (!e || !out_len || !sk_pcm::aiff_encoding_known(encoding) || channels == 0 || channels > sk_pcm::kMaxAiffChannels) return SK_ERR_INVALID_ARG;
     *out_len = 0;
     const bool ima = encoding == SK_AIFF_IMA4;
     if (ima && (channels > 2 || !state || state[0].step_index > 88 || state[1].step_index > 88)) return SK_ERR_INVALID_ARG;

@@ -1,5 +1,5 @@
 // mp4_stream.h -- ISO base media (MP4 / M4A / fragmented MP4) on the host, audio only: the box header, the `moov` parser for the first
-// audio track whose codec is built here (`mp4a` -> AAC, `alac`), the streaming demuxer in its two layouts (soundkit-audio-demux/src/lib.rs:
+// audio track whose codec is built here (`mp4a` -> AAC, `alac`, `fLaC`, the PCM entries), the streaming demuxer in its two layouts (soundkit-audio-demux/src/lib.rs:
 // RegularMp4AudioDemuxer 1400-1678, the fragment walk of Mp4MediaDemuxer 1846-2299), the whole-file sample index (Mp4MediaIndex,
 // 925-1080), the edit-list trim of a decoded packet (resolve_pcm_packet_trim, 117-174) and the 7-byte ADTS header an AAC sample is
 // wrapped in (create_adts_header, 4102-4120).  Serial byte parsing per stream, no per-sample work, no HIP; header-only.  The input is
@@ -9,12 +9,16 @@
 // a `moov` that holds `mvex` is fragmented, any other `moov` regular) and then builds one of two demuxers; here the same rule is applied
 // at the first `moov` or `moof` the top-level walk meets, so nothing is collected for detection and an `mdat` in front of `moov` is
 // refused from its 8-byte header.  Not read: `ctts` and `stss` (audio samples present in decode order and are all sync samples), every
-// edit but the first media edit, `flac` and PCM sample entries, version-two sound descriptions, video.  A QuickTime `wave` atom is looked
-// into for `esds` / `alac` as the reference does, but no fixture holds one: that path is untested and not claimed.
+// edit but the first media edit, the `ulaw` / `alaw` / `ima4` / `raw ` QuickTime entries, `chan` layouts, video.  `fLaC` and the PCM entries
+// (`sowt twos in24 in32 fl32 fl64 lpcm`, sound descriptions of version 0, 1 and 2) are decoded out of regular files only: a fragmented file with
+// such a track is described, and decode_file refuses it.  A PCM track's samples leave as runs of frames (build_constant_pcm_runs,
+// coalesce_pcm_runs), the same runs from the index and from the demuxer.  A QuickTime `wave` atom is looked into for `esds` / `alac` /
+// `enda` / `dfLa` as the reference does.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <deque>
 #include <string>
@@ -26,7 +30,8 @@ constexpr uint64_t kMaxMetadataBytes = 64ull * 1024 * 1024;  // MAX_MP4_METADATA
 constexpr uint32_t kMaxPacketBytes = 128u * 1024 * 1024;     // MAX_MEDIA_PACKET_BYTES
 constexpr size_t kMaxUnits = 8000000;                        // MAX_MP4_MATERIALIZED_ACCESS_UNITS
 constexpr size_t kMaxInputChunkBytes = 4u * 1024 * 1024;     // MAX_CONTAINER_INPUT_CHUNK_BYTES
-constexpr uint8_t kCodecAac = 1, kCodecAlac = 2;
+constexpr uint8_t kCodecAac = 1, kCodecAlac = 2, kCodecFlac = 3, kCodecPcm = 4;
+constexpr uint32_t kMaxPcmRunFrames = 4096, kMaxPcmRunBytes = 1024 * 1024;  // MAX_PCM_PACKET_FRAMES, MAX_PCM_PACKET_BYTES
 
 inline uint32_t be16(const uint8_t *p) { return (uint32_t)p[0] << 8 | p[1]; }
 inline uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
@@ -83,10 +88,19 @@ struct Sample {
     uint32_t size = 0, duration = 0;
 };
 
+// a PCM sample entry (`sowt twos in24 in32 fl32 fl64 lpcm`): signed (or float), packed, interleaved samples of Track::bits bits
+struct PcmEntry {
+    char name[4] = {0, 0, 0, 0};  // the entry's name
+    bool big_endian = false, is_float = false;
+    uint32_t bytes_per_frame = 0, frames_per_packet = 0;  // 0: not stated
+};
+
 struct Track {
-    uint8_t codec = 0;  // kCodecAac / kCodecAlac
+    uint8_t codec = 0;  // kCodecAac / kCodecAlac / kCodecFlac / kCodecPcm
+    PcmEntry pcm;       // kCodecPcm
     uint32_t id = 0, timescale = 0, sample_rate = 0, channels = 0, bits = 0;
-    std::vector<uint8_t> codec_private;  // AAC: the AudioSpecificConfig; ALAC: the `alac` child's payload (the cookie in its MP4 wrapping)
+    std::vector<uint8_t> codec_private;  // AAC: the AudioSpecificConfig; ALAC: the `alac` child's payload (the cookie in its MP4 wrapping);
+                                         // FLAC: `fLaC` and the metadata blocks of `dfLa` (normalize_flac_config); PCM: none
     bool has_edit = false;               // the first media edit, in the track's timescale
     uint64_t edit_presentation_start = 0, edit_media_start = 0, edit_duration = 0;
     bool fragmented = false;  // `moov` holds `mvex`, or the sample tables are empty: the samples come in `moof`s
@@ -156,6 +170,28 @@ inline bool find_entry_child(Span s, const char *target, Span *out, int depth = 
     return false;
 }
 
+// normalize_mp4_flac_decoder_configuration: what the FLAC decoder is fed before the packets -- `fLaC`, then the metadata blocks.  Taken:
+// data that already begins with `fLaC`, a bare 34-byte STREAMINFO, a `dfLa` payload (version and flags, then the metadata blocks)
+inline bool normalize_flac_config(const uint8_t *d, size_t n, std::vector<uint8_t> *out, std::string *error) {
+    static const uint8_t magic[4] = {'f', 'L', 'a', 'C'}, head[4] = {0x80, 0, 0, 34};
+    out->clear();
+    if (n >= 4 && std::memcmp(d, magic, 4) == 0) return out->assign(d, d + n), true;
+    out->assign(magic, magic + 4);
+    if (n == 34) {
+        out->insert(out->end(), head, head + 4);
+        out->insert(out->end(), d, d + n);
+        return true;
+    }
+    if (n < 4) return *error = "MP4 dfLa decoder configuration is truncated", false;
+    const uint8_t *m = d + 4;
+    const size_t mn = n - 4;
+    if (mn < 38 || (m[0] & 0x7f) != 0) return *error = "MP4 dfLa has no leading FLAC STREAMINFO block", false;
+    const size_t info = (size_t)m[1] << 16 | (size_t)m[2] << 8 | m[3];
+    if (info != 34 || mn < 4 + info) return *error = "MP4 dfLa has an invalid FLAC STREAMINFO block", false;
+    out->insert(out->end(), m, m + mn);
+    return true;
+}
+
 // parse_stsd_audio, for the entries built here.  found = false: no such entry (the track is stepped over)
 inline bool parse_stsd(Span s, Track *t, bool *found, std::string *error) {
     *found = false;
@@ -168,25 +204,48 @@ inline bool parse_stsd(Span s, Track *t, bool *found, std::string *error) {
         if (h.size > s.n - pos) return *error = "MP4 stsd audio entry is truncated", false;
         const Span e{s.d + pos + h.header, (size_t)h.size - h.header};
         pos += (size_t)h.size;
-        const bool aac = h.is("mp4a"), alac = h.is("alac");
-        if ((!aac && !alac) || e.n < 28) continue;
+        const bool aac = h.is("mp4a"), alac = h.is("alac"), flac = h.is("fLaC");
+        const bool sowt = h.is("sowt"), twos = h.is("twos"), lpcm = h.is("lpcm");
+        const uint32_t fixed_bits = h.is("in24") ? 24 : h.is("in32") || h.is("fl32") ? 32 : h.is("fl64") ? 64 : 0;
+        if ((!aac && !alac && !flac && !sowt && !twos && !lpcm && !fixed_bits) || e.n < 28) continue;
         uint32_t version = 0, channels = 0, bits = 0, rate = 0;
         (void)e.u16(8, &version), (void)e.u16(16, &channels), (void)e.u16(18, &bits), (void)e.u32(24, &rate);
         rate >>= 16;
+        if (channels > 255) return *error = "QuickTime audio channel count exceeds u8", false;
+        if (bits > 255) bits = 0;  // 0: not stated
         size_t children = 28;
+        uint32_t bytes_per_frame = 0, frames_per_packet = 1, flags = 0;  // 0: not stated
         if (version == 1) {
             if (e.n < 44) return *error = "QuickTime version-one audio sample entry is truncated", false;
             children = 44;
+            uint32_t bytes_per_sample = 0;
+            (void)e.u32(28, &frames_per_packet), (void)e.u32(36, &bytes_per_frame), (void)e.u32(40, &bytes_per_sample);
+            if (bits == 0 && bytes_per_sample < 32) bits = bytes_per_sample * 8;
         } else if (version == 2) {
             if (e.n < 64) return *error = "QuickTime version-two audio sample entry is truncated", false;
-            return *error = "QuickTime version-two audio sample entries are not supported", false;
+            children = 64;
+            uint64_t rate_bits = 0;
+            uint32_t bytes_per_packet = 0;
+            (void)e.u64(32, &rate_bits), (void)e.u32(40, &channels), (void)e.u32(48, &bits), (void)e.u32(52, &flags);
+            (void)e.u32(56, &bytes_per_packet), (void)e.u32(60, &frames_per_packet);
+            double r;
+            std::memcpy(&r, &rate_bits, 8);
+            if (!(r > 0.0) || !(r <= 4294967295.0)) {  // (a NaN fails both)
+                char text[80];
+                std::snprintf(text, sizeof text, "invalid QuickTime version-two sample rate %g", r);
+                return *error = text, false;
+            }
+            rate = (uint32_t)(r + 0.5);
+            if (channels > 255) return *error = "QuickTime version-two channel count exceeds u8", false;
+            if (bits > 255) return *error = "QuickTime version-two sample depth exceeds u8", false;
+            bytes_per_frame = bytes_per_packet && frames_per_packet && bytes_per_packet % frames_per_packet == 0 ? bytes_per_packet / frames_per_packet : 0;
         } else if (version != 0) {
             return *error = "unsupported QuickTime audio sample-entry version " + std::to_string(version), false;
         }
-        if (channels > 255) return *error = "QuickTime audio channel count exceeds u8", false;
         const Span rest{e.d + children, e.n - children};
         Span body;
         t->codec_private.clear();
+        t->pcm = PcmEntry{};
         if (aac) {
             Span asc;
             bool bad = false;
@@ -194,12 +253,43 @@ inline bool parse_stsd(Span s, Track *t, bool *found, std::string *error) {
                 t->codec_private.assign(asc.d, asc.d + asc.n);
             if (bad) return *error = "MP4 esds descriptor length runs past its box", false;
             (void)asc_rate_channels(t->codec_private.data(), t->codec_private.size(), &rate, &channels);
-        } else if (find_entry_child(rest, "alac", &body)) {
-            t->codec_private.assign(body.d, body.d + body.n);
         }
         if (rate == 0 || channels == 0) return *error = "QuickTime audio sample entry has zero sample rate or channels", false;
-        t->codec = aac ? kCodecAac : kCodecAlac;
-        t->sample_rate = rate, t->channels = channels, t->bits = aac ? 0 : (bits > 255 ? 0 : bits);
+        if (alac && find_entry_child(rest, "alac", &body)) t->codec_private.assign(body.d, body.d + body.n);
+        if (flac) {
+            body = Span{};
+            (void)find_entry_child(rest, "dfLa", &body);
+            if (!normalize_flac_config(body.d, body.n, &t->codec_private, error)) return false;
+        }
+        if (!aac && !alac && !flac) {
+            bool have_enda = false, big = true;
+            if (find_entry_child(rest, "enda", &body)) {
+                uint32_t flag;
+                if (!body.u16(0, &flag)) return *error = "QuickTime enda atom is truncated", false;
+                if (flag > 1) return *error = "invalid QuickTime enda flag " + std::to_string(flag), false;
+                have_enda = true, big = flag == 0;
+            }
+            PcmEntry &p = t->pcm;
+            std::memcpy(p.name, h.name, 4);
+            if (sowt || twos) {
+                p.big_endian = twos;
+            } else if (lpcm) {
+                if (version != 2) return *error = "QuickTime lpcm requires a version-two sample entry", false;
+                if (flags & 32u) return *error = "non-interleaved QuickTime LPCM is unsupported", false;
+                p.big_endian = (flags & 2u) != 0, p.is_float = (flags & 1u) != 0;
+                // the reference carries the three flags below and then reads every entry as signed, packed and low-aligned
+                if (!p.is_float && !(flags & 4u)) return *error = "unsigned QuickTime LPCM is unsupported", false;
+                if (!p.is_float && !(flags & 8u)) return *error = "unpacked QuickTime LPCM is unsupported", false;
+                if (!p.is_float && (flags & 16u)) return *error = "aligned-high QuickTime LPCM is unsupported", false;
+            } else {
+                bits = fixed_bits;
+                p.big_endian = have_enda ? big : true, p.is_float = h.is("fl32") || h.is("fl64");
+            }
+            if (bytes_per_frame == 0) bytes_per_frame = (bits + 7) / 8 * channels;
+            p.bytes_per_frame = bytes_per_frame, p.frames_per_packet = frames_per_packet;
+        }
+        t->codec = aac ? kCodecAac : alac ? kCodecAlac : flac ? kCodecFlac : kCodecPcm;
+        t->sample_rate = rate, t->channels = channels, t->bits = aac ? 0 : bits;
         *found = true;
         return true;
     }
@@ -320,8 +410,62 @@ inline bool scale_time(uint64_t v, uint32_t from, uint32_t to, uint64_t *out, st
     return *out = (uint64_t)r, true;
 }
 
-// build_regular_samples
-inline bool build_samples(const Tables &t, std::vector<Sample> *out, std::string *error) {
+// build_constant_pcm_samples: a PCM track whose `stsz` states one size and whose `stts` one duration.  A "sample" of such a track is a
+// single frame; what is handed out is runs of them, cut at every chunk's end, after kMaxPcmRunFrames frames and before kMaxPcmRunBytes
+// bytes.  No record per frame is ever made.  (build_samples has checked that `stsc` maps exactly n_sizes frames.)
+inline bool build_constant_pcm_runs(const Tables &t, std::vector<Sample> *out, std::string *error) {
+    const uint32_t size = t.constant_size, duration = t.stts[1];
+    const uint32_t by_bytes = std::max(kMaxPcmRunBytes / size, 1u), by_duration = duration ? std::max(UINT32_MAX / duration, 1u) : kMaxPcmRunFrames;
+    const uint32_t most = std::min(kMaxPcmRunFrames, std::min(by_bytes, by_duration));
+    const uint64_t estimate = ((uint64_t)t.n_sizes + most - 1) / most + t.chunks.size();
+    if (estimate > kMaxUnits) return *error = "PCM track requires more than " + std::to_string(kMaxUnits) + " indexed packet runs", false;
+    out->clear();
+    out->reserve((size_t)std::min<uint64_t>(estimate, t.n_sizes));
+    size_t stsc_at = 0;
+    uint64_t time = 0, frames = 0;
+    for (size_t c = 0; c < t.chunks.size(); ++c) {
+        while (stsc_at + 3 < t.stsc.size() && t.stsc[stsc_at + 3] <= c + 1) stsc_at += 3;
+        uint32_t left = t.stsc[stsc_at + 1];
+        uint64_t at = t.chunks[c];
+        while (left > 0) {
+            const uint32_t n = std::min(left, most);
+            const uint64_t bytes = (uint64_t)size * n, ticks = (uint64_t)duration * n;
+            if (bytes > UINT32_MAX) return *error = "PCM packet size overflow", false;
+            if (ticks > UINT32_MAX) return *error = "PCM packet duration overflow", false;
+            Sample s;
+            s.offset = at, s.size = (uint32_t)bytes, s.duration = (uint32_t)ticks, s.start = time;
+            out->push_back(s);
+            if (at > UINT64_MAX - bytes) return *error = "PCM sample offset overflow", false;
+            at += bytes;
+            if (time > UINT64_MAX - ticks) return *error = "PCM sample timestamp overflow", false;
+            time += ticks;
+            frames += n, left -= n;
+        }
+    }
+    if (frames != t.n_sizes)
+        return *error = "MP4 stsc maps " + std::to_string(frames) + " PCM frames, but stsz describes " + std::to_string(t.n_sizes), false;
+    return true;
+}
+
+// coalesce_regular_pcm_samples: neighbours that are contiguous in bytes and in time merge, up to kMaxPcmRunFrames ticks and
+// kMaxPcmRunBytes bytes a run (the reference counts a run's frames by its duration; so does this)
+inline void coalesce_pcm_runs(std::vector<Sample> *samples) {
+    size_t n = 0;
+    for (const Sample &s : *samples) {
+        Sample *cur = n ? &(*samples)[n - 1] : nullptr;
+        if (cur && cur->offset + cur->size == s.offset && cur->start + cur->duration == s.start &&
+            (uint64_t)cur->duration + s.duration <= kMaxPcmRunFrames && (uint64_t)cur->size + s.size <= kMaxPcmRunBytes) {
+            cur->size += s.size, cur->duration += s.duration;
+        } else {
+            (*samples)[n++] = s;
+        }
+    }
+    samples->resize(n);
+    samples->shrink_to_fit();
+}
+
+// build_regular_samples; pcm: the samples of a PCM track leave as runs of frames
+inline bool build_samples(const Tables &t, bool pcm, std::vector<Sample> *out, std::string *error) {
     if (t.n_sizes == 0) return *error = "MP4 audio track is missing stsz sample sizes", false;
     if (t.chunks.empty()) return *error = "MP4 audio track is missing stco/co64 chunk offsets", false;
     if (t.stsc.empty()) return *error = "MP4 audio track is missing stsc sample-to-chunk table", false;
@@ -343,6 +487,7 @@ inline bool build_samples(const Tables &t, std::vector<Sample> *out, std::string
         const std::string m = mapped > UINT64_MAX ? std::string("more than 2^64") : std::to_string((uint64_t)mapped);
         return *error = "MP4 stsc maps " + m + " samples, but stsz describes " + std::to_string(n), false;
     }
+    if (pcm && t.constant_size && t.stts.size() == 2) return build_constant_pcm_runs(t, out, error);
     if (n > kMaxUnits) return *error = "MP4 track has " + std::to_string(n) + " access units; the materialized limit is " + std::to_string(kMaxUnits), false;
     out->clear();
     out->reserve((size_t)n);
@@ -372,6 +517,7 @@ inline bool build_samples(const Tables &t, std::vector<Sample> *out, std::string
     }
     if (out->size() != n)
         return *error = "MP4 sample tables described " + std::to_string(n) + " samples but only " + std::to_string(out->size()) + " were mapped to chunks", false;
+    if (pcm) coalesce_pcm_runs(out);
     return true;
 }
 
@@ -424,7 +570,7 @@ inline bool parse_trak(Span trak, bool have_movie_timescale, uint32_t movie_time
         if (!scale_time(t.elst_empty, movie_timescale, tr.timescale, &tr.edit_presentation_start, error)) return false;
     }
     tr.fragmented = t.n_sizes == 0 && t.chunks.empty() && t.stsc.empty();
-    if (!tr.fragmented && !build_samples(t, &tr.samples, error)) return false;
+    if (!tr.fragmented && !build_samples(t, tr.codec == kCodecPcm, &tr.samples, error)) return false;
     *track = std::move(tr);
     *chosen = true;
     return true;

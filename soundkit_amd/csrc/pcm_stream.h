@@ -411,10 +411,14 @@ private:
 // An empty add is the finalising one.  After an error every further add repeats it.
 enum AiffEncoding : uint8_t {  // = enum sk_aiff_encoding
     kAiffU8, kAiffS8, kAiffS16BE, kAiffS16LE, kAiffS24BE, kAiffS32BE, kAiffS32LE, kAiffF32BE, kAiffF64BE, kAiffUlaw, kAiffAlaw, kAiffIma4,
+    kAiffUnassigned12,  // refused, as every unknown value is (aiff_encoding_known)
+    kAiffF64LE,  // = 13; container PCM (QuickTime `fl64` with enda = 1, CAF lpcm flags 3); no AIFF-C compression type names it
     kAiffEncodings
 };
 constexpr size_t kMaxAiffCommBytes = 4096;
 constexpr uint32_t kMaxAiffChannels = 32;
+
+inline bool aiff_encoding_known(int enc) { return enc >= 0 && enc < kAiffEncodings && enc != kAiffUnassigned12; }
 
 // bytes of one encoded sample group, and of what it decodes to (the output contract, lib.rs:41-54)
 inline size_t aiff_group_bytes(int enc, uint32_t channels) {
@@ -423,12 +427,12 @@ inline size_t aiff_group_bytes(int enc, uint32_t channels) {
     case kAiffS16BE: case kAiffS16LE: return 2;
     case kAiffS24BE: return 3;
     case kAiffS32BE: case kAiffS32LE: case kAiffF32BE: return 4;
-    case kAiffF64BE: return 8;
+    case kAiffF64BE: case kAiffF64LE: return 8;
     default: return (size_t)34 * channels;
     }
 }
-inline uint32_t aiff_contract_bits(int enc) { return enc == kAiffS24BE ? 24 : (enc >= kAiffS32BE && enc <= kAiffF64BE ? 32 : 16); }
-inline bool aiff_contract_float(int enc) { return enc == kAiffF32BE || enc == kAiffF64BE; }
+inline uint32_t aiff_contract_bits(int enc) { return enc == kAiffS24BE ? 24 : ((enc >= kAiffS32BE && enc <= kAiffF64BE) || enc == kAiffF64LE ? 32 : 16); }
+inline bool aiff_contract_float(int enc) { return enc == kAiffF32BE || enc == kAiffF64BE || enc == kAiffF64LE; }
 inline size_t aiff_group_out_bytes(int enc, uint32_t channels) {
     return enc == kAiffIma4 ? (size_t)128 * channels : aiff_contract_bits(enc) / 8;
 }

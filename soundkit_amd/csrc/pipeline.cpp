@@ -18,6 +18,7 @@
 #include "sk_abi.h"
 #include "mp3_internal.h"  // sk_mp3_internal::PipelineGpuHooks: how this file reaches the device Huffman stage and the PCM tick
 #include "alac_stream.h"
+#include "caf_stream.h"
 #include "ogg_stream.h"
 #include "vorbis_stream.h"
 #include "g72x_stream.h"
@@ -141,7 +142,7 @@ struct PStream {
     // wrapped in an ADTS header and is appended to `pending`, where the ADTS pass finds it as it finds an ADTS stream's frame.  mp4_error:
     // what ends the stream once the frames in front of it have gone; mp4_done: nothing more is pulled
     std::unique_ptr<sk_mp4::Demuxer> mp4;
-    bool mp4_checked = false, mp4_done = false;
+    bool mp4_checked = false, mp4_done = false, mp4_flac_head = false;  // mp4_flac_head: a `fLaC` track's configuration has still to go to the reader
     std::string mp4_error;
     // WebM / Matroska streams (taken by their EBML magic): the demuxer runs on the worker thread.  At the first Cluster its single audio
     // track decides where the frames go (webm_open), and the stream is from then on a Vorbis stream whose packets come from the demuxer,
@@ -522,14 +523,38 @@ int pull_input(PStream &s) {
     return 1;
 }
 
-// An MP4 stream's demuxer output joins `pending` as ADTS frames.  The config event comes first: a track that is not AAC, or an
+// An MP4 stream's demuxer output joins `pending` as ADTS frames.  The config event comes first and decides what the stream is from there
+// on: a `fLaC` track makes it a FLAC stream and an integer or f32 PCM track a raw PCM stream (s.codec changes; parse_some sends the pass
+// to that stream's parser, which takes the packets from the demuxer).  No edit trim is applied, as none is for AAC.  Any other track
+// that is not AAC, or an
 // AudioSpecificConfig the AAC-LC config check refuses (sk_aac_decoder_create: explicit SBR or PS, another object type, 960-sample frames, a
 // program config element, more than two channels), ends the stream before any audio.  AacDecoderMp4's queue budget holds.
 void mp4_drain(PStream &s) {
     sk_mp4::Demuxer &m = *s.mp4;
     if (m.have_track && !s.mp4_checked && s.mp4_error.empty()) {
         s.mp4_checked = true;
-        if (m.track.codec != sk_mp4::kCodecAac) {
+        const sk_mp4::Track &t = m.track;
+        if ((t.codec == sk_mp4::kCodecFlac || t.codec == sk_mp4::kCodecPcm) && t.fragmented) {  // described, not decoded: as decode_file says
+            s.mp4_error = std::string("fragmented MP4 ") + (t.codec == sk_mp4::kCodecFlac ? "flac" : "pcm") + " tracks are not built";
+        } else if (t.codec == sk_mp4::kCodecFlac) {  // as a WebM A_FLAC track: the configuration, then the packets, are a native FLAC stream
+            s.codec = kCodecFlac;
+            s.mp4_flac_head = true;
+        } else if (t.codec == sk_mp4::kCodecPcm) {  // as a transport stream's LPCM: a raw PCM stream of the entry's format
+            const uint32_t width = (t.bits + 7) / 8 * t.channels;
+            if (t.pcm.is_float && t.bits == 64) {
+                s.mp4_error = "MP4 64-bit float PCM is not decoded in a stream; decode the whole file (decode_file)";
+            } else if ((t.bits != 16 && t.bits != 24 && t.bits != 32) || (t.pcm.is_float && t.bits != 32)) {
+                s.mp4_error = "unsupported container PCM sample depth: " + std::to_string(t.bits);
+            } else if (t.pcm.bytes_per_frame != width) {
+                s.mp4_error = "MP4 PCM frames of " + std::to_string(t.pcm.bytes_per_frame) + " bytes are not " + std::to_string(t.channels) +
+                              " channels of " + std::to_string(t.bits) + " packed bits";
+            } else {
+                const int le = t.pcm.is_float ? SK_FMT_F32LE : (t.bits == 16 ? SK_FMT_S16LE : (t.bits == 24 ? SK_FMT_S24LE : SK_FMT_S32LE));
+                s.codec = kCodecRawPcm;
+                s.raw_format = sk_raw_pcm_format{t.sample_rate, (uint8_t)t.channels, (uint8_t)(le + (t.pcm.big_endian ? 1 : 0)), 0};
+                s.raw.reset(new sk_pcm::RawPcmStream(width));
+            }
+        } else if (t.codec != sk_mp4::kCodecAac) {
             s.mp4_error = "MP4/M4A audio track is not AAC";
         } else {
             static const uint8_t none[1] = {0};
@@ -540,7 +565,7 @@ void mp4_drain(PStream &s) {
             sk_aac_decoder_destroy(probe);
         }
     }
-    while (!m.packets.empty()) {
+    while (s.codec == kCodecMp4 && !m.packets.empty()) {  // (a FLAC or PCM track's packets wait in the demuxer for their pass)
         if (s.mp4_error.empty()) {
             const std::vector<uint8_t> &raw = m.packets.front().data;
             if (raw.size() + 7 > 8191) {
@@ -659,6 +684,19 @@ void webm_flac_bytes(PStream &s, std::vector<uint8_t> &out) {
     while (!w.packets.empty()) {
         out.insert(out.end(), w.packets.front().data.begin(), w.packets.front().data.end());
         w.pop_packet();
+    }
+}
+
+// The same for a `fLaC` track of an MP4 stream: the normalised `dfLa` once, then the samples (one frame each)
+void mp4_flac_bytes(PStream &s, std::vector<uint8_t> &out) {
+    sk_mp4::Demuxer &m = *s.mp4;
+    if (s.mp4_flac_head) {
+        s.mp4_flac_head = false;
+        out = m.track.codec_private;
+    }
+    while (!m.packets.empty()) {
+        out.insert(out.end(), m.packets.front().data.begin(), m.packets.front().data.end());
+        m.packets.pop_front();
     }
 }
 
@@ -1573,9 +1611,10 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
     // an A_FLAC track of a WebM stream: the chunks go through the demuxer, and what it hands out -- the CodecPrivate, then the frames --
     // is the native stream the reader takes.  A feed gets at most the demuxer's queue budget
     std::vector<uint8_t> demuxed;
-    if (s.webm) {
+    auto container_bytes = [&] { s.webm ? webm_flac_bytes(s, demuxed) : mp4_flac_bytes(s, demuxed); };  // (an MP4 `fLaC` track: the same)
+    if (s.webm || s.mp4) {
         if (s.more && !feed(nullptr, 0, s.saw_eof && s.flac->finalised())) return;  // frames left over by the pass before
-        if (!r.more) webm_flac_bytes(s, demuxed);  // (else they stay with the demuxer for the next pass)
+        if (!r.more) container_bytes();  // (else they stay with the demuxer for the next pass)
         if (!demuxed.empty() && !feed(demuxed.data(), demuxed.size(), false)) return;
     } else if (s.pending.size() > s.pending_pos) {  // the pending bytes of the detection (parse_some gathered them) go in first
         std::vector<uint8_t> first(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
@@ -1600,7 +1639,7 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         {
             std::lock_guard<std::mutex> lk(s.mu);
             if (s.in.empty()) break;
-            if (!s.in.front().empty() && !r.pcm_units.empty() && !fits(s.webm ? kMaxWebmQueuedBytes : s.in.front().size())) {
+            if (!s.in.front().empty() && !r.pcm_units.empty() && !fits(s.webm ? kMaxWebmQueuedBytes : (s.mp4 ? s.mp4->buffered() : 0) + s.in.front().size())) {
                 r.more = true;
                 break;
             }
@@ -1615,6 +1654,21 @@ void parse_some_flac(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
             webm_flac_bytes(s, demuxed);
             if (!demuxed.empty() && !feed(demuxed.data(), demuxed.size(), false)) break;
             if (!s.webm_error.empty()) r.fail(SK_WEBM_ERR_STREAM, "Decoding failed: " + s.webm_error);
+            continue;
+        }
+        if (s.mp4) {  // the same for an MP4 stream
+            if (chunk.empty()) {
+                s.saw_eof = s.mp4_done = true;
+                (void)s.mp4->finish();
+            } else {
+                s.queued_bytes.fetch_sub(chunk.size());
+                (void)s.mp4->add(chunk.data(), chunk.size());
+            }
+            if (s.mp4->failed && s.mp4_error.empty()) s.mp4_error = s.mp4->error;
+            demuxed.clear();
+            mp4_flac_bytes(s, demuxed);
+            if (!demuxed.empty() && !feed(demuxed.data(), demuxed.size(), false)) break;
+            if (!s.mp4_error.empty()) r.fail(SK_MP4_ERR_STREAM, "Decoding failed: " + s.mp4_error);
             continue;
         }
         if (chunk.empty()) {
@@ -1728,6 +1782,26 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
             if (!process(pk.data.data(), pk.data.size())) break;
             continue;
         }
+        if (s.mp4) {  // a PCM track of an MP4 stream: every run of frames the demuxer hands out is one piece
+            if (!s.mp4->packets.empty()) {
+                if (full(s.mp4->packets.front().data.size())) {
+                    r.more = true;
+                    break;
+                }
+                const sk_mp4::Packet pk = std::move(s.mp4->packets.front());
+                s.mp4->packets.pop_front();
+                if (!process(pk.data.data(), pk.data.size())) break;
+                continue;
+            }
+            if (!s.mp4_error.empty()) {  // every complete run has gone: what the demuxer refused
+                r.fail(SK_MP4_ERR_STREAM, "Decoding failed: " + s.mp4_error);
+                break;
+            }
+            if (!s.saw_eof) {
+                if (pull_mp4(s) == 0) break;
+                continue;
+            }
+        }
         if (s.saw_eof) {  // flush_decoder (lib.rs:3139-3169): the framer's partial frame is an error, the resampler is flushed by the tick
             std::string err;
             if (s.raw && !s.raw->flush(err)) r.fail(SK_PCM_ERR_STREAM, "Decoding failed: " + err);
@@ -1838,6 +1912,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         }
         mp4_drain(s);
     }
+    if (s.mp4 && s.codec != kCodecMp4) {  // the config event made it a FLAC or a raw PCM stream: that stream's pass, from here on
+        parse_some(p, s, limit, coeffs, descs, au_stage, au_items, room, r);
+        return;
+    }
     while (r.n_frames < limit && !r.failed) {
         // make sure a whole frame is in `pending`
         size_t avail = s.pending.size() - s.pending_pos;
@@ -1857,6 +1935,10 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
         if (!have) {
             if (s.mp4 && !s.mp4_done) {  // an MP4 stream: more frames come out of the demuxer
                 if (pull_mp4(s) == 0) break;
+                if (s.codec != kCodecMp4) {  // moov has arrived and the track is FLAC or PCM (nothing has been staged before the config)
+                    parse_some(p, s, limit, coeffs, descs, au_stage, au_items, room, r);
+                    return;
+                }
                 continue;
             }
             if (s.webm && !s.webm_done) {  // a WebM stream's A_AAC track: more frames come out of the demuxer
@@ -3068,7 +3150,7 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.alac = s.alac_plain = false;
     s.alac_cfg = sk_alac_config{};
     s.mp4.reset();
-    s.mp4_checked = s.mp4_done = false;
+    s.mp4_checked = s.mp4_done = s.mp4_flac_head = false;
     s.mp4_error.clear();
     s.webm.reset();
     s.webm_routed = s.webm_done = s.webm_flac_head = false;
@@ -3872,6 +3954,10 @@ struct sk_mp4_index {
     sk_mp4::Track track;
 };
 
+struct sk_caf_index {
+    sk_caf::Index index;
+};
+
 namespace {
 
 void mp4_text(char *error, size_t cap, const std::string &text) {
@@ -3894,9 +3980,135 @@ int mp4_track_info(const sk_mp4::Track &t, bool have, sk_mp4_track_info *info, u
     return SK_OK;
 }
 
+int mp4_pcm_info(const sk_mp4::Track &t, bool have, sk_mp4_pcm_info *info) {
+    std::memset(info, 0, sizeof *info);
+    if (!have || t.codec != sk_mp4::kCodecPcm) return SK_OK;
+    std::memcpy(info->codec_id, t.pcm.name, 4);
+    info->big_endian = t.pcm.big_endian ? 1 : 0, info->is_float = t.pcm.is_float ? 1 : 0, info->bits_per_sample = t.bits;
+    info->bytes_per_frame = t.pcm.bytes_per_frame, info->frames_per_packet = t.pcm.frames_per_packet;
+    return SK_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+// ---- CAF (caf_stream.h) -------------------------------------------------------------------------------------------------------------------
+
+int sk_caf_index_from_file(const uint8_t *file, size_t len, sk_caf_index **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !file) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    mp4_text(error, error_cap, "");
+    std::unique_ptr<sk_caf_index> ix(new sk_caf_index());
+    std::string text;
+    static const uint8_t none[1] = {0};
+    if (!sk_caf::index_from_file(len ? file : none, len, &ix->index, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_CAF_ERR_STREAM;
+    }
+    *out = ix.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_index_from_file");
+}
+
+int sk_caf_index_create(const uint8_t *desc, size_t desc_len, const uint8_t *cookie, size_t cookie_len, const uint8_t *pakt, size_t pakt_len,
+                        uint64_t data_offset, uint64_t data_size, sk_caf_index **out, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((desc_len && !desc) || (cookie_len && !cookie) || !out) return SK_ERR_INVALID_ARG;
+    *out = nullptr;
+    mp4_text(error, error_cap, "");
+    std::unique_ptr<sk_caf_index> ix(new sk_caf_index());
+    std::string text;
+    static const uint8_t none[1] = {0};
+    if (!sk_caf::index_from_metadata(desc ? desc : none, desc_len, cookie ? cookie : none, cookie_len, pakt, pakt_len, data_offset, data_size, &ix->index,
+                                     &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_CAF_ERR_STREAM;
+    }
+    *out = ix.release();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_index_create");
+}
+
+void sk_caf_index_destroy(sk_caf_index *ix) try {
+    sk::abi_enter();
+    delete ix;
+} catch (...) {
+    (void)sk::abi_caught("sk_caf_index_destroy");
+}
+
+int sk_caf_index_info(const sk_caf_index *ix, sk_caf_info *info, uint8_t *cookie, size_t cookie_cap) try {
+    sk::abi_enter();
+    if (!ix || !info || (cookie_cap && !cookie)) return SK_ERR_INVALID_ARG;
+    const sk_caf::Index &x = ix->index;
+    std::memset(info, 0, sizeof *info);
+    info->codec = x.codec;
+    std::memcpy(info->format_id, x.format_id, 4);
+    info->sample_rate = x.sample_rate, info->channels = x.channels, info->bits_per_sample = x.bits, info->format_flags = x.format_flags;
+    info->big_endian = x.big_endian ? 1 : 0, info->is_float = x.is_float ? 1 : 0, info->bytes_per_frame = x.bytes_per_frame;
+    info->frames_per_packet = x.frames_per_packet, info->priming_frames = x.priming_frames, info->remainder_frames = x.remainder_frames;
+    info->n_packets = (uint32_t)x.packets.size(), info->cookie_len = (uint32_t)x.cookie.size(), info->valid_frames = x.valid_frames;
+    if (cookie_cap < x.cookie.size()) return SK_ERR_CAPACITY;
+    if (!x.cookie.empty()) std::memcpy(cookie, x.cookie.data(), x.cookie.size());
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_index_info");
+}
+
+int sk_caf_index_packets(const sk_caf_index *ix, uint64_t *offsets, uint32_t *sizes, uint32_t *frames, uint64_t *start_frames, uint32_t cap) try {
+    sk::abi_enter();
+    if (!ix) return SK_ERR_INVALID_ARG;
+    const std::vector<sk_caf::Packet> &p = ix->index.packets;
+    if (cap < p.size()) return SK_ERR_CAPACITY;
+    for (size_t i = 0; i < p.size(); ++i) {
+        if (offsets) offsets[i] = p[i].offset;
+        if (sizes) sizes[i] = p[i].size;
+        if (frames) frames[i] = p[i].frames;
+        if (start_frames) start_frames[i] = p[i].start;
+    }
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_caf_index_packets");
+}
+
+// ---- MP4: the PCM description and the FLAC configuration ------------------------------------------------------------------------------
+
+int sk_mp4_demuxer_pcm_info(const sk_mp4_demuxer *d, sk_mp4_pcm_info *info) try {
+    sk::abi_enter();
+    if (!d || !info) return SK_ERR_INVALID_ARG;
+    return mp4_pcm_info(d->demuxer.track, d->demuxer.have_track, info);
+} catch (...) {
+    return sk::abi_caught("sk_mp4_demuxer_pcm_info");
+}
+
+int sk_mp4_index_pcm_info(const sk_mp4_index *ix, sk_mp4_pcm_info *info) try {
+    sk::abi_enter();
+    if (!ix || !info) return SK_ERR_INVALID_ARG;
+    return mp4_pcm_info(ix->track, true, info);
+} catch (...) {
+    return sk::abi_caught("sk_mp4_index_pcm_info");
+}
+
+int sk_mp4_flac_config(const uint8_t *data, size_t len, uint8_t *out, size_t out_cap, size_t *out_len, char *error, size_t error_cap) try {
+    sk::abi_enter();
+    if ((len && !data) || !out_len) return SK_ERR_INVALID_ARG;
+    mp4_text(error, error_cap, "");
+    std::vector<uint8_t> got;
+    std::string text;
+    if (!sk_mp4::normalize_flac_config(data, len, &got, &text)) {
+        mp4_text(error, error_cap, text);
+        return SK_MP4_ERR_STREAM;
+    }
+    *out_len = got.size();
+    if (out_cap < got.size() || !out) return SK_ERR_CAPACITY;
+    std::memcpy(out, got.data(), got.size());
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_mp4_flac_config");
+}
 
 int sk_mp4_demuxer_create(sk_mp4_demuxer **out) try {
     sk::abi_enter();
