@@ -1050,8 +1050,11 @@ const char *sk_raw_pcm_framer_last_error(const sk_raw_pcm_framer *);
 enum sk_aiff_encoding {
     SK_AIFF_U8 = 0, SK_AIFF_S8, SK_AIFF_S16BE, SK_AIFF_S16LE, SK_AIFF_S24BE, SK_AIFF_S32BE, SK_AIFF_S32LE, SK_AIFF_F32BE, SK_AIFF_F64BE,
     SK_AIFF_ULAW, SK_AIFF_ALAW, SK_AIFF_IMA4,
-    SK_AIFF_F64LE = 13 /* 64-bit float, little-endian: no AIFF-C file holds it; container PCM does (QuickTime `fl64` with enda = 1, CAF
+    SK_AIFF_F64LE = 13, /* 64-bit float, little-endian: no AIFF-C file holds it; container PCM does (QuickTime `fl64` with enda = 1, CAF
                           lpcm).  12 stays unassigned: it has always been refused as unknown, and still is */
+    SK_AIFF_DVD_S24 = 14 /* DVD LPCM at 24 bits (MPEG program streams): every 12-byte group holds four samples, first their four
+                            big-endian 16-bit high parts, then their four low bytes; sample i leaves as the little-endian bytes
+                            [g[8+i], g[2i+1], g[2i]].  A group is 12 bytes in and 12 bytes out: len is a multiple of 12 */
 };
 typedef struct sk_aiff_info { /* zeros (but buffered_bytes) until COMM has been read */
     uint32_t sample_rate;
@@ -1078,6 +1081,8 @@ const char *sk_aiff_reader_last_error(const sk_aiff_reader *);
  * a predictor within 0x7f of the carried one continues from the carried predictor; any other packet restarts from its header.
  * len is a whole number of groups (SK_ERR_INVALID_ARG otherwise, or when out_cap is too small); *out_len receives the decoded size:
  * 2 bytes a sample for the 16-bit contracts, 3 for s24be, 4 for the 32-bit and float ones, 128 bytes per IMA4 packet.
+ * SK_AIFF_DVD_S24 (DVD LPCM out of an MPEG program stream, no AIFF file holds it): len is a multiple of 12, a group of four samples;
+ * 12 bytes of little-endian s24 leave per group, whatever the channel count.
  * The _dev form takes 16-byte aligned device pointers and is queued on the engine's stream; it waits only for the state. */
 typedef struct sk_aiff_ima_state {
     int16_t predictor;
@@ -1619,6 +1624,65 @@ int sk_ts_sniff(const uint8_t *bytes, size_t len);
 /* a stream known to be a transport stream, for a join in mid-segment where the first bytes are no sync (the demuxer finds it);
  * sk_pipeline_spawn takes a transport stream by sk_ts_sniff itself */
 int sk_pipeline_spawn_mpeg_ts(sk_pipeline *, const sk_decode_options *opt /* NULL = defaults */, uint32_t *handle);
+
+/* ---- AVI audio demuxer (host only, csrc/avi_stream.h) --------------------------------------------------------------- */
+/* What decode_avi_audio reads (soundkit-decoder/src/lib.rs:257-570) as an incremental walk, audio only: `RIFF....AVI ` and any number of
+ * `RIFF....AVIX` forms; `LIST hdrl` -> `LIST strl` -> `strh` / `strf`, the first `auds` stream is the track and its index its position
+ * among all strl lists; `LIST movi` chunk by chunk (never buffered whole), nested LISTs to a depth of 8; `##wb` chunks whose two hex
+ * digits are the track's index are the packets, one per chunk.  Events in order: the config once `hdrl` has been read, then packets.
+ * A file cut inside a chunk gives the complete chunks in front of it.  Budgets: 4 MiB a call, 1 000 000 chunks a container, 512 MiB of
+ * payload, 16 MiB of `hdrl` (this project's).  A refusal is SK_AVI_ERR_STREAM with a text (sk_avi_demuxer_last_error); the events
+ * complete in front of it stay takeable and the demuxer stays refused.  What the format tag means is the caller's business: 0x0001
+ * integer PCM, 0x0003 float PCM, 0x0055 MPEG audio.  Not read: `idx1` / `indx`, video, text and MIDI streams. */
+enum sk_avi_status { SK_AVI_ERR_STREAM = -1401 };
+enum sk_demux_event { SK_DEMUX_NONE = 0, SK_DEMUX_CONFIG = 1, SK_DEMUX_PACKET = 2 };
+typedef struct sk_avi_track_info {
+    uint32_t stream_index;
+    uint32_t sample_rate;
+    uint16_t format_tag; /* WAVEFORMAT's wFormatTag */
+    uint8_t channels;    /* 1 ... 255 */
+    uint8_t bits;        /* wBitsPerSample, clamped to 255 */
+} sk_avi_track_info;
+typedef struct sk_avi_demuxer sk_avi_demuxer;
+int sk_avi_demuxer_create(sk_avi_demuxer **out);
+void sk_avi_demuxer_destroy(sk_avi_demuxer *);
+int sk_avi_demuxer_add(sk_avi_demuxer *, const uint8_t *bytes, size_t len);
+int sk_avi_demuxer_finish(sk_avi_demuxer *);
+/* the next waiting event: *event = SK_DEMUX_NONE (nothing waits), SK_DEMUX_CONFIG (*info is filled) or SK_DEMUX_PACKET (*len bytes in
+ * out).  cap too small for the packet: SK_ERR_CAPACITY, *len is what it needs and the packet stays */
+int sk_avi_demuxer_next(sk_avi_demuxer *, int *event, sk_avi_track_info *info, uint8_t *out, size_t cap, size_t *len);
+const char *sk_avi_demuxer_last_error(const sk_avi_demuxer *);
+
+/* ---- MPEG program stream audio demuxer (host only, csrc/ps_stream.h) ------------------------------------------------- */
+/* What decode_mpeg_ps_audio reads (soundkit-decoder/src/lib.rs:572-804) as an incremental walk, audio only: start codes, the pack
+ * header by its own layout, every id from BB on by its 16-bit length, PES headers in the MPEG-2 and the MPEG-1 form.  DVD LPCM
+ * (private_stream_1, substream A0 ... AF): the sample bytes behind the 4 + 3 header bytes leave in whole blocks (block_bytes), the
+ * remainder is carried to the next packet; 16 bits: big-endian samples (SK_FMT_S16BE), 24 bits: SK_AIFF_DVD_S24's groups; 20 bits are
+ * refused.  MPEG audio (C0 ... DF): the payloads, one packet each, are the elementary stream.  track_mode: SK_PS_TRACK_FIRST -- the
+ * first audio packet of either kind names the track; SK_PS_TRACK_LPCM / SK_PS_TRACK_MPEG_AUDIO -- that kind alone, the other is stepped
+ * over.  Beyond the reference: packets are walked by their length field, only the first LPCM substream is the track, MPEG audio is a
+ * track.  Budgets: 4 MiB a call, 512 MiB of payload.  A refusal is SK_PS_ERR_STREAM with a text; the events complete in front of it
+ * stay takeable and the demuxer stays refused.  Not read: AC-3 / DTS substreams, video, the system header's contents, SCR. */
+enum sk_ps_status { SK_PS_ERR_STREAM = -1501 };
+enum sk_ps_track_mode { SK_PS_TRACK_FIRST = 0, SK_PS_TRACK_LPCM = 1, SK_PS_TRACK_MPEG_AUDIO = 2 };
+enum sk_ps_kind { SK_PS_KIND_LPCM = 1, SK_PS_KIND_MPEG_AUDIO = 2 };
+typedef struct sk_ps_track_info {
+    uint32_t sample_rate; /* DVD LPCM; 0 for MPEG audio, whose frames say it */
+    uint32_t block_bytes; /* DVD LPCM: every packet is a whole number of these */
+    uint8_t kind;         /* sk_ps_kind */
+    uint8_t stream_id;    /* BD, or C0 ... DF */
+    uint8_t substream_id; /* DVD LPCM: A0 ... AF */
+    uint8_t channels;     /* DVD LPCM: 1 ... 8 */
+    uint8_t bits;         /* DVD LPCM: 16 / 24 */
+    uint8_t reserved[3];
+} sk_ps_track_info;
+typedef struct sk_ps_demuxer sk_ps_demuxer;
+int sk_ps_demuxer_create(int track_mode, sk_ps_demuxer **out);
+void sk_ps_demuxer_destroy(sk_ps_demuxer *);
+int sk_ps_demuxer_add(sk_ps_demuxer *, const uint8_t *bytes, size_t len);
+int sk_ps_demuxer_finish(sk_ps_demuxer *);
+int sk_ps_demuxer_next(sk_ps_demuxer *, int *event, sk_ps_track_info *info, uint8_t *out, size_t cap, size_t *len); /* as sk_avi_demuxer_next */
+const char *sk_ps_demuxer_last_error(const sk_ps_demuxer *);
 
 /* ---- ALAC decode stage (GPU, csrc/alac_decode.hip)-------------------------------------------------------------------- */
 /* packets[i] lies at bytes + packets[i].offset, a multiple of 16.  Output: the packets one after the other in the order given, each

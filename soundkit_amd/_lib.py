@@ -30,6 +30,8 @@ ERR_NAMES = {0: "SK_OK", -1: "SK_ERR_INVALID_ARG", -2: "SK_ERR_NO_DEVICE", -3: "
              -1101: "TsStreamRejected",
              -1201: "WavBadBlock",
              -1301: "CafStreamRejected",
+             -1401: "AviStreamRejected",
+             -1501: "PsStreamRejected",
              -201: "InputBufferFull", -202: "PipelineClosed", -203: "InputChunkTooLarge"}
 
 
@@ -264,6 +266,17 @@ class TsPacketInfo(C.Structure):
     """sk_ts_packet_info"""
     _fields_ = [("pts", C.c_uint64), ("dts", C.c_uint64), ("duration", C.c_uint32), ("has_pts", C.c_uint8), ("has_dts", C.c_uint8), ("has_duration", C.c_uint8),
                 ("continuity_counter", C.c_uint8), ("discontinuity", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
+class AviTrackInfo(C.Structure):
+    """sk_avi_track_info"""
+    _fields_ = [("stream_index", C.c_uint32), ("sample_rate", C.c_uint32), ("format_tag", C.c_uint16), ("channels", C.c_uint8), ("bits", C.c_uint8)]
+
+
+class PsTrackInfo(C.Structure):
+    """sk_ps_track_info"""
+    _fields_ = [("sample_rate", C.c_uint32), ("block_bytes", C.c_uint32), ("kind", C.c_uint8), ("stream_id", C.c_uint8), ("substream_id", C.c_uint8),
+                ("channels", C.c_uint8), ("bits", C.c_uint8), ("reserved", C.c_uint8 * 3)]
 
 
 class AlacTickStream(C.Structure):
@@ -701,6 +714,18 @@ _sig = {
     "sk_ts_demuxer_take": (_i, [_vp, _vp, _sz, C.POINTER(_sz), C.POINTER(TsPacketInfo)]),
     "sk_ts_sniff": (_i, [_vp, _sz]),
     "sk_pipeline_spawn_mpeg_ts": (_i, [_vp, _vp, C.POINTER(_u32)]),
+    "sk_avi_demuxer_create": (_i, [C.POINTER(_vp)]),
+    "sk_avi_demuxer_destroy": (None, [_vp]),
+    "sk_avi_demuxer_add": (_i, [_vp, _vp, _sz]),
+    "sk_avi_demuxer_finish": (_i, [_vp]),
+    "sk_avi_demuxer_next": (_i, [_vp, C.POINTER(_i), C.POINTER(AviTrackInfo), _vp, _sz, C.POINTER(_sz)]),
+    "sk_avi_demuxer_last_error": (C.c_char_p, [_vp]),
+    "sk_ps_demuxer_create": (_i, [_i, C.POINTER(_vp)]),
+    "sk_ps_demuxer_destroy": (None, [_vp]),
+    "sk_ps_demuxer_add": (_i, [_vp, _vp, _sz]),
+    "sk_ps_demuxer_finish": (_i, [_vp]),
+    "sk_ps_demuxer_next": (_i, [_vp, C.POINTER(_i), C.POINTER(PsTrackInfo), _vp, _sz, C.POINTER(_sz)]),
+    "sk_ps_demuxer_last_error": (C.c_char_p, [_vp]),
     "sk_alac_decode_packets": (_i, [_vp, _vp, _vp, _u32, _vp, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_alac_decode_packets_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, _sz, C.POINTER(_sz), _vp, _vp]),
     "sk_tick_alac_out_bound_on": (_sz, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_u32)]),

@@ -2,7 +2,7 @@
 // reference's AiffDecoder does to the sound bytes in decode_stream_bytes (soundkit-aiff/src/lib.rs:477-560), for every unit of
 // every stream of a tick.  Source-encoded sample groups in, little-endian PCM of the output contract (lib.rs:41-54) out:
 //
-//   k_aiff_elem   every encoding but IMA4: u8 / s8 widened to s16, 2- / 3- / 4-byte big-endian samples reversed (f32be as an integer
+//   k_aiff_elem   every encoding but IMA4 (DVD LPCM's 24-bit groups are permuted byte for byte: SK_AIFF_DVD_S24): u8 / s8 widened to s16, 2- / 3- / 4-byte big-endian samples reversed (f32be as an integer
 //                 swap: NaN payloads and subnormals survive), the little-endian forms copied, f64be and f64le rounded to f32 in integer
 //                 arithmetic (nearest even, subnormal results kept, overflow to infinity), mu-law and A-law expanded to s16.
 //                 pcm_tick.hip's conventions: a job table, grid = (slices of kPcmSliceSamples samples, jobs), units at 16-byte
@@ -26,13 +26,16 @@ namespace sk {
 namespace {
 
 enum : uint32_t {  // enum sk_aiff_encoding
-    kU8, kS8, kS16BE, kS16LE, kS24BE, kS32BE, kS32LE, kF32BE, kF64BE, kUlaw, kAlaw, kIma4, kUnassigned12, kF64LE  // kF64LE = 13: appended, the range tests below rest on the order
+    kU8, kS8, kS16BE, kS16LE, kS24BE, kS32BE, kS32LE, kF32BE, kF64BE, kUlaw, kAlaw, kIma4, kUnassigned12, kF64LE,  // kF64LE = 13: appended, the range tests below rest on the order
+    kDvdS24  // = 14: DVD LPCM's 24-bit packing, appended for the same reason
 };
 
 __device__ __forceinline__ int enc_in_bytes(uint32_t enc) {
-    return enc <= kS8 || enc == kUlaw || enc == kAlaw ? 1 : (enc <= kS16LE ? 2 : (enc == kS24BE ? 3 : (enc == kF64BE || enc == kF64LE ? 8 : 4)));
+    return enc <= kS8 || enc == kUlaw || enc == kAlaw ? 1 : (enc <= kS16LE ? 2 : (enc == kS24BE || enc == kDvdS24 ? 3 : (enc == kF64BE || enc == kF64LE ? 8 : 4)));
 }
-__device__ __forceinline__ int enc_out_bytes(uint32_t enc) { return enc == kS24BE ? 3 : ((enc >= kS32BE && enc <= kF64BE) || enc == kF64LE ? 4 : 2); }
+__device__ __forceinline__ int enc_out_bytes(uint32_t enc) {
+    return enc == kS24BE || enc == kDvdS24 ? 3 : ((enc >= kS32BE && enc <= kF64BE) || enc == kF64LE ? 4 : 2);
+}
 
 // ITU-T G.711 expansion to 16-bit linear
 __device__ __forceinline__ uint32_t ulaw_to_s16(uint32_t code) {
@@ -85,6 +88,16 @@ __device__ __forceinline__ uint32_t elem_decode(uint32_t enc, uint32_t raw) {
     }
 }
 
+// One 12-byte group of 24-bit DVD LPCM (four big-endian 16-bit high parts g[0..7], then the four low bytes g[8..11]) as the three dwords
+// that hold it -> the three dwords of its four little-endian samples [g[8+i], g[2i+1], g[2i]].  Every output byte is one input byte:
+// v_perm_b32 selects (0 ... 3: the second operand's bytes, 4 ... 7: the first's), one for the outer dwords, two for the middle one,
+// whose bytes come from all three inputs.
+__device__ __forceinline__ void dvd_s24_group(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t &o0, uint32_t &o1, uint32_t &o2) {
+    o0 = __builtin_amdgcn_perm(w2, w0, 0x05000104u);                                          // g8 g1 g0 g9
+    o1 = __builtin_amdgcn_perm(w1, __builtin_amdgcn_perm(w2, w0, 0x06060203u), 0x05020100u);  // g3 g2 g10 g5
+    o2 = __builtin_amdgcn_perm(w2, w1, 0x02030700u);                                          // g4 g11 g7 g6
+}
+
 // 16 samples of OB = 2 or 3 bytes each as OB 16-byte stores
 template <int OB>
 __device__ __forceinline__ void store16(uint8_t *dst, const uint32_t (&v)[16]) {
@@ -114,6 +127,31 @@ __global__ __launch_bounds__(256) void k_aiff_elem(const AiffElemJob *jobs, uint
     if (s0 >= total) return;
     const uint32_t enc = job.enc;
     const int ib = enc_in_bytes(enc), ob = enc_out_bytes(enc);
+    if (enc == kDvdS24) {  // DVD LPCM at 24 bits: a byte permutation inside every 12-byte group; total is a multiple of 4 (the host checks it)
+        const uint8_t *src = job.src + (size_t)s0 * 3;
+        uint8_t *dst = job.dst + (size_t)s0 * 3;
+        if (s0 + 16 <= total) {  // four groups: three 16-byte loads, three 16-byte stores (a lane's offset is a multiple of 48)
+            const uint4 *p = reinterpret_cast<const uint4 *>(src);
+            const uint4 a = p[0], b = p[1], c = p[2];
+            uint4 x, y, z;
+            dvd_s24_group(a.x, a.y, a.z, x.x, x.y, x.z);
+            dvd_s24_group(a.w, b.x, b.y, x.w, y.x, y.y);
+            dvd_s24_group(b.z, b.w, c.x, y.z, y.w, z.x);
+            dvd_s24_group(c.y, c.z, c.w, z.y, z.z, z.w);
+            uint4 *d = reinterpret_cast<uint4 *>(dst);
+            d[0] = x, d[1] = y, d[2] = z;
+            return;
+        }
+        // the unit's last 4, 8 or 12 samples: group by group, dword loads and stores (a group's offset is a multiple of 4)
+        for (uint32_t s = s0; s + 4 <= total; s += 4, src += 12, dst += 12) {
+            const uint32_t *p = reinterpret_cast<const uint32_t *>(src);
+            uint32_t *d = reinterpret_cast<uint32_t *>(dst);
+            uint32_t o0, o1, o2;
+            dvd_s24_group(p[0], p[1], p[2], o0, o1, o2);
+            d[0] = o0, d[1] = o1, d[2] = o2;
+        }
+        return;
+    }
     if (s0 + 16 <= total && ib == 4) {  // 4-byte samples move dword for dword: four 16-byte loads, four 16-byte stores
         const uint4 *p = reinterpret_cast<const uint4 *>(job.src + (size_t)s0 * 4);
         uint4 *d = reinterpret_cast<uint4 *>(job.dst + (size_t)s0 * 4);

@@ -613,6 +613,8 @@ const char *sk_strerror(int status) try {
     case SK_CAF_ERR_STREAM: return "CAF stream rejected";
     case SK_WEBM_ERR_STREAM: return "WebM stream rejected";
     case SK_TS_ERR_STREAM: return "MPEG-TS stream rejected";
+    case SK_AVI_ERR_STREAM: return "AVI stream rejected";
+    case SK_PS_ERR_STREAM: return "MPEG-PS stream rejected";
     case SK_WAV_BAD_BLOCK: return "WAV ADPCM block header is invalid";
     case SK_AAC_ERR_UNSUPPORTED_FEATURE: return "unsupported AAC feature";
     case SK_AAC_ERR_INVALID_CONFIG: return "invalid AAC config";
@@ -4824,7 +4826,7 @@ int tick_pcm_body(sk_engine *e, const sk_pcm_tick_stream *ts, uint32_t n_streams
                 if (a.encoding == SK_AIFF_IMA4) {
                     ima_units.push_back(sk::AiffImaUnit{d_src + un.byte_offset, dst_of(i, u), (uint32_t)(un.byte_len / group), 0});
                 } else {
-                    const uint32_t samples = (uint32_t)(un.byte_len / group);
+                    const uint32_t samples = (uint32_t)(un.byte_len / group) * sk_pcm::aiff_group_samples(a.encoding);
                     elems.push_back(sk::AiffElemJob{d_src + un.byte_offset, dst_of(i, u), samples, a.encoding});
                     max_samples = std::max(max_samples, samples);
                 }
@@ -5439,7 +5441,8 @@ static int aiff_decode_one(sk_engine *e, int encoding, uint32_t channels, const 
     const bool ima = encoding == SK_AIFF_IMA4;
     if (ima && (channels > 2 || !state || state[0].step_index > 88 || state[1].step_index > 88)) return SK_ERR_INVALID_ARG;
     const size_t group = sk_pcm::aiff_group_bytes(encoding, channels), group_out = sk_pcm::aiff_group_out_bytes(encoding, channels);
-    if (len % group || len / group > 0x7fffffffu || (len && (!bytes || !out))) return SK_ERR_INVALID_ARG;
+    const uint32_t per_group = sk_pcm::aiff_group_samples(encoding);
+    if (len % group || len / group > 0x7fffffffu / per_group || (len && (!bytes || !out))) return SK_ERR_INVALID_ARG;
     const size_t groups = len / group, need = groups * group_out;
     if (need > out_cap) return SK_ERR_INVALID_ARG;
     if (on_device && (((uintptr_t)bytes | (uintptr_t)out) & 15)) return SK_ERR_INVALID_ARG;
@@ -5468,10 +5471,10 @@ static int aiff_decode_one(sk_engine *e, int encoding, uint32_t channels, const 
                                     (uint32_t *)(table + offsetof(decltype(t), states)), e->stream), "launch aiff ima4");
         SK_HIP(hipMemcpyAsync(got, table + offsetof(decltype(t), states), sizeof got, hipMemcpyDeviceToHost, e->stream), "D2H aiff ima4 states");
     } else {
-        const sk::AiffElemJob job{d_src, d_dst, (uint32_t)groups, (uint32_t)encoding};
+        const sk::AiffElemJob job{d_src, d_dst, (uint32_t)groups * per_group, (uint32_t)encoding};
         SK_HIP(hipMemcpyAsync(table, &job, sizeof job, hipMemcpyHostToDevice, e->stream), "H2D aiff job");
         SK_HIP(hipStreamSynchronize(e->stream), "aiff table sync");
-        SK_HIP(sk::launch_aiff_elem((const sk::AiffElemJob *)table, 1, (uint32_t)groups, e->stream), "launch aiff decode");
+        SK_HIP(sk::launch_aiff_elem((const sk::AiffElemJob *)table, 1, (uint32_t)groups * per_group, e->stream), "launch aiff decode");
     }
     if (!on_device) SK_HIP(hipMemcpyAsync(out, d_dst, need, hipMemcpyDeviceToHost, e->stream), "D2H aiff");
     SK_HIP(hipStreamSynchronize(e->stream), "aiff sync");

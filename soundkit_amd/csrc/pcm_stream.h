@@ -413,6 +413,7 @@ enum AiffEncoding : uint8_t {  // = enum sk_aiff_encoding
     kAiffU8, kAiffS8, kAiffS16BE, kAiffS16LE, kAiffS24BE, kAiffS32BE, kAiffS32LE, kAiffF32BE, kAiffF64BE, kAiffUlaw, kAiffAlaw, kAiffIma4,
     kAiffUnassigned12,  // refused, as every unknown value is (aiff_encoding_known)
     kAiffF64LE,  // = 13; container PCM (QuickTime `fl64` with enda = 1, CAF lpcm flags 3); no AIFF-C compression type names it
+    kAiffDvdS24,  // = 14; DVD LPCM at 24 bits (MPEG program streams): 12-byte groups of four samples, high parts first
     kAiffEncodings
 };
 constexpr size_t kMaxAiffCommBytes = 4096;
@@ -428,14 +429,16 @@ inline size_t aiff_group_bytes(int enc, uint32_t channels) {
     case kAiffS24BE: return 3;
     case kAiffS32BE: case kAiffS32LE: case kAiffF32BE: return 4;
     case kAiffF64BE: case kAiffF64LE: return 8;
+    case kAiffDvdS24: return 12;  // four samples
     default: return (size_t)34 * channels;
     }
 }
-inline uint32_t aiff_contract_bits(int enc) { return enc == kAiffS24BE ? 24 : ((enc >= kAiffS32BE && enc <= kAiffF64BE) || enc == kAiffF64LE ? 32 : 16); }
+inline uint32_t aiff_contract_bits(int enc) { return enc == kAiffS24BE || enc == kAiffDvdS24 ? 24 : ((enc >= kAiffS32BE && enc <= kAiffF64BE) || enc == kAiffF64LE ? 32 : 16); }
 inline bool aiff_contract_float(int enc) { return enc == kAiffF32BE || enc == kAiffF64BE || enc == kAiffF64LE; }
 inline size_t aiff_group_out_bytes(int enc, uint32_t channels) {
-    return enc == kAiffIma4 ? (size_t)128 * channels : aiff_contract_bits(enc) / 8;
+    return enc == kAiffIma4 ? (size_t)128 * channels : (enc == kAiffDvdS24 ? 12 : aiff_contract_bits(enc) / 8);
 }
+inline uint32_t aiff_group_samples(int enc) { return enc == kAiffDvdS24 ? 4 : 1; }  // samples the elementwise kernel counts per group
 
 class AiffStream {
 public:

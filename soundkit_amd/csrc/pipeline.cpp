@@ -27,6 +27,8 @@
 #include "mp4_stream.h"
 #include "webm_stream.h"
 #include "ts_stream.h"
+#include "avi_stream.h"
+#include "ps_stream.h"
 #include "pcm_stream.h"    // the WAV walker and the raw PCM framer
 
 #include <hip/hip_runtime.h>
@@ -160,6 +162,17 @@ struct PStream {
     std::unique_ptr<sk_ts::Demuxer> ts;
     bool ts_routed = false, ts_done = false;
     std::string ts_error;
+    // AVI and MPEG program streams (taken by their magic): the demuxer runs on the worker thread.  Its config event decides what the
+    // stream is from there on (avi_open / ps_open): a PCM track a raw PCM stream whose pieces are the demuxer's packets -- source-encoded
+    // where raw_enc says so (AVI's 8-bit samples, DVD LPCM's 24-bit groups: units of the AIFF tick, aiff_enc says which) -- and an MPEG
+    // audio track an MPEG audio stream, the payloads appended to `pending` as a transport stream's are.  cont_error: what ends the stream
+    // once the units in front of it have gone; cont_done: nothing more is pulled
+    std::unique_ptr<sk_avi::Demuxer> avi;
+    std::unique_ptr<sk_ps::Demuxer> ps;
+    bool cont_routed = false, cont_done = false, raw_enc = false;
+    std::string cont_error;
+    std::vector<uint8_t> cont_piece;  // the packet a PCM pass is working through
+    size_t cont_piece_pos = 0;
     sk_raw_pcm_format raw_format{};  // sk_pipeline_spawn_raw_pcm's
     bool pcm_detected = false;       // WAV: the detection buffer has gone through the processor
     uint8_t pcm_route = 0;           // 0 not decided yet, kPcmFast: pieces are delivered as they are, kPcmTick: units of the PCM tick
@@ -167,7 +180,7 @@ struct PStream {
     uint8_t pcm_bits = 0;
     uint32_t pcm_fill = 0;           // frames waiting in the resampler's chunk, mirrored for the output-room estimate
 };
-constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11, kCodecWebm = 12, kCodecTs = 13;
+constexpr uint8_t kCodecAac = 1, kCodecMp3 = 2, kCodecWav = 3, kCodecRawPcm = 4, kCodecAiff = 5, kCodecFlac = 6, kCodecAlac = 7, kCodecG72x = 8, kCodecGsm = 9, kCodecVorbis = 10, kCodecMp4 = 11, kCodecWebm = 12, kCodecTs = 13, kCodecAvi = 14, kCodecPs = 15;
 constexpr uint8_t kPcmFast = 1, kPcmTick = 2, kPcmAiffTick = 3, kPcmFlacTick = 4, kPcmAlacTick = 5, kPcmG72xTick = 6, kPcmGsmTick = 7, kPcmVorbisTick = 8, kPcmWavAdpcmTick = 9;  // kPcmAiffTick: units of the AIFF tick (decode, then whatever the PCM tick would do)
 // The PCM input of one tick (and so of one worker pass): pieces are staged in a pinned buffer of this size per batch, each at a
 // 16-byte aligned offset.  A piece is never split: one `add` takes at most 4 MiB and returns at most that plus a carried partial frame.
@@ -496,9 +509,54 @@ int ts_pull(PStream &s) {
     return 1;
 }
 
+// The same three for an AVI or a program stream.  cont_take: the demuxer's first waiting packet, into `out`
+bool cont_has_packets(const PStream &s) { return s.avi ? !s.avi->packets.empty() : !s.ps->packets.empty(); }
+void cont_take(PStream &s, std::vector<uint8_t> &out) {
+    if (s.avi) out = s.avi->take_packet().data;
+    else out = s.ps->take_packet().data;
+}
+void cont_drain(PStream &s) {
+    if (!s.cont_routed || s.codec == kCodecRawPcm) return;
+    if (s.pending_pos > 0 && s.pending_pos >= s.pending.size() / 2) {  // compact
+        s.pending.erase(s.pending.begin(), s.pending.begin() + (ptrdiff_t)s.pending_pos);
+        s.pending_pos = 0;
+    }
+    std::vector<uint8_t> data;
+    while (cont_has_packets(s)) {
+        cont_take(s, data);
+        s.pending.insert(s.pending.end(), data.begin(), data.end());
+    }
+}
+void cont_feed(PStream &s, const uint8_t *data, size_t len, bool end) {
+    if (end) s.cont_done = true;
+    const bool ok = s.avi ? (end ? s.avi->finish() : s.avi->add(data, len)) : (end ? s.ps->finish() : s.ps->add(data, len));
+    if (!ok && s.cont_error.empty()) s.cont_error = s.avi ? s.avi->error : s.ps->error;
+    cont_drain(s);
+    if (!s.cont_error.empty()) s.cont_done = s.saw_eof = true;
+}
+int cont_pull(PStream &s) {
+    if (s.cont_done) return 0;
+    std::vector<uint8_t> chunk;
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (s.in.empty()) return 0;
+        chunk = std::move(s.in.front());
+        s.in.pop_front();
+    }
+    if (chunk.empty()) {
+        s.saw_eof = true;
+        cont_feed(s, nullptr, 0, true);
+        return -1;
+    }
+    s.queued_bytes.fetch_sub(chunk.size());
+    cont_feed(s, chunk.data(), chunk.size(), false);
+    return 1;
+}
+
 // 1 = a chunk was appended to s.pending, 0 = nothing queued right now, -1 = the end-of-stream marker was taken (s.saw_eof set)
 int pull_input(PStream &s) {
     if (s.ts) return ts_pull(s);  // (1: a chunk went through the demuxer, whatever it handed out)
+    if (s.avi || s.ps) return cont_pull(s);
     std::vector<uint8_t> chunk;
     bool got = false;
     {
@@ -727,6 +785,7 @@ uint8_t sniff_codec(const uint8_t *d, size_t n, bool eof) {
     if (n >= 4 && (std::memcmp(d, "RIFF", 4) == 0 || std::memcmp(d, "RF64", 4) == 0)) {
         if (n < 12) return 0;
         if (std::memcmp(d + 8, "WAVE", 4) == 0) return kCodecWav;
+        if (sk_avi::sniff(d, n)) return kCodecAvi;  // RIFF....AVI  (looks_like_avi)
     } else if (n > 0 && n < 4 && (std::memcmp(d, "RIFF", n) == 0 || std::memcmp(d, "RF64", n) == 0)) {
         return 0;
     }
@@ -748,6 +807,10 @@ uint8_t sniff_codec(const uint8_t *d, size_t n, bool eof) {
     // fLaC -> native FLAC (AudioType::Flac); fewer than 4 bytes that match so far: wait
     if (n >= 4 && std::memcmp(d, "fLaC", 4) == 0) return kCodecFlac;
     if (n > 0 && n < 4 && std::memcmp(d, "fLaC", n) == 0) return 0;
+    // 00 00 01 BA -> an MPEG program stream (looks_like_mpeg_ps), before the rules that would find a sync inside it; fewer than 4 bytes
+    // that match so far: wait
+    static const uint8_t pack[4] = {0x00, 0x00, 0x01, 0xBA};
+    if (n > 0 && std::memcmp(d, pack, std::min<size_t>(n, 4)) == 0) return n < 4 ? 0 : kCodecPs;
     // an MPEG transport stream (looks_like_mpeg_ts: three syncs at stride 188, or at 192 behind four bytes), before the MPEG sync scan,
     // which would stop at the first FF Fx inside some PES payload.  A 47 where the first sync would be: wait for the 389 bytes that
     // settle it, unless the stream has ended; a stream that is none goes on to the rules below as it always did
@@ -1033,6 +1096,9 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         if (s.wav_g711 || s.wav_adpcm) bits = 16;  // what the decode emits, as for AIFF-C
         if (s.wav_g711) s.aiff_enc = tag == SK_WAV_TAG_ALAW ? SK_AIFF_ALAW : SK_AIFF_ULAW;
         if (s.wav_adpcm) s.wav_parse_left = s.wav_tick_left = s.wav->total_frames();
+    } else if (s.raw_enc) {  // a container's source-encoded PCM: what the AIFF tick makes of it
+        rate = s.raw_format.sample_rate, channels = s.raw_format.channels;
+        bits = sk_pcm::aiff_contract_bits(s.aiff_enc), is_float = false;
     } else {
         const int f = s.raw_format.format;
         rate = s.raw_format.sample_rate, channels = s.raw_format.channels;
@@ -1101,7 +1167,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     }
     if (target_rate == rate && target_bits == bits && target_channels == channels) {
         // sowt / 23ni are the contract's bytes already; every other encoding has per-sample work, which is the tick's
-        if ((!s.aiff && !s.wav_g711) || (s.aiff && (s.aiff_enc == SK_AIFF_S16LE || s.aiff_enc == SK_AIFF_S32LE))) {
+        if ((!s.aiff && !s.wav_g711 && !s.raw_enc) || (s.aiff && (s.aiff_enc == SK_AIFF_S16LE || s.aiff_enc == SK_AIFF_S32LE))) {
             s.pcm_route = kPcmFast;
             return true;
         }
@@ -1119,7 +1185,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
     // 3 ... 8 channels: the tick takes them on an engine whose pool of wide streams was reserved (sk_engine_enable_wide_pcm)
     if (channels > SK_MAX_CHANNELS && (channels > SK_MAX_PCM_CHANNELS || !hooks.wide_pcm_streams || hooks.wide_pcm_streams(p->engine) == 0))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: conversion of PCM with more than 2 channels is not supported");
-    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound || ((s.aiff || s.wav_g711) && (!hooks.tick_aiff || !hooks.tick_aiff_out_bound)))
+    if (!hooks.tick_pcm || !hooks.tick_pcm_out_bound || ((s.aiff || s.wav_g711 || s.raw_enc) && (!hooks.tick_aiff || !hooks.tick_aiff_out_bound)))
         return r.fail(SK_ERR_UNSUPPORTED, "Decoding failed: PCM conversion needs the device tick, which this build lacks");
     s.pcm_fmt = (uint8_t)((bits == 16 ? SK_FMT_S16LE : (bits == 24 ? SK_FMT_S24LE : (is_float ? SK_FMT_F32LE : SK_FMT_S32LE))) + (big_endian ? 1 : 0));
     int rc = ensure_pcm(p);
@@ -1131,7 +1197,7 @@ bool pcm_open(sk_lane *p, PStream &s, Parsed &r) {
         rc = sk_resampler_open(p->engine, s.engine_stream, rate, target_rate);
         if (rc != SK_OK) return r.fail(rc, "Decoding failed: Failed to create resampler: unsupported rate pair");
     }
-    s.pcm_route = s.vorbis ? kPcmVorbisTick : s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff || s.wav_g711 ? kPcmAiffTick : (s.wav_adpcm ? kPcmWavAdpcmTick : kPcmTick)));
+    s.pcm_route = s.vorbis ? kPcmVorbisTick : s.gsm ? kPcmGsmTick : s.g72x ? kPcmG72xTick : s.alac ? kPcmAlacTick : (s.flac ? kPcmFlacTick : (s.aiff || s.wav_g711 || s.raw_enc ? kPcmAiffTick : (s.wav_adpcm ? kPcmWavAdpcmTick : kPcmTick)));
     return true;
 }
 
@@ -1520,6 +1586,78 @@ bool ts_open(PStream &s, Parsed &r) {
     return true;
 }
 
+// An AVI or a program stream up to its config event: the demuxer starts with the bytes of the detection.  false: more input is needed, or
+// the stream has failed (r says how).
+bool cont_begin(PStream &s, Parsed &r, int32_t status, const char *none) {
+    if (!s.avi && !s.ps) {
+        if (s.codec == kCodecAvi) s.avi.reset(new sk_avi::Demuxer());
+        else s.ps.reset(new sk_ps::Demuxer(sk_ps::kTrackFirst));
+        const std::vector<uint8_t> head(s.pending.begin() + (ptrdiff_t)s.pending_pos, s.pending.end());
+        s.pending.clear();
+        s.pending_pos = 0;
+        for (size_t at = 0; at < head.size() && !s.cont_done; at += 1u << 20) cont_feed(s, head.data() + at, std::min<size_t>(1u << 20, head.size() - at), false);
+        if (s.saw_eof && !s.cont_done) cont_feed(s, nullptr, 0, true);
+    }
+    while (!(s.avi ? s.avi->configured : s.ps->configured)) {
+        if (!s.cont_error.empty()) return r.fail(status, "Invalid input format: " + s.cont_error);
+        if (s.cont_done) return r.fail(status, std::string("Invalid input format: ") + none);
+        if (cont_pull(s) == 0) return false;
+    }
+    return true;
+}
+
+// An AVI stream becomes what its track is (decode_avi_audio's two matches on the format tag, lib.rs:288-308): integer PCM at 16 / 24 / 32
+// bits and 32-bit float a raw PCM stream of that little-endian format, every `##wb` chunk's whole frames one piece and a partial frame
+// carried to the next chunk (the framer's); 8-bit PCM a stream of the AIFF tick with SK_AIFF_U8; MPEG audio an MPEG audio stream.
+bool avi_open(PStream &s, Parsed &r) {
+    if (!cont_begin(s, r, SK_AVI_ERR_STREAM, "AVI has no audio stream")) return false;
+    const sk_avi::Config &c = s.avi->config;
+    char tag[8];
+    std::snprintf(tag, sizeof tag, "%04x", (unsigned)c.format_tag);
+    if (c.format_tag == 0x0001 || c.format_tag == 0x0003) {
+        const bool is_float = c.format_tag == 0x0003;
+        if (is_float && c.bits != 32) return r.fail(SK_AVI_ERR_STREAM, "Invalid input format: unsupported AVI float PCM depth " + std::to_string(c.bits));
+        if (!is_float && c.bits != 8 && c.bits != 16 && c.bits != 24 && c.bits != 32)
+            return r.fail(SK_AVI_ERR_STREAM, "Invalid input format: unsupported AVI integer PCM depth " + std::to_string(c.bits));
+        if (c.bits == 8 && c.channels > sk_pcm::kMaxAiffChannels)
+            return r.fail(SK_AVI_ERR_STREAM, "Invalid input format: AVI 8-bit PCM with more than " + std::to_string(sk_pcm::kMaxAiffChannels) + " channels is not built");
+        s.codec = kCodecRawPcm;
+        const uint8_t fmt = (uint8_t)(is_float ? SK_FMT_F32LE : (c.bits == 24 ? SK_FMT_S24LE : (c.bits == 32 ? SK_FMT_S32LE : SK_FMT_S16LE)));
+        s.raw_format = sk_raw_pcm_format{c.sample_rate, c.channels, fmt, 0};
+        if (c.bits == 8) s.raw_enc = true, s.aiff_enc = SK_AIFF_U8;
+        s.raw.reset(new sk_pcm::RawPcmStream((size_t)c.channels * (c.bits / 8)));
+    } else if (c.format_tag == 0x0055) {
+        s.codec = kCodecMp3;
+    } else if (c.format_tag >= 0x0160 && c.format_tag <= 0x0163) {
+        return r.fail(SK_AVI_ERR_STREAM, "Invalid input format: AVI WMA decoding is not implemented");
+    } else if (c.format_tag == 0x2000) {
+        return r.fail(SK_AVI_ERR_STREAM, "Invalid input format: AVI AC-3 audio is not built");
+    } else {
+        return r.fail(SK_AVI_ERR_STREAM, std::string("Invalid input format: unsupported AVI audio format tag 0x") + tag);
+    }
+    s.cont_routed = true;
+    cont_drain(s);
+    return true;
+}
+
+// A program stream becomes what its track is: DVD LPCM at 16 bits a raw PCM stream of big-endian samples, at 24 bits a stream of the
+// AIFF tick with SK_AIFF_DVD_S24 whose pieces are whole blocks; MPEG audio an MPEG audio stream.
+bool ps_open(PStream &s, Parsed &r) {
+    if (!cont_begin(s, r, SK_PS_ERR_STREAM, "MPEG-PS has no supported DVD LPCM track")) return false;
+    const sk_ps::Config &c = s.ps->config;
+    if (c.kind == sk_ps::kKindLpcm) {
+        s.codec = kCodecRawPcm;
+        s.raw_format = sk_raw_pcm_format{c.sample_rate, c.channels, (uint8_t)(c.bits == 16 ? SK_FMT_S16BE : SK_FMT_S24LE), 0};
+        if (c.bits == 24) s.raw_enc = true, s.aiff_enc = SK_AIFF_DVD_S24;
+        s.raw.reset(new sk_pcm::RawPcmStream(c.block_bytes));
+    } else {
+        s.codec = kCodecMp3;
+    }
+    s.cont_routed = true;
+    cont_drain(s);
+    return true;
+}
+
 // A WebM stream up to its first Cluster: the demuxer starts with the bytes of the detection, and the first audio track it reports
 // decides what the stream is from here on (WebmDecoder::configure: the first configuration is taken or refused, a second one is
 // refused).  A_VORBIS: the three headers out of the CodecPrivate go through the steps an Ogg stream's go through.  A_AAC: the
@@ -1727,7 +1865,7 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
         if (s.wav_adpcm) return process_wav_adpcm(piece);
         // (an AIFF piece is source-encoded: its frames follow from its sample groups; so is a G.711 WAV's, a byte a sample)
         const uint32_t frame_bytes = (uint32_t)s.pcm_bits / 8 * s.channels;
-        const uint32_t frames = s.wav_g711 ? (uint32_t)(piece.len / s.channels) : s.aiff ? (uint32_t)(piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) * (s.aiff_enc == SK_AIFF_IMA4 ? 64 : 1) /
+        const uint32_t frames = s.wav_g711 ? (uint32_t)(piece.len / s.channels) : s.raw_enc ? (uint32_t)(piece.len / (s.aiff_enc == SK_AIFF_U8 ? 1 : 3) / s.channels) : s.aiff ? (uint32_t)(piece.len / sk_pcm::aiff_group_bytes(s.aiff_enc, s.channels) * (s.aiff_enc == SK_AIFF_IMA4 ? 64 : 1) /
                                                     (s.aiff_enc == SK_AIFF_IMA4 ? 1 : s.channels))
                                        : (uint32_t)(piece.len / frame_bytes);
         // the decoder emits every complete SAMPLE of an add: a piece may end inside a frame.  Delivered as it is that is what the
@@ -1780,6 +1918,27 @@ void parse_some_pcm(sk_lane *p, PStream &s, uint32_t room, Parsed &r) {
             }
             const sk_ts::Packet pk = s.ts->take_packet();
             if (!process(pk.data.data(), pk.data.size())) break;
+            continue;
+        }
+        // an AVI's `##wb` chunks, a program stream's whole blocks: one piece each (a chunk above 1 MiB goes in slices of that size)
+        if ((s.avi || s.ps) && (s.cont_piece_pos < s.cont_piece.size() || cont_has_packets(s) || !s.saw_eof)) {
+            if (s.cont_piece_pos >= s.cont_piece.size()) {
+                if (!cont_has_packets(s)) {
+                    if (cont_pull(s) == 0) break;
+                    continue;
+                }
+                cont_take(s, s.cont_piece);
+                s.cont_piece_pos = 0;
+                continue;
+            }
+            const size_t n = std::min<size_t>(1u << 20, s.cont_piece.size() - s.cont_piece_pos);
+            if (full(n)) {
+                r.more = true;
+                break;
+            }
+            const uint8_t *data = s.cont_piece.data() + s.cont_piece_pos;
+            s.cont_piece_pos += n;
+            if (!process(data, n)) break;
             continue;
         }
         if (s.mp4) {  // a PCM track of an MP4 stream: every run of frames the demuxer hands out is one piece
@@ -1847,6 +2006,8 @@ void parse_some(sk_lane *p, PStream &s, uint32_t limit, float *coeffs, sk_aac_fr
     }
     if (s.codec == kCodecWebm && !webm_open(s, r)) return;  // taken by its EBML magic: from its first Cluster on it is one of the streams below
     if (s.codec == kCodecTs && !ts_open(s, r)) return;      // a transport stream: from its track's first packet on it is one of the streams below
+    if (s.codec == kCodecAvi && !avi_open(s, r)) return;    // an AVI, a program stream: the same from the config event on
+    if (s.codec == kCodecPs && !ps_open(s, r)) return;
     if (s.codec == kCodecMp3) {
         // MPEG audio of which layer: that of the stream's first confirmed frame (two consistent headers one frame length apart)
         const sk_mp3_internal::PipelineGpuHooks &hooks = sk_mp3_internal::pipeline_gpu_hooks();
@@ -2159,6 +2320,10 @@ void worker_body(sk_lane *p) {
             if (s.ts && r.eof && !r.failed && !s.ts_error.empty()) {
                 r.eof = false;
                 r.fail(SK_TS_ERR_STREAM, "Invalid input format: " + s.ts_error);
+            }
+            if ((s.avi || s.ps) && r.eof && !r.failed && !s.cont_error.empty()) {  // the same for an AVI or a program stream
+                r.eof = false;
+                r.fail(s.avi ? SK_AVI_ERR_STREAM : SK_PS_ERR_STREAM, "Invalid input format: " + s.cont_error);
             }
         } catch (...) {
             // whatever was thrown while this stream's input was parsed is this stream's error and nobody else's
@@ -3159,6 +3324,12 @@ int lane_spawn(sk_lane *p, const sk_decode_options *opt, const sk_raw_pcm_format
     s.ts.reset();
     s.ts_routed = s.ts_done = false;
     s.ts_error.clear();
+    s.avi.reset();
+    s.ps.reset();
+    s.cont_routed = s.cont_done = s.raw_enc = false;
+    s.cont_error.clear();
+    s.cont_piece.clear();
+    s.cont_piece_pos = 0;
     s.aiff_plain = false;
     s.aiff_ima[0] = s.aiff_ima[1] = sk_aiff_ima_state{};
     s.raw_format = sk_raw_pcm_format{};
@@ -4520,6 +4691,148 @@ int sk_ts_sniff(const uint8_t *bytes, size_t len) try {
 } catch (...) {
     (void)sk::abi_caught("sk_ts_sniff");
     return 0;
+}
+
+}  // extern "C"
+
+// ---- AVI and MPEG program stream (avi_stream.h, ps_stream.h) --------------------------------------------------------------------------
+
+struct sk_avi_demuxer {
+    sk_avi::Demuxer demuxer;
+    bool config_taken = false;
+};
+struct sk_ps_demuxer {
+    explicit sk_ps_demuxer(uint8_t mode) : demuxer(mode) {}
+    sk_ps::Demuxer demuxer;
+    bool config_taken = false;
+};
+
+namespace {
+void demux_info(const sk_avi::Config &c, sk_avi_track_info *info) {
+    info->stream_index = c.stream_index, info->sample_rate = c.sample_rate, info->format_tag = c.format_tag, info->channels = c.channels, info->bits = c.bits;
+}
+void demux_info(const sk_ps::Config &c, sk_ps_track_info *info) {
+    info->sample_rate = c.sample_rate, info->block_bytes = c.block_bytes, info->kind = c.kind, info->stream_id = c.stream_id;
+    info->substream_id = c.substream_id, info->channels = c.channels, info->bits = c.bits;
+}
+// sk_avi_demuxer_next / sk_ps_demuxer_next: the config in front of the first packet, then the packets in order
+template <class Handle, class Info>
+int demux_next(Handle *d, int *event, Info *info, uint8_t *out, size_t cap, size_t *len) {
+    if (!d || !event || !len || (cap && !out)) return SK_ERR_INVALID_ARG;
+    *event = SK_DEMUX_NONE, *len = 0;
+    if (d->demuxer.configured && !d->config_taken) {
+        if (!info) return SK_ERR_INVALID_ARG;
+        std::memset(info, 0, sizeof *info);
+        demux_info(d->demuxer.config, info);
+        d->config_taken = true;
+        *event = SK_DEMUX_CONFIG;
+        return SK_OK;
+    }
+    if (d->demuxer.packets.empty()) return SK_OK;
+    const std::vector<uint8_t> &data = d->demuxer.packets.front().data;
+    *len = data.size();
+    if (cap < data.size()) return SK_ERR_CAPACITY;
+    if (!data.empty()) std::memcpy(out, data.data(), data.size());
+    (void)d->demuxer.take_packet();
+    *event = SK_DEMUX_PACKET;
+    return SK_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sk_avi_demuxer_create(sk_avi_demuxer **out) try {
+    sk::abi_enter();
+    if (!out) return SK_ERR_INVALID_ARG;
+    *out = new sk_avi_demuxer();
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_avi_demuxer_create");
+}
+
+void sk_avi_demuxer_destroy(sk_avi_demuxer *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_avi_demuxer_destroy");
+}
+
+int sk_avi_demuxer_add(sk_avi_demuxer *d, const uint8_t *bytes, size_t len) try {
+    sk::abi_enter();
+    if (!d || (len && !bytes)) return SK_ERR_INVALID_ARG;
+    return d->demuxer.add(bytes, len) ? SK_OK : SK_AVI_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_avi_demuxer_add");
+}
+
+int sk_avi_demuxer_finish(sk_avi_demuxer *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    return d->demuxer.finish() ? SK_OK : SK_AVI_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_avi_demuxer_finish");
+}
+
+int sk_avi_demuxer_next(sk_avi_demuxer *d, int *event, sk_avi_track_info *info, uint8_t *out, size_t cap, size_t *len) try {
+    sk::abi_enter();
+    return demux_next(d, event, info, out, cap, len);
+} catch (...) {
+    return sk::abi_caught("sk_avi_demuxer_next");
+}
+
+const char *sk_avi_demuxer_last_error(const sk_avi_demuxer *d) try {
+    sk::abi_enter();
+    return d ? d->demuxer.error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_avi_demuxer_last_error");
+    return "";
+}
+
+int sk_ps_demuxer_create(int track_mode, sk_ps_demuxer **out) try {
+    sk::abi_enter();
+    if (!out || track_mode < SK_PS_TRACK_FIRST || track_mode > SK_PS_TRACK_MPEG_AUDIO) return SK_ERR_INVALID_ARG;
+    *out = new sk_ps_demuxer((uint8_t)track_mode);
+    return SK_OK;
+} catch (...) {
+    return sk::abi_caught("sk_ps_demuxer_create");
+}
+
+void sk_ps_demuxer_destroy(sk_ps_demuxer *d) try {
+    sk::abi_enter();
+    delete d;
+} catch (...) {
+    (void)sk::abi_caught("sk_ps_demuxer_destroy");
+}
+
+int sk_ps_demuxer_add(sk_ps_demuxer *d, const uint8_t *bytes, size_t len) try {
+    sk::abi_enter();
+    if (!d || (len && !bytes)) return SK_ERR_INVALID_ARG;
+    return d->demuxer.add(bytes, len) ? SK_OK : SK_PS_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_ps_demuxer_add");
+}
+
+int sk_ps_demuxer_finish(sk_ps_demuxer *d) try {
+    sk::abi_enter();
+    if (!d) return SK_ERR_INVALID_ARG;
+    return d->demuxer.finish() ? SK_OK : SK_PS_ERR_STREAM;
+} catch (...) {
+    return sk::abi_caught("sk_ps_demuxer_finish");
+}
+
+int sk_ps_demuxer_next(sk_ps_demuxer *d, int *event, sk_ps_track_info *info, uint8_t *out, size_t cap, size_t *len) try {
+    sk::abi_enter();
+    return demux_next(d, event, info, out, cap, len);
+} catch (...) {
+    return sk::abi_caught("sk_ps_demuxer_next");
+}
+
+const char *sk_ps_demuxer_last_error(const sk_ps_demuxer *d) try {
+    sk::abi_enter();
+    return d ? d->demuxer.error.c_str() : "";
+} catch (...) {
+    (void)sk::abi_caught("sk_ps_demuxer_last_error");
+    return "";
 }
 
 int sk_debug_throw_in_thread(int n, int where) {

@@ -18,9 +18,9 @@ SINE, KBD = 0, 1
 FMT_S16LE, FMT_S16BE, FMT_S24LE, FMT_S24BE, FMT_S32LE, FMT_S32BE, FMT_F32LE, FMT_F32BE = range(8)
 # enum sk_aiff_encoding: how an AIFF / AIFF-C file encodes its samples
 (AIFF_U8, AIFF_S8, AIFF_S16BE, AIFF_S16LE, AIFF_S24BE, AIFF_S32BE, AIFF_S32LE, AIFF_F32BE, AIFF_F64BE, AIFF_ULAW, AIFF_ALAW,
- AIFF_IMA4, _, AIFF_F64LE) = range(14)  # 12 is unassigned and refused; AIFF_F64LE = 13: container PCM only (QuickTime `fl64` with enda = 1); no AIFF-C file holds it
+ AIFF_IMA4, _, AIFF_F64LE, AIFF_DVD_S24) = range(15)  # 12 is unassigned and refused; AIFF_F64LE = 13: container PCM only (QuickTime `fl64` with enda = 1); no AIFF-C file holds it; AIFF_DVD_S24 = 14: DVD LPCM's 24-bit groups (12 bytes = four samples), MPEG program streams only
 AIFF_GROUP_BYTES = {AIFF_U8: 1, AIFF_S8: 1, AIFF_S16BE: 2, AIFF_S16LE: 2, AIFF_S24BE: 3, AIFF_S32BE: 4, AIFF_S32LE: 4, AIFF_F32BE: 4,
-                    AIFF_F64BE: 8, AIFF_ULAW: 1, AIFF_ALAW: 1, AIFF_F64LE: 8}  # IMA4: 34 bytes per channel
+                    AIFF_F64BE: 8, AIFF_ULAW: 1, AIFF_ALAW: 1, AIFF_F64LE: 8, AIFF_DVD_S24: 12}  # IMA4: 34 bytes per channel
 
 # enum sk_wav_tag: the format tags the coded WAV walker takes; WAV_BAD_BLOCK = SK_WAV_BAD_BLOCK, a block's status
 WAV_TAG_PCM, WAV_TAG_MS_ADPCM, WAV_TAG_FLOAT, WAV_TAG_ALAW, WAV_TAG_ULAW, WAV_TAG_IMA_ADPCM = 1, 2, 3, 6, 7, 0x11
@@ -546,7 +546,7 @@ class Engine:
         from ._lib import AiffImaState
         data = np.frombuffer(bytes(data), np.uint8)
         group = 34 * channels if encoding == AIFF_IMA4 else AIFF_GROUP_BYTES.get(encoding, 1)  # (an unknown encoding is the library's to refuse)
-        per_group = 128 * channels if encoding == AIFF_IMA4 else (3 if encoding == AIFF_S24BE else (4 if AIFF_S32BE <= encoding <= AIFF_F64BE or encoding == AIFF_F64LE else 2))
+        per_group = 128 * channels if encoding == AIFF_IMA4 else 12 if encoding == AIFF_DVD_S24 else (3 if encoding == AIFF_S24BE else (4 if AIFF_S32BE <= encoding <= AIFF_F64BE or encoding == AIFF_F64LE else 2))
         out = np.zeros(max(data.size // max(group, 1) * per_group, 16), np.uint8)
         st = (AiffImaState * 2)()
         for c, (p, i) in enumerate(ima_state or []):

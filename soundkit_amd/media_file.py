@@ -60,8 +60,6 @@ def looks_like_ebml(data):
 def decode_audio_file(data, options=None, scheduler=None, engine=None):
     """-> DecodedAudioFile.  Refusals raise SoundkitError: `media file is empty`; `AVI is not built`, `MPEG-PS is not built`, `MXF is not
     built`; whatever the container's decode_file or the stream's decoder says."""
-    from .audio_types import AudioData
-    from .pipeline import DecodeError, DecodeOptions, default_scheduler
     if len(data) == 0:
         raise SoundkitError(INVALID_INPUT, "decode_audio_file", "media file is empty")
     data = bytes(data)
@@ -87,7 +85,13 @@ def decode_audio_file(data, options=None, scheduler=None, engine=None):
         from . import webm
         config, frames = webm.decode_file(data, options, scheduler, engine)
         return DecodedAudioFile("webm", config, frames)
-    # decode_complete_stream: everything else through spawn() to the end of the stream
+    return DecodedAudioFile(None, None, decode_complete_stream(data, options, scheduler))
+
+
+def decode_complete_stream(data, options=None, scheduler=None):
+    """decode_complete_stream: the bytes through spawn() to the end of the stream -> [AudioData]"""
+    from .audio_types import AudioData
+    from .pipeline import DecodeError, DecodeOptions, default_scheduler
     h = (scheduler or default_scheduler()).spawn(options or DecodeOptions())
     frames = []
 
@@ -117,4 +121,4 @@ def decode_audio_file(data, options=None, scheduler=None, engine=None):
             pass
     finally:
         h.cancel()
-    return DecodedAudioFile(None, None, frames)
+    return frames

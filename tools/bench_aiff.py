@@ -5,6 +5,7 @@ scheduler is built for.
 Two encodings, 4096 stereo streams x 1 s at 44.1 kHz each, one unit per stream:
   ima4    690 groups of two 34-byte packets per stream (44 160 frames): 46 920 bytes in, 176 640 bytes of s16 out
   s24be   44 100 frames: 264 600 bytes in, the same out
+  dvds24  (not in the default cases) DVD LPCM's 24-bit groups, SK_AIFF_DVD_S24: the same bytes in and out as s24be; --rate 48000 for a DVD's
 each in two forms of the tick:
   plain   delivered as decoded (nothing further to change): the decode launch writes the output records
   to16k   -> 16 kHz mono s16: the decode launch fills the decoded buffer, then what sk_tick_run_pcm runs (k_pcm_ingest, the
@@ -30,7 +31,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import soundkit_amd  # noqa: E402
 from soundkit_amd._lib import AiffTickStream, PcmUnit, TickOutput, check, lib  # noqa: E402
-from soundkit_amd.engine import AIFF_IMA4, AIFF_S24BE  # noqa: E402
+from soundkit_amd.engine import AIFF_DVD_S24, AIFF_IMA4, AIFF_S24BE  # noqa: E402
 
 
 def main():
@@ -50,7 +51,7 @@ def main():
             enc, groups = AIFF_IMA4, (args.rate + 63) // 64
             frames, unit_bytes, decoded_bytes = groups * 64, groups * 34 * ch, groups * 128 * ch
         else:
-            enc, frames = AIFF_S24BE, args.rate
+            enc, frames = (AIFF_DVD_S24 if name == "dvds24" else AIFF_S24BE), args.rate // 2 * 2  # (whole 12-byte groups of four samples)
             unit_bytes = decoded_bytes = frames * 3 * ch
         stride = (unit_bytes + 15) & ~15
         blob = rng.integers(0, 256, n * stride, dtype=np.uint8)
